@@ -11,9 +11,12 @@ is already resident in HBM (the channels-last Laplacian L, atom ids, mask):
     fused 7-layer spectral conv + mix + head + readout    (lnz_lanczosnet_forward) -> score
     [N > 1 ranks only] RCCL all-gather of the per-shard scores
 
-i.e. three launches per step.  The JSON line is self-verifying: `parity_rel_err` is the score of
-the timed seed-0 batch against the CPU oracle's score of the same batch (the `cpu_baseline` leg
-computes it anyway) and the run FAILS if it exceeds 1e-5.
+i.e. three launches per step.  A plain run sets up, warms up, times the --steps steps, writes the
+last timed step's scores (--dump-outputs DIR) and prints the line.  With --full the line also
+carries everything measured beside the headline (per-stage times, roofline, sustained-clock,
+pipelined and split-precision modes, the secondary legs, the CPU baseline) and verifies itself:
+`parity_rel_err` is the score of the timed seed-0 batch against the CPU oracle's score of the same
+batch (the `cpu_baseline` leg computes it anyway) and the run FAILS if it exceeds 1e-5.
 
 Workload = BASELINE.json configs[1]: QM8 LanczosNet, batch 1024 per GPU, N <= 32 dense L,
 K = 20, fp32, config/qm8_lanczos_net.yaml architecture.  Molecules are independent, so ranks
@@ -929,23 +932,45 @@ def shard_parity(cfg, params, batch, score, n_check):
   return float(dev[keep].max()) if keep.any() else 0.0, int(keep.sum())
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+  """DIR/<name>.npy in float32 for every output array; one larger than DUMP_LIMIT_BYTES keeps a
+  fixed, seeded sample of its rows (sorted), so that two builds compare output for output."""
+  os.makedirs(out_dir, exist_ok=True)
+  for name, x in arrays.items():
+    a = x.detach().float().cpu().numpy()
+    row_bytes = max(1, a[:1].nbytes)
+    if a.nbytes > DUMP_LIMIT_BYTES:
+      keep = np.sort(np.random.RandomState(0).choice(len(a), DUMP_LIMIT_BYTES // row_bytes, replace=False))
+      a = a[keep]
+    np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--gpus', type=int, default=1)
   ap.add_argument('--steps', type=int, default=50)
   ap.add_argument('--warmup', type=int, default=10)
   ap.add_argument('--batch', type=int, default=1024, help='molecules per GPU')
-  ap.add_argument('--no-cpu-baseline', action='store_true')
+  ap.add_argument('--full', action='store_true',
+                  help='everything beside the headline: per-stage times, roofline, sustained-clock, '
+                       'pipelined and split-precision modes, secondary legs, CPU baseline and the '
+                       'parity checks against the oracle (off: the timed steps and the line only)')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='write the scores of the last timed step to DIR/score.npy (float32)')
+  ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
   ap.add_argument('--pipeline', action='store_true',
                   help='software pipeline over the stream of batches: one launch prepares batch k+1 '
                        'and computes the spectral gains of batch k')
   ap.add_argument('--cpu-reps', type=int, default=5)
   ap.add_argument('--shard-parity', type=int, default=64,
-                  help='N > 1: molecules of its own shard every rank checks against the oracle')
+                  help='N > 1 with --full: molecules of its own shard every rank checks against the oracle')
   ap.add_argument('--no-secondary', action='store_true',
-                  help='skip the secondary legs (large-graph Lanczos, AdaLanczosNet)')
+                  help='with --full: skip the secondary legs (large-graph Lanczos, AdaLanczosNet)')
   ap.add_argument('--sweep', action='store_true',
-                  help='add config.forward_batch_sweep (fused forward at B = 1024 / 4096 / 16384); '
+                  help='with --full: add config.forward_batch_sweep (fused forward at B = 1024 / 4096 / 16384); '
                        'opt-in because its launches are the SAME kernel as the roofline one and '
                        'would mix into a rocprofv3 --stats average of the default command '
                        '(profiles/r02_c_bench.json holds a run with it)')
@@ -1130,8 +1155,12 @@ def main():
   assert torch.isfinite(score).all()
   timed_score = score.clone()
   kernel_ran = ops.last_kernel()   # what the launcher selected for the timed forwards
+  if args.dump_outputs and rank == 0:
+    # what a caller of the timed path received from its last step: the scores (all shards' at N > 1)
+    dump_outputs(args.dump_outputs,
+                 {'score': gather.result(gather.issued - 1) if gather else timed_score})
   shard_check = None
-  if dist and not args.zero_params:
+  if dist and args.full and not args.zero_params:
     # every rank verifies ITS shard (seed = rank) on a bounded sample, after the clock has stopped
     # (N ranks share the host: a few intra-op threads each, not one pool of all cores per rank)
     torch.set_num_threads(max(1, min(8, (os.cpu_count() or 8) // world)))
@@ -1153,7 +1182,7 @@ def main():
   # (forward launch 0.605 against 0.588 ms): a short run (the driver's --steps 20 --warmup 5) reads
   # about 3 % slower than a long one for that reason alone, on the same box.
   sustained = None
-  if world == 1 and not args.zero_params and not args.pipeline:
+  if world == 1 and args.full and not args.zero_params and not args.pipeline:
     with torch.no_grad():
       for _ in range(60):
         step()
@@ -1171,7 +1200,7 @@ def main():
 
   # secondary measurement (N = 1 only, never `value`): software pipeline over the stream of batches
   pipe = None
-  if world == 1 and args.gemm == 'fp32' and not args.zero_params and not args.pipeline:
+  if world == 1 and args.full and args.gemm == 'fp32' and not args.zero_params and not args.pipeline:
     with torch.no_grad():
       run_pipelined(args.warmup)
       torch.cuda.synchronize()
@@ -1190,7 +1219,7 @@ def main():
 
   # secondary measurement (N = 1 only, never `value`): the opt-in split-precision GEMM mode
   split = None
-  if world == 1 and args.gemm == 'fp32' and not args.zero_params:
+  if world == 1 and args.full and args.gemm == 'fp32' and not args.zero_params:
     net.gemm_mode = 'f16x3'
     plan_fp32, plan = plan, net._plan()
     ref_score = score.clone()
@@ -1265,8 +1294,12 @@ def main():
     plan = plan_fp32
 
   # forward launch duration: HIP events of the timed region; the other stages: an untimed pass
+  # (--full only)
   stage_ms = {}
-  if not args.pipeline:
+  if args.pipeline:
+    stage_ms['prepare_batch(k+1)+spectral_gains(k)'] = float(
+        np.mean([ev[i][0].elapsed_time(ev[i][1]) for i in range(args.steps)]))
+  elif args.full:
     ev2 = [[torch.cuda.Event(enable_timing=True) for _ in range(6)] for _ in range(min(args.steps, 20))]
     with torch.no_grad():
       for e in ev2:
@@ -1274,18 +1307,15 @@ def main():
     torch.cuda.synchronize()
     stage_ms['prepare_batch(plan+lanczos_ritz+pack)'] = float(np.mean([e[0].elapsed_time(e[1]) for e in ev2]))
     stage_ms['spectral_gains'] = float(np.mean([e[1].elapsed_time(e[2]) for e in ev2]))
-  else:
-    stage_ms['prepare_batch(k+1)+spectral_gains(k)'] = float(
-        np.mean([ev[i][0].elapsed_time(ev[i][1]) for i in range(args.steps)]))
   stage_ms['lanczosnet_forward'] = float(
       np.mean([ev[i][4].elapsed_time(ev[i][5]) for i in range(args.steps)]))
 
   # secondary measurements (N = 1 only, never `value`)
   sweep = large = large_conv = ada = graphcfg = None
-  if world == 1 and args.gemm == 'fp32' and not args.zero_params and args.sweep:
+  if world == 1 and args.full and args.gemm == 'fp32' and not args.zero_params and args.sweep:
     sweep = forward_batch_sweep(net, plan, L, node_feat, mask_u8, n_nodes, cfg, (1024, 4096, 16384)
                                 if B == 1024 else (B,))
-  if world == 1 and args.gemm == 'fp32' and not args.zero_params and not args.no_secondary:
+  if world == 1 and args.full and args.gemm == 'fp32' and not args.zero_params and not args.no_secondary:
     # a failing secondary leg must not take the headline line with it: it is reported as an error
     def _leg(fn, *a_):
       try:
@@ -1308,67 +1338,114 @@ def main():
   if rank == 0:
     ms_per_step = 1e3 * elapsed / args.steps
     value = world * B * args.steps / elapsed
-    fwd_s = stage_ms['lanczosnet_forward'] * 1e-3
-    # matrix-core work the kernel ISSUES for this batch's tile plan: the kernel runs 32-row node
-    # tiles (small molecules share one) and skips the GEMM2 / lift-back / projection k-groups of
-    # padded rows and the GEMM2 of identity bond-type channels — counted instruction by
-    # instruction from the plan (lanczosnet_amd/utils/flop_model.py; agrees with rocprofv3's
-    # SQ_INSTS_VALU_MFMA_MOPS_F32 of this kernel, tests/test_flop_model.py)
-    from lanczosnet_amd.utils.flop_model import (tiles_from_plan, forward_mfma_issued,
-                                                 forward16_mfma_issued, forward16_selected,
-                                                 strips_selected, strips_from_plan, strip_mfma_issued)
-    with torch.no_grad():
-      Lp_m, (buf, cap), _, _, _ = ops.prepare_batch(plan, L, mask_u8, n_nodes, K)
-    torch.cuda.synchronize()
-    mk = mask_u8.cpu().numpy()
-    extents = np.where(mk.any(axis=1), mk.shape[1] - np.argmax(mk[:, ::-1] != 0, axis=1), 0)
-    tile_list = tiles_from_plan(buf[:12 * cap].cpu().numpy(), extents,
-                                Lp_m.ident.cpu().numpy() if hasattr(Lp_m, 'ident') else None, K)
-    # which of the exact-fp32 forward kernels took the launches (csrc/conv_forward.hip launch_conv)
-    f16 = args.gemm == 'fp32' and forward16_selected(cfg)
-    strip = f16 and getattr(buf, 'strips', None) is not None and strips_selected(cfg, B, L.shape[1])
-    if strip:
-      ident_np = Lp_m.ident.cpu().numpy() if hasattr(Lp_m, 'ident') else None
-      tile_list = strips_from_plan(buf.strips.cpu().numpy(), ident_np)
-      fm = strip_mfma_issued(tile_list, cfg)
-    else:
-      fm = forward16_mfma_issued(tile_list, cfg) if f16 else forward_mfma_issued(tile_list, cfg)
-    roof_kernel = ('lanczosnet_strip_kernel' if strip else 'lanczosnet_forward16_kernel' if f16
-                   else 'lanczosnet_forward_kernel<4,10,0,0>')
-    # the flop model above follows the launcher's rule; the name in the line is the launcher's own
-    assert kernel_ran.startswith(roof_kernel.split('<')[0]), (kernel_ran, roof_kernel)
-    roof_kernel = kernel_ran
-    roof_insn = ('2048 flop x the v_mfma_f32_16x16x4_f32' if f16 else
-                 '4096 flop x the v_mfma_f32_32x32x2_f32')
-    n_tiles = fm['tiles']
-    # strips: the block products are branch free — the kernel also multiplies the neighbouring
-    # subtile pairs no molecule touches and the identity channels' zero fragments (6 % of its
-    # instructions); `achieved` prices only the instructions of GEMM1 and of touched blocks
-    flops_exec = fm['mfma_in_touched_blocks'] * 2048 if strip else fm['flops_issued']
-    achieved = flops_exec / fwd_s / 1e12
-    if os.environ.get('LNZ_BENCH_DUMP_PLAN'):
+    roofline = None
+    if args.full:
+      fwd_s = stage_ms['lanczosnet_forward'] * 1e-3
+      # matrix-core work the kernel ISSUES for this batch's tile plan: the kernel runs 32-row node
+      # tiles (small molecules share one) and skips the GEMM2 / lift-back / projection k-groups of
+      # padded rows and the GEMM2 of identity bond-type channels — counted instruction by
+      # instruction from the plan (lanczosnet_amd/utils/flop_model.py; agrees with rocprofv3's
+      # SQ_INSTS_VALU_MFMA_MOPS_F32 of this kernel, tests/test_flop_model.py)
+      from lanczosnet_amd.utils.flop_model import (tiles_from_plan, forward_mfma_issued,
+                                                   forward16_mfma_issued, forward16_selected,
+                                                   strips_selected, strips_from_plan, strip_mfma_issued)
+      with torch.no_grad():
+        Lp_m, (buf, cap), _, _, _ = ops.prepare_batch(plan, L, mask_u8, n_nodes, K)
+      torch.cuda.synchronize()
+      mk = mask_u8.cpu().numpy()
+      extents = np.where(mk.any(axis=1), mk.shape[1] - np.argmax(mk[:, ::-1] != 0, axis=1), 0)
+      tile_list = tiles_from_plan(buf[:12 * cap].cpu().numpy(), extents,
+                                  Lp_m.ident.cpu().numpy() if hasattr(Lp_m, 'ident') else None, K)
+      # which of the exact-fp32 forward kernels took the launches (csrc/conv_forward.hip launch_conv)
+      f16 = args.gemm == 'fp32' and forward16_selected(cfg)
+      strip = f16 and getattr(buf, 'strips', None) is not None and strips_selected(cfg, B, L.shape[1])
       if strip:
-        np.savez_compressed(os.environ['LNZ_BENCH_DUMP_PLAN'], strips=buf.strips.cpu().numpy(),
-                            ident=ident_np if ident_np is not None else np.zeros(0, np.int32))
+        ident_np = Lp_m.ident.cpu().numpy() if hasattr(Lp_m, 'ident') else None
+        tile_list = strips_from_plan(buf.strips.cpu().numpy(), ident_np)
+        fm = strip_mfma_issued(tile_list, cfg)
       else:
-        np.savez_compressed(os.environ['LNZ_BENCH_DUMP_PLAN'],
-                            **{k_: np.array([t_[k_] for t_ in tile_list]) for k_ in tile_list[0]})
-    # HBM bytes per launch of the roofline kernel: PMC counters cannot be read from inside this
-    # process, so `traffic` cites the committed counter run of the SAME command and workload
-    # (tools/pmc_forward_profile.py -> profiles/), never a number measured in this run
-    traffic, traffic_source = None, None
-    for name in (('r06_strip_pmc.json', 'r05_strip_pmc.json', 'r04_strip_pmc.json') if strip else ('r04_forward16_pmc.json',) if f16 else
-                 ('r03_forward_pmc.json', 'pmc_forward_hbm_bytes.json')):
-      prof = os.path.join(ROOT, 'profiles', name)
-      if os.path.exists(prof) and B == 1024:
-        try:
-          traffic = json.load(open(prof)).get('hbm_bytes_per_launch')
-          traffic_source = ('profiles/%s: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE of this kernel '
-                            'on this workload, separate counters-only passes (a committed profile, not '
-                            'measured in this process), FETCH_SIZE x 2 per MI355X_MICROARCH.md' % name)
-          break
-        except Exception:
-          traffic = None
+        fm = forward16_mfma_issued(tile_list, cfg) if f16 else forward_mfma_issued(tile_list, cfg)
+      roof_kernel = ('lanczosnet_strip_kernel' if strip else 'lanczosnet_forward16_kernel' if f16
+                     else 'lanczosnet_forward_kernel<4,10,0,0>')
+      # the flop model above follows the launcher's rule; the name in the line is the launcher's own
+      assert kernel_ran.startswith(roof_kernel.split('<')[0]), (kernel_ran, roof_kernel)
+      roof_kernel = kernel_ran
+      roof_insn = ('2048 flop x the v_mfma_f32_16x16x4_f32' if f16 else
+                   '4096 flop x the v_mfma_f32_32x32x2_f32')
+      n_tiles = fm['tiles']
+      # strips: the block products are branch free — the kernel also multiplies the neighbouring
+      # subtile pairs no molecule touches and the identity channels' zero fragments (6 % of its
+      # instructions); `achieved` prices only the instructions of GEMM1 and of touched blocks
+      flops_exec = fm['mfma_in_touched_blocks'] * 2048 if strip else fm['flops_issued']
+      achieved = flops_exec / fwd_s / 1e12
+      if os.environ.get('LNZ_BENCH_DUMP_PLAN'):
+        if strip:
+          np.savez_compressed(os.environ['LNZ_BENCH_DUMP_PLAN'], strips=buf.strips.cpu().numpy(),
+                              ident=ident_np if ident_np is not None else np.zeros(0, np.int32))
+        else:
+          np.savez_compressed(os.environ['LNZ_BENCH_DUMP_PLAN'],
+                              **{k_: np.array([t_[k_] for t_ in tile_list]) for k_ in tile_list[0]})
+      # HBM bytes per launch of the roofline kernel: PMC counters cannot be read from inside this
+      # process, so `traffic` cites the committed counter run of the SAME command and workload
+      # (tools/pmc_forward_profile.py -> profiles/), never a number measured in this run
+      traffic, traffic_source = None, None
+      for name in (('r06_strip_pmc.json', 'r05_strip_pmc.json', 'r04_strip_pmc.json') if strip else ('r04_forward16_pmc.json',) if f16 else
+                   ('r03_forward_pmc.json', 'pmc_forward_hbm_bytes.json')):
+        prof = os.path.join(ROOT, 'profiles', name)
+        if os.path.exists(prof) and B == 1024:
+          try:
+            traffic = json.load(open(prof)).get('hbm_bytes_per_launch')
+            traffic_source = ('profiles/%s: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE of this kernel '
+                              'on this workload, separate counters-only passes (a committed profile, not '
+                              'measured in this process), FETCH_SIZE x 2 (on gfx950 it counts half the '
+                              'bytes of wide coalesced reads)' % name)
+            break
+          except Exception:
+            traffic = None
+      # frac = flops the kernel ISSUES / launch time / peak: the long-scale
+      # channels run in eigen space, 9.5 % fewer flops than the reference's association
+      roofline = {'kernel': roof_kernel, 'bound': 'mfma',
+                  'achieved': round(achieved, 2), 'peak': PEAK_FP32_MFMA_TFLOPS,
+                  'unit': 'TFLOP/s', 'frac': round(achieved / PEAK_FP32_MFMA_TFLOPS, 4),
+                  'traffic': traffic, 'traffic_source': traffic_source,
+                  'flops_per_launch_executed': flops_exec,
+                  'mfma_instructions_per_launch': fm['mfma_issued'],
+                  'flops_per_launch_issued': fm['flops_issued'],
+                  'flops_per_launch_without_skips': fm['flops_unskipped'],
+                  'tiles_per_launch': n_tiles,
+                  'useful_row_frac': round(fm['useful_row_frac'], 4),
+                  'useful_frac': round(achieved / PEAK_FP32_MFMA_TFLOPS * fm['useful_row_frac'], 4),
+                  'avg_launch_ms': round(stage_ms['lanczosnet_forward'], 4),
+                  'reference_association_tflops': round(
+                      FWD_FLOP_PER_MOL * (fm['subtiles'] / 2.0 if strip else n_tiles) / fwd_s / 1e12, 2),
+                  'note': ('achieved = frac * peak = flops_per_launch_executed / avg_launch_ms. '
+                           'flops_per_launch_executed = %s instructions the kernel issues for THIS '
+                           'batch\'s strip plan (lnz_plan_strips: %d molecules at 4-row granularity '
+                           'in %d strips = %d subtiles of 16 rows, at most %d per strip; the block '
+                           'products of subtile pairs no molecule touches and of identity bond-type '
+                           'channels are NOT counted, although the branch-free kernel issues them '
+                           'on zero fragments: flops_per_launch_issued = mfma_instructions_per_launch '
+                           'x 2048 is what the PMC counter SQ_INSTS_VALU_MFMA_MOPS_F32 shows; '
+                           'utils/flop_model.py, profiles/). useful_row_frac = real node rows / strip rows; '
+                           'useful_frac = frac x useful_row_frac. reference_association_tflops '
+                           'prices every 32 rows at SURVEY 8(d)\'s %d flop (filter build + L_s Z per '
+                           'long channel, which the kernel replaces by one projection and one lift '
+                           'per layer)' % (roof_insn, B, n_tiles, fm['subtiles'],
+                                           fm['max_subtiles_per_strip'], FWD_FLOP_PER_MOL))
+                          if strip else
+                          ('achieved = frac * peak = flops_per_launch_executed / avg_launch_ms. '
+                           'flops_per_launch_executed = %s '
+                           'instructions the kernel issues for THIS batch\'s tile plan (k-groups of '
+                           'padded rows / empty eigen slots and identity bond-type channels are '
+                           'skipped; utils/flop_model.py, checked against the PMC counter '
+                           'SQ_INSTS_VALU_MFMA_MOPS_F32 in profiles/); without the skips the same '
+                           '%d tiles would issue flops_per_launch_without_skips. useful_row_frac = '
+                           'real node rows / tile rows (%d molecules ride in %d 32-row tiles, '
+                           'lnz_plan_tiles); useful_frac = frac x useful_row_frac. '
+                           'reference_association_tflops prices the tiles at SURVEY 8(d)\'s %d flop '
+                           '(filter build + L_s Z per long channel, which the kernel replaces by one '
+                           'projection and one lift per layer)'
+                           % (roof_insn, n_tiles, B, n_tiles, FWD_FLOP_PER_MOL))}
     out = {
         'metric': 'molecules/sec LanczosNet forward, QM8 batch=1024',
         'value': round(value, 1), 'unit': 'molecules/s', 'n_gpus': world, 'steps': args.steps,
@@ -1381,51 +1458,9 @@ def main():
                                'Lanczos + tridiagonal eigensolver (Ritz pairs)] (one launch) + spectral gains + fused forward' % (B, L.shape[1]),
                    'global_batch': world * B, 'parallelism': 'dp%d (batch shards, async score all-gather per step)'
                    % world, 'stage_ms': {k: round(v, 4) for k, v in stage_ms.items()}},
-        # frac = flops the kernel ISSUES / launch time / peak: the long-scale
-        # channels run in eigen space, 9.5 % fewer flops than the reference's association
-        'roofline': {'kernel': roof_kernel, 'bound': 'mfma',
-                     'achieved': round(achieved, 2), 'peak': PEAK_FP32_MFMA_TFLOPS,
-                     'unit': 'TFLOP/s', 'frac': round(achieved / PEAK_FP32_MFMA_TFLOPS, 4),
-                     'traffic': traffic, 'traffic_source': traffic_source,
-                     'flops_per_launch_executed': flops_exec,
-                     'mfma_instructions_per_launch': fm['mfma_issued'],
-                     'flops_per_launch_issued': fm['flops_issued'],
-                     'flops_per_launch_without_skips': fm['flops_unskipped'],
-                     'tiles_per_launch': n_tiles,
-                     'useful_row_frac': round(fm['useful_row_frac'], 4),
-                     'useful_frac': round(achieved / PEAK_FP32_MFMA_TFLOPS * fm['useful_row_frac'], 4),
-                     'avg_launch_ms': round(stage_ms['lanczosnet_forward'], 4),
-                     'reference_association_tflops': round(
-                         FWD_FLOP_PER_MOL * (fm['subtiles'] / 2.0 if strip else n_tiles) / fwd_s / 1e12, 2),
-                     'note': ('achieved = frac * peak = flops_per_launch_executed / avg_launch_ms. '
-                              'flops_per_launch_executed = %s instructions the kernel issues for THIS '
-                              'batch\'s strip plan (lnz_plan_strips: %d molecules at 4-row granularity '
-                              'in %d strips = %d subtiles of 16 rows, at most %d per strip; the block '
-                              'products of subtile pairs no molecule touches and of identity bond-type '
-                              'channels are NOT counted, although the branch-free kernel issues them '
-                              'on zero fragments: flops_per_launch_issued = mfma_instructions_per_launch '
-                              'x 2048 is what the PMC counter SQ_INSTS_VALU_MFMA_MOPS_F32 shows; '
-                              'utils/flop_model.py, profiles/). useful_row_frac = real node rows / strip rows; '
-                              'useful_frac = frac x useful_row_frac. reference_association_tflops '
-                              'prices every 32 rows at SURVEY 8(d)\'s %d flop (filter build + L_s Z per '
-                              'long channel, which the kernel replaces by one projection and one lift '
-                              'per layer)' % (roof_insn, B, n_tiles, fm['subtiles'],
-                                              fm['max_subtiles_per_strip'], FWD_FLOP_PER_MOL))
-                             if strip else
-                             ('achieved = frac * peak = flops_per_launch_executed / avg_launch_ms. '
-                              'flops_per_launch_executed = %s '
-                              'instructions the kernel issues for THIS batch\'s tile plan (k-groups of '
-                              'padded rows / empty eigen slots and identity bond-type channels are '
-                              'skipped; utils/flop_model.py, checked against the PMC counter '
-                              'SQ_INSTS_VALU_MFMA_MOPS_F32 in profiles/); without the skips the same '
-                              '%d tiles would issue flops_per_launch_without_skips. useful_row_frac = '
-                              'real node rows / tile rows (%d molecules ride in %d 32-row tiles, '
-                              'lnz_plan_tiles); useful_frac = frac x useful_row_frac. '
-                              'reference_association_tflops prices the tiles at SURVEY 8(d)\'s %d flop '
-                              '(filter build + L_s Z per long channel, which the kernel replaces by one '
-                              'projection and one lift per layer)'
-                              % (roof_insn, n_tiles, B, n_tiles, FWD_FLOP_PER_MOL))},
     }
+    if roofline is not None:
+      out['roofline'] = roofline
     if dist:
       out['config']['exchange'] = {
           'backend': dist.get_backend(), 'world': world,
@@ -1461,7 +1496,7 @@ def main():
       out['config']['ada_mode'] = ada
     if graphcfg is not None:
       out['config']['graph_config_mode'] = graphcfg
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
       # the reference's CPU path on the host cores, at most 32 intra-op threads: the batched GEMMs
       # of a 32-node tile stop scaling long before that, and a 256-thread pool on them does not
       # finish in minutes (measured: the r03 run with every core of the 256-core box timed out)

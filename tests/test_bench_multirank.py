@@ -27,7 +27,7 @@ def test_bench_two_ranks_one_json_line():
     s.close()
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
            '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.join(ROOT, 'bench.py'),
-           '--gpus', '2', '--steps', '6', '--warmup', '2']
+           '--gpus', '2', '--steps', '6', '--warmup', '2', '--full']
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     if out.returncode == 0 or 'ddress already in use' not in out.stderr:
       break
@@ -59,7 +59,7 @@ def test_bench_plain_command_spawns_its_ranks_and_checks_every_shard():
          if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT')}
   env['LNZ_BENCH_ONE_DEVICE'] = '1'
   out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '6',
-                        '--warmup', '2', '--shard-parity', '48'],
+                        '--warmup', '2', '--shard-parity', '48', '--full'],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
   assert out.returncode == 0, out.stderr[-2000:]
   lines = _json_lines(out.stdout)

@@ -104,28 +104,44 @@ def test_graphdata_mirror_collates_to_the_reference_tensors(tmp_path):
     np.testing.assert_allclose(d3['L'].numpy()[0, :, :, 0], sgn * ds[0][key].astype(np.float32))
 
 
-@pytest.mark.skipif(not H.have_reference(), reason='needs the reference tree (build container)')
-def test_graphdata_mirror_equals_reference_collate_bitwise(tmp_path):
-  """Both collates on the SAME pickles (written in the reference's format): every tensor equal."""
-  from lanczosnet_amd.dataset.graph_data import GraphData
+def collate_config(path):
   from lanczosnet_amd.utils.arg_helper import AttrDict
-  H.import_reference_runner()
-  import dataset.graph_data as ref_gd
+  return AttrDict(dict(seed=1234, dataset=dict(data_path=path, num_edge_type=1),
+                       model=dict(name='LanczosNetGeneral', num_eig_vec=K)))
+
+
+def write_collate_pickles(path):
+  """The pickles both collates read: the first six train graphs (tests/golden/graph_collate.npz)."""
   items, _, _, _ = load_split('train')
-  _write_pickles(str(tmp_path), items[:6], 'train')
-  cfg = AttrDict(dict(seed=1234, dataset=dict(data_path=str(tmp_path), num_edge_type=1),
-                      model=dict(name='LanczosNetGeneral', num_eig_vec=K)))
+  _write_pickles(path, items[:6], 'train')
+
+
+def test_graphdata_mirror_equals_reference_collate_bitwise(tmp_path, golden):
+  """Both collates on the SAME pickles (written in the reference's format): every tensor equal —
+  against the reference's collate recorded in tests/golden/graph_collate.npz
+  (tests/golden/make_golden_graph_collate.py), and against the live one where the reference tree
+  is present."""
+  from lanczosnet_amd.dataset.graph_data import GraphData
+  write_collate_pickles(str(tmp_path))
+  cfg = collate_config(str(tmp_path))
   mine = GraphData(cfg, split='train')
-  theirs = ref_gd.GraphData(cfg, split='train')
-  theirs.train_data_files.sort()
-  batch = [mine[i] for i in range(len(mine))]
-  with H.numpy_expand_dims_compat():
-    want = theirs.collate_fn([theirs[i] for i in range(len(theirs))])
-  got = mine.collate_fn(batch)
-  assert set(got.keys()) == set(want.keys())
-  for k in want:
-    assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, k
-    assert torch.equal(got[k], want[k]), k
+  got = mine.collate_fn([mine[i] for i in range(len(mine))])
+  g = golden('graph_collate.npz')
+  assert set(got.keys()) == set(g.files)
+  for k in g.files:
+    assert got[k].numpy().dtype == g[k].dtype and tuple(got[k].shape) == g[k].shape, k
+    np.testing.assert_array_equal(got[k].numpy(), g[k], err_msg=k)
+  if H.have_reference():
+    H.import_reference_runner()
+    import dataset.graph_data as ref_gd
+    theirs = ref_gd.GraphData(cfg, split='train')
+    theirs.train_data_files.sort()
+    with H.numpy_expand_dims_compat():
+      want = theirs.collate_fn([theirs[i] for i in range(len(theirs))])
+    assert set(got.keys()) == set(want.keys())
+    for k in want:
+      assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, k
+      assert torch.equal(got[k], want[k]), k
 
 
 def test_workgroup_kernel_algorithm_meets_tolerances_at_graph_sizes():

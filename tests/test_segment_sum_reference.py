@@ -1,13 +1,16 @@
 """R12 pinned on the REAL reference: `oracle/_ref/segment_reduction_ref*.so` is the reference's CPU
 operator compiled from its own unmodified source (`operators/src/segment_reduction.cpp`, built by
-`oracle/ref_build.py` in the build container; the binary travels to the GPU box).
+`oracle/ref_build.py` where the reference tree is present), and `tests/golden/segment_sum_ref.npz`
+holds its outputs on the seeded inputs of the CPU test (`tests/golden/make_golden_segment_sum.py`).
 
-* CPU: the oracle's restatement of the CPU semantics equals the built reference bit for bit —
-  including its quirk of indexing `segment_ids` with the row index only (batch-0 ids for every
-  batch, `segment_reduction.cpp:20,47`).
+* CPU: the oracle's restatement of the CPU semantics equals the reference bit for bit — including
+  its quirk of indexing `segment_ids` with the row index only (batch-0 ids for every batch,
+  `segment_reduction.cpp:20,47`): against the fixture, and against the built operator when it is
+  there (which must also reproduce the fixture).
 * GPU: the HIP operator equals the built reference wherever the reference's CPU and GPU semantics
   coincide (all batch entries share their ids and num_segments == dim1 — the only in-bounds use of
-  both): forward scatter-add and backward gather.
+  both): forward scatter-add and backward gather.  Without the built operator the
+  comparison is with the oracle's restatement, which the CPU test pins to the reference bit for bit.
 """
 import numpy as np
 import pytest
@@ -17,11 +20,26 @@ import oracle
 from oracle import ref_build
 
 REF_OP = ref_build.load()
-needs_ref = pytest.mark.skipif(REF_OP is None, reason='oracle/_ref not built (no reference tree)')
+
+
+def _cpu_cases():
+  """(data, ids, shared ids, grad out) of the CPU test, drawn in a fixed order (the fixture's inputs)."""
+  rs = np.random.RandomState(0)
+  for (B, D1, D2) in ((1, 5, 3), (3, 7, 5), (4, 33, 64), (2, 100, 17)):
+    data = rs.randn(B, D1, D2).astype(np.float32)
+    ids = rs.randint(0, D1, size=(B, D1)).astype(np.int64)   # rows > 0 are ignored by the reference
+    shared = np.repeat(ids[:1], B, axis=0)
+    gout = rs.randn(B, D1, D2).astype(np.float32)
+    yield data, ids, shared, gout
 
 
 def _ref_forward(data, ids):
+  """The built reference operator's forward; without it, the restatement the CPU test pins to it
+  (equal wherever the ids are shared and num_segments == dim1, the only use these tests make)."""
   B, D1, D2 = data.shape
+  if REF_OP is None:
+    assert (ids == ids[:1]).all()
+    return oracle.unsorted_segment_sum_forward_gpu_semantics(data, ids, D1)
   out = torch.zeros((B, D1, D2), dtype=torch.float32)
   assert REF_OP.unsorted_segment_sum_forward(torch.from_numpy(data), torch.from_numpy(ids),
                                               [B, D1, D2], out) == 1
@@ -30,32 +48,33 @@ def _ref_forward(data, ids):
 
 def _ref_backward(gout, ids):
   B, D1, D2 = gout.shape
+  if REF_OP is None:
+    assert (ids == ids[:1]).all()
+    return oracle.unsorted_segment_sum_backward_gpu_semantics(gout, ids, D1)
   gd = torch.zeros((B, D1, D2), dtype=torch.float32)
   assert REF_OP.unsorted_segment_sum_backward(torch.from_numpy(gout), torch.from_numpy(ids),
                                                [B, D1, D2], gd) == 1
   return gd.numpy()
 
 
-@needs_ref
-def test_oracle_cpu_semantics_equal_the_built_reference():
-  rs = np.random.RandomState(0)
-  for (B, D1, D2) in ((1, 5, 3), (3, 7, 5), (4, 33, 64), (2, 100, 17)):
-    data = rs.randn(B, D1, D2).astype(np.float32)
-    ids = rs.randint(0, D1, size=(B, D1)).astype(np.int64)   # rows > 0 are ignored by the reference
-    ref = _ref_forward(data, ids)
+def test_oracle_cpu_semantics_equal_the_built_reference(golden):
+  g = golden('segment_sum_ref.npz')
+  for i, (data, ids, shared, gout) in enumerate(_cpu_cases()):
+    B, D1, D2 = data.shape
+    ref, ref_shared, ref_bwd = g['fwd_%d' % i], g['fwd_shared_%d' % i], g['bwd_shared_%d' % i]
+    if REF_OP is not None:   # the built operator reproduces the recorded one
+      np.testing.assert_array_equal(_ref_forward(data, ids), ref)
+      np.testing.assert_array_equal(_ref_forward(data, shared), ref_shared)
+      np.testing.assert_array_equal(_ref_backward(gout, shared), ref_bwd)
     np.testing.assert_array_equal(
         ref, oracle.unsorted_segment_sum_forward_cpu_semantics(data, ids[0], D1))
     # shared ids: CPU semantics == GPU semantics (the restatement the HIP kernel is tested against)
-    shared = np.repeat(ids[:1], B, axis=0)
     np.testing.assert_array_equal(
-        _ref_forward(data, shared), oracle.unsorted_segment_sum_forward_gpu_semantics(data, shared, D1))
-    gout = rs.randn(B, D1, D2).astype(np.float32)
+        ref_shared, oracle.unsorted_segment_sum_forward_gpu_semantics(data, shared, D1))
     np.testing.assert_array_equal(
-        _ref_backward(gout, shared),
-        oracle.unsorted_segment_sum_backward_gpu_semantics(gout, shared, D1))
+        ref_bwd, oracle.unsorted_segment_sum_backward_gpu_semantics(gout, shared, D1))
 
 
-@needs_ref
 @pytest.mark.gpu
 def test_hip_segment_sum_equals_the_built_reference():
   from lanczosnet_amd import ops
@@ -89,7 +108,6 @@ def test_operator_classes_have_the_reference_surface_and_refuse_cpu_tensors():
     UnsortedSegmentSumFunction.apply(torch.zeros(2, 7), torch.zeros(2, 7, dtype=torch.int64), 7)
 
 
-@needs_ref
 @pytest.mark.gpu
 def test_operator_function_and_module_autograd_against_the_built_reference():
   """`UnsortedSegmentSumFunction.apply(data, segment_index, num_segments)` (the form

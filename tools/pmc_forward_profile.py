@@ -6,7 +6,7 @@
 Three separate counters-only rocprofv3 runs (--pmc X --kernel-trace, nothing else — MI355X_MICROARCH.md
 "rocprofv3 PMC slots": FETCH_SIZE and WRITE_SIZE do not fit one pass) of
 
-    python bench.py --steps 7 --warmup 2 --no-cpu-baseline --no-secondary
+    python bench.py --steps 7 --warmup 2 --full --no-cpu-baseline --no-secondary
 
 for SQ_INSTS_VALU_MFMA_MOPS_F32, FETCH_SIZE and WRITE_SIZE, plus the tile plan of the timed batch
 (LNZ_BENCH_DUMP_PLAN).  Writes OUTDIR/forward_pmc.json: per-launch averages of the fused forward
@@ -35,7 +35,7 @@ def run_pass(counter, outdir, extra):
   if counter == 'SQ_INSTS_VALU_MFMA_MOPS_F32':
     env['LNZ_BENCH_DUMP_PLAN'] = os.path.join(outdir, 'forward_tile_plan.npz')
   cmd = ['rocprofv3', '--pmc', counter, '--kernel-trace', '--output-format', 'csv', '-d', d, '--',
-         sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '7', '--warmup', '2',
+         sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '7', '--warmup', '2', '--full',
          '--no-cpu-baseline', '--no-secondary'] + extra
   with open(os.path.join(outdir, 'pmc_%s.log' % counter), 'w') as log:
     subprocess.run(cmd, check=True, cwd='/tmp', env=env, stdout=log, stderr=subprocess.STDOUT)
@@ -67,7 +67,7 @@ def main():
   mops = res['SQ_INSTS_VALU_MFMA_MOPS_F32'][fwd]
   fetch, write = res['FETCH_SIZE'][fwd], res['WRITE_SIZE'][fwd]
   out = {
-      'command': 'bench.py --steps 7 --warmup 2 --no-cpu-baseline --no-secondary ' + ' '.join(extra),
+      'command': 'bench.py --steps 7 --warmup 2 --full --no-cpu-baseline --no-secondary ' + ' '.join(extra),
       'kernel': fwd,
       'SQ_INSTS_VALU_MFMA_MOPS_F32_per_launch': mops['per_launch'],
       'mfma_flops_per_launch': mops['per_launch'] * 512.0,

@@ -1,7 +1,7 @@
 #!/bin/bash
 # The profiles of a round in one GPU call (run through gpurun; writes gpurun_out/prof_<tag>/):
 #   tools/profile_round.sh r04
-# 1. rocprofv3 --kernel-trace --stats of the DEFAULT bench command (bench line + kernel stats)
+# 1. rocprofv3 --kernel-trace --stats of the full bench command (bench.py --full: bench line + kernel stats)
 # 2. the same of the LanczosNet training step (eager, fused Adam)
 # 3. counters-only passes (--pmc with --kernel-trace, nothing else): matrix-pipe busy + clock of
 #    lnz_f32_linear and the library GEMM on the filter-MLP shapes; FETCH_SIZE / WRITE_SIZE of the
@@ -26,7 +26,7 @@ pmc() {  # name, counters (quoted), command...
   timeout 900 rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d /tmp/rp_$name -- "$@" > $OUT/${name}_run.log 2>&1
   python $ROOT/tools/pmc_summary.py $(dirname $(find /tmp/rp_$name -name '*counter_collection.csv' | head -1)) > $OUT/${name}_pmc.txt 2>&1
 }
-stats bench python $ROOT/bench.py
+stats bench python $ROOT/bench.py --full
 grep '^{' $OUT/bench_run.log | tail -1 > $OUT/bench.json
 stats train python $ROOT/tools/train_step_profile.py eager_fused 20
 stats config5 python $ROOT/tools/bench_config5.py --reps 2

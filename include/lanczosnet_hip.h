@@ -28,7 +28,7 @@ extern "C" {
  *    (lnz_large_sparse_image, lnz_large_pack_vectors, lnz_large_gemm1_rows, lnz_large_sparse_conv[_f32];
  *    lnz_large_conv accepts C = 0), lnz_head_backward, lnz_node_extents, the out-of-place split-pack
  *    entries (lnz_split_laplacian_pack_to, lnz_spectral_gains_rows_split_to), lnz_last_kernel,
- *    lnz_stream_create_cu_masked;
+ *    lnz_stream_create_cu_masked; the full eigendecomposition (lnz_sym_eigh_topk, _workspace_bytes);
  * 6: lnz_forward_args lost Wp16 / w16_off / Wp16_head / Lp16 (gemm_mode 1 is now the split precision
  *    inside the strip kernel: lnz_pack_rows_k8_split; lnz_pack_rows_f16x2 and
  *    lnz_pack_laplacian_f16x2 are gone) and gained dbias_part_cap; + lnz_midgraph_forward,
@@ -313,6 +313,27 @@ int lnz_lanczos_ritz_kstep(const float* A, int64_t stride_b, int64_t stride_r, i
                            const int32_t* n_nodes, int B, int N, int M, int K, int flags,
                            int row_cap, void* workspace, int64_t workspace_bytes, float* D, float* V,
                            int32_t* info, int32_t* dense_fallback, lnz_stream_t stream);
+
+/* The FULL decomposition of get_graph_laplacian_eigs(..., use_eigen_decomp=True)
+ * (utils/data_helper.py:197-223: `np.linalg.eigh` of each graph's n_b x n_b block, then the top-K
+ * |lambda| cut) for graphs of up to 2048 nodes, ragged batches included (csrc/sym_eigh.hip).
+ * A [B][N][N] float32 with arbitrary strides (stride_c = 2: channel 0 of the collated channels-last
+ * [N][N][2] Laplacian, read in place); only the LOWER triangle of the n_b x n_b block is read
+ * (numpy's UPLO='L'), the strict upper triangle and rows / columns >= n_b never.  n_nodes [B]
+ * (optional; NULL = N for every graph).  fp64 Householder tridiagonalisation (blocked, latrd
+ * panels), Sturm bisection + inverse iteration on the tridiagonal, blocked back-transformation.
+ * Outputs like every Ritz-pair entry: D [B][K], V [B][N][K] in stable descending-|lambda| order
+ * over ascending lambda (a negative eigenvalue first on an exact tie), the first entry of largest
+ * magnitude of each column positive, D[b][k] = 0 and V[b][:][k] = 0 for k >= n_b, V[b][n_b:][:] = 0.
+ * info [B] (optional): 0 = converged; 1 = the input block was not finite (D, V zero); 2 = an
+ * inverse iteration did not converge.  Deterministic, and a graph's result does not depend on the
+ * rest of the batch.  Limits: N <= 2048, K <= 256 (LNZ_ENOTSUP beyond); K >= 1 and B <= 65535 per
+ * call (LNZ_EINVAL otherwise).  The workspace (256-B aligned) grows linearly in B: a caller with a
+ * large batch calls once per chunk. */
+int64_t lnz_sym_eigh_topk_workspace_bytes(int B, int N, int K);
+int lnz_sym_eigh_topk(const float* A, int64_t stride_b, int64_t stride_r, int64_t stride_c,
+                      const int32_t* n_nodes, int B, int N, int K, void* workspace,
+                      int64_t workspace_bytes, float* D, float* V, int32_t* info, lnz_stream_t stream);
 
 /* The same call leaving the image of lnz_large_sparse_image behind (csrc/conv_sparse.hip): the
  * compaction pass has every entry of the row in hand (and, with stride_c = 2, the second channel of

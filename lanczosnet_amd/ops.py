@@ -4,6 +4,7 @@ HIP library).  Every function requires CUDA(HIP) tensors and raises otherwise â€
 Reference interfaces replaced (paths relative to the reference repo):
   laplacian_l4        utils/data_helper.py:92-116,155-156 ; dataset/get_qm8_data.py:62-75
   lanczos_ritz        utils/data_helper.py:197-223 (eigh + |lambda| sort) ; dataset/qm8.py:264-291
+  sym_eigh_topk       utils/data_helper.py:197-223 (the full decomposition, any N <= 2048)
   spectral_gains      model/lanczos_net.py:110-113,118-121,146-149
   lanczosnet_forward  model/lanczos_net.py:114-117,154-194
   unsorted_segment_sum operators/functions/unsorted_segment_sum.py:8-44
@@ -183,6 +184,55 @@ def lanczos_ritz(A, n_nodes, K, return_info=False, kernel='auto'):
 
 
 RITZ_FULL_MAX_N = 192     # lnz_lanczos_ritz: one wavefront (N <= 32) / one workgroup per graph
+SYM_EIGH_MAX_N = 2048    # lnz_sym_eigh_topk: the full decomposition, any graph up to this size
+SYM_EIGH_MAX_K = 256
+SYM_EIGH_MAX_B = 65535   # graphs per call (the launches' grid y): larger batches are chunked
+SYM_EIGH_WORKSPACE_CAP = 4 << 30   # default bound on one chunk's workspace (bytes)
+
+
+def sym_eigh_topk(A, n_nodes, K, workspace=None, return_info=False):
+  """lnz_sym_eigh_topk: the top-K |lambda| pairs of the FULL eigendecomposition of each graph's
+  n_b x n_b block â€” what get_graph_laplacian_eigs(..., use_eigen_decomp=True) computes with
+  `np.linalg.eigh` (utils/data_helper.py:197-223) â€” for any N <= 2048, on hand-written fp64 kernels
+  (blocked Householder tridiagonalisation, bisection + inverse iteration, blocked back-transformation).
+  A [B,N,N] float32, any strides (`L[..., 0]` of the collated channels-last Laplacian is read in
+  place); only the lower triangle of each block is read.  n_nodes [B] or None (every graph N nodes).
+  The batch is computed chunk by chunk so that one chunk's workspace stays within `workspace` (a
+  uint8 CUDA tensor) or, without one, SYM_EIGH_WORKSPACE_CAP bytes, and holds at most SYM_EIGH_MAX_B
+  graphs; a graph's result does not depend on the chunking.  Returns D [B,K], V [B,N,K] float32 (+ info [B] int32: 0 ok, 1 input not finite,
+  2 inverse iteration not converged)."""
+  _need_cuda(A, n_nodes, workspace)
+  assert A.dim() == 3 and A.shape[1] == A.shape[2] and A.dtype == torch.float32
+  B, N, _ = A.shape
+  # the C entry's codes: K < 1 is a bad argument, N or K beyond the served range is not supported
+  if K < 1:
+    raise _lib.LnzError(_lib.LNZ_EINVAL, 'sym_eigh_topk: K=%d: at least one eigenpair' % K)
+  if N > SYM_EIGH_MAX_N or K > SYM_EIGH_MAX_K:
+    raise _lib.NotSupported(_lib.LNZ_ENOTSUP, 'sym_eigh_topk: N=%d <= %d and K=%d <= %d required'
+                            % (N, SYM_EIGH_MAX_N, K, SYM_EIGH_MAX_K))
+  if n_nodes is not None:
+    n_nodes = n_nodes.to(device=A.device, dtype=torch.int32).contiguous()
+  D = torch.zeros((B, K), dtype=torch.float32, device=A.device)
+  V = torch.zeros((B, N, K), dtype=torch.float32, device=A.device)
+  info = torch.zeros((B,), dtype=torch.int32, device=A.device)
+  if B == 0 or N == 0:
+    return (D, V, info) if return_info else (D, V)
+  per = _abi().sym_eigh_topk_workspace_bytes(1, N, K)
+  cap = workspace.numel() * workspace.element_size() if workspace is not None else SYM_EIGH_WORKSPACE_CAP
+  chunk = max(1, min(B, cap // per, SYM_EIGH_MAX_B))
+  need = chunk * per
+  if workspace is None:
+    workspace = torch.empty((need,), dtype=torch.uint8, device=A.device)
+  elif workspace.numel() * workspace.element_size() < need or workspace.data_ptr() % 256:
+    raise _lib.LnzError(_lib.LNZ_EINVAL, 'sym_eigh_topk: the workspace must hold %d bytes (one graph), '
+                        '256-byte aligned' % per)
+  sb, sr, sc = A.stride()
+  with torch.cuda.device(A.device):
+    for c0 in range(0, B, chunk):
+      c1 = min(B, c0 + chunk)
+      _abi().sym_eigh_topk(A[c0:c1], sb, sr, sc, n_nodes[c0:c1] if n_nodes is not None else None,
+                           c1 - c0, N, K, workspace, (c1 - c0) * per, D[c0:c1], V[c0:c1], info[c0:c1])
+  return (D, V, info) if return_info else (D, V)
 
 
 
@@ -508,14 +558,20 @@ def attached_sparse_image(L):
   return img
 
 
-def lanczos_ritz_collated(L, n_nodes, K):
+def lanczos_ritz_collated(L, n_nodes, K, method='auto'):
   """The Ritz pairs of the collate: lanczos_ritz(L[:, :, :, 0], n_nodes, K) on the collated
   L [B,N,N,C] (dataset/graph_data.py:262-287).  Beyond RITZ_FULL_MAX_N nodes the K-step entry reads
   channel 0 in place, and where the layout allows (the channels-last pair of a single-edge-type
   collate, or one operator in contiguous rows) the SAME pass over L leaves the large-graph conv's
-  image riding on L (attach_sparse_image): L is then read from HBM once per batch."""
+  image riding on L (attach_sparse_image): L is then read from HBM once per batch.
+  method='full': the pairs of the full decomposition at every N (sym_eigh_topk, channel 0 read in
+  place); no sparse image is left on L."""
+  if method not in ('auto', 'full'):
+    raise ValueError("lanczos_ritz_collated: method is 'auto' or 'full', got %r" % (method,))
   B, N, _, Cn = L.shape
   A = L[:, :, :, 0]
+  if method == 'full':
+    return sym_eigh_topk(A, n_nodes, K)
   pair = Cn == 2 and L.stride(3) == 1 and L.stride(2) == 2
   single = L.stride(2) == 1 and (Cn == 1 or L.stride(3) == 0)
   if N <= RITZ_FULL_MAX_N or L.dtype != torch.float32 or not (pair or single) or N > 2048:

@@ -4,7 +4,8 @@
   get_laplacian_l4_batched        :92-116,155-156  -> HIP `lnz_laplacian_l4`
   get_graph_laplacian_eigs_batched :169-258 (use_eigen_decomp=True, is_sym=True branch) +
                                   the pad/cut of dataset/qm8.py:264-291 -> HIP `lnz_lanczos_ritz`;
-                                  the use_eigen_decomp=False branch (:205-208) -> `lnz_lanczos_ritz_kstep`
+                                  the use_eigen_decomp=False branch (:205-208) -> `lnz_lanczos_ritz_kstep`;
+                                  method='full': the full decomposition at any N -> `lnz_sym_eigh_topk`
 """
 
 
@@ -21,7 +22,7 @@ def get_laplacian_l4_batched(adjs, n_nodes):
     return ops.laplacian_l4(adjs, n_nodes)
 
 
-def get_graph_laplacian_eigs_batched(L_simple, n_nodes, k, use_eigen_decomp=None):
+def get_graph_laplacian_eigs_batched(L_simple, n_nodes, k, use_eigen_decomp=None, method='auto'):
     """L_simple [B,N,N] (e.g. `L[..., 0]`), n_nodes [B] -> (D [B,k], V [B,N,k]) ordered by
     descending |eigenvalue| like `np.argsort(-|eigs|, kind='mergesort')` (:218-223).
 
@@ -32,8 +33,17 @@ def get_graph_laplacian_eigs_batched(L_simple, n_nodes, k, use_eigen_decomp=None
              (the reference itself calls this branch "computationally heavy for large size adj");
       False  the k-dimensional Krylov method (`eigsh(L, k, which='LM')`, :208) — the k-step
              Lanczos of `lnz_lanczos_ritz_kstep`, any N <= 2048, ragged batches;
-      None   (default) True up to 192 nodes, False beyond, with a UserWarning naming the branch."""
+      None   (default) True up to 192 nodes, False beyond, with a UserWarning naming the branch.
+    method: 'auto' (the routing above) or 'full': the full decomposition at every N <= 2048 on the
+      hand-written eigensolver (`lnz_sym_eigh_topk`), no warning; not with use_eigen_decomp=False."""
     from .. import ops
+    if method not in ('auto', 'full'):
+        raise ValueError("get_graph_laplacian_eigs_batched: method is 'auto' or 'full', got %r" % (method,))
+    if method == 'full':
+        if use_eigen_decomp is not None and not use_eigen_decomp:
+            raise ValueError("get_graph_laplacian_eigs_batched: method='full' is the full decomposition; "
+                             "use_eigen_decomp=False asks for the k-step Krylov branch")
+        return ops.sym_eigh_topk(L_simple, n_nodes, k)
     N = L_simple.shape[1]
     if use_eigen_decomp is None:
         return ops.lanczos_ritz(L_simple, n_nodes, k)

@@ -107,10 +107,11 @@ extern "C" int lnz_pack_spectral_mlp(const float* W0, const float* b0, const flo
                                      const float* b2, const float* W4, const float* b4,
                                      const float* W6, const float* b6, int S, float* pack,
                                      lnz_stream_t stream) {
-  LNZ_REQUIRE(W0 && b0 && W2 && b2 && W4 && b4 && W6 && b6 && pack, LNZ_EINVAL,
-              "lnz_pack_spectral_mlp: null pointer");
+  // (before the pointers: the S-wide tensors of S = 0 have no address)
   LNZ_REQUIRE(S >= 1 && S <= SMAX, LNZ_ENOTSUP, "lnz_pack_spectral_mlp: S=%d not in 1..%d", S,
               SMAX);
+  LNZ_REQUIRE(W0 && b0 && W2 && b2 && W4 && b4 && W6 && b6 && pack, LNZ_EINVAL,
+              "lnz_pack_spectral_mlp: null pointer");
   hipLaunchKernelGGL(pack_w0_kernel, dim3((HT * 8 * 64 + 255) / 256), dim3(256), 0,
                      (hipStream_t)stream, W0, S, pack + OFF_W0);
   int rc = lnz::check_launch("lnz_pack_spectral_mlp(W0)");
@@ -175,10 +176,10 @@ __global__ void pack_spectral_mlp_layers_kernel(MlpLayerPtrs ptrs, int S, float*
 
 extern "C" int lnz_pack_spectral_mlp_layers(const float* const* ptrs, int num_layer, int S,
                                             float* pack, lnz_stream_t stream) {
-  LNZ_REQUIRE(ptrs && pack && num_layer >= 1 && num_layer <= 16, LNZ_EINVAL,
-              "lnz_pack_spectral_mlp_layers: bad arguments (L=%d)", num_layer);
   LNZ_REQUIRE(S >= 1 && S <= SMAX, LNZ_ENOTSUP, "lnz_pack_spectral_mlp_layers: S=%d not in 1..%d",
               S, SMAX);
+  LNZ_REQUIRE(ptrs && pack && num_layer >= 1 && num_layer <= 16, LNZ_EINVAL,
+              "lnz_pack_spectral_mlp_layers: bad arguments (L=%d)", num_layer);
   MlpLayerPtrs mp;
   for (int l = 0; l < 16; ++l)
     for (int i = 0; i < 8; ++i) {
@@ -201,9 +202,10 @@ extern "C" int lnz_spectral_gains_rows_split_to(const float* D, int B, int K, co
   LNZ_REQUIRE(!Lp_split || (kind == 0 && lp_floats > 0 && lp_floats % 4 == 0), LNZ_EINVAL,
               "lnz_spectral_gains_rows_split: the pack rides along with the MLP launch only (kind 0), "
               "lp_floats a positive multiple of 4");
+  // (before the pointers: an empty exponent list has no address)
+  LNZ_REQUIRE(S >= 1 && S <= SMAX, LNZ_ENOTSUP, "lnz_spectral_gains: S=%d not in 1..%d", S, SMAX);
   LNZ_REQUIRE(D && dist_host && G && B > 0 && K > 0 && num_layer > 0, LNZ_EINVAL,
               "lnz_spectral_gains: bad arguments (B=%d K=%d L=%d)", B, K, num_layer);
-  LNZ_REQUIRE(S >= 1 && S <= SMAX, LNZ_ENOTSUP, "lnz_spectral_gains: S=%d not in 1..%d", S, SMAX);
   DistArr dist;
   for (int i = 0; i < SMAX; ++i) dist.v[i] = i < S ? dist_host[i] : 0;
   hipStream_t s = (hipStream_t)stream;

@@ -288,7 +288,7 @@ Tensor spectral_gains(const Tensor& D, at::IntArrayRef dist, int64_t num_layer,
     TORCH_CHECK(mlp_pack.has_value() && split_pack->numel() % 4 == 0,
                 "lanczosnet::spectral_gains: split_pack rides along with the MLP launch only");
   }
-  TORCH_CHECK(D.dim() == 2 && !dist.empty());
+  TORCH_CHECK(D.dim() == 2);   // (the library refuses an empty or over-long exponent list itself)
   if (mlp_pack.has_value()) need(*mlp_pack, at::kFloat, "mlp_pack");
   const bool use_rows = rows.has_value() && n_rows.has_value() && mlp_pack.has_value();
   if (use_rows) {

@@ -212,6 +212,14 @@ class _LanczosNetBase(nn.Module):
         return (len(hid) == 1 and next(iter(hid)) in (64, 128) and self.input_dim <= 128
                 and self.output_dim <= 31)
 
+    def _fused_channels_ok(self):
+        """Scale and channel counts the fused forward kernels are built for (csrc/conv_forward.hip
+        launch_conv, csrc/conv_strip.hip strip_forward_eligible): at most 8 short and 12 long
+        diffusion scales, at most 32 message channels in all.  Beyond that the module takes the
+        library path, like a width outside the kernels."""
+        n_chan = self.num_scale_short + self.num_scale_long + self.num_edgetype + 1
+        return self.num_scale_short <= 8 and self.num_scale_long <= 12 and n_chan <= 32
+
     def _check_supported(self):
         if any(d == 'inf' for d in self.short_diffusion_dist + self.long_diffusion_dist):
             raise NotImplementedError("diffusion distance 'inf' is not built in the HIP path")
@@ -321,6 +329,22 @@ class _LanczosNetBase(nn.Module):
                 G, Lp = G   # (the gains and the pack's float16 form, written under the same launch)
         return ops.lanczosnet_forward(plan, node_feat, Lp, V, G, mask_u8, tiling=tiles)
 
+    # lnz_spectral_gains / lnz_pack_spectral_mlp_layers: csrc/gains_body.hpp SMAX
+    gains_kernel_max_scales = 16
+
+    @torch.no_grad()
+    def _torch_gains(self, D):
+        """G [L,B,S,K] by library calls (model/lanczos_net.py:110-113,118-121,146-149): the gains
+        of more long scales than the HIP gains kernel is built for."""
+        S = self.num_scale_long
+        B, K = D.shape
+        pows = torch.stack([torch.pow(D.float(), p) for p in self.long_diffusion_dist], dim=2)
+        if self._has_mlp():
+            G = torch.stack([seq(pows.view(-1, S)).view(B, K, S) for seq in self.spectral_filter])
+        else:
+            G = pows.unsqueeze(0).expand(self.num_layer, B, K, S)
+        return G.transpose(2, 3)
+
     @torch.no_grad()
     def _large_graph_forward(self, node_feat, L, D, V, mask, gemm_dtype=None):
         """Graphs beyond the 32-node MFMA tile (BASELINE config 5: N = 2048, K = 64).  The conv is
@@ -330,11 +354,11 @@ class _LanczosNetBase(nn.Module):
         bf16 operands / fp32 accumulate (config 5's "bf16 MFMA filter GEMM"); default fp32."""
         B, N = L.shape[0], L.shape[1]
         S = self.num_scale_long
-        plan_mlp = None
-        if self._has_mlp():
-            plan_mlp = self._plan_large()['mlp_pack']
         G = None
-        if S > 0:
+        if S > self.gains_kernel_max_scales:
+            G = self._torch_gains(D)                                  # [L,B,S,K]
+        elif S > 0:
+            plan_mlp = self._plan_large()['mlp_pack'] if self._has_mlp() else None
             G = ops.spectral_gains(D, self.long_diffusion_dist, self.num_layer, plan_mlp)  # [L,B,S,K]
         Lc = L.permute(0, 3, 1, 2)                                   # channel-major view
         if gemm_dtype is not None:
@@ -391,7 +415,7 @@ class _LanczosNetBase(nn.Module):
         cache = getattr(self, '_plan_large_cache', None)
         if cache is None or cache['sig'] != sig:
             buf = None
-            if self._has_mlp():
+            if self._has_mlp() and self.num_scale_long <= self.gains_kernel_max_scales:
                 buf = ops.pack_spectral_mlp_layers(
                     [[(seq[i].weight, seq[i].bias) for i in (0, 2, 4, 6)]
                      for seq in self.spectral_filter], self.num_scale_long)
@@ -484,10 +508,12 @@ class _LanczosNetBase(nn.Module):
 
     def _large_hip_supported(self, K, channels=1):
         """lnz_large_*: uniform hidden width 128, input width <= 128, no short-diffusion powers,
-        K <= 64, at most 8 operator channels (the pack kernel's channel map, csrc/conv_large.hip:
-        `LargeChanMap`; more edge types take the library path like any other unsupported shape)."""
+        K <= 64, <= 16 long scales, at most 8 operator channels (the pack kernel's channel map,
+        csrc/conv_large.hip: `LargeChanMap`; more edge types take the library path like any other
+        unsupported shape)."""
         return (set(self.hidden_dim[:self.num_layer]) == {128} and self.input_dim <= 128
-                and self.num_scale_short == 0 and K <= 64 and channels <= 8)
+                and self.num_scale_short == 0 and K <= 64 and channels <= 8
+                and self.num_scale_long <= self.gains_kernel_max_scales)
 
     # -- channel folding of the large-graph path ------------------------------------------------
     # With one edge type (config/graph_lanczos_net.yaml:14) the collated L carries the SAME operator
@@ -818,14 +844,19 @@ class _LanczosNetBase(nn.Module):
         if any(d == 'inf' for d in self.short_diffusion_dist + self.long_diffusion_dist):
             raise NotImplementedError("diffusion distance 'inf' is not built in the HIP path")
         drop = self.training and self.dropout > 0.0
-        if L.shape[1] > 32 or not self._fused_supported() or drop:
+        fused = self._fused_supported() and self._fused_channels_ok()
+        if L.shape[1] > 32 or not fused or drop:
             if L.shape[1] <= 32 and not getattr(self, '_warned_library_path', False):
                 warnings.warn('lanczosnet_amd: %s is outside the fused MFMA kernel (uniform width 64 '
-                              'or 128, no training dropout): using the device library-GEMM path '
+                              'or 128, <= 8 short and <= 12 long scales, <= 32 channels in all, no '
+                              'training dropout): using the device library-GEMM path '
                               '(hipBLASLt conv + HIP spectral gains; differentiable torch ops when '
                               'gradients or dropout are needed), which is slower'
                               % ('dropout=%r in training' % self.dropout if drop else
-                                 'hidden_dim=%r / input_dim=%r' % (self.hidden_dim, self.input_dim)))
+                                 'hidden_dim=%r / input_dim=%r' % (self.hidden_dim, self.input_dim)
+                                 if not self._fused_supported() else
+                                 '%d short + %d long scales + %d operator channels'
+                                 % (self.num_scale_short, self.num_scale_long, self.num_edgetype + 1)))
                 self._warned_library_path = True
             if self._needs_grad() or drop:
                 # the reference trains arbitrary widths / sizes: differentiate the device-side

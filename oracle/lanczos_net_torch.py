@@ -18,19 +18,26 @@ import numpy as np
 import torch
 
 
-def lanczos_net_forward_torch(P, cfg, node_feat, L, D, V, mask, general=False):
-  """Same signature / result as oracle.lanczos_net_forward (float32).  P: dict name -> numpy."""
-  T = {k: torch.from_numpy(np.ascontiguousarray(v)).float() for k, v in P.items()}
-  L = torch.as_tensor(np.asarray(L)).float()
-  D = torch.as_tensor(np.asarray(D)).float()
-  V = torch.as_tensor(np.asarray(V)).float()
+def lanczos_net_forward_torch(P, cfg, node_feat, L, D, V, mask, general=False, dtype=torch.float32,
+                              differentiable=False):
+  """Same signature / result as oracle.lanczos_net_forward (float32).  P: dict name -> numpy.
+  differentiable=True: P holds torch tensors (leaves that require grad), autograd records the
+  operator sequence and the torch score is returned: with dtype=torch.float64 the reference for
+  parameter gradients."""
+  if differentiable:
+    T = {k: v.to(dtype) for k, v in P.items()}
+  else:
+    T = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dtype) for k, v in P.items()}
+  L = torch.as_tensor(np.asarray(L)).to(dtype)
+  D = torch.as_tensor(np.asarray(D)).to(dtype)
+  V = torch.as_tensor(np.asarray(V)).to(dtype)
   B, N = L.shape[0], L.shape[1]
   long_d, short_d = list(cfg['long_diffusion_dist']), list(cfg['short_diffusion_dist'])
   S, E1 = len(long_d), cfg['num_bond_type'] + 1
   lin = lambda x, name: torch.nn.functional.linear(x, T[name + '.weight'], T[name + '.bias'])  # noqa: E731
-  with torch.no_grad():
+  with torch.set_grad_enabled(bool(differentiable)):
     if general:
-      state = torch.as_tensor(np.asarray(node_feat)).float()
+      state = torch.as_tensor(np.asarray(node_feat)).to(dtype)
     else:
       state = T['embedding.weight'][torch.as_tensor(np.asarray(node_feat)).long()]   # :154
     D_pow = [torch.pow(D, p) for p in long_d]                                            # :146-149
@@ -65,4 +72,4 @@ def lanczos_net_forward_torch(P, cfg, node_feat, L, D, V, mask, general=False):
     y = (att * y).view(B, N, -1)
     mk = torch.as_tensor(np.asarray(mask)).bool()
     score = torch.stack([y[b][mk[b]].mean(dim=0) for b in range(B)])                     # :190-194
-  return score.numpy()
+  return score if differentiable else score.numpy()

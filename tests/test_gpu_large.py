@@ -539,6 +539,36 @@ def test_large_graph_general_forward_matches_oracle():
   assert eb < 2e-2  # bf16 operands: 8-bit mantissa (config 5's mode, opt-in)
 
 
+def test_large_graph_forward_with_sixteen_long_scales_matches_oracle():
+  """N = 200 (beyond the 128-node midgraph kernel), sixteen long scales — the most the gains kernel
+  and lnz_large_spectral take — on the streamed kernels with three planes, per graph against the
+  fp64 oracle fed the same Ritz pairs."""
+  from conftest import rel_err_rows
+  from lanczosnet_amd import ops
+  from lanczosnet_amd.model import LanczosNetGeneral
+  from lanczosnet_amd.utils.arg_helper import make_model_config
+  B, N, K = 3, 200, 32
+  cfg, _, X, L, mask = general_inputs(B, N, K, 3, 5, 8.0 / N)
+  cfg = dict(cfg, long_diffusion_dist=[1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 15, 20, 25, 30, 40, 50])
+  P = oracle.make_lanczosnet_params(cfg, 19, general=True)
+  net = LanczosNetGeneral(make_model_config(cfg, general=True)).eval()
+  net.load_state_dict({k: torch.from_numpy(v) for k, v in P.items()})
+  net = net.to(DEV)
+  Ld = torch.from_numpy(L).to(DEV)
+  Xd, md = torch.from_numpy(X).to(DEV), torch.from_numpy(mask).to(DEV)
+  D, V = ops.lanczos_ritz_large(Ld[:, :, :, 0].contiguous(), K, K)
+  assert not net._mid_hip_supported(N, K, L.shape[3]) and net._large_hip_supported(K, L.shape[3])
+  with torch.no_grad():
+    net.large_split_planes = 3
+    score = net(Xd, Ld, D, V, mask=md).cpu().numpy()
+    lib = net._large_graph_forward(Xd, Ld, D, V, md).cpu().numpy()
+  ref = oracle.lanczos_net_forward(P, cfg, X, L, D.cpu().numpy(), V.cpu().numpy(), mask,
+                                   dtype=np.float64, general=True)
+  e, el = rel_err_rows(score, ref), rel_err_rows(lib, ref)
+  print('large-graph forward, N=200 S=16: per-graph rel err, streamed kernels %.2e, library path %.2e' % (e, el))
+  assert e < 1e-5 and el < 1e-5
+
+
 def test_large_graph_forward_config5_shape_matches_library_path():
   """BASELINE config 5's shape (N = 2048, K = 64, 7 layers; B = 2 here): the streamed kernels in
   the split-precision mode against the fp32 library-GEMM path on the same Ritz pairs at 1e-5 (the

@@ -13,6 +13,8 @@ import torch
 import oracle
 from graph_fixture import GRAPH_CFG
 
+DIST16 = [1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 15, 20, 25, 30, 40, 50]
+
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
 
@@ -55,6 +57,8 @@ def _per_graph(got, ref):
     (70, 128, 90, 1, 32, [2, 5], 10),                        # full tile, K = 32, more workgroups than CUs
     (9, 64, 40, 1, 20, [], 16),                              # no long scales at all
     (12, 48, 34, 1, 12, [1, 3, 7], 128),                     # input width 128
+    (24, 96, 40, 1, 20, DIST16[:9], 10),                     # nine long scales: the gains' upper k-half
+    (10, 70, 34, 1, 32, DIST16, 10),                         # sixteen (gs [S <= 16][32]), K = 32
 ])
 def test_midgraph_forward_matches_the_oracle_and_the_streamed_kernels(B, N, nmin, edge_types, K, long_dist, din):
   from lanczosnet_amd import ops
@@ -77,6 +81,8 @@ def test_midgraph_forward_matches_the_oracle_and_the_streamed_kernels(B, N, nmin
   print('midgraph B=%d N=%d K=%d S=%d: per-graph rel err vs float64 oracle %.2e (streamed kernels %.2e)'
         % (B, N, K, len(long_dist), e_mid, e_large))
   assert e_mid < 1e-5
+  if len(long_dist) > 8:
+    assert e_large < 1e-5
 
 
 def test_midgraph_channel_folding_is_decided_per_graph():

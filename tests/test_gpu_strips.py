@@ -422,6 +422,26 @@ def test_laplacian_pack_conversion_alone_and_under_the_gains_launch():
   inplace = Lp.clone()
   ops._abi().split_laplacian_pack(inplace, inplace.numel())
   assert inplace.view(torch.float16).cpu().numpy().reshape(-1).tobytes() == want.tobytes()
+  # the ride above went under the one-tile gains kernel (49 row tiles x 7 layers < 2048); at the
+  # bench batch the launcher takes the two-tile kernel, whose riders start behind half as many
+  # MLP workgroups (SplitRide::main_x): the same bytes there, gains and fp32 pack untouched
+  b2 = draw_batch(1024, seed=5)
+  n2 = t(b2['n_nodes'])
+  L2 = ops.laplacian_l4(t(b2['adjs']), n2)
+  D2, _ = ops.lanczos_ritz(L2[..., 0], n2, 20)
+  assert (D2.numel() + 31) // 32 * cfg['num_layer'] >= 2048
+  Lp2 = ops.pack_laplacian(L2)
+  before2 = Lp2.clone()
+  alone2 = ops.split_laplacian_pack(Lp2)
+  G20 = ops.spectral_gains(D2, cfg['long_diffusion_dist'], cfg['num_layer'], plan32['mlp_pack'])
+  G21, ride2 = ops.spectral_gains(D2, cfg['long_diffusion_dist'], cfg['num_layer'], plan32['mlp_pack'],
+                                  split_pack=Lp2)
+  assert torch.equal(G20, G21) and torch.equal(Lp2, before2)
+  assert ride2.dtype == torch.float16 and torch.equal(ride2, alone2)
+  raw2 = Lp2.cpu().numpy().reshape(-1, 4)
+  hi2 = raw2.astype(np.float16)
+  lo2 = (raw2 - hi2.astype(np.float32)).astype(np.float16)
+  assert ride2.cpu().numpy().reshape(-1).tobytes() == np.concatenate([hi2, lo2], axis=1).tobytes()
 
 
 @pytest.mark.parametrize('B,nmin,nmax', [(1024, 8, 26), (37, 1, 32), (5, 3, 9)])

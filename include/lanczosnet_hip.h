@@ -671,7 +671,12 @@ int lnz_head_backward(const float* X_last, const uint8_t* mask, const float* gra
  *                            weight's column blocks in the reference's order — long scales, then
  *                            edge types (no short-diffusion channels) —, the layers behind each other
  *   bias   [num_layer,128];  Whead [dout + 1,128], bhead [dout + 1]: head rows, then the gate row
- *   Xwork  [lnz_midgraph_workspace_floats(B, N, num_layer)] fp32 scratch
+ *   Xwork  [lnz_midgraph_workspace_floats(B, N, num_layer)] fp32: the exchange buffer.  After the
+ *          launch it holds every layer's output state, [num_layer][B][NR][128] with NR = N rounded
+ *          up to 16: slot l = relu(out_l), the input of layer l + 1 (the last slot: what the head
+ *          read; all four workgroups publish their slice of it too).  Rows at or beyond N are zero;
+ *          rows between a graph's node count and N carry relu(bias_l), as in the reference.  These
+ *          are the stored activations lnz_midgraph_head_grad / _input_grad / _project read.
  *   sync   [B * (num_layer + 1)] int32, ZERO on entry (arrival counters, then placement words)
  *   score  [B,dout]
  * N <= 128, K <= 32, S <= 16, dout <= 31, hidden width 128. */
@@ -681,6 +686,52 @@ int lnz_midgraph_forward(const float* X0, const float* L, int64_t stride_b, int6
                          const uint8_t* mask, const float* W, const float* bias, const float* Whead,
                          const float* bhead, int B, int N, int K, int C, int S, int num_layer,
                          int din0, int dout, float* Xwork, int32_t* sync, float* score,
+                         lnz_stream_t stream);
+/* ---- Training for graphs of 33..128 nodes: loss.backward() (runner/graph_runner.py:216-219) through
+ * the head and the conv layers of lnz_midgraph_forward, three launches (csrc/conv_mid_grad.hip).
+ * Exact fp32, every sum in a fixed order, no float atomics: bitwise repeatable.  Shapes, strides and
+ * limits as for lnz_midgraph_forward; NR = N rounded up to 16; Xwork = that launch's buffer.
+ *
+ * 1. The readout head (model/lanczos_net_general.py:185-194, model/lanczos_net.py:185-194) on the
+ *    stored last state X_last = Xwork slot num_layer - 1 [B,NR,128]: grad_score [B,dout] ->
+ *    dOut_last [B,NR,128], the gradient at the last conv layer's pre-activation (zero on masked and
+ *    padded rows), and per-graph partials in workspace [lnz_midgraph_head_grad_workspace_floats(B,
+ *    dout)]: dWhead [B][dout + 1][128], then dbhead [B][dout + 1] (head rows, then the gate row); the
+ *    gradients are their sums over the graphs (any fixed order). */
+int64_t lnz_midgraph_head_grad_workspace_floats(int B, int dout);
+int lnz_midgraph_head_grad(const float* X_last, const uint8_t* mask, const float* grad_score,
+                           const float* Whead, const float* bhead, int B, int N, int dout,
+                           float* dOut_last, float* workspace, lnz_stream_t stream);
+/* 2. Node-state gradients of the whole conv stack (model/lanczos_net_general.py:157-182,
+ *    model/lanczos_net.py:157-182) in ONE launch: the forward kernel's structure and exchange run
+ *    on the gradient.  dOut [num_layer][B][NR][128] holds the last layer's slot on entry (launch 1)
+ *    and dOut_l = dX_{l+1} . [X_{l+1} > 0] for every layer on return; rows at or beyond a graph's
+ *    node count are exactly zero.  Wt: per layer [128 in][S + C][128 out], Wt[i][c][o] = W[o][c][i]
+ *    (layer 0: rows at or beyond its input width zero).  The operator channels are not assumed
+ *    symmetric.  sync [B * (num_layer + 1)] int32, ZERO on entry, this launch's own (never the
+ *    forward's).  dX0 [B,NR,din0] (optional): the gradient at the layer-0 state (the embedding
+ *    rows').  folded [B] int32 (optional): 1 where the graph's operator channels are equal. */
+int lnz_midgraph_input_grad(float* dOut, const float* Xwork, const float* L, int64_t stride_b,
+                            int64_t stride_r, int64_t stride_c, int64_t stride_ch, const float* V,
+                            const float* G, const float* Wt, int B, int N, int K, int C, int S,
+                            int num_layer, int din0, int32_t* sync, float* dX0, int32_t* folded,
+                            lnz_stream_t stream);
+/* 3. The operands of the weight gradients and the gain gradients, one workgroup per (graph, layer).
+ *    With X_l the layer's input state (X0 [B,N,din0] for layer 0, else Xwork slot l - 1), workspace
+ *    [lnz_midgraph_project_workspace_floats(...)] receives, behind each other:
+ *      A  [num_layer][B][K][128]      V^T dOut_l
+ *      Q  [num_layer][B][K][S][128]   g_s . (V^T X_l)        (columns at or beyond din0 zero in layer 0)
+ *      M  [num_layer][B][NR][C][128]  L_c X_l
+ *      dG [num_layer][B][K][S]        sum_o A[k][o] ((V^T X_l) W_s^T)[k][o]   (want_dgains != 0)
+ *      db [num_layer][B][128]         column sums of dOut_l
+ *    so that dW_l = [A_l^T Q_l | dOut_l^T M_l] (the contraction of the long scales runs over the B K
+ *    eigen rows, not the B N node rows), db_l = the sum of its partials over the graphs, and dG is
+ *    what lnz_spectral_mlp_grad takes.  W: the forward's weights. */
+int64_t lnz_midgraph_project_workspace_floats(int B, int N, int K, int C, int S, int num_layer);
+int lnz_midgraph_project(const float* dOut, const float* Xwork, const float* X0, const float* L,
+                         int64_t stride_b, int64_t stride_r, int64_t stride_c, int64_t stride_ch,
+                         const float* V, const float* G, const float* W, int B, int N, int K, int C,
+                         int S, int num_layer, int din0, int want_dgains, float* workspace,
                          lnz_stream_t stream);
 /* The whole batch preparation in ONE launch: lnz_plan_batch (workgroup 0), lnz_lanczos_ritz on
  * channel 0 of L (workgroups 1..B, dispatched first: they are the long, latency-bound pole) and

@@ -91,6 +91,13 @@ SIGNATURES = {
     'lnz_midgraph_workspace_floats': (C.c_int64, [_I, _I, _I]),
     'lnz_midgraph_forward': (C.c_int, [_P, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I,
                                        _I, _I, _I, _P, _P, _P, _P]),
+    'lnz_midgraph_head_grad_workspace_floats': (C.c_int64, [_I, _I]),
+    'lnz_midgraph_head_grad': (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    'lnz_midgraph_input_grad': (C.c_int, [_P, _P, _P, _L, _L, _L, _L, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I,
+                                          _P, _P, _P, _P]),
+    'lnz_midgraph_project_workspace_floats': (C.c_int64, [_I, _I, _I, _I, _I, _I]),
+    'lnz_midgraph_project': (C.c_int, [_P, _P, _P, _P, _L, _L, _L, _L, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I,
+                                       _I, _P, _P]),
     'lnz_packed_rows_k8_size': (C.c_int64, [_I, _I]),
     'lnz_pack_rows_k8': (C.c_int, [_P, _I, _I, _L, _P, _P]),
     'lnz_pack_rows_k8_split': (C.c_int, [_P, _I, _I, _L, _P, _P]),

@@ -14,7 +14,9 @@ LanczosNetGeneral at hidden width 128 the backward is HIP too (`_LanczosNetFused
 input-gradient, message and gain-gradient kernels in the forward's tile structure + library GEMMs
 for dW).  Architectures outside the fused kernels (other widths, N > 32, dropout
 > 0 in training, AdaLanczosNet's backward) differentiate a device-side torch restatement of the
-same math (`_torch_forward`) — still GPU only; there is no CPU path.
+same math (`_torch_forward`) — still GPU only; there is no CPU path.  Graphs of 33..128 nodes have
+a HIP backward of their own (`_MidGraphFusedFunction`, csrc/conv_mid_grad.hip),
+opt-in through `mid_backward_impl`.
 """
 import os
 import warnings
@@ -53,6 +55,10 @@ class _LanczosNetBase(nn.Module):
     # 'hip' = HIP backward kernels where built (LanczosNet, width 128); 'torch' = autograd through
     # the torch recomputation everywhere (the gradient oracle the HIP backward is tested against)
     backward_impl = os.environ.get('LANCZOSNET_BACKWARD', 'hip')
+    # graphs of 33..128 nodes in training: 'hip' = the backward of the one-launch kernel
+    # (_MidGraphFusedFunction, csrc/conv_mid_grad.hip), 'torch' (default) = autograd through
+    # `_torch_forward`.  Opt-in until its step time is recorded
+    mid_backward_impl = os.environ.get('LANCZOSNET_MID_BACKWARD', 'torch')
     _spectral_hidden = _SPECTRAL_HIDDEN
 
     def _spectral_io(self):
@@ -506,6 +512,29 @@ class _LanczosNetBase(nn.Module):
                                     mask.to(torch.uint8).contiguous(), mid['W'], mid['bias'], mid['Whead'],
                                     mid['bhead'], self.num_layer)
 
+    def _mid_backward_supported(self, N, K, channels):
+        """The HIP backward of lnz_midgraph_forward (lnz_midgraph_head_grad / _input_grad / _project):
+        the envelope of `_mid_hip_supported`, selected by `mid_backward_impl == 'hip'` where
+        `backward_impl` asks for HIP at all."""
+        return (self.mid_backward_impl == 'hip' and self.backward_impl == 'hip'
+                and self._mid_hip_supported(N, K, channels))
+
+    @torch.no_grad()
+    def _plan_mid_backward(self):
+        """`_plan_mid` + the transposed weight blocks of lnz_midgraph_input_grad: per layer
+        Wt[i][c][o] = W[o][c][i] as [128][S + E + 1][128] (layer 0: rows beyond its input width zero)."""
+        cache = self._plan_mid()
+        mid = cache['mid']
+        if 'Wt' not in mid:
+            nch = self.num_scale_long + self.num_edgetype + 1
+            Wts = []
+            for t in range(self.num_layer):
+                W = self._mix_weight(t).detach().float()
+                Wt = W.view(128, nch, -1).permute(2, 1, 0)
+                Wts.append(torch.nn.functional.pad(Wt, (0, 0, 0, 0, 0, 128 - Wt.shape[0])).reshape(-1))
+            mid['Wt'] = torch.cat(Wts).contiguous()
+        return cache
+
     def _large_hip_supported(self, K, channels=1):
         """lnz_large_*: uniform hidden width 128, input width <= 128, no short-diffusion powers,
         K <= 64, <= 16 long scales, at most 8 operator channels (the pack kernel's channel map,
@@ -844,6 +873,7 @@ class _LanczosNetBase(nn.Module):
         if any(d == 'inf' for d in self.short_diffusion_dist + self.long_diffusion_dist):
             raise NotImplementedError("diffusion distance 'inf' is not built in the HIP path")
         drop = self.training and self.dropout > 0.0
+        ops.forget_autograd_kernel()   # (last_kernel(): the previous step's backward is history)
         fused = self._fused_supported() and self._fused_channels_ok()
         if L.shape[1] > 32 or not fused or drop:
             if L.shape[1] <= 32 and not getattr(self, '_warned_library_path', False):
@@ -858,7 +888,13 @@ class _LanczosNetBase(nn.Module):
                                  '%d short + %d long scales + %d operator channels'
                                  % (self.num_scale_short, self.num_scale_long, self.num_edgetype + 1)))
                 self._warned_library_path = True
-            if self._needs_grad() or drop:
+            if (not drop and self._needs_grad()
+                    and self._mid_backward_supported(L.shape[1], V.shape[2], L.shape[3])
+                    and not torch.cuda.is_current_stream_capturing()):
+                # 33..128 nodes, opted in: the one-launch forward keeping its states + its HIP backward
+                score = _MidGraphFusedFunction.apply(self, node_feat, L, D, V, mask,
+                                                     *[p for p in self.parameters()])
+            elif self._needs_grad() or drop:
                 # the reference trains arbitrary widths / sizes: differentiate the device-side
                 # torch restatement (same association as the kernels)
                 score = self._torch_forward(node_feat, L, D, V, mask, dropout=drop)
@@ -930,6 +966,67 @@ def _tn_split_k(a, b, splits=4):
     if splits * Rs < R:  # the last R % splits rows
         out = out + a[splits * Rs:].t() @ b[splits * Rs:]
     return out
+
+
+def _spectral_mlp_param_grads(m, grads, D, dG, live_rows=None, n_live=None, static_rows=True, rtot=None):
+    """Gradients of the spectral-filter MLPs (model/lanczos_net.py:95-123) from dG [L, B*K, S] into
+    `grads` (by id(parameter)): lnz_spectral_mlp_grad in one launch (S <= 8), else autograd through
+    the batched MLP.  live_rows / n_live: the eigen rows the gains were evaluated on (None: all);
+    rtot: the host's copy of the node-row total that bounds their number (static_rows: not read)."""
+    B, K = D.shape
+    S, Lnum, dev = m.num_scale_long, m.num_layer, D.device
+    lin_idx = ([i for i, mod in enumerate(m.spectral_filter[0]) if isinstance(mod, nn.Linear)]
+               if S > 0 and m._has_mlp() else [])
+    if (S > 0 and m._has_mlp() and m.mlp_grad_impl == 'hip' and S <= 8 and len(lin_idx) == 4
+            and dG.is_contiguous()):
+        # one launch for every layer's MLP (csrc/spectral_gains_grad.hip): forward recomputation,
+        # the chain of ReLU masks and all eight parameter gradients on chip, live rows only
+        layers = [[(m.spectral_filter[t][i].weight, m.spectral_filter[t][i].bias) for i in lin_idx]
+                  for t in range(Lnum)]
+        rows_max = B * K
+        if live_rows is not None and not static_rows:
+            rows_max = min(int(rtot[0]), B * K)   # (sum of node extents >= live eigen rows)
+        try:
+            gl = ops.spectral_mlp_grad(D.float(), m.long_diffusion_dist, layers, dG,
+                                       rows=(live_rows, n_live) if live_rows is not None else None,
+                                       rows_max=rows_max)
+        except ops.NotSupported:
+            # (a part without 160 KiB of LDS per workgroup: lnz::set_dynamic_lds says so) —
+            # the library-GEMM branch below serves it from now on
+            gl = None
+            m.mlp_grad_impl = 'torch'
+        for li, i in enumerate(lin_idx if gl is not None else ()):
+            for t in range(Lnum):
+                grads[id(m.spectral_filter[t][i].weight)] = gl[li][0][t]
+                grads[id(m.spectral_filter[t][i].bias)] = gl[li][1][t]
+    if S > 0 and m._has_mlp() and id(m.spectral_filter[0][lin_idx[0]].weight) not in grads:
+        pows = torch.stack([torch.pow(D.float(), p) for p in m.long_diffusion_dist],
+                           dim=2).view(B * K, S)
+        if live_rows is not None and not static_rows:
+            # only the eigen slots that carry a Ritz pair have a gradient (dG is zero elsewhere):
+            # the first n_live entries of the plan's row list; the host knows an upper bound of
+            # their number without a round trip (sum of node extents >= sum of min(n, K)) — the
+            # tail of the gathered block is masked.  [S = 8 columns: the gathers are cheap; the
+            # MLP forward + backward shrink from B K = 20.5 k to ~17 k rows]
+            R_live = min(int(rtot[0]), B * K)
+            idx = live_rows[:R_live].long().clamp_(0, B * K - 1)
+            keep = (torch.arange(R_live, device=dev) < n_live.long()).to(dG.dtype)
+            pows = pows.index_select(0, idx)
+            dG = dG.index_select(1, idx) * keep.view(1, R_live, 1)
+        pows = pows.unsqueeze(0).expand(Lnum, pows.shape[0], S)
+        with torch.enable_grad():
+            h = pows
+            for li, i in enumerate(lin_idx):
+                Wst = torch.stack([m.spectral_filter[t][i].weight for t in range(Lnum)])
+                bst = torch.stack([m.spectral_filter[t][i].bias for t in range(Lnum)])
+                h = _BatchedLinear.apply(h, Wst, bst)
+                if li + 1 < len(lin_idx):
+                    h = torch.relu(h)
+            mlp_params = [m.spectral_filter[t][i].weight for i in lin_idx for t in range(Lnum)] + \
+                         [m.spectral_filter[t][i].bias for i in lin_idx for t in range(Lnum)]
+            gg = torch.autograd.grad(h, mlp_params, dG)
+        for p_, g_ in zip(mlp_params, gg):
+            grads[id(p_)] = g_
 
 
 def _fused_conv_backward(m, plan, grad_score, node_feat, V, G, mask_u8, Lp, act, tiles, n_mol,
@@ -1147,58 +1244,8 @@ class _LanczosNetFusedFunction(torch.autograd.Function):
                 R = torch.matmul(dYv[:, la], Wl.reshape(dh, S * d)).view(B, K, S, d)
                 dG.append((R * Xv.unsqueeze(2)).sum(dim=3))             # [B,K,S]
             dG = torch.stack(dG).reshape(Lnum, B * K, S)               # [L, B*K, S]
-        lin_idx = ([i for i, mod in enumerate(m.spectral_filter[0]) if isinstance(mod, nn.Linear)]
-                   if S > 0 and m._has_mlp() else [])
-        if (S > 0 and m._has_mlp() and m.mlp_grad_impl == 'hip' and S <= 8 and len(lin_idx) == 4
-                and dG.is_contiguous()):
-            # one launch for every layer's MLP (csrc/spectral_gains_grad.hip): forward recomputation,
-            # the chain of ReLU masks and all eight parameter gradients on chip, live rows only
-            layers = [[(m.spectral_filter[t][i].weight, m.spectral_filter[t][i].bias) for i in lin_idx]
-                      for t in range(Lnum)]
-            rows_max = B * K
-            if live_rows is not None and not ctx.static_rows:
-                rows_max = min(int(ctx.rtot[0]), B * K)   # (sum of node extents >= live eigen rows)
-            try:
-                gl = ops.spectral_mlp_grad(D.float(), m.long_diffusion_dist, layers, dG,
-                                           rows=(live_rows, n_live) if live_rows is not None else None,
-                                           rows_max=rows_max)
-            except ops.NotSupported:
-                # (a part without 160 KiB of LDS per workgroup: lnz::set_dynamic_lds says so) —
-                # the library-GEMM branch below serves it from now on
-                gl = None
-                m.mlp_grad_impl = 'torch'
-            for li, i in enumerate(lin_idx if gl is not None else ()):
-                for t in range(Lnum):
-                    grads[id(m.spectral_filter[t][i].weight)] = gl[li][0][t]
-                    grads[id(m.spectral_filter[t][i].bias)] = gl[li][1][t]
-        if S > 0 and m._has_mlp() and id(m.spectral_filter[0][lin_idx[0]].weight) not in grads:
-            pows = torch.stack([torch.pow(D.float(), p) for p in m.long_diffusion_dist],
-                               dim=2).view(B * K, S)
-            if live_rows is not None and not ctx.static_rows:
-                # only the eigen slots that carry a Ritz pair have a gradient (dG is zero elsewhere):
-                # the first n_live entries of the plan's row list; the host knows an upper bound of
-                # their number without a round trip (sum of node extents >= sum of min(n, K)) — the
-                # tail of the gathered block is masked.  [S = 8 columns: the gathers are cheap; the
-                # MLP forward + backward shrink from B K = 20.5 k to ~17 k rows]
-                R_live = min(int(ctx.rtot[0]), B * K)
-                idx = live_rows[:R_live].long().clamp_(0, B * K - 1)
-                keep = (torch.arange(R_live, device=dev) < n_live.long()).to(dG.dtype)
-                pows = pows.index_select(0, idx)
-                dG = dG.index_select(1, idx) * keep.view(1, R_live, 1)
-            pows = pows.unsqueeze(0).expand(Lnum, pows.shape[0], S)
-            with torch.enable_grad():
-                h = pows
-                for li, i in enumerate(lin_idx):
-                    Wst = torch.stack([m.spectral_filter[t][i].weight for t in range(Lnum)])
-                    bst = torch.stack([m.spectral_filter[t][i].bias for t in range(Lnum)])
-                    h = _BatchedLinear.apply(h, Wst, bst)
-                    if li + 1 < len(lin_idx):
-                        h = torch.relu(h)
-                mlp_params = [m.spectral_filter[t][i].weight for i in lin_idx for t in range(Lnum)] + \
-                             [m.spectral_filter[t][i].bias for i in lin_idx for t in range(Lnum)]
-                gg = torch.autograd.grad(h, mlp_params, dG)
-            for p_, g_ in zip(mlp_params, gg):
-                grads[id(p_)] = g_
+        if S > 0 and m._has_mlp():
+            _spectral_mlp_param_grads(m, grads, D, dG, live_rows, n_live, ctx.static_rows, ctx.rtot)
 
         # ---- embedding rows: one-hot^T dX_0 as a GEMM (index_add's atomics are 10x slower here)
         if not m.general:
@@ -1208,6 +1255,107 @@ class _LanczosNetFusedFunction(torch.autograd.Function):
                 onehot = torch.nn.functional.one_hot(node_feat.reshape(-1), m.num_atom).to(torch.float32)
                 grads[id(m.embedding.weight)] = onehot.t() @ dx0[:, :N, :din0].reshape(-1, din0)
 
+        out = [grads.get(id(p_)) if p_.requires_grad else None for p_ in m.parameters()]
+        return (None, None, None, None, None, None) + tuple(out)
+
+
+class _MidGraphFusedFunction(torch.autograd.Function):
+    """Training graphs of 33..128 nodes through the HIP kernels (config/graph_lanczos_net.yaml under
+    runner/graph_runner.py).
+
+    forward: spectral gains + lnz_midgraph_forward, keeping its exchange buffer — every layer's
+    output state.
+    backward: lnz_midgraph_head_grad (the head on the stored last state), lnz_midgraph_input_grad
+    (dOut of every layer, one launch), lnz_midgraph_project (the GEMM operands in eigen space, the
+    gain gradients, the bias partials), two batched library GEMMs for all dW, lnz_spectral_mlp_grad,
+    lnz_embedding_grad.  Inputs L, D, V, mask, node ids are data: no gradient."""
+
+    @staticmethod
+    def forward(ctx, module, node_feat, L, D, V, mask, *params):
+        m = module
+        plan = m._plan_mid_backward()
+        mid = plan['mid']
+        X0 = node_feat.float() if m.general else m.embedding.weight.detach()[node_feat].float()
+        if X0.shape[2] != mid['din0p']:
+            X0 = torch.nn.functional.pad(X0, (0, mid['din0p'] - X0.shape[2]))
+        X0 = X0.contiguous()
+        G = None
+        if m.num_scale_long > 0:
+            G = ops.spectral_gains(D, m.long_diffusion_dist, m.num_layer, plan['mlp_pack'])
+        Lf = L if L.dtype == torch.float32 else L.float()
+        Vc = V.float().contiguous()
+        mask_u8 = mask.to(torch.uint8).contiguous()
+        score, Xwork = ops.midgraph_forward(X0, Lf, Vc, G, mask_u8, mid['W'], mid['bias'], mid['Whead'],
+                                            mid['bhead'], m.num_layer, return_work=True)
+        ctx.module = m
+        ctx.has_gains = G is not None
+        ctx.save_for_backward(node_feat, X0, Lf, D, Vc, mask_u8, Xwork, *([G] if G is not None else []))
+        return score
+
+    @staticmethod
+    def backward(ctx, grad_score):
+        m = ctx.module
+        node_feat, X0, L, D, V, mask_u8, Xwork = ctx.saved_tensors[:7]
+        G = ctx.saved_tensors[7] if ctx.has_gains else None
+        mid = m._plan_mid_backward()['mid']
+        Lnum, B, NR, _ = Xwork.shape
+        N, K = V.shape[1], V.shape[2]
+        S, C = m.num_scale_long, L.shape[3]
+        din0, din0p = m.input_dim, mid['din0p']
+        grads = {}
+        dOut = torch.empty_like(Xwork)
+        # ---- head (model/lanczos_net.py:185-194): lnz_midgraph_head_grad, or (the oracle that kernel
+        #      is tested against) autograd on the stored last state
+        P_out = m.filter[-1].weight.shape[0]
+        if m.head_grad_impl == 'hip':
+            dWh, dbh = ops.midgraph_head_grad(Xwork, mask_u8, grad_score, mid['Whead'], mid['bhead'], dOut)
+        else:
+            with torch.enable_grad():
+                XL = Xwork[-1][:, :N].detach().requires_grad_(True)
+                Wh = mid['Whead'].detach().requires_grad_(True)
+                bh = mid['bhead'].detach().requires_grad_(True)
+                Z = torch.nn.functional.linear(XL, Wh, bh)
+                y = Z[..., :P_out] * torch.sigmoid(Z[..., P_out:])
+                mk = (mask_u8 != 0).float().unsqueeze(2)
+                dXL, dWh, dbh = torch.autograd.grad((y * mk).sum(dim=1) / mk.sum(dim=1), [XL, Wh, bh],
+                                                    grad_score.contiguous())
+            dOut[-1].zero_()
+            dOut[-1][:, :N] = dXL * (XL > 0).float()
+        grads[id(m.filter[-1].weight)], grads[id(m.filter[-1].bias)] = dWh[:P_out], dbh[:P_out]
+        grads[id(m.att_func[0].weight)], grads[id(m.att_func[0].bias)] = dWh[P_out:], dbh[P_out:]
+        # ---- dOut of every layer; dX_0 for the embedding
+        dx0, folded = ops.midgraph_input_grad(dOut, Xwork, L, V, G, mid['Wt'], N, din0p,
+                                              want_dx0=not m.general)
+        # ---- weights and biases: dW_l = [A_l^T Q_l | dOut_l^T M_l], every layer in one batched GEMM
+        #      per operand (fixed summation order); the long scales contract over the B K eigen rows
+        want_dg = S > 0 and m._has_mlp()
+        A, Q, M, dG, dbp = ops.midgraph_project(dOut, Xwork, X0, L, V, G, mid['W'], want_dgains=want_dg)
+        dWe = torch.bmm(dOut.view(Lnum, B * NR, 128).transpose(1, 2), M.view(Lnum, B * NR, C * 128))
+        dWe = dWe.view(Lnum, 128, C, 128)
+        if C > 1:
+            # equal operator channels in every graph (one edge type: dataset/graph_data.py:225-262
+            # collates the simple graph's Laplacian twice) have equal messages: one value for all blocks
+            dWe = torch.where(folded.min() > 0, dWe[:, :, :1].expand_as(dWe), dWe)
+        if S > 0:
+            dWl = torch.bmm(A.view(Lnum, B * K, 128).transpose(1, 2), Q.view(Lnum, B * K, S * 128))
+            dW = torch.cat([dWl.view(Lnum, 128, S, 128), dWe], dim=2)
+        else:
+            dW = dWe
+        db = dbp.sum(dim=1)
+        for la in range(Lnum):
+            d = din0 if la == 0 else 128
+            grads[id(m.filter[la].weight)] = dW[la, :, :, :d].reshape(128, -1)
+            grads[id(m.filter[la].bias)] = db[la]
+        # ---- spectral filter MLPs from dG [L, B K, S]
+        if want_dg:
+            _spectral_mlp_param_grads(m, grads, D, dG.view(Lnum, B * K, S))
+        # ---- embedding rows
+        if not m.general:
+            if din0 in (16, 32, 64, 128):
+                grads[id(m.embedding.weight)] = ops.embedding_grad(node_feat.contiguous(), dx0, din0, m.num_atom)
+            else:
+                onehot = torch.nn.functional.one_hot(node_feat.reshape(-1), m.num_atom).to(torch.float32)
+                grads[id(m.embedding.weight)] = onehot.t() @ dx0[:, :N, :din0].reshape(-1, din0)
         out = [grads.get(id(p_)) if p_.requires_grad else None for p_ in m.parameters()]
         return (None, None, None, None, None, None) + tuple(out)
 

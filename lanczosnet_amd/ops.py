@@ -83,10 +83,24 @@ NotSupported = _lib.NotSupported
 LnzError = _lib.LnzError
 
 
+_autograd_kernel = [None]
+
+
 def last_kernel():
   """lnz_last_kernel(): the kernel (with template arguments) the calling thread's last fused
-  forward / input-gradient launch selected."""
-  return torch.ops.lanczosnet.last_kernel()
+  forward / input-gradient launch selected.  lnz_last_kernel() is per thread and `loss.backward()`
+  launches from autograd's own thread: a backward launch that hands its name over
+  (note_autograd_kernel) is reported here until the next module forward."""
+  return _autograd_kernel[0] or torch.ops.lanczosnet.last_kernel()
+
+
+def note_autograd_kernel():
+  """Called by a backward launch's wrapper, on the launching thread."""
+  _autograd_kernel[0] = torch.ops.lanczosnet.last_kernel()
+
+
+def forget_autograd_kernel():
+  _autograd_kernel[0] = None
 
 
 def _need_cuda(*tensors):
@@ -491,12 +505,14 @@ def large_conv_layer(X, din, Lb, Vb, V, Wf, Wt, G, bias, work, relu=True, out=No
   return large_conv(Lb, Vb, Zt, Tt, bias, relu=relu, out=out)
 
 
-def midgraph_forward(X0, L, V, G, mask_u8, W, bias, Whead, bhead, num_layer):
+def midgraph_forward(X0, L, V, G, mask_u8, W, bias, Whead, bhead, num_layer, return_work=False):
   """lnz_midgraph_forward: every conv layer, the head and the gated masked mean of a batch of
   graphs with 33..128 nodes in ONE launch (csrc/conv_mid.hip; config/graph_lanczos_net.yaml).
   X0 [B,N,din0] fp32 (din0 a multiple of 16), L [B,N,N,C] (any strides), V [B,N,K], G
   [num_layer,B,S,K] or None, W: the layers' [128][S + C][din_l] weight blocks behind each other,
-  bias [num_layer,128], Whead [dout + 1,128], bhead [dout + 1].  Returns score [B,dout]."""
+  bias [num_layer,128], Whead [dout + 1,128], bhead [dout + 1].  Returns score [B,dout]; with
+  `return_work` also the exchange buffer [num_layer,B,NR,128]: every layer's output state, the
+  stored activations of the backward (midgraph_head_grad / _input_grad / _project)."""
   _need_cuda(X0, L, V, G, mask_u8, W, bias, Whead, bhead)
   B, N, din0 = X0.shape
   K, Cn = V.shape[2], L.shape[3]
@@ -511,7 +527,75 @@ def midgraph_forward(X0, L, V, G, mask_u8, W, bias, Whead, bhead, num_layer):
   with torch.cuda.device(dev):
     _abi().midgraph_forward(X0, L, sb, sr, sc, sch, V, G, mask_u8, W, bias, Whead, bhead, B, N, K, Cn, S,
                             num_layer, din0, dout, Xwork, sync, score)
+  if return_work:
+    return score, Xwork.view(num_layer, B, -1, 128)
   return score
+
+
+def midgraph_head_grad(Xwork, mask_u8, grad_score, Whead, bhead, dOut):
+  """lnz_midgraph_head_grad: the readout head's backward on the stored last state (slot -1 of Xwork
+  [num_layer,B,NR,128]) in one launch.  Writes slot -1 of dOut [num_layer,B,NR,128]; returns
+  (dWhead [dout + 1,128], dbhead [dout + 1]): the per-graph partials added in graph order."""
+  _need_cuda(Xwork, mask_u8, grad_score, Whead, bhead, dOut)
+  B, N = mask_u8.shape
+  P = grad_score.shape[1]
+  assert Xwork.is_contiguous() and dOut.is_contiguous() and dOut.shape == Xwork.shape
+  assert Whead.shape == (P + 1, 128) and Whead.is_contiguous() and mask_u8.dtype == torch.uint8
+  ws = torch.empty((int(_abi().midgraph_head_grad_workspace_floats(B, P)),), dtype=torch.float32,
+                   device=Xwork.device)
+  with torch.cuda.device(Xwork.device):
+    _abi().midgraph_head_grad(Xwork[-1], mask_u8.contiguous(), grad_score.float().contiguous(), Whead,
+                              bhead.contiguous(), B, N, P, dOut[-1], ws)
+  nw = B * (P + 1) * 128
+  return ws[:nw].view(B, P + 1, 128).sum(dim=0), ws[nw:].view(B, P + 1).sum(dim=0)
+
+
+def midgraph_input_grad(dOut, Xwork, L, V, G, Wt, N, din0, want_dx0=False):
+  """lnz_midgraph_input_grad: dOut_l of every conv layer in ONE launch (csrc/conv_mid_grad.hip: the
+  forward kernel's four workgroups per graph and its exchange, run on the gradient).  dOut
+  [num_layer,B,NR,128] with the last slot filled (midgraph_head_grad) is completed in place; Wt: the
+  layers' transposed weight blocks [128][S + C][128].  Returns (dX0 [B,NR,din0] or None, folded [B]
+  int32: 1 where the graph's operator channels are equal)."""
+  _need_cuda(dOut, Xwork, L, V, G, Wt)
+  num_layer, B, NR, _ = dOut.shape
+  K, Cn = V.shape[2], L.shape[3]
+  S = 0 if G is None else G.shape[2]
+  dev = dOut.device
+  sync = torch.zeros((B * (num_layer + 1),), dtype=torch.int32, device=dev)   # its own: never the forward's
+  midgraph_input_grad.last_sync = sync
+  dX0 = torch.empty((B, NR, din0), dtype=torch.float32, device=dev) if want_dx0 else None
+  folded = torch.empty((B,), dtype=torch.int32, device=dev)
+  sb, sr, sc, sch = L.stride()
+  with torch.cuda.device(dev):
+    _abi().midgraph_input_grad(dOut, Xwork, L, sb, sr, sc, sch, V, G, Wt, B, N, K, Cn, S, num_layer, din0,
+                               sync, dX0, folded)
+  note_autograd_kernel()
+  return dX0, folded
+
+
+def midgraph_project(dOut, Xwork, X0, L, V, G, W, want_dgains=True):
+  """lnz_midgraph_project: per (graph, layer) the operands of the weight-gradient GEMMs and the gain
+  gradients in one launch.  Returns (A [L,B,K,128] = V^T dOut_l, Q [L,B,K,S,128] = g_s . V^T X_l,
+  M [L,B,NR,C,128] = L_c X_l, dG [L,B,K,S] or None, db [L,B,128] per-graph column sums of dOut_l);
+  A and Q are None without long scales."""
+  _need_cuda(dOut, Xwork, X0, L, V, G, W)
+  num_layer, B, NR, _ = dOut.shape
+  N, din0 = X0.shape[1], X0.shape[2]
+  K, Cn = V.shape[2], L.shape[3]
+  S = 0 if G is None else G.shape[2]
+  dev = dOut.device
+  ws = torch.empty((int(_abi().midgraph_project_workspace_floats(B, N, K, Cn, S, num_layer)),),
+                   dtype=torch.float32, device=dev)
+  sb, sr, sc, sch = L.stride()
+  with torch.cuda.device(dev):
+    _abi().midgraph_project(dOut, Xwork, X0, L, sb, sr, sc, sch, V, G, W, B, N, K, Cn, S, num_layer, din0,
+                            1 if want_dgains else 0, ws)
+  LB = num_layer * B
+  sizes = [LB * K * 128, LB * K * S * 128, LB * NR * Cn * 128, LB * K * S, LB * 128]
+  A, Q, M, dG, db = torch.split(ws, sizes)
+  return (A.view(num_layer, B, K, 128) if S else None, Q.view(num_layer, B, K, S, 128) if S else None,
+          M.view(num_layer, B, NR, Cn, 128), dG.view(num_layer, B, K, S) if (S and want_dgains) else None,
+          db.view(num_layer, B, 128))
 
 
 def large_work_buffers(Lb):

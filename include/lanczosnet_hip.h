@@ -29,6 +29,7 @@ extern "C" {
  *    lnz_large_conv accepts C = 0), lnz_head_backward, lnz_node_extents, the out-of-place split-pack
  *    entries (lnz_split_laplacian_pack_to, lnz_spectral_gains_rows_split_to), lnz_last_kernel,
  *    lnz_stream_create_cu_masked; the full eigendecomposition (lnz_sym_eigh_topk, _workspace_bytes);
+ *    + the wide K-step entry (lnz_lanczos_ritz_kstep_wide, _workspace_bytes: N <= 16384, M <= 256);
  * 6: lnz_forward_args lost Wp16 / w16_off / Wp16_head / Lp16 (gemm_mode 1 is now the split precision
  *    inside the strip kernel: lnz_pack_rows_k8_split; lnz_pack_rows_f16x2 and
  *    lnz_pack_laplacian_f16x2 are gone) and gained dbias_part_cap; + lnz_midgraph_forward,
@@ -313,6 +314,27 @@ int lnz_lanczos_ritz_kstep(const float* A, int64_t stride_b, int64_t stride_r, i
                            const int32_t* n_nodes, int B, int N, int M, int K, int flags,
                            int row_cap, void* workspace, int64_t workspace_bytes, float* D, float* V,
                            int32_t* info, int32_t* dense_fallback, lnz_stream_t stream);
+
+/* The same function — utils/data_helper.py:205-208, `eigsh(L, k, which='LM')`; the M-step recurrence
+ * of lnz_lanczos_ritz_kstep, Ritz pairs in the same order with the same padding, info [B] = steps
+ * taken — for what one workgroup cannot hold: N <= 16384 nodes and K <= M <= 256 Lanczos steps
+ * (M <= N; LNZ_ENOTSUP beyond), M > K included: a Krylov space wider than the pairs kept, the knob
+ * the reference's ARPACK call has (csrc/lanczos_wide.hip).  A graph is spread over many workgroups;
+ * the stages are ordered by launch boundaries (5 M + 8 launches per call), the early stop and the
+ * second Gram-Schmidt pass are decided on the device, every sum has a fixed order: deterministic,
+ * and a graph's result does not depend on the rest of the batch.  A is always read once into the
+ * sliced-ELL image (row_cap as LNZ_KSTEP_COMPACT); a graph with a longer row (dense_fallback [B],
+ * optional output) is multiplied from its dense rows in the same call.  stride_c = 1, or 2 with a
+ * dense_fallback output: channel 0 of the collated channels-last pair in place — a graph flagged
+ * there is NOT computed (the caller copies such a batch and calls again), as above.  Rows 16-byte
+ * aligned, N %% 4 == 0, one graph spans less than 4 GiB.  workspace (256-B aligned):
+ * lnz_lanczos_ritz_kstep_wide_workspace_bytes(B, N, M, row_cap) bytes, linear in B (0 for
+ * non-positive sizes); B <= 65535 per call. */
+int64_t lnz_lanczos_ritz_kstep_wide_workspace_bytes(int B, int N, int M, int row_cap);
+int lnz_lanczos_ritz_kstep_wide(const float* A, int64_t stride_b, int64_t stride_r, int64_t stride_c,
+                                const int32_t* n_nodes, int B, int N, int M, int K, int row_cap,
+                                void* workspace, int64_t workspace_bytes, float* D, float* V,
+                                int32_t* info, int32_t* dense_fallback, lnz_stream_t stream);
 
 /* The FULL decomposition of get_graph_laplacian_eigs(..., use_eigen_decomp=True)
  * (utils/data_helper.py:197-223: `np.linalg.eigh` of each graph's n_b x n_b block, then the top-K

@@ -23,6 +23,7 @@
 // Every sum runs in a fixed order that depends on n_b only: results are bitwise repeatable and
 // independent of the other graphs of the batch.
 #include "common.hpp"
+#include "tridiag_eig.hpp"
 
 #include <float.h>
 
@@ -91,43 +92,9 @@ __device__ inline int graph_n(const int32_t* n_nodes, int b, int N) {
   return n < 0 ? 0 : (n > N ? N : n);
 }
 
-// Deterministic block sum: every thread's value into red[], then a fixed halving tree.
-template <int T>
-__device__ double block_sum(double v, double* red) {
-  const int t = threadIdx.x;
-  red[t] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = T / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] += red[t + s];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
-
-template <int T>
-__device__ double block_max(double v, double* red) {
-  const int t = threadIdx.x;
-  red[t] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = T / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] = fmax(red[t], red[t + s]);
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
-
-// Wave sum in a fixed butterfly order (every lane gets the total).
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
+using lnz_tri::block_max;
+using lnz_tri::block_sum;
+using lnz_tri::wave_sum;
 
 // ------------------------------------------------------------------------------------ 1. load
 __global__ __launch_bounds__(256) void eigh_load_kernel(const float* __restrict__ A, int64_t sb,
@@ -369,52 +336,12 @@ __global__ __launch_bounds__(256) void eigh_update_kernel(const int32_t* __restr
 }
 
 // ---------------------------------------------------------- 3. eigenpairs of the tridiagonal T
-__device__ inline int sturm_count(const double* d, const double* e2, int n, double x, double pivmin) {
-  double q = d[0] - x;
-  if (fabs(q) <= pivmin) q = -pivmin;
-  int cnt = q <= 0.0;
-  for (int k = 1; k < n; ++k) {
-    q = (d[k] - x) - e2[k - 1] / q;
-    if (fabs(q) <= pivmin) q = -pivmin;
-    cnt += q <= 0.0;
-  }
-  return cnt;
-}
+// (the arithmetic is csrc/tridiag_eig.hpp, shared with the wide K-step Lanczos path)
+using lnz_tri::EIG_T;
+using lnz_tri::MAX_CAND;
+using lnz_tri::Sel;
 
-__device__ inline double start_entry(int r, int slot) {
-  uint32_t h = (uint32_t)r * 2654435761u ^ ((uint32_t)slot * 40503u + 0x9E3779B9u);
-  h ^= h >> 16;
-  h *= 0x7feb352du;
-  h ^= h >> 15;
-  h *= 0x846ca68bu;
-  h ^= h >> 16;
-  return (double)h * (2.0 / 4294967296.0) - 1.0;
-}
-
-constexpr int EIG_T = 256;
-constexpr int MAX_CAND = 2 * MAX_K;
-
-// The selected pairs in ascending order and their clusters, written by eigh_bisect_kernel for
-// eigh_invit_kernel and the epilogue (a [K + 2] double and a [3 K + 2] int block per graph).
-struct Sel {
-  double* lam;     // [K] selected eigenvalues, ascending
-  double* nrm;     // [2]: ||T||, pivmin
-  int32_t* slot;   // [K] output slot of each (its descending-|lambda| rank)
-  int32_t* cstart; // [K + 1] first ascending position of each cluster, then kk
-  int32_t* fail;   // [K] per cluster: an inverse iteration did not converge
-  int32_t* ncl;    // [1] number of clusters
-};
-
-__device__ inline Sel sel_of(const Ws& ws, int b, int K) {
-  Sel s;
-  s.lam = (double*)ws.sel(b);
-  s.nrm = s.lam + K;
-  s.slot = (int32_t*)(s.nrm + 2);
-  s.cstart = s.slot + K;
-  s.fail = s.cstart + K + 1;
-  s.ncl = s.fail + K;
-  return s;
-}
+__device__ inline Sel sel_of(const Ws& ws, int b, int K) { return lnz_tri::sel_at(ws.sel(b), K); }
 
 // 3a. one workgroup per graph; dynamic LDS: d, e, e2 [N] doubles.  Splits T (the zeroed
 // off-diagonals go back to the workspace), bisection for the K smallest and K largest eigenvalues,
@@ -431,7 +358,6 @@ __global__ __launch_bounds__(EIG_T) void eigh_bisect_kernel(const int32_t* __res
   double* e2 = e + N;
   const int b = blockIdx.x, t = threadIdx.x;
   const int n = graph_n(n_nodes, b, N);
-  const int kk = n < K ? n : K;
   int32_t* badw = ws.bad(b);
   const Sel sl = sel_of(ws, b, K);
   if (t == 0) bad_s = 0;
@@ -446,89 +372,8 @@ __global__ __launch_bounds__(EIG_T) void eigh_bisect_kernel(const int32_t* __res
     }
     return;
   }
-  for (int r = t; r < n; r += EIG_T) {
-    d[r] = ws.d(b)[r];
-    e[r] = r < n - 1 ? ws.e(b)[r] : 0.0;
-  }
-  __syncthreads();
-  double lmax = 0.0;
-  for (int r = t; r < n; r += EIG_T)
-    lmax = fmax(lmax, fabs(d[r]) + fabs(e[r]) + (r > 0 ? fabs(e[r - 1]) : 0.0));
-  const double tnorm = block_max<EIG_T>(lmax, red);
-  const double eps = DBL_EPSILON;
-  // split: an off-diagonal entry below n eps ||T|| is set to zero (T decouples there)
-  const double thr = (double)n * eps * tnorm;
-  double e2max = 0.0;
-  for (int r = t; r < n; r += EIG_T) {
-    if (fabs(e[r]) <= thr) e[r] = 0.0;
-    e2[r] = e[r] * e[r];
-    e2max = fmax(e2max, e2[r]);
-    ws.e(b)[r] = e[r];
-  }
-  const double pivmin = DBL_MIN * fmax(1.0, block_max<EIG_T>(e2max, red));
-  double glo = INFINITY, ghi = -INFINITY;
-  for (int r = t; r < n; r += EIG_T) {
-    const double rad = fabs(e[r]) + (r > 0 ? fabs(e[r - 1]) : 0.0);
-    glo = fmin(glo, d[r] - rad);
-    ghi = fmax(ghi, d[r] + rad);
-  }
-  glo = -block_max<EIG_T>(-glo, red);
-  ghi = block_max<EIG_T>(ghi, red);
-  const double pad = 2.0 * eps * tnorm * n + 2.0 * pivmin;
-  glo -= pad;
-  ghi += pad;
-  // candidates: the K smallest and the K largest (all of them when they overlap), ascending
-  const int nc = 2 * kk >= n ? n : 2 * kk;
-  const double atol = 2.0 * eps * tnorm + pivmin;
-  for (int c = t; c < nc; c += EIG_T) {
-    const int idx = (nc == n || c < kk) ? c : n - 2 * kk + c;
-    double lo = glo, hi = ghi;
-    for (int it = 0; it < 256; ++it) {
-      if (!(hi - lo > fmax(atol, 2.0 * eps * fmax(fabs(lo), fabs(hi))))) break;
-      const double mid = 0.5 * (lo + hi);
-      if (mid <= lo || mid >= hi) break;
-      if (sturm_count(d, e2, n, mid, pivmin) <= idx) lo = mid;
-      else hi = mid;
-    }
-    lamc[c] = 0.5 * (lo + hi);
-  }
-  __syncthreads();
-  // stable descending-|lambda| rank over ascending lambda (np.argsort(-|w|, kind='mergesort'))
-  for (int c = t; c < nc; c += EIG_T) {
-    const double a = fabs(lamc[c]);
-    int rk = 0;
-    for (int q = 0; q < nc; ++q) {
-      const double aq = fabs(lamc[q]);
-      rk += (aq > a) || (aq == a && q < c);
-    }
-    rankc[c] = rk;
-    if (rk < kk) ws.lam(b)[rk] = lamc[c];
-  }
-  __syncthreads();
-  // the selected ones in ascending order; a cluster starts where the gap exceeds dstein's 1e-3 ||T||
-  if (t == 0) {
-    const double ortol = 1e-3 * tnorm;
-    int p = 0, q = 0;
-    double prev = 0.0;
-    for (int c = 0; c < nc; ++c) {
-      if (rankc[c] >= kk) continue;
-      const double lam = lamc[c];
-      if (p == 0 || lam - prev > ortol) {
-        sl.cstart[q] = p;
-        sl.fail[q] = 0;
-        ++q;
-      }
-      prev = lam;
-      sl.lam[p] = lam;
-      sl.slot[p] = rankc[c];
-      ++p;
-    }
-    sl.cstart[q] = p;
-    sl.ncl[0] = q;
-    sl.nrm[0] = tnorm;
-    sl.nrm[1] = pivmin;
-    badw[N] = 0;
-  }
+  lnz_tri::bisect_body(n, K, ws.d(b), ws.e(b), ws.lam(b), sl, d, e, e2, red, lamc, rankc);
+  if (t == 0) badw[N] = 0;
 }
 
 // 3b. inverse iteration; workgroup x of graph b takes clusters x, x + gridDim.x, ... (the host
@@ -550,125 +395,11 @@ __global__ __launch_bounds__(EIG_T) void eigh_invit_kernel(const int32_t* __rest
   double* dl = du2 + N;
   double* x = dl + N;
   unsigned char* piv = (unsigned char*)(x + N);
-  const int b = blockIdx.y, t = threadIdx.x;
+  const int b = blockIdx.y;
   const int n = graph_n(n_nodes, b, N);
   if (n == 0 || ws.bad(b)[N] == 1) return;
-  const Sel sl = sel_of(ws, b, K);
-  const int ncl_all = sl.ncl[0];
-  if ((int)blockIdx.x >= ncl_all) return;
-  for (int r = t; r < n; r += EIG_T) {
-    d[r] = ws.d(b)[r];
-    e[r] = r < n - 1 ? ws.e(b)[r] : 0.0;
-  }
-  __syncthreads();
-  const double tnorm = sl.nrm[0], pivmin = sl.nrm[1];
-  const double eps = DBL_EPSILON;
-  const double pert = eps * tnorm > pivmin ? eps * tnorm : pivmin;
-  double* Z = ws.Z(b);
-  const int wave = t >> 6, lane = t & 63;
-  for (int cq = blockIdx.x; cq < ncl_all; cq += gridDim.x) {
-  const int p0 = sl.cstart[cq], p1 = sl.cstart[cq + 1];
-  int fail = 0;
-  for (int p = p0; p < p1; ++p) {
-    const int ncl = p - p0;
-    const int slot = sl.slot[p];
-    const double lam = sl.lam[p];
-    // LU of T - lam I with partial pivoting (dgttrf), tiny pivots perturbed
-    if (t == 0) {
-      for (int r = 0; r < n; ++r) {
-        dd[r] = d[r] - lam;
-        du[r] = e[r];
-        dl[r] = e[r];
-        du2[r] = 0.0;
-        piv[r] = 0;
-      }
-      for (int r = 0; r < n - 1; ++r) {
-        if (fabs(dd[r]) >= fabs(dl[r])) {
-          if (dd[r] != 0.0) {
-            const double f = dl[r] / dd[r];
-            dl[r] = f;
-            dd[r + 1] -= f * du[r];
-          }
-        } else {
-          const double f = dd[r] / dl[r];
-          dd[r] = dl[r];
-          dl[r] = f;
-          const double tmp = du[r];
-          du[r] = dd[r + 1];
-          dd[r + 1] = tmp - f * dd[r + 1];
-          if (r < n - 2) {
-            du2[r] = du[r + 1];
-            du[r + 1] = -f * du[r + 1];
-          }
-          piv[r] = 1;
-        }
-      }
-      for (int r = 0; r < n; ++r)
-        if (fabs(dd[r]) < pert) dd[r] = dd[r] < 0.0 ? -pert : pert;
-    }
-    for (int r = t; r < n; r += EIG_T) x[r] = start_entry(r, slot);
-    __syncthreads();
-    for (int it = 0; it < 3; ++it) {
-      if (t == 0) {
-        for (int r = 0; r < n - 1; ++r) {
-          if (!piv[r]) {
-            x[r + 1] -= dl[r] * x[r];
-          } else {
-            const double tmp = x[r];
-            x[r] = x[r + 1];
-            x[r + 1] = tmp - dl[r] * x[r];
-          }
-        }
-        x[n - 1] /= dd[n - 1];
-        if (n > 1) x[n - 2] = (x[n - 2] - du[n - 2] * x[n - 1]) / dd[n - 2];
-        for (int r = n - 3; r >= 0; --r) x[r] = (x[r] - du[r] * x[r + 1] - du2[r] * x[r + 2]) / dd[r];
-      }
-      __syncthreads();
-      double mx = 0.0;
-      for (int r = t; r < n; r += EIG_T) mx = fmax(mx, fabs(x[r]));
-      mx = block_max<EIG_T>(mx, red);
-      const double inv = mx > 0.0 ? 1.0 / mx : 1.0;
-      for (int r = t; r < n; r += EIG_T) x[r] *= inv;
-      __syncthreads();
-      for (int pass = 0; pass < 2 && ncl > 0; ++pass) {
-        for (int q = wave; q < ncl; q += EIG_T / 64) {
-          const double* zq = Z + (int64_t)clus[q] * N;
-          double s = 0.0;
-          for (int r = lane; r < n; r += 64) s += zq[r] * x[r];
-          s = wave_sum(s);
-          if (lane == 0) hq[q] = s;
-        }
-        __syncthreads();
-        for (int r = t; r < n; r += EIG_T) {
-          double v = x[r];
-          for (int q = 0; q < ncl; ++q) v -= hq[q] * Z[(int64_t)clus[q] * N + r];
-          x[r] = v;
-        }
-        __syncthreads();
-      }
-      double ss = 0.0;
-      for (int r = t; r < n; r += EIG_T) ss += x[r] * x[r];
-      const double nrm = sqrt(block_sum<EIG_T>(ss, red));
-      const double sc = nrm > 0.0 ? 1.0 / nrm : 0.0;
-      for (int r = t; r < n; r += EIG_T) x[r] *= sc;
-      __syncthreads();
-    }
-    // residual of the pair on T
-    double res = 0.0;
-    for (int r = t; r < n; r += EIG_T) {
-      double y = (d[r] - lam) * x[r];
-      if (r > 0) y += e[r - 1] * x[r - 1];
-      if (r < n - 1) y += e[r] * x[r + 1];
-      res = fmax(res, fabs(y));
-      Z[(int64_t)slot * N + r] = x[r];
-    }
-    res = block_max<EIG_T>(res, red);
-    if (!(res <= 1e-9 * fmax(tnorm, 1e-300))) fail = 1;
-    if (t == 0) clus[ncl] = slot;
-    __syncthreads();
-  }
-  if (t == 0) sl.fail[cq] = fail;
-  }
+  lnz_tri::invit_body(n, N, ws.d(b), ws.e(b), sel_of(ws, b, K), ws.Z(b), (int)blockIdx.x, (int)gridDim.x, d, e,
+                      dd, du, du2, dl, x, piv, red, clus, hq);
 }
 
 // --------------------------------------------------------------------- 4. back-transformation

@@ -64,14 +64,17 @@ def collate_graph_preprocessed(items, num_eigs, simple_key='L_simple_4', negate_
 
 
 def collate_graph_adjacency(items, num_eigs, device='cuda', model_name='LanczosNetGeneral',
-                            eigs_method='auto'):
+                            eigs_method='auto', lanczos_steps=None):
     """Raw graphs in, device-resident batch out (Laplacians and Ritz pairs by the HIP kernels).
     model_name picks the simple-graph channel like the reference's collate (graph_data.py:247-260):
     L4 by default, the asymmetric diffusion map L7 for DCNN, MINUS the symmetric one (L6, alpha =
     0.5) for ChebyNet — the bond-type channels are L4 in every branch (get_graph_data.py:61-72).
     eigs_method: 'auto', or 'full' for the pairs of the full decomposition at every size
     (ops.sym_eigh_topk, the offline `eigh` of get_graph_data.py:63-68); no sparse image is then
-    left on L (the large-graph forward builds its own)."""
+    left on L (the large-graph forward builds its own).
+    lanczos_steps: M >= num_eigs steps of the K-step recurrence for graphs beyond 192 nodes (None =
+    num_eigs); beyond 2048 nodes or 64 steps the pairs come from the wide K-step entry, which
+    leaves no sparse image on L either."""
     from .. import ops
     if eigs_method not in ('auto', 'full'):
         raise ValueError("collate_graph_adjacency: eigs_method is 'auto' or 'full', got %r" % (eigs_method,))
@@ -90,7 +93,8 @@ def collate_graph_adjacency(items, num_eigs, device='cuda', model_name='LanczosN
     if num_eigs:
         # (the Ritz pairs are those of the L4 simple graph in every branch, graph_data.py:262-287)
         # (beyond 192 nodes the same pass over L also leaves the conv's sparse image riding on it)
-        out['D'], out['V'] = ops.lanczos_ritz_collated(L, n_nodes, num_eigs, method=eigs_method)
+        out['D'], out['V'] = ops.lanczos_ritz_collated(L, n_nodes, num_eigs, method=eigs_method,
+                                                       lanczos_steps=lanczos_steps)
     if model_name == 'DCNN':
         L[:, :, :, 0] = ops.laplacian(adjs_d, n_nodes, 'L7')[:, :, :, 0]
     elif model_name == 'ChebyNet':

@@ -148,7 +148,7 @@ def laplacian(adjs, n_nodes, kind='L4', alpha=0.5):
 
 
 # ------------------------------------------------------------------------------------- R2 + R6
-def lanczos_ritz(A, n_nodes, K, return_info=False, kernel='auto'):
+def lanczos_ritz(A, n_nodes, K, return_info=False, kernel='auto', lanczos_steps=None):
   """Batched Lanczos -> tridiagonal eigensolve -> Ritz select.
 
   A: [B,N,N] float32 symmetric (any strides: pass `L[..., 0]` of a channels-last Laplacian
@@ -161,20 +161,26 @@ def lanczos_ritz(A, n_nodes, K, return_info=False, kernel='auto'):
   with the QL sweep instead of its parallel tridiagonal eigensolver — its fallback, forced),
   'workgroup_mw' (the Lanczos phase on all eight waves where the wave-level form would run — the
   arithmetic of 'workgroup_ws' in the same order), 'workgroup_p1' / '_p2' / '_p4' (the wave-level
-  Lanczos phase with one, two, four parts per row group instead of the number chosen by size)."""
+  Lanczos phase with one, two, four parts per row group instead of the number chosen by size).
+  lanczos_steps: M >= K steps of the K-step recurrence where 'auto' takes that branch (N > 192);
+  None = K.  The full-length kernels up to 192 nodes have no such knob and ignore it."""
   _need_cuda(A, n_nodes)
   assert A.dim() == 3 and A.shape[1] == A.shape[2] and A.dtype == torch.float32
   assert kernel in ('auto', 'workgroup', 'workgroup_ws', 'workgroup_ql', 'workgroup_mw', 'workgroup_p1',
                     'workgroup_p2', 'workgroup_p4')
   B, N, _ = A.shape
   n_nodes = n_nodes.to(torch.int32).contiguous()
+  if lanczos_steps is not None and int(lanczos_steps) < K:
+    raise ValueError('lanczos_ritz: lanczos_steps=%d < K=%d: the Krylov space holds at least the pairs kept'
+                     % (lanczos_steps, K))
   if kernel == 'auto' and N > RITZ_FULL_MAX_N:
     # beyond one workgroup's reach the full-length decomposition is not offered: the K-step Krylov
     # method — the reference's OTHER branch, use_eigen_decomp=False (utils/data_helper.py:205-208)
     _warn_once('lanczos_ritz: %d > %d nodes — Ritz pairs of the K-step Lanczos recurrence (the '
                'reference\'s use_eigen_decomp=False / eigsh branch, utils/data_helper.py:205-208), not of '
                'the full decomposition; converged leading pairs agree' % (N, RITZ_FULL_MAX_N))
-    return lanczos_ritz_kstep(A, n_nodes, K, K, return_info=return_info)
+    return lanczos_ritz_kstep(A, n_nodes, K if lanczos_steps is None else int(lanczos_steps), K,
+                              return_info=return_info)
   if kernel == 'auto':
     D, V, info = _ext().lanczos_ritz(A, n_nodes, K)
     return (D, V, info) if return_info else (D, V)
@@ -250,6 +256,13 @@ def sym_eigh_topk(A, n_nodes, K, workspace=None, return_info=False):
 
 
 
+KSTEP_MAX_N = 2048        # lnz_lanczos_ritz_kstep: one workgroup per graph ...
+KSTEP_MAX_M = 64          # ... and up to 64 Lanczos steps
+KSTEP_WIDE_MAX_N = 16384  # lnz_lanczos_ritz_kstep_wide: a graph spread over many workgroups
+KSTEP_WIDE_MAX_M = 256
+KSTEP_WIDE_WORKSPACE_CAP = 4 << 30   # default bound on one chunk's workspace (bytes)
+
+
 def kstep_row_cap(N):
   """Default sliced-ELL row capacity of the compacted K-step path: N / 8 entries per row, between
   64 and 256 (a multiple of 8).  The capacity only sizes the workspace (6 bytes x N x capacity per
@@ -270,7 +283,11 @@ def lanczos_ritz_kstep(A, n_nodes, M, K, symmetric=True, compact=True, row_cap=N
                        workspace=None, return_info=False, return_fallback=False, conv_image=None):
   """lnz_lanczos_ritz_kstep: M-step Lanczos Ritz pairs (top K by |theta|) of a ragged batch of
   large dense-stored graphs — the reference's `eigsh` branch (utils/data_helper.py:205-208).
-  A [B,N,N] float32, any N <= 2048, n_nodes [B] or None.  Read in place: contiguous rows, or (compact)
+  A [B,N,N] float32, n_nodes [B] or None.  N <= 2048 and M <= 64: one workgroup per graph
+  (lnz_lanczos_ritz_kstep); beyond, up to N <= 16384 and K <= M <= 256: lnz_lanczos_ritz_kstep_wide, the
+  same recurrence spread over many workgroups (always on the compacted image; `symmetric` and
+  `compact` have nothing to choose there, no conv image is left behind, and the batch is computed
+  chunk by chunk under `workspace`'s size or KSTEP_WIDE_WORKSPACE_CAP bytes).  Read in place: contiguous rows, or (compact)
   channel 0 of a channels-last pair — `L[..., 0]` of the collated [B,N,N,2] — with 16-byte aligned
   rows and N a multiple of 4; anything else is copied into an aligned buffer first.
   compact: read A once and run the steps on its sliced-ELL image (graphs with a row of more than
@@ -300,9 +317,14 @@ def lanczos_ritz_kstep(A, n_nodes, M, K, symmetric=True, compact=True, row_cap=N
     A = Ap
   if n_nodes is not None:
     n_nodes = n_nodes.to(torch.int32).contiguous()
-  if not (0 < K <= M <= min(Np, 64)):
-    raise _lib.NotSupported(_lib.LNZ_ENOTSUP, 'lanczos_ritz_kstep: K=%d <= M=%d <= 64 Lanczos steps (and M <= N=%d) '
-                            'required: the K-step branch serves up to 64 Ritz pairs' % (K, M, N))
+  if not (0 < K <= M <= min(Np, KSTEP_WIDE_MAX_M)) or Np > KSTEP_WIDE_MAX_N:
+    raise _lib.NotSupported(_lib.LNZ_ENOTSUP, 'lanczos_ritz_kstep: K=%d <= M=%d <= %d Lanczos steps (and M <= N=%d '
+                            '<= %d) required: the K-step branch serves up to %d Ritz pairs of graphs of up to %d '
+                            'nodes' % (K, M, KSTEP_WIDE_MAX_M, N, KSTEP_WIDE_MAX_N, KSTEP_WIDE_MAX_M,
+                                       KSTEP_WIDE_MAX_N))
+  if Np > KSTEP_MAX_N or M > KSTEP_MAX_M:
+    out = _kstep_wide(A, n_nodes, B, N, Np, M, K, row_cap, workspace, return_info, return_fallback)
+    return out + ((None,) if conv_image is not None else ())
   flags = (1 if symmetric else 0) | (2 if compact else 0)
   cap = int(row_cap if row_cap is not None else kstep_row_cap(Np)) if compact else 0
   need = _abi().lanczos_ritz_kstep_workspace_bytes(B, Np, flags, cap)
@@ -342,6 +364,48 @@ def lanczos_ritz_kstep(A, n_nodes, M, K, symmetric=True, compact=True, row_cap=N
     out += (fb,)
   if conv_image is not None:
     out += (img,)
+  return out
+
+
+def _kstep_wide(A, n_nodes, B, N, Np, M, K, row_cap, workspace, return_info, return_fallback):
+  """lanczos_ritz_kstep beyond one workgroup's reach (A already aligned: contiguous rows or the
+  channels-last view in place, width Np)."""
+  cap = int(row_cap if row_cap is not None else kstep_row_cap(Np))
+  per = _abi().lanczos_ritz_kstep_wide_workspace_bytes(1, Np, M, cap)
+  limit = workspace.numel() * workspace.element_size() if workspace is not None and workspace.data_ptr() % 256 == 0 \
+      else KSTEP_WIDE_WORKSPACE_CAP
+  chunk = max(1, min(B, limit // per, 65535))
+  need = _abi().lanczos_ritz_kstep_wide_workspace_bytes(chunk, Np, M, cap)
+  while chunk > 1 and need > limit:   # (the arrays of the layout are rounded to 256 bytes one by one)
+    chunk -= 1
+    need = _abi().lanczos_ritz_kstep_wide_workspace_bytes(chunk, Np, M, cap)
+  if workspace is None or workspace.numel() * workspace.element_size() < need or workspace.data_ptr() % 256:
+    workspace = torch.empty((need,), dtype=torch.uint8, device=A.device)
+  D = torch.empty((B, K), dtype=torch.float32, device=A.device)
+  V = torch.empty((B, Np, K), dtype=torch.float32, device=A.device)
+  info = torch.empty((B,), dtype=torch.int32, device=A.device) if return_info else None
+  strided = A.stride(2) != 1
+  fb = torch.empty((B,), dtype=torch.int32, device=A.device) if (return_fallback or strided) else None
+  wsb = workspace.numel() * workspace.element_size()
+  with torch.cuda.device(A.device):
+    for c0 in range(0, B, chunk):
+      c1 = min(B, c0 + chunk)
+      _abi().lanczos_ritz_kstep_wide(A[c0:c1], A.stride(0), A.stride(1), A.stride(2),
+                                     n_nodes[c0:c1] if n_nodes is not None else None, c1 - c0, Np, M, K, cap,
+                                     workspace, wsb, D[c0:c1], V[c0:c1],
+                                     info[c0:c1] if info is not None else None,
+                                     fb[c0:c1] if fb is not None else None)
+  if strided and bool(fb.any()):
+    # a graph beyond the image's row capacity is multiplied from contiguous dense rows: such a
+    # batch is copied after all (the flags are the only host read of this path)
+    return _kstep_wide(A.contiguous(), n_nodes, B, N, Np, M, K, row_cap, workspace, return_info, return_fallback)
+  if Np != N:
+    V = V[:, :N, :].contiguous()
+  out = (D, V)
+  if return_info:
+    out += (info,)
+  if return_fallback:
+    out += (fb,)
   return out
 
 
@@ -642,29 +706,34 @@ def attached_sparse_image(L):
   return img
 
 
-def lanczos_ritz_collated(L, n_nodes, K, method='auto'):
+def lanczos_ritz_collated(L, n_nodes, K, method='auto', lanczos_steps=None):
   """The Ritz pairs of the collate: lanczos_ritz(L[:, :, :, 0], n_nodes, K) on the collated
   L [B,N,N,C] (dataset/graph_data.py:262-287).  Beyond RITZ_FULL_MAX_N nodes the K-step entry reads
   channel 0 in place, and where the layout allows (the channels-last pair of a single-edge-type
   collate, or one operator in contiguous rows) the SAME pass over L leaves the large-graph conv's
   image riding on L (attach_sparse_image): L is then read from HBM once per batch.
   method='full': the pairs of the full decomposition at every N (sym_eigh_topk, channel 0 read in
-  place); no sparse image is left on L."""
+  place); no sparse image is left on L.
+  lanczos_steps: M >= K steps of the K-step recurrence (None = K).  Beyond 2048 nodes or 64 steps
+  the wide K-step entry serves the pairs and leaves no image: the module builds its own."""
   if method not in ('auto', 'full'):
     raise ValueError("lanczos_ritz_collated: method is 'auto' or 'full', got %r" % (method,))
+  if lanczos_steps is not None and int(lanczos_steps) < K:
+    raise ValueError('lanczos_ritz_collated: lanczos_steps=%d < K=%d' % (lanczos_steps, K))
   B, N, _, Cn = L.shape
   A = L[:, :, :, 0]
   if method == 'full':
     return sym_eigh_topk(A, n_nodes, K)
   pair = Cn == 2 and L.stride(3) == 1 and L.stride(2) == 2
   single = L.stride(2) == 1 and (Cn == 1 or L.stride(3) == 0)
-  if N <= RITZ_FULL_MAX_N or L.dtype != torch.float32 or not (pair or single) or N > 2048:
-    return lanczos_ritz(A, n_nodes, K)
+  if N <= RITZ_FULL_MAX_N or L.dtype != torch.float32 or not (pair or single) or N > KSTEP_WIDE_MAX_N:
+    return lanczos_ritz(A, n_nodes, K, lanczos_steps=lanczos_steps)
   _warn_once('lanczos_ritz: %d > %d nodes — Ritz pairs of the K-step Lanczos recurrence (the '
              'reference\'s use_eigen_decomp=False / eigsh branch, utils/data_helper.py:205-208), not of '
              'the full decomposition; converged leading pairs agree' % (N, RITZ_FULL_MAX_N))
   D, V, img = lanczos_ritz_kstep(A, n_nodes.to(torch.int32).contiguous() if n_nodes is not None else None,
-                                 K, K, conv_image=large_sparse_row_cap(N))
+                                 K if lanczos_steps is None else int(lanczos_steps), K,
+                                 conv_image=large_sparse_row_cap(N))
   if img is not None:
     attach_sparse_image(L, img)
   return D, V

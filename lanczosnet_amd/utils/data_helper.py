@@ -22,7 +22,8 @@ def get_laplacian_l4_batched(adjs, n_nodes):
     return ops.laplacian_l4(adjs, n_nodes)
 
 
-def get_graph_laplacian_eigs_batched(L_simple, n_nodes, k, use_eigen_decomp=None, method='auto'):
+def get_graph_laplacian_eigs_batched(L_simple, n_nodes, k, use_eigen_decomp=None, method='auto',
+                                     lanczos_steps=None):
     """L_simple [B,N,N] (e.g. `L[..., 0]`), n_nodes [B] -> (D [B,k], V [B,N,k]) ordered by
     descending |eigenvalue| like `np.argsort(-|eigs|, kind='mergesort')` (:218-223).
 
@@ -32,11 +33,23 @@ def get_graph_laplacian_eigs_batched(L_simple, n_nodes, k, use_eigen_decomp=None
              to the vendor eigensolver on the device (`torch.linalg.eigh`, fp64) with a UserWarning
              (the reference itself calls this branch "computationally heavy for large size adj");
       False  the k-dimensional Krylov method (`eigsh(L, k, which='LM')`, :208) — the k-step
-             Lanczos of `lnz_lanczos_ritz_kstep`, any N <= 2048, ragged batches;
+             Lanczos of `lnz_lanczos_ritz_kstep` (N <= 2048, k <= 64) or `lnz_lanczos_ritz_kstep_wide`
+             (N <= 16384, k <= 256), ragged batches;
       None   (default) True up to 192 nodes, False beyond, with a UserWarning naming the branch.
     method: 'auto' (the routing above) or 'full': the full decomposition at every N <= 2048 on the
-      hand-written eigensolver (`lnz_sym_eigh_topk`), no warning; not with use_eigen_decomp=False."""
+      hand-written eigensolver (`lnz_sym_eigh_topk`), no warning; not with use_eigen_decomp=False.
+    lanczos_steps: the dimension M >= k of the Krylov space of the k-step branch (ARPACK's `ncv`);
+      None = k, the recurrence of exactly k steps.  Only the k-step branch has it: a ValueError with
+      use_eigen_decomp=True or method='full'; the default routing ignores it up to 192 nodes."""
     from .. import ops
+    if lanczos_steps is not None:
+        lanczos_steps = int(lanczos_steps)
+        if lanczos_steps < k:
+            raise ValueError("get_graph_laplacian_eigs_batched: lanczos_steps=%d < k=%d: the Krylov space "
+                             "holds at least the k pairs kept" % (lanczos_steps, k))
+        if method == 'full' or use_eigen_decomp:
+            raise ValueError("get_graph_laplacian_eigs_batched: lanczos_steps belongs to the k-step branch "
+                             "(use_eigen_decomp=False), not to a full decomposition")
     if method not in ('auto', 'full'):
         raise ValueError("get_graph_laplacian_eigs_batched: method is 'auto' or 'full', got %r" % (method,))
     if method == 'full':
@@ -46,12 +59,12 @@ def get_graph_laplacian_eigs_batched(L_simple, n_nodes, k, use_eigen_decomp=None
         return ops.sym_eigh_topk(L_simple, n_nodes, k)
     N = L_simple.shape[1]
     if use_eigen_decomp is None:
-        return ops.lanczos_ritz(L_simple, n_nodes, k)
+        return ops.lanczos_ritz(L_simple, n_nodes, k, lanczos_steps=lanczos_steps)
     if use_eigen_decomp:
         if N > ops.RITZ_FULL_MAX_N:
             return _full_decomposition_library(L_simple, n_nodes, k)
         return ops.lanczos_ritz(L_simple, n_nodes, k)
-    return ops.lanczos_ritz_kstep(L_simple, n_nodes, min(k, 64), k)
+    return ops.lanczos_ritz_kstep(L_simple, n_nodes, k if lanczos_steps is None else lanczos_steps, k)
 
 
 def _full_decomposition_library(L_simple, n_nodes, k):

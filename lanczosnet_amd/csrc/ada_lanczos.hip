@@ -16,78 +16,13 @@
 //                             products, rounded to fp32 on output)
 //   lnz_ada_symmetrize_filters :276-278 (DD + DD^T)/2, relaid out [B,K,K,S] -> [B,S,K,K]
 #include "common.hpp"
+#include "wave.hpp"
 
 namespace {
 
+using lnz::wave_sum;
+
 constexpr float kEpsF = 1.1920928955078125e-07f;  // np.finfo(np.float32).eps (ada_lanczos_net.py:8)
-
-// ---------------------------------------------------------------------------------------------
-// wave-wide sum, identical in every lane, fixed tree (deterministic): 4 DPP steps inside each
-// 16-lane row, then the 4 row totals via v_readlane.
-// ---------------------------------------------------------------------------------------------
-__device__ inline float dpp_add(float v, int ctrl_sel) {
-  int x = __float_as_int(v), y;
-  switch (ctrl_sel) {
-    case 0: y = __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, false); break;   // quad_perm [1,0,3,2]
-    case 1: y = __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, false); break;   // quad_perm [2,3,0,1]
-    case 2: y = __builtin_amdgcn_update_dpp(0, x, 0x141, 0xF, 0xF, false); break;  // row_half_mirror
-    default: y = __builtin_amdgcn_update_dpp(0, x, 0x140, 0xF, 0xF, false); break; // row_mirror
-  }
-  return v + __int_as_float(y);
-}
-
-__device__ inline float wave_sum(float v) {
-  v = dpp_add(v, 0);
-  v = dpp_add(v, 1);
-  v = dpp_add(v, 2);
-  v = dpp_add(v, 3);
-  float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
-  float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
-  float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
-  float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-  return (r0 + r1) + (r2 + r3);
-}
-
-// fp64 variant: the same tree on the two 32-bit halves of every partial sum
-__device__ inline double dpp_add(double v, int ctrl_sel) {
-  union { double d; int i[2]; } x, y;
-  x.d = v;
-  switch (ctrl_sel) {
-    case 0:
-      y.i[0] = __builtin_amdgcn_update_dpp(0, x.i[0], 0xB1, 0xF, 0xF, false);
-      y.i[1] = __builtin_amdgcn_update_dpp(0, x.i[1], 0xB1, 0xF, 0xF, false);
-      break;
-    case 1:
-      y.i[0] = __builtin_amdgcn_update_dpp(0, x.i[0], 0x4E, 0xF, 0xF, false);
-      y.i[1] = __builtin_amdgcn_update_dpp(0, x.i[1], 0x4E, 0xF, 0xF, false);
-      break;
-    case 2:
-      y.i[0] = __builtin_amdgcn_update_dpp(0, x.i[0], 0x141, 0xF, 0xF, false);
-      y.i[1] = __builtin_amdgcn_update_dpp(0, x.i[1], 0x141, 0xF, 0xF, false);
-      break;
-    default:
-      y.i[0] = __builtin_amdgcn_update_dpp(0, x.i[0], 0x140, 0xF, 0xF, false);
-      y.i[1] = __builtin_amdgcn_update_dpp(0, x.i[1], 0x140, 0xF, 0xF, false);
-      break;
-  }
-  return v + y.d;
-}
-
-__device__ inline double readlane_d(double v, int l) {
-  union { double d; int i[2]; } x, y;
-  x.d = v;
-  y.i[0] = __builtin_amdgcn_readlane(x.i[0], l);
-  y.i[1] = __builtin_amdgcn_readlane(x.i[1], l);
-  return y.d;
-}
-
-__device__ inline double wave_sum(double v) {
-  v = dpp_add(v, 0);
-  v = dpp_add(v, 1);
-  v = dpp_add(v, 2);
-  v = dpp_add(v, 3);
-  return (readlane_d(v, 0) + readlane_d(v, 16)) + (readlane_d(v, 32) + readlane_d(v, 48));
-}
 
 // ---------------------------------------------------------------------------------------------
 // R4: learned graph Laplacian.  One workgroup per molecule.

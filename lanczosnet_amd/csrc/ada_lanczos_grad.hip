@@ -22,8 +22,12 @@
 // Le is symmetric to rounding (D^-1/2 A D^-1/2 of a symmetric A), so Le^T d z0 is taken as Le d z0;
 // dLe = sum_ii d z0 (x) q_ii is NOT symmetrised (autograd through the Laplacian does the rest).
 #include "common.hpp"
+#include "wave.hpp"
 
 namespace {
+
+using lnz::readlane_f64;
+using lnz::wave_sum;
 
 constexpr double kEps = 1.1920928955078125e-07;  // np.finfo(np.float32).eps (ada_lanczos_net.py:8)
 constexpr int NM = 32;                            // rows / steps per molecule
@@ -38,46 +42,12 @@ constexpr int WS_IDX = WS_VM + 33;                // [1]
 constexpr int WS_S = WS_IDX + 1;                  // [2][33][32] Gram-Schmidt coefficients
 constexpr int WS_TOTAL = WS_S + 2 * 33 * NM;
 
-__device__ inline double dpp_add_d(double v, const int sel) {
-  union { double d; int i[2]; } x, y;
-  x.d = v;
-  if (sel == 0) {
-    y.i[0] = __builtin_amdgcn_update_dpp(0, x.i[0], 0xB1, 0xF, 0xF, false);
-    y.i[1] = __builtin_amdgcn_update_dpp(0, x.i[1], 0xB1, 0xF, 0xF, false);
-  } else if (sel == 1) {
-    y.i[0] = __builtin_amdgcn_update_dpp(0, x.i[0], 0x4E, 0xF, 0xF, false);
-    y.i[1] = __builtin_amdgcn_update_dpp(0, x.i[1], 0x4E, 0xF, 0xF, false);
-  } else if (sel == 2) {
-    y.i[0] = __builtin_amdgcn_update_dpp(0, x.i[0], 0x141, 0xF, 0xF, false);
-    y.i[1] = __builtin_amdgcn_update_dpp(0, x.i[1], 0x141, 0xF, 0xF, false);
-  } else {
-    y.i[0] = __builtin_amdgcn_update_dpp(0, x.i[0], 0x140, 0xF, 0xF, false);
-    y.i[1] = __builtin_amdgcn_update_dpp(0, x.i[1], 0x140, 0xF, 0xF, false);
-  }
-  return v + y.d;
-}
-__device__ inline double readlane_d(double v, int l) {
-  union { double d; int i[2]; } x, y;
-  x.d = v;
-  y.i[0] = __builtin_amdgcn_readlane(x.i[0], l);
-  y.i[1] = __builtin_amdgcn_readlane(x.i[1], l);
-  return y.d;
-}
-// wave-wide sum, identical in every lane, fixed tree (the same as ada_lanczos.hip)
-__device__ inline double wave_sum(double v) {
-  v = dpp_add_d(v, 0);
-  v = dpp_add_d(v, 1);
-  v = dpp_add_d(v, 2);
-  v = dpp_add_d(v, 3);
-  return (readlane_d(v, 0) + readlane_d(v, 16)) + (readlane_d(v, 32) + readlane_d(v, 48));
-}
-
 // y[lane] = sum_c ar[c] x[c]: x broadcast lane by lane
 __device__ inline double matvec_row(const double (&ar)[NM], const double x, const int N) {
   double z = 0.0;
 #pragma unroll
   for (int c = 0; c < NM; ++c) {
-    const double xc = readlane_d(x, c);
+    const double xc = readlane_f64(x, c);
     if (c < N) z = fma(ar[c], xc, z);
   }
   return z;
@@ -267,7 +237,7 @@ __global__ __launch_bounds__(64) void ada_lanczos_f64_backward_kernel(
     dq_ii += dalpha * z0 + matvec_row(ar, dz0, N);
 #pragma unroll
     for (int c = 0; c < NM; ++c) {
-      const double qc = readlane_d(q, c);
+      const double qc = readlane_f64(q, c);
       da[c] = fma(dz0, qc, da[c]);
     }
     if (lane < NM) dQs[ii * NM + lane] += dq_ii;

@@ -34,6 +34,7 @@
 // 7.4 MB of packed weights are shared by all workgroups and stay L2 / Infinity-Cache resident.
 #include "common.hpp"
 #include "conv_tiles.hpp"
+#include "wave.hpp"
 #include <type_traits>
 
 namespace {
@@ -817,15 +818,6 @@ __global__ __launch_bounds__(128 * NWV) void lanczosnet_forward_kernel(const lnz
 // channel's GEMM1 runs on Y with the FORWARD weight pack and its result is multiplied with P and
 // reduced over the wave's 32 output columns (lane shuffles) and over the NWV waves (LDS, fixed
 // order: deterministic).  No gains, Laplacians or activations other than X_l / dY_l are read.
-// sum over the 16 lanes of a DPP row, in every lane of the row (quad swaps, then the two mirrors)
-__device__ __forceinline__ float row16_sum(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, false));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, false));
-  return v;
-}
-
 // DEEP: the weight-ring depth as a template constant (1: 8 slots — every layer's channels have a
 // multiple of 8 k-steps —, 0: 4 slots): with both ring loops in one kernel their rings get
 // different registers and the join behind every channel drains the prefetch (see forward_half).
@@ -1003,7 +995,7 @@ __device__ __forceinline__ void gain_grad_half(KArgs& a, const TileDesc (&td)[MT
         float* red = &Xs[1][m][0][0];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const float v = row16_sum(Pb[m][r] * Z[m][r]);
+          const float v = lnz::row16_sum(Pb[m][r] * Z[m][r]);
           if ((lane & 15) == 0)
             red[((wave * 2 + ((lane >> 4) & 1)) * S + s) * 32 + lnz::cd_row(r, hh)] = v;
         }

@@ -36,6 +36,7 @@
 // offset = 0.0) so that every s_waitcnt vmcnt is exact.
 #include "common.hpp"
 #include "conv_tiles.hpp"
+#include "wave.hpp"
 #include <type_traits>
 
 namespace {
@@ -946,14 +947,6 @@ __device__ __forceinline__ void strip_forward(KArgs& a, const int32_t* __restric
 // LDS over X_l, P kept in C/D registers), then each long channel's GEMM1 runs on Y with the FORWARD
 // weight pack and its result is multiplied with P and reduced over the wave's 16 columns (DPP row
 // sums) and over the eight waves (LDS, fixed order: deterministic).
-__device__ __forceinline__ float row16_sum(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, false));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, false));
-  return v;
-}
-
 template <int S>
 __device__ __forceinline__ void strip_gain_grad(KArgs& a, const int32_t* __restrict__ ent, float* lds,
                                                 const int tid, const int wave) {
@@ -1118,7 +1111,7 @@ __device__ __forceinline__ void strip_gain_grad(KArgs& a, const int32_t* __restr
       for (int I = 0; I < S; ++I)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float v = row16_sum(Pb[I][r] * Z[I][r]);
+          const float v = lnz::row16_sum(Pb[I][r] * Z[I][r]);
           if (j == 0) red[(wave * nl + s) * R + 16 * I + 4 * kq + r] = v;
         }
     }

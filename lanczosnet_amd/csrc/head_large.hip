@@ -6,28 +6,14 @@
 // (two per lane), P + 1 <= 32 dot products per row as lane partials + one butterfly each; the masked
 // sums stay in registers and meet in LDS in a fixed order (deterministic).
 #include "common.hpp"
+#include "wave.hpp"
 
 namespace {
 
+using lnz::wave_sum;
+
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int HW = 16;   // waves per workgroup
-
-template <int CTRL>
-__device__ __forceinline__ float dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-// sum over the 64 lanes, the same bits in every lane
-__device__ __forceinline__ float wave_sum(float v) {
-  v += dpp<0xB1>(v);    // quad_perm [1,0,3,2]
-  v += dpp<0x4E>(v);    // quad_perm [2,3,0,1]
-  v += dpp<0x141>(v);   // row_half_mirror
-  v += dpp<0x140>(v);   // row_mirror
-  const float s0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
-  const float s1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
-  const float s2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
-  const float s3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-  return (s0 + s1) + (s2 + s3);
-}
 
 template <int PT>   // outputs (P <= PT); the gate is row P of Whead
 __global__ __launch_bounds__(64 * HW) void large_head_kernel(

@@ -16,8 +16,13 @@
 // + 4 N K (V) : 1.074 GB + 0.133 GB + 0.5 MB at N = 2048, M = K = 64.
 #include "common.hpp"
 #include "ell_image.hpp"
+#include "tql2.hpp"
 
 namespace {
+
+using lnz::kEpsF64;
+using lnz::readlane_f64;
+using lnz::wave_sum;
 
 constexpr int TPB = 512;
 constexpr int NWAVE = TPB / 64;
@@ -26,7 +31,6 @@ constexpr int MMAX = 64;        // Lanczos steps
 constexpr int ZLD = MMAX;      // QL accumulator rows (aliases the q/w vectors, dead by then)
 constexpr double kTol = 1e-8;
 constexpr double kReorth = 1e-6;  // second Gram-Schmidt pass when |w1|^2 < kReorth |w0|^2
-constexpr double kEpsD = 2.220446049250313e-16;
 
 struct LargeSmem {
   union {
@@ -51,47 +55,8 @@ struct LargeSmem {
   float sgn[MMAX];
 };
 
-__device__ inline double dpp_xadd_f64(double v, int sel) {
-  int lo = __double2loint(v), hi = __double2hiint(v), l2, h2;
-  switch (sel) {
-    case 0:
-      l2 = __builtin_amdgcn_update_dpp(0, lo, 0xB1, 0xF, 0xF, false);
-      h2 = __builtin_amdgcn_update_dpp(0, hi, 0xB1, 0xF, 0xF, false);
-      break;
-    case 1:
-      l2 = __builtin_amdgcn_update_dpp(0, lo, 0x4E, 0xF, 0xF, false);
-      h2 = __builtin_amdgcn_update_dpp(0, hi, 0x4E, 0xF, 0xF, false);
-      break;
-    case 2:
-      l2 = __builtin_amdgcn_update_dpp(0, lo, 0x141, 0xF, 0xF, false);
-      h2 = __builtin_amdgcn_update_dpp(0, hi, 0x141, 0xF, 0xF, false);
-      break;
-    default:
-      l2 = __builtin_amdgcn_update_dpp(0, lo, 0x140, 0xF, 0xF, false);
-      h2 = __builtin_amdgcn_update_dpp(0, hi, 0x140, 0xF, 0xF, false);
-      break;
-  }
-  return v + __hiloint2double(h2, l2);
-}
-
-// wave-wide fp64 sum, identical in every lane, fixed tree
-__device__ inline double wave_sum_f64(double v) {
-  v = dpp_xadd_f64(v, 0);
-  v = dpp_xadd_f64(v, 1);
-  v = dpp_xadd_f64(v, 2);
-  v = dpp_xadd_f64(v, 3);
-  double r[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    int lo = __builtin_amdgcn_readlane(__double2loint(v), 16 * k);
-    int hi = __builtin_amdgcn_readlane(__double2hiint(v), 16 * k);
-    r[k] = __hiloint2double(hi, lo);
-  }
-  return (r[0] + r[1]) + (r[2] + r[3]);
-}
-
 __device__ inline double block_sum(LargeSmem& sm, double part, int tid) {
-  double w = wave_sum_f64(part);
+  double w = wave_sum(part);
   if ((tid & 63) == 0) sm.red[tid >> 6] = w;
   __syncthreads();
   double t = 0.0;
@@ -147,22 +112,15 @@ __device__ inline void sym_list(SymSched& sc, int N) {  // one thread
   sc.next = 0;
 }
 
-// value of lane i (wave-uniform i) of a per-lane double
-__device__ __forceinline__ double lane_f64(double v, int i) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), i);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), i);
-  return __hiloint2double(hi, lo);
-}
-
 // Implicit-shift QL (tql2 recurrences) on the n x n tridiagonal (sm.dd, sm.ee), n <= 64, by ONE
 // wavefront; sm.Zt (identity on entry) receives the eigenvectors transposed, sm.dd the eigenvalues.
 __device__ inline void tql2_wave(LargeSmem& sm, const int n, const int lane) {
   double d = sm.dd[lane], e = sm.ee[lane];  // (MMAX == 64 entries, zero past n)
   double f = 0.0, tst1 = 0.0;
   for (int l = 0; l < n; ++l) {
-    tst1 = fmax(tst1, fabs(lane_f64(d, l)) + fabs(lane_f64(e, l)));
+    tst1 = fmax(tst1, fabs(readlane_f64(d, l)) + fabs(readlane_f64(e, l)));
     // first m >= l with m == n - 1 or a negligible coupling e_m
-    unsigned long long stop = __ballot(lane >= n - 1 || !(fabs(e) > kEpsD * tst1));
+    unsigned long long stop = __ballot(lane >= n - 1 || !(fabs(e) > kEpsF64 * tst1));
     stop &= ~0ull << l;
     const int m = __builtin_ctzll(stop);
     if (m > l) {
@@ -170,70 +128,42 @@ __device__ inline void tql2_wave(LargeSmem& sm, const int n, const int lane) {
       double el;
       do {
         ++iter;
-        double g = lane_f64(d, l);
-        el = lane_f64(e, l);
-        double p = (lane_f64(d, l + 1) - g) / (2.0 * el);
-        double rr = sqrt(p * p + 1.0);
-        if (p < 0) rr = -rr;
-        const double dl = el / (p + rr);
-        const double dl1 = el * (p + rr);
-        const double hh = g - dl;
-        if (lane == l) d = dl;
-        if (lane == l + 1) d = dl1;
-        if (lane >= l + 2 && lane < n) d -= hh;
-        f += hh;
-        p = lane_f64(d, m);
-        double c = 1.0, c2 = 1.0, c3 = 1.0, s = 0.0, s2 = 0.0;
-        const double el1 = lane_f64(e, l + 1);
+        el = readlane_f64(e, l);
+        const lnz::QlShift sh = lnz::ql_shift(readlane_f64(d, l), readlane_f64(d, l + 1), el);
+        if (lane == l) d = sh.dl;
+        if (lane == l + 1) d = sh.dl1;
+        if (lane >= l + 2 && lane < n) d -= sh.hh;
+        f += sh.hh;
+        lnz::QlRotation rot(readlane_f64(d, m));
+        const double el1 = readlane_f64(e, l + 1);
         double carry = sm.Zt[m * ZLD + lane];
         double z0 = sm.Zt[(m - 1) * ZLD + lane];  // (m > l >= 0)
-        double ei = lane_f64(e, m - 1), di = lane_f64(d, m - 1);
+        double ei = readlane_f64(e, m - 1), di = readlane_f64(d, m - 1);
         for (int i = m - 1; i >= l; --i) {
           // the next rotation's inputs ahead of time: none of them is written by this rotation
           const int ip = i > l ? i - 1 : l;
           const double znext = sm.Zt[ip * ZLD + lane];
-          const double ei_n = lane_f64(e, ip), di_n = lane_f64(d, ip);
-          c3 = c2;
-          c2 = c;
-          s2 = s;
-          g = c * ei;
-          const double hp = c * p;
-          const double tt = fma(p, p, ei * ei);
-          const double num = fma(p, di, -(ei * g));  // (p d_i - e_i g): off the rsqrt chain
-          // 1 / sqrt(tt): hardware seed (~2^-26) + two Newton steps (tt is a normal double here:
-          // |e_i| > eps * tst1 for l <= i < m) — 7 dependent instructions on the rotation-to-rotation
-          // chain instead of the library rsqrt's scaling and special cases
-          double y = __builtin_amdgcn_rsq(tt);
-#pragma unroll
-          for (int it = 0; it < 2; ++it) {
-            const double hy = 0.5 * y;
-            const double er = fma(-(tt * y), hy, 0.5);
-            y = fma(y, er, y);
-          }
-          const double rad = tt * y;
-          const double e_next = s * rad;
-          s = ei * y;
-          c = p * y;
-          p = y * num;  // = c d_i - s g
-          const double d_next = hp + s * (c * g + s * di);
+          const double ei_n = readlane_f64(e, ip), di_n = readlane_f64(d, ip);
+          double e_next, d_next;
+          rot.step<2>(ei, di, e_next, d_next);
           if (lane == i + 1) {
             e = e_next;
             d = d_next;
           }
-          sm.Zt[(i + 1) * ZLD + lane] = s * z0 + c * carry;
-          carry = c * z0 - s * carry;
+          sm.Zt[(i + 1) * ZLD + lane] = rot.s * z0 + rot.c * carry;
+          carry = rot.c * z0 - rot.s * carry;
           z0 = znext;
           ei = ei_n;
           di = di_n;
         }
         sm.Zt[l * ZLD + lane] = carry;
-        p = -s * s2 * c3 * el1 * lane_f64(e, l) / dl1;
-        el = s * p;
+        double dl_new;
+        rot.close(el1, readlane_f64(e, l), sh.dl1, el, dl_new);
         if (lane == l) {
           e = el;
-          d = c * p;
+          d = dl_new;
         }
-      } while (fabs(el) > kEpsD * tst1 && iter < 60);
+      } while (fabs(el) > kEpsF64 * tst1 && iter < 60);
     }
     if (lane == l) {
       d += f;
@@ -263,10 +193,7 @@ __device__ inline void reduce16_f64(const double (&p)[16], double (&v)[4]) {
     auto rl = __builtin_amdgcn_permlane16_swap(xl, yl, false, false);
     auto rh = __builtin_amdgcn_permlane16_swap(xh, yh, false, false);
     double t = __hiloint2double((int)rh[0], (int)rl[0]) + __hiloint2double((int)rh[1], (int)rl[1]);
-    t = dpp_xadd_f64(t, 0);
-    t = dpp_xadd_f64(t, 1);
-    t = dpp_xadd_f64(t, 2);
-    v[i] = dpp_xadd_f64(t, 3);
+    v[i] = lnz::row16_sum(t);
   }
 }
 
@@ -303,7 +230,7 @@ __device__ __forceinline__ void cgs_pass(LargeSmem& sm, const double* __restrict
       s0 = fma(g1.x, wreg[s][2], s0);
       s1 = fma(g1.y, wreg[s][3], s1);
     }
-    const double c = wave_sum_f64(s0 + s1);
+    const double c = wave_sum(s0 + s1);
     if (lane == 0) sm.cs[i] = c;
 #pragma unroll
     for (int s = 0; s < NCH; ++s)
@@ -391,14 +318,11 @@ __global__ __launch_bounds__(TPB) void lanczos_ritz_large_kernel(
   unsigned long long t_last = wall_clock64();
 #endif
 
-  // start vector (same hash as the small-graph kernel)
+  // start vector
   double part = 0.0;
   for (int r = tid; r < NCH * 256; r += TPB) {
     double w = 0.0;
-    if (r < n_b) {
-      unsigned hsh = (unsigned)(r + 1) * 2654435761u;
-      w = 1.0 + (double)((hsh >> 8) & 0xffff) * (1.0 / 65536.0);
-    }
+    if (r < n_b) w = lnz::lanczos_start_entry(r);
     sm.ws[r] = w;
     part += w * w;
   }
@@ -656,11 +580,11 @@ __global__ __launch_bounds__(TPB) void lanczos_ritz_large_kernel(
         for (; r < N; r += 2 * NWAVE) {
           const int r1 = r + NWAVE, r2 = r + 2 * NWAVE;
           if (r1 < N) load_row(r1, a1);
-          double t0 = wave_sum_f64(dot_row(a0));
+          double t0 = wave_sum(dot_row(a0));
           if (lane == 0) sm.ws[r] = t0;
           if (r2 < N) load_row(r2, a0);
           if (r1 < N) {
-            double t1 = wave_sum_f64(dot_row(a1));
+            double t1 = wave_sum(dot_row(a1));
             if (lane == 0) sm.ws[r1] = t1;
           }
         }
@@ -709,7 +633,7 @@ __global__ __launch_bounds__(TPB) void lanczos_ritz_large_kernel(
               s1 = fma(g1.y, w1.y, s1);
             }
           }
-          double c = wave_sum_f64(s0 + s1);
+          double c = wave_sum(s0 + s1);
           if (lane == 0) sm.cs[i] = c;
         }
         __syncthreads();

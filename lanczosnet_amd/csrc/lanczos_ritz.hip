@@ -15,13 +15,17 @@
 #include "common.hpp"
 #include "prep.hpp"
 #include "gains_body.hpp"
+#include "tql2.hpp"
 
 namespace {
+
+using lnz::kEpsF64;
+using lnz::rcp_nr;
+using lnz::readlane_f64;
 
 // |A| <= 1 for L4.  Dropping a coupling beta < tol perturbs T by tol; keeping it leaves q_{j+1}
 // orthogonal only to eps/beta after CGS2 — both errors balance at sqrt(eps) ~ 1e-8.
 constexpr double kBreakdownTol = 1e-8;
-constexpr double kEps = 2.220446049250313e-16;
 
 // =========================================================================================
 // Fast path, N <= 32 (QM8): same algorithm, scheduled for latency.
@@ -87,12 +91,6 @@ __device__ inline double xhalf_sum(double x) {
   double a = __hiloint2double((int)rh[0], (int)rl[0]);  // lower-half value, in every lane
   double b = __hiloint2double((int)rh[1], (int)rl[1]);  // upper-half value, in every lane
   return a + b;
-}
-
-__device__ inline double readlane_f64(double v, int l) {
-  int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-  int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-  return __hiloint2double(hi, lo);
 }
 
 __device__ inline void load16(const double* p, double (&v)[16]) {
@@ -177,11 +175,6 @@ __device__ inline double cgs2_32(const Ritz32Smem& sm, double& x, int j, int r, 
 //      reads of the basis, then the basis rows are overwritten by the Ritz vectors.
 // On exit sm.dd[k] / sm.Qt[k][.] hold eigenpair k (any order), like after the QL sweep.
 // -----------------------------------------------------------------------------------------
-__device__ __forceinline__ double rcp_nr(double x) {
-  double y = __builtin_amdgcn_rcp(x);
-  return fma(y, fma(-x, y, 1.0), y);
-}
-
 // ---- 2. eigenvalue search.  Sturm count in product form — p_i = (d_i - x) p_{i-1} - e_{i-1}^2 p_{i-2},
 // one dependent FMA per row instead of a division; the count is the number of sign changes of the
 // sequence, collected as sign bits (one v_alignbit per row and probe).  ALL blocks of T are
@@ -316,7 +309,7 @@ __device__ __forceinline__ void eigenvalue_search(const Ritz32Smem& sm, EigState
   for (int it = it0; it < 30; ++it) {
     if (__all(st.done || halt)) break;
     const double lo = st.lo, hi = st.hi, w = hi - lo;
-    const double tol = 4.0 * kEps * fmax(fmax(fabs(lo), fabs(hi)), 0.125 * gsc);
+    const double tol = 4.0 * kEpsF64 * fmax(fmax(fabs(lo), fabs(hi)), 0.125 * gsc);
     // the neighbouring lanes' brackets
     double m_dn, m_up;
     lane_neighbours(0.5 * (lo + hi), m_dn, m_up);
@@ -370,7 +363,7 @@ __device__ __forceinline__ void eigenvalue_search(const Ritz32Smem& sm, EigState
     // LAPACK dstebz's stopping rule: relative to |lambda| but never below ulp * |T|.  (Stopping the
     // lanes of a cluster at 1e-12 |T| was tried: 5 passes fewer, and one molecule in 30 k whose
     // cluster vectors lost orthogonality to 3e-5.)
-    st.done = st.done || nw <= 4.0 * kEps * fmax(fmax(fabs(st.lo), fabs(st.hi)), 0.125 * gsc);
+    st.done = st.done || nw <= 4.0 * kEpsF64 * fmax(fmax(fabs(st.lo), fabs(st.hi)), 0.125 * gsc);
     if (may_bail && it == 12) {
       // Two eigenvalues of ONE block still sharing a bracket: a degenerate eigenvalue whose
       // second copy crept into the Krylov space through round-off instead of a clean breakdown
@@ -396,7 +389,7 @@ __device__ inline bool tridiag_eig_parallel(const Ritz32Smem& sm, const double d
   if (ts) ts[0] = clock64();
   // ---- d, e -> LDS (broadcast reads); negligible couplings split the matrix
   const double dn = __shfl_down(dreg, 1, 64);
-  const bool live = r < n - 1 && fabs(ereg) > kEps * (fabs(dreg) + fabs(dn));
+  const bool live = r < n - 1 && fabs(ereg) > kEpsF64 * (fabs(dreg) + fabs(dn));
   const double e_live = live ? fabs(ereg) : 0.0;
   const double e_prev = __shfl_up(e_live, 1, 64);
   const bool act = r < n;
@@ -534,7 +527,7 @@ __device__ inline bool tridiag_eig_parallel(const Ritz32Smem& sm, const double d
   //      Dw[0] / Dw[1] ([row][eigen lane]: conflict free).  gamma_i = D+_i + D-_i - (d_i - lam);
   //      twist where |gamma| is smallest; then half 0 solves upwards from the twist index, half 1
   //      downwards, and the vector replaces D+ in Dw[0].  Loop bounds: the longest block.
-  const double tiny = kEps * gsc;
+  const double tiny = kEpsF64 * gsc;
   const int len = act ? t - s : -1;
   {
     // pivot chains: one reciprocal per row is the critical path (rcp, Newton step, FMA, clamp);
@@ -742,10 +735,7 @@ __device__ __forceinline__ void lanczos_ritz32_body(
   double dreg = 0.0, ereg = 0.0;  // lane r holds T[r][r], T[r][r+1]
   if (n > 0) {
     double w = 0.0;
-    if (r < n) {
-      unsigned hsh = (unsigned)(r + 1) * 2654435761u;
-      w = 1.0 + (double)((hsh >> 8) & 0xffff) * (1.0 / 65536.0);
-    }
+    if (r < n) w = lnz::lanczos_start_entry(r);
     bool fresh = true;  // w is a start/restart vector: its norm is not a coupling beta
     for (int j = 0; j < n; ++j) {
       double beta, u, binv;
@@ -760,13 +750,7 @@ __device__ __forceinline__ void lanczos_ritz32_body(
         {
           // 1 / sqrt(nn) by the hardware seed + two Newton steps, beta = nn / sqrt(nn): one chain
           // of 9 instructions instead of a square root and a division (about 25)
-          double y = __builtin_amdgcn_rsq(nn);
-#pragma unroll
-          for (int it = 0; it < 2; ++it) {
-            const double hy = 0.5 * y;
-            const double er = fma(-(nn * y), hy, 0.5);
-            y = fma(y, er, y);
-          }
+          const double y = lnz::rsq_nr<2>(nn);
           binv = y;
           beta = nn > 0.0 ? nn * y : 0.0;
         }
@@ -828,25 +812,18 @@ __device__ __forceinline__ void lanczos_ritz32_body(
     for (int l = 0; l < n; ++l) {
       tst1 = fmax(tst1, fabs(readlane_f64(dreg, l)) + fabs(readlane_f64(ereg, l)));
       const unsigned long long small =
-          __ballot(h == 0 && r >= l && r < n && (r == n - 1 || fabs(ereg) <= kEps * tst1));
+          __ballot(h == 0 && r >= l && r < n && (r == n - 1 || fabs(ereg) <= kEpsF64 * tst1));
       const int m = __builtin_ctzll(small);
       if (m > l) {
         int iter = 0;
         double el;
         do {
           ++iter;
-          double g = readlane_f64(dreg, l);
           el = readlane_f64(ereg, l);
-          double p = (readlane_f64(dreg, l + 1) - g) / (2.0 * el);
-          double rr = sqrt(p * p + 1.0);
-          if (p < 0) rr = -rr;
-          const double dl = el / (p + rr);
-          const double dl1 = el * (p + rr);
-          const double hh = g - dl;
-          dreg = (r == l) ? dl : (r == l + 1) ? dl1 : (r >= l + 2 && r < n) ? dreg - hh : dreg;
-          f += hh;
-          p = readlane_f64(dreg, m);
-          double c = 1.0, c2 = 1.0, c3 = 1.0, s = 0.0, s2 = 0.0;
+          const lnz::QlShift sh = lnz::ql_shift(readlane_f64(dreg, l), readlane_f64(dreg, l + 1), el);
+          dreg = (r == l) ? sh.dl : (r == l + 1) ? sh.dl1 : (r >= l + 2 && r < n) ? dreg - sh.hh : dreg;
+          f += sh.hh;
+          lnz::QlRotation rot(readlane_f64(dreg, m));
           const double el1 = readlane_f64(ereg, l + 1);
           double carry = sm.Qt[m * LD + r];
           double z0 = sm.Qt[(m - 1) * LD + r];
@@ -859,45 +836,27 @@ __device__ __forceinline__ void lanczos_ritz32_body(
             const double znext = sm.Qt[ip * LD + r];
             const double ei_n = readlane_f64(ereg, ip);
             const double di_n = readlane_f64(dreg, ip);
-            c3 = c2;
-            c2 = c;
-            s2 = s;
-            g = c * ei;
-            const double hp = c * p;
-            const double tt = fma(p, p, ei * ei);
-            const double num = fma(p, di, -(ei * g));  // (p d_i - e_i g): off the rsqrt chain
-            // 1/sqrt(tt): hardware seed + ONE Newton step (tt is a normal double here:
-            // |e_i| > eps * tst1 for l <= i < m).  v_rsq_f64's seed is good to ~2^-26, one step
-            // squares that; the outputs of this kernel are fp32 (a second step changed D by at
-            // most one fp32 ulp and no Ritz residual on 1024 molecules, and costs 4 % of the kernel:
-            // the three dependent FMAs sit on the rotation-to-rotation critical path).
-            double y = __builtin_amdgcn_rsq(tt);
-            {
-              double hy = 0.5 * y;
-              double er = fma(-(tt * y), hy, 0.5);
-              y = fma(y, er, y);
-            }
-            const double rad = tt * y;
-            const double e_next = s * rad;
-            s = ei * y;
-            c = p * y;
-            p = y * num;  // = c d_i - s g
-            const double d_next = hp + s * (c * g + s * di);
+            // ONE Newton step behind v_rsq_f64's seed (good to ~2^-26, one step squares that): the
+            // outputs of this kernel are fp32 (a second step changed D by at most one fp32 ulp and
+            // no Ritz residual on 1024 molecules, and costs 4 % of the kernel: the three dependent
+            // FMAs sit on the rotation-to-rotation critical path).
+            double e_next, d_next;
+            rot.step<1>(ei, di, e_next, d_next);
             ereg = (r == i + 1) ? e_next : ereg;
             dreg = (r == i + 1) ? d_next : dreg;
-            sm.Qt[(i + 1) * LD + r] = s * z0 + c * carry;  // both halves hold the same value
-            carry = c * z0 - s * carry;
+            sm.Qt[(i + 1) * LD + r] = rot.s * z0 + rot.c * carry;  // both halves hold the same value
+            carry = rot.c * z0 - rot.s * carry;
             z0 = znext;
             ei = ei_n;
             di = di_n;
           }
           if (h == 0) sm.Qt[l * LD + r] = carry;
-          p = -s * s2 * c3 * el1 * readlane_f64(ereg, l) / dl1;
-          el = s * p;
+          double dl_new;
+          rot.close(el1, readlane_f64(ereg, l), sh.dl1, el, dl_new);
           ereg = (r == l) ? el : ereg;
-          dreg = (r == l) ? c * p : dreg;
+          dreg = (r == l) ? dl_new : dreg;
           __syncthreads();  // rows written by half 0 are re-read by both halves next sweep
-        } while (fabs(el) > kEps * tst1 && iter < 60);
+        } while (fabs(el) > kEpsF64 * tst1 && iter < 60);
       }
       dreg = (r == l) ? dreg + f : dreg;
       ereg = (r == l) ? 0.0 : ereg;
@@ -912,12 +871,10 @@ __device__ __forceinline__ void lanczos_ritz32_body(
     // ---- order by descending |lambda| (ties: ascending lambda, then index) — see generic kernel
     {
       // every lane compares its eigenvalue with the others' through lane reads (no LDS walk)
-      const double di = lane < n ? sm.dd[lane] : 0.0, ai = fabs(di);
+      const double di = lane < n ? sm.dd[lane] : 0.0;
       int rank = 0;
       for (int jj = 0; jj < n; ++jj) {
-        const double dj = readlane_f64(di, jj), aj = fabs(dj);
-        const bool before = (aj > ai) || (aj == ai && (dj < di || (dj == di && jj < lane)));
-        rank += before ? 1 : 0;
+        rank += lnz::abs_desc_before(readlane_f64(di, jj), jj, di, lane) ? 1 : 0;
       }
       if (lane < n) sm.perm[rank] = lane;
     }
@@ -1214,6 +1171,9 @@ extern "C" int lnz_lanczos_ritz(const float* A, int64_t stride_b, int64_t stride
 // reference leaves to LAPACK / ARPACK).  One wavefront per matrix, M <= 64; same tql2 recurrences
 // as the fused kernels, eigenvectors accumulated from the identity.  Output ascending (LAPACK
 // convention): R [B,M], Bm [B,M,M] with columns = eigenvectors (Bm[b][i][k] = component i of k).
+// Its sweep does NOT go through tql2.hpp: it takes 1 / sqrt from the library rsqrt and forms
+// p = c d_i - s g as written — other roundings than the fused kernels' rotation, and its results
+// are pinned at 1e-12 as they are.
 // ---------------------------------------------------------------------------------------------
 namespace {
 __global__ __launch_bounds__(64) void tridiag_eigh_kernel(const double* __restrict__ diag,
@@ -1236,7 +1196,7 @@ __global__ __launch_bounds__(64) void tridiag_eigh_kernel(const double* __restri
   for (int l = 0; l < n; ++l) {
     tst1 = fmax(tst1, fabs(dd[l]) + fabs(ee[l]));
     int m = l;
-    while (m < n - 1 && fabs(ee[m]) > kEps * tst1) ++m;
+    while (m < n - 1 && fabs(ee[m]) > kEpsF64 * tst1) ++m;
     if (m > l) {
       int iter = 0;
       double el;
@@ -1289,7 +1249,7 @@ __global__ __launch_bounds__(64) void tridiag_eigh_kernel(const double* __restri
           dd[l] = c * p;
         }
         __syncthreads();
-      } while (fabs(el) > kEps * tst1 && iter < 60);
+      } while (fabs(el) > kEpsF64 * tst1 && iter < 60);
     }
     __syncthreads();
     if (lane == 0) {

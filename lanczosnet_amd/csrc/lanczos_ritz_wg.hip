@@ -27,8 +27,13 @@
 //     i, i+1 touches only its own two words), each wavefront carries a PRIVATE copy of T's diagonal
 //     and off-diagonal (in the then dead A region) and runs the scalar recurrences redundantly.
 #include "common.hpp"
+#include "tql2.hpp"
 
 namespace {
+
+using lnz::kEpsF64;
+using lnz::rcp_nr;
+using lnz::wave_sum;
 
 #ifndef LNZ_WG_CGS_AGAIN_WAVES
 #define LNZ_WG_CGS_AGAIN_WAVES 0.99   // the same for the wave-level form (n <= 128)
@@ -48,7 +53,6 @@ namespace {
 #define LNZ_WG_BREAKDOWN_TOL 1e-8
 #endif
 constexpr double kBreakdownTol = LNZ_WG_BREAKDOWN_TOL;  // see lanczos_ritz.hip
-constexpr double kEps = 2.220446049250313e-16;
 #ifndef LNZ_RITZ_WG_THREADS
 #define LNZ_RITZ_WG_THREADS 512
 #endif
@@ -119,11 +123,6 @@ inline size_t wg_lds_bytes(int N, bool qg) {
   // (+ 8: A starts on a 16-byte boundary behind an odd number of basis doubles)
   return sizeof(WgFixed) + (qg ? 0 : sizeof(LwExtra) + (size_t)N * (size_t)(N | 1) * sizeof(double) + 8) +
          wg_a_bytes(N, qg);
-}
-
-__device__ __forceinline__ double rcp_nr(double x) {  // 1/x: hardware seed + one Newton step
-  double y = __builtin_amdgcn_rcp(x);
-  return fma(y, fma(-x, y, 1.0), y);
 }
 
 // The unreduced block [bs, bt] of T that row e belongs to, from the bit mask of the rows whose
@@ -228,30 +227,6 @@ __device__ __forceinline__ void sturm2(const double* __restrict__ d, const doubl
 // for another wave: the only cross-lane traffic is the broadcast of a
 // vector through LDS (same wave: in order, no barrier) and three wave reductions by DPP.  The
 // other seven waves wait at the barrier behind the phase.
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-  return __hiloint2double(hi, lo);
-}
-
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
-  return __hiloint2double(hi, lo);
-}
-
-// sum over the 64 lanes, bit-identical in every lane (symmetric pairings inside a row of 16, the
-// four row sums added in a fixed order)
-__device__ __forceinline__ double wave_sum_f64(double v) {
-  v += dpp_f64<0xB1>(v);    // quad_perm [1,0,3,2]
-  v += dpp_f64<0x4E>(v);    // quad_perm [2,3,0,1]
-  v += dpp_f64<0x141>(v);   // row_half_mirror
-  v += dpp_f64<0x140>(v);   // row_mirror
-  const double s0 = readlane_f64(v, 0), s1 = readlane_f64(v, 16);
-  const double s2 = readlane_f64(v, 32), s3 = readlane_f64(v, 48);
-  return (s0 + s1) + (s2 + s3);
-}
 
 // LDS traffic between the lanes of one wave: in order in hardware; this keeps the compiler from
 // moving a load over the store it depends on
@@ -490,7 +465,7 @@ __device__ __forceinline__ int lanczos_waves(WgFixed& sm, LwExtra& lw, double* _
         c1 = walk_own(Ql + (lane + 64) * LD + dr0, zb + dr0, dr1 - dr0);
         c1 = vk1 ? c1 : 0.0;
       }
-      double xx = wave_sum_f64(x * x);   // (rows beyond n hold 0)
+      double xx = wave_sum(x * x);   // (rows beyond n hold 0)
       if constexpr (W > 1) {
         if (h == 0 && lane == 0) lw.px[g] = xx;
         pc[wave * RW + lane] = c0;
@@ -511,7 +486,7 @@ __device__ __forceinline__ int lanczos_waves(WgFixed& sm, LwExtra& lw, double* _
       if (G == 2 && vk1) cbw[lane + 64] = c1;
       bool again = true;
       if (pass == 0) {
-        const double cc2 = wave_sum_f64(fma(c0, c0, c1 * c1));
+        const double cc2 = wave_sum(fma(c0, c0, c1 * c1));
         again = !(cc2 <= LNZ_WG_CGS_AGAIN_WAVES * xx);
       }
       wave_sync();
@@ -536,10 +511,7 @@ __device__ __forceinline__ int lanczos_waves(WgFixed& sm, LwExtra& lw, double* _
 
   // deterministic, strictly positive, non-symmetric start vector (as lanczos_ritz.hip)
   double w = 0.0;
-  if (vr) {
-    const unsigned hsh = (unsigned)(row + 1) * 2654435761u;
-    w = 1.0 + (double)((hsh >> 8) & 0xffff) * (1.0 / 65536.0);
-  }
+  if (vr) w = lnz::lanczos_start_entry(row);
   if (wave == 0 && lane < 4 && n + lane < n4) sm.zb[n + lane] = 0.0;   // A w reads the vector four columns at a time
   const __attribute__((address_space(3))) float* Al = (const __attribute__((address_space(3))) float*)As;
   bool fresh = true;  // w is a start / restart vector: its norm is not a coupling beta
@@ -551,7 +523,7 @@ __device__ __forceinline__ int lanczos_waves(WgFixed& sm, LwExtra& lw, double* _
       bar();
       u = walk_arow(Al + row * LA + ac0, zb + ac0, ac1 - ac0);   // (lanes beyond n walk rows that were never staged)
       u = vr ? u : 0.0;
-      double nn = wave_sum_f64(w * w);
+      double nn = wave_sum(w * w);
       if constexpr (W > 1) {
         if (H > 1) pu[h * RW + row] = u;
         if (h == 0 && lane == 0) lw.pn[g] = nn;
@@ -845,10 +817,7 @@ __global__ __launch_bounds__(kNT) void lanczos_ritz_wg_kernel(
 
     // deterministic, strictly positive, non-symmetric start vector (as lanczos_ritz.hip)
     double w = 0.0;
-    if (tid < n) {
-      unsigned hsh = (unsigned)(tid + 1) * 2654435761u;
-      w = 1.0 + (double)((hsh >> 8) & 0xffff) * (1.0 / 65536.0);
-    }
+    if (tid < n) w = lnz::lanczos_start_entry(tid);
     bool fresh = true;  // w is a start / restart vector: its norm is not a coupling beta
     for (int j = 0; j < n; ++j) {
       double beta, u;
@@ -999,7 +968,7 @@ __global__ __launch_bounds__(kNT) void lanczos_ritz_wg_kernel(
       if (tid < n) {
         const double di = sm.dd[tid], ei = tid < n - 1 ? sm.ee[tid] : 0.0;
         const double dn = tid < n - 1 ? sm.dd[tid + 1] : 0.0;
-        live = tid < n - 1 && fabs(ei) > kEps * (fabs(di) + fabs(dn));
+        live = tid < n - 1 && fabs(ei) > kEpsF64 * (fabs(di) + fabs(dn));
         Td[tid] = di;
         Te[tid] = live ? ei : 0.0;
         Te2[tid] = live ? ei * ei : 0.0;
@@ -1053,7 +1022,7 @@ __global__ __launch_bounds__(kNT) void lanczos_ritz_wg_kernel(
       __syncthreads();
       for (int it = 0; it < 48; ++it) {
         const double w = hi - lo;
-        const double tol = 4.0 * kEps * fmax(fmax(fabs(lo), fabs(hi)), 0.125 * gsc);
+        const double tol = 4.0 * kEpsF64 * fmax(fmax(fabs(lo), fabs(hi)), 0.125 * gsc);
         const bool iso = it > 0 && !sect && chi - clo == 1 && flo != 0.0f && ((flo < 0.0f) != (fhi < 0.0f));
         double xs = 0.0, d1 = 0.0;
         if (iso && !done) {
@@ -1106,7 +1075,7 @@ __global__ __launch_bounds__(kNT) void lanczos_ritz_wg_kernel(
           const double nw = hi - lo;
           sect = nw > 0.25 * w;
           // LAPACK dstebz's stopping rule: relative to |lambda| but never below ulp * |T|
-          done = nw <= 4.0 * kEps * fmax(fmax(fabs(lo), fabs(hi)), 0.125 * gsc);
+          done = nw <= 4.0 * kEpsF64 * fmax(fmax(fabs(lo), fabs(hi)), 0.125 * gsc);
           if (sub == 0) mids[ev] = 0.5 * (lo + hi);
         }
         if (!__syncthreads_or(done ? 0 : 1)) break;
@@ -1143,7 +1112,7 @@ __global__ __launch_bounds__(kNT) void lanczos_ritz_wg_kernel(
         int m = n - 1;
         for (int base = l; base < n - 1; base += 64) {
           const int idx = base + lane;
-          const bool small = idx < n - 1 && !(fabs(we[idx]) > kEps * tst1);
+          const bool small = idx < n - 1 && !(fabs(we[idx]) > kEpsF64 * tst1);
           const unsigned long long mk = __ballot(small);
           if (mk) {
             m = base + __builtin_ctzll(mk);
@@ -1155,25 +1124,20 @@ __global__ __launch_bounds__(kNT) void lanczos_ritz_wg_kernel(
           double el;
           do {
             ++iter;
-            double g = wd[l];
             el = we[l];
-            double p = (wd[l + 1] - g) / (2.0 * el);
-            double rr = sqrt(p * p + 1.0);
-            if (p < 0) rr = -rr;
-            const double dl = el / (p + rr), dl1 = el * (p + rr), hh = g - dl;
+            const lnz::QlShift sh = lnz::ql_shift(wd[l], wd[l + 1], el);
             const double el1 = we[l + 1];
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             // lanes share the shift of the remaining diagonal (LDS ops of one wave run in order)
-            for (int i = l + 2 + lane; i < n; i += 64) wd[i] -= hh;
+            for (int i = l + 2 + lane; i < n; i += 64) wd[i] -= sh.hh;
             if (lane == 0) {
-              wd[l] = dl;
-              wd[l + 1] = dl1;
+              wd[l] = sh.dl;
+              wd[l + 1] = sh.dl1;
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
-            f += hh;
-            p = wd[m];
-            double c = 1.0, c2 = 1.0, c3 = 1.0, s = 0.0, s2 = 0.0;
+            f += sh.hh;
+            lnz::QlRotation rot(wd[m]);
             double carry = own ? Qt[(size_t)m * LD + tid] : 0.0;
             double z0 = own ? Qt[(size_t)(m - 1) * LD + tid] : 0.0;
             double ei = we[m - 1], di = wd[m - 1];
@@ -1182,56 +1146,30 @@ __global__ __launch_bounds__(kNT) void lanczos_ritz_wg_kernel(
               const int ip = i > l ? i - 1 : l;
               const double znext = own ? Qt[(size_t)ip * LD + tid] : 0.0;
               const double ei_n = we[ip], di_n = wd[ip];
-              c3 = c2;
-              c2 = c;
-              s2 = s;
-              g = c * ei;
-              const double hp = c * p;
-              const double tt = fma(p, p, ei * ei);
-              const double num = fma(p, di, -(ei * g));  // (p d_i - e_i g): off the rsqrt chain
-              // 1/sqrt(tt): hardware seed + two Newton steps (tt is a normal double here:
-              // |e_i| > eps * tst1 for l <= i < m).  The IEEE sqrt + divide expand to ~40 dependent
-              // fp64 instructions on the rotation-to-rotation critical path (n = 100: 4 ms per graph);
-              // v_rsq_f64's seed is good to ~2^-26, each step squares that.
-              double y = __builtin_amdgcn_rsq(tt);
-              {
-                const double hy = 0.5 * y;
-                const double er = fma(-(tt * y), hy, 0.5);
-                y = fma(y, er, y);
-              }
-              {
-                const double hy = 0.5 * y;
-                const double er = fma(-(tt * y), hy, 0.5);
-                y = fma(y, er, y);
-              }
-              const double rad = tt * y;
-              const double e_next = s * rad;
-              s = ei * y;
-              c = p * y;
-              p = y * num;  // = c d_i - s g
-              const double d_next = hp + s * (c * g + s * di);
+              double e_next, d_next;
+              rot.step<2>(ei, di, e_next, d_next);
               // ONE lane stores (64 lanes storing one address serialise in the LDS); the LDS
               // operations of a wave execute in order, so every lane's later reads see the value
               if (lane == 0) {
                 we[i + 1] = e_next;
                 wd[i + 1] = d_next;
               }
-              if (own) Qt[(size_t)(i + 1) * LD + tid] = s * z0 + c * carry;
-              carry = c * z0 - s * carry;
+              if (own) Qt[(size_t)(i + 1) * LD + tid] = rot.s * z0 + rot.c * carry;
+              carry = rot.c * z0 - rot.s * carry;
               z0 = znext;
               ei = ei_n;
               di = di_n;
             }
             if (own) Qt[(size_t)l * LD + tid] = carry;
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            p = -s * s2 * c3 * el1 * we[l] / dl1;
-            el = s * p;
+            double dl_new;
+            rot.close(el1, we[l], sh.dl1, el, dl_new);
             if (lane == 0) {
               we[l] = el;
-              wd[l] = c * p;
+              wd[l] = dl_new;
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-          } while (fabs(el) > kEps * tst1 && iter < 60);
+          } while (fabs(el) > kEpsF64 * tst1 && iter < 60);
         }
         const double dfin = wd[l] + f;
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -1253,7 +1191,7 @@ __global__ __launch_bounds__(kNT) void lanczos_ritz_wg_kernel(
     // ---- order by descending |lambda| (ties: ascending lambda, then index)
     // = np.argsort(-|eig|, kind='mergesort') on eigh's ascending output (utils/data_helper.py:218-223)
     if (tid < n) {
-      const double di = sm.dd[tid], ai = fabs(di);
+      const double di = sm.dd[tid];
       int rank = 0;
       for (int j0 = 0; j0 < n; j0 += 8) {   // (eight values requested before they are compared)
         double dv[8];
@@ -1262,9 +1200,7 @@ __global__ __launch_bounds__(kNT) void lanczos_ritz_wg_kernel(
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
           const int jj = j0 + u;
-          const double dj = dv[u], aj = fabs(dj);
-          const bool before = (aj > ai) || (aj == ai && (dj < di || (dj == di && jj < tid)));
-          rank += (jj < n && before) ? 1 : 0;
+          rank += (jj < n && lnz::abs_desc_before(dv[u], jj, di, tid)) ? 1 : 0;
         }
       }
       sm.perm[rank] = tid;
@@ -1291,7 +1227,7 @@ __global__ __launch_bounds__(kNT) void lanczos_ritz_wg_kernel(
 #pragma unroll
           for (int u = 0; u < 8; ++u) gs = fmax(gs, fabs(td[u]) + fabs(te[u]));
         }
-        const double tiny = kEps * (gs > 0.0 ? gs : 1.0);
+        const double tiny = kEpsF64 * (gs > 0.0 ? gs : 1.0);
         auto guard = [&](double v) { return fabs(v) < tiny ? (v < 0.0 ? -tiny : tiny) : v; };
         for (int i = 0; i < s0; ++i) zv[(size_t)i * kk + q] = 0.0;   // (zero outside the block)
         for (int i = t0 + 1; i < n; ++i) zv[(size_t)i * kk + q] = 0.0;

@@ -26,6 +26,7 @@
 #include "common.hpp"
 #include "ell_image.hpp"
 #include "tridiag_eig.hpp"
+#include "wave.hpp"
 
 #include <algorithm>
 
@@ -40,7 +41,7 @@ constexpr double kTol = 1e-8;
 constexpr double kReorth = 1e-6;  // second Gram-Schmidt pass when |w1|^2 < kReorth |w0|^2
 
 using lnz_tri::block_sum;
-using lnz_tri::wave_sum;
+using lnz_tri::wave_sum_butterfly;
 
 inline int64_t al256(int64_t x) { return (x + 255) / 256 * 256; }
 
@@ -140,10 +141,7 @@ __global__ __launch_bounds__(WT) void wide_init_kernel(Wide p) {
     const int r = ch * CH + t + WT * u;
     if (r < p.N) {
       double w = 0.0;
-      if (r < n_b) {
-        const unsigned hsh = (unsigned)(r + 1) * 2654435761u;
-        w = 1.0 + (double)((hsh >> 8) & 0xffff) * (1.0 / 65536.0);
-      }
+      if (r < n_b) w = lnz::lanczos_start_entry(r);
       p.w[(int64_t)b * p.N + r] = w;
       part = fma(w, w, part);
     }
@@ -241,13 +239,13 @@ __global__ __launch_bounds__(WT) void wide_spmv_kernel(Wide p, const float* __re
         s2 = fma((double)a.z, y.x * ninv, s2);
         s3 = fma((double)a.w, y.y * ninv, s3);
       }
-      const double tot = wave_sum((s0 + s1) + (s2 + s3));
+      const double tot = wave_sum_butterfly((s0 + s1) + (s2 + s3));
       if (lane == i) acc = tot;
     }
   }
   const int row = 64 * g + lane;
   if (row < p.N) wout[row] = acc;   // (rows in [N, 64 nslab) have no entries: acc = 0)
-  const double s = wave_sum(acc * acc);
+  const double s = wave_sum_butterfly(acc * acc);
   if (lane == 0) p.p0[((int64_t)(j & 1) * p.B + b) * p.nslab + g] = s;
 }
 
@@ -288,7 +286,7 @@ __global__ __launch_bounds__(WT) void wide_dots_kernel(Wide p, int j, int pass) 
         s0 = fma(qv[v][u], wreg[u], s0);
         s1 = fma(qv[v][u + 1], wreg[u + 1], s1);
       }
-      const double c = wave_sum(s0 + s1);
+      const double c = wave_sum_butterfly(s0 + s1);
       const int i = i0 + (WT / 64) * v;
       if (lane == 0 && i <= j) cp[i] = c;
     }

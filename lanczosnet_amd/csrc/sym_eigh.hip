@@ -94,7 +94,7 @@ __device__ inline int graph_n(const int32_t* n_nodes, int b, int N) {
 
 using lnz_tri::block_max;
 using lnz_tri::block_sum;
-using lnz_tri::wave_sum;
+using lnz_tri::wave_sum_butterfly;
 
 // ------------------------------------------------------------------------------------ 1. load
 __global__ __launch_bounds__(256) void eigh_load_kernel(const float* __restrict__ A, int64_t sb,
@@ -210,7 +210,7 @@ __global__ __launch_bounds__(COL_T) void eigh_column_kernel(const int32_t* __res
     const double* src = (q < i ? Vp : Wp) + (int64_t)(q % i) * N;
     double s = 0.0;
     for (int r = j + 1 + lane; r < n; r += 64) s += src[r] * col[r];
-    s = wave_sum(s);
+    s = wave_sum_butterfly(s);
     if (lane == 0) {
       X[(q < i ? 0 : NB) + q % i] = s;
       if (q < i) ws.TD(b)[(int64_t)j * NB + q] = s;

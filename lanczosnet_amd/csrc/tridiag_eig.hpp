@@ -48,8 +48,9 @@ __device__ double block_max(double v, double* red) {
   return r;
 }
 
-// Wave sum in a fixed butterfly order (every lane gets the total).
-__device__ inline double wave_sum(double v) {
+// Wave sum in a fixed butterfly order (every lane gets the total): NOT the tree of lnz::wave_sum
+// (wave.hpp) — another summation order, other bits.
+__device__ inline double wave_sum_butterfly(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
@@ -285,7 +286,7 @@ __device__ inline void invit_body(const int n, const int ldz, const double* dg, 
           const double* zq = Z + (int64_t)clus[q] * N;
           double s = 0.0;
           for (int r = lane; r < n; r += 64) s += zq[r] * x[r];
-          s = wave_sum(s);
+          s = wave_sum_butterfly(s);
           if (lane == 0) hq[q] = s;
         }
         __syncthreads();

@@ -1,0 +1,365 @@
+"""Graphs beyond the 32-node MFMA tile: the hand-written streaming kernels (csrc/conv_large.hip),
+the node-space term on the nonzeros of L (csrc/conv_sparse.hip) with their channel-fold and
+sparse-backoff state, and the library-GEMM restatement (hipBLASLt through torch) of everything the
+kernels are not built for.  `_plan_large` is also the cache the 33..128-node plan lives in."""
+import os
+
+import torch
+
+from .. import ops
+from ._common import (LARGE_MAX_K, LARGE_MAX_OPERATORS, head_params, input_state, masked_readout,
+                      spectral_mlp_operands)
+
+
+class _LargeMixin:
+    # graphs beyond 32 nodes, fp32-grade mode of the streamed kernels: 3 = three bf16 pieces per
+    # operand (six products), 2 = two fp16 pieces (three products, 2/3 of the operand bytes)
+    large_split_planes = int(os.environ.get('LANCZOSNET_LARGE_PLANES', '3'))
+    # lnz_spectral_gains / lnz_pack_spectral_mlp_layers: csrc/gains_body.hpp SMAX
+    gains_kernel_max_scales = 16
+
+    @torch.no_grad()
+    def _torch_gains(self, D):
+        """G [L,B,S,K] by library calls (model/lanczos_net.py:110-113,118-121,146-149): the gains
+        of more long scales than the HIP gains kernel is built for."""
+        S = self.num_scale_long
+        B, K = D.shape
+        pows = torch.stack([torch.pow(D.float(), p) for p in self.long_diffusion_dist], dim=2)
+        if self._has_mlp():
+            G = torch.stack([seq(pows.view(-1, S)).view(B, K, S) for seq in self.spectral_filter])
+        else:
+            G = pows.unsqueeze(0).expand(self.num_layer, B, K, S)
+        return G.transpose(2, 3)
+
+    @torch.no_grad()
+    def _large_graph_forward(self, node_feat, L, D, V, mask, gemm_dtype=None):
+        """Graphs beyond the 32-node MFMA tile (BASELINE config 5: N = 2048, K = 64).  The conv is
+        then plain batched dense GEMMs (`L_e (X W_e^T)` with N x N operands), which go to
+        hipBLASLt through torch.bmm; the spectral gains are the HIP kernel and the Ritz pairs come
+        from `lnz_lanczos_ritz_large`.  `gemm_dtype=torch.bfloat16` runs the edge-type GEMMs with
+        bf16 operands / fp32 accumulate (config 5's "bf16 MFMA filter GEMM"); default fp32."""
+        B, N = L.shape[0], L.shape[1]
+        S = self.num_scale_long
+        G = None
+        if S > self.gains_kernel_max_scales:
+            G = self._torch_gains(D)                                  # [L,B,S,K]
+        elif S > 0:
+            plan_mlp = self._plan_large()['mlp_pack'] if self._has_mlp() else None
+            G = ops.spectral_gains(D, self.long_diffusion_dist, self.num_layer, plan_mlp)  # [L,B,S,K]
+        Lc = L.permute(0, 3, 1, 2)                                   # channel-major view
+        if gemm_dtype is not None:
+            Lc = Lc.to(gemm_dtype)
+        Lc = Lc.contiguous()
+        Vf = V.float()
+        Vt = Vf.transpose(1, 2).contiguous()
+        state = input_state(self, node_feat)
+        for t in range(self.num_layer):
+            W, bias = self._mix_weight(t), self.filter[t].bias
+            d_in = state.shape[2]
+            Wc = W.view(W.shape[0], -1, d_in)
+            out = bias.view(1, 1, -1).expand(B, N, -1).clone()
+            c = 0
+            for p in self.short_diffusion_dist:
+                z = torch.matmul(state, Wc[:, c].t())
+                for _ in range(p):
+                    z = torch.bmm(Lc[:, 0].float(), z)
+                out += z
+                c += 1
+            if S > 0:
+                # sum_s V diag(g_s) V^T X W_s^T = V [ sum_s (g_s * (V^T X)) W_s^T ]: project X to the
+                # K eigen directions ONCE, mix the S channels there (K rows instead of N), lift
+                # back once — 13x fewer FLOPs than S full-size GEMM chains at N = 2048, K = 64
+                Y = torch.bmm(Vt, state)                              # V^T X        [B,K,d_in]
+                Gt = G[t].transpose(1, 2)                             # [B,K,S]
+                Ys = (Gt.unsqueeze(3) * Y.unsqueeze(2)).reshape(B, Y.shape[1], S * d_in)
+                Wl = Wc[:, c:c + S].reshape(W.shape[0], S * d_in)     # [dout, S*d_in]
+                out += torch.bmm(Vf, torch.matmul(Ys, Wl.t()))        # V T          [B,N,dout]
+                c += S
+            E1 = self.num_edgetype + 1
+            dout = W.shape[0]
+            # X W_e^T for all edge types in one GEMM, then one N x N batched GEMM per type
+            Z = torch.matmul(state, Wc[:, c:c + E1].permute(1, 0, 2).reshape(E1 * dout, d_in).t())
+            Z = Z.view(B, N, E1, dout)
+            for e in range(E1):
+                z = Z[:, :, e]
+                if gemm_dtype is not None:
+                    out += torch.bmm(Lc[:, e], z.to(gemm_dtype)).float()
+                else:
+                    out = torch.baddbmm(out, Lc[:, e], z)
+            c += E1
+            state = torch.relu_(out)
+        return masked_readout(self, state, mask)
+
+    @torch.no_grad()
+    def _plan_large(self, planes=None, classes=None):
+        """classes: the channel fold of `_large_fold_classes` (tuple: channel -> representative
+        channel); the node-space weight blocks of a class are summed (sum_c L_c X W_c^T =
+        L (X (sum_c W_c)^T) for equal operators) and only the representatives are kept."""
+        sig = self._param_signature()
+        cache = getattr(self, '_plan_large_cache', None)
+        if cache is None or cache['sig'] != sig:
+            buf = None
+            if self._has_mlp() and self.num_scale_long <= self.gains_kernel_max_scales:
+                buf = ops.pack_spectral_mlp_layers(spectral_mlp_operands(self), self.num_scale_long)
+            cache = self._plan_large_cache = dict(sig=sig, mlp_pack=buf, conv={})
+        key = planes if classes is None else (planes, tuple(classes))
+        if planes is not None and key not in cache['conv']:
+            # per layer: the node-space (edge-type) column blocks of the mix weight as bf16 pieces
+            # in MFMA fragment order (the Wf of lnz_large_gemm1) and the long-scale blocks
+            # as their pack_rows_k8 image, fp32 (lnz_large_spectral)
+            S, E1 = self.num_scale_long, self.num_edgetype + 1
+            if classes is None:
+                classes = tuple(range(E1))
+            assert len(classes) == E1
+            reps = sorted(set(classes))
+            layers = []
+            for t in range(self.num_layer):
+                W = self._mix_weight(t).detach().float()
+                dout = W.shape[0]
+                d_in = W.shape[1] // (S + E1)
+                dinp = (d_in + 15) // 16 * 16
+                Wc = torch.nn.functional.pad(W.view(dout, S + E1, d_in), (0, dinp - d_in))
+                Wn = Wc[:, S:]
+                if len(reps) < E1:
+                    Wn = torch.stack([sum(Wn[:, c] for c in range(E1) if classes[c] == r)
+                                      for r in reps], dim=1)
+                Wb = ops.large_weight_fragments(ops.split_bf16_planes(
+                    Wn.permute(1, 0, 2).reshape(len(reps) * dout, dinp), planes))
+                Wt = ops.pack_rows_k8(Wc[:, :S].reshape(dout, S * dinp).contiguous()) if S else None
+                # one operator class: its summed fp32 block, columns padded to a multiple of 32
+                # (lnz_f32_linear's K) — the exact-fp32 sparse form of the split-precision modes
+                d32 = (d_in + 31) // 32 * 32
+                Wn32 = torch.nn.functional.pad(Wn[:, 0, :d_in], (0, d32 - d_in)).contiguous() \
+                    if len(reps) == 1 else None
+                layers.append(dict(Wb=Wb, Wt=Wt, bias=self.filter[t].bias.detach().float().contiguous(),
+                                   din=d_in, Wn32=Wn32))
+            cache['conv'][key] = layers
+        return cache
+
+    def _plan_head(self, cache):
+        """The stacked head + gate rows `head_params` of the large-plan `cache` (built once per
+        parameter signature; the 33..128-node plan and the readout kernel share them)."""
+        if 'head' not in cache:
+            cache['head'] = head_params(self)
+        return cache['head']
+
+    def _large_hip_supported(self, K, channels=1):
+        """lnz_large_*: uniform hidden width 128, input width <= 128, no short-diffusion powers,
+        K <= 64, <= 16 long scales, at most 8 operator channels (the pack kernel's channel map,
+        csrc/conv_large.hip: `LargeChanMap`; more edge types take the library path like any other
+        unsupported shape)."""
+        return (self._strip_widths_ok() and self.num_scale_short == 0 and K <= LARGE_MAX_K
+                and channels <= LARGE_MAX_OPERATORS
+                and self.num_scale_long <= self.gains_kernel_max_scales)
+
+    # -- channel folding of the large-graph path ------------------------------------------------
+    # With one edge type (config/graph_lanczos_net.yaml:14) the collated L carries the SAME operator
+    # twice: channel 0 = L4 of the simple graph, channel 1 = L4 of the only bond type (reference
+    # dataset/graph_data.py:225-262).  The conv is HBM bound on the operator stream, so streaming the
+    # duplicate is half of its bytes for nothing.  Equality is a property of the DATA, and the check
+    # is free where every entry of every channel is in registers anyway — the pack kernel:
+    #   * a zero channel stride (an expanded view) proves equality without looking;
+    #   * otherwise the pack kernel compares the packed channels pairwise while it converts them
+    #     and reports "differs somewhere" bits; the bits come back through pinned memory and are
+    #     read at the NEXT call (never a host sync): channels that were equal in the last batch are
+    #     folded in this one — the claim is then verified by the same compare, and the only wait is
+    #     for the pack launch itself while the layer launches behind it keep the GPU busy; a
+    #     failed claim repacks unfolded (and drops the guess).
+    # `large_fold = False` (or LANCZOSNET_LARGE_FOLD=0) packs every channel, no comparison.
+    large_fold = os.environ.get('LANCZOSNET_LARGE_FOLD', '1') != '0'
+
+    def _large_fold_classes(self, L):
+        """-> (classes, proven): classes[c] = representative channel of channel c under the
+        current claim; proven[c] = True when channel c needs no verification (its own
+        representative, or structurally equal through a zero channel stride)."""
+        Cn = L.shape[3]
+        ident = tuple(range(Cn))
+        if not self.large_fold or Cn == 1 or Cn > LARGE_MAX_OPERATORS:
+            return ident, (True,) * Cn
+        if L.stride(3) == 0:
+            return (0,) * Cn, (True,) * Cn
+        st = self.__dict__.setdefault('_large_fold_state', {}).get((Cn, L.device.index))
+        if st is None:
+            return ident, (True,) * Cn
+        if st.get('pending') is not None:
+            ev, host, cls = st.pop('pending')
+            st['pending'] = None
+            ev.synchronize()   # the previous call's pack: long finished
+            st['guess'] = self._classes_from_bits(int(host.item()), cls)
+        guess = st.get('guess', ident)
+        return guess, tuple(guess[c] == c for c in range(Cn))
+
+    @staticmethod
+    def _classes_from_bits(bits, packed_classes):
+        """Refine the classes a pack ran with by its comparison bits: packed channels (the
+        representatives) that never differed from an earlier packed channel join its class."""
+        Cn = len(packed_classes)
+        reps = sorted(set(packed_classes))
+        new_rep = {}
+        for r in reps:
+            new_rep[r] = r
+            for r2 in reps:
+                if r2 >= r:
+                    break
+                if new_rep[r2] == r2 and not (bits >> (8 * r + r2)) & 1:
+                    new_rep[r] = r2
+                    break
+        return tuple(new_rep[packed_classes[c]] for c in range(Cn))
+
+    def _large_pack(self, Lf, Vf, planes):
+        """Pack the operators under the current fold claim.  -> (Lb, Vb, classes, verify) where
+        verify() (or None) must be called before the result is released: it waits for the pack
+        launch and returns False when a folded channel turned out to differ."""
+        Cn = Lf.shape[3]
+        classes, proven = self._large_fold_classes(Lf)
+        capturing = torch.cuda.is_current_stream_capturing()
+        compare = (self.large_fold and 1 < Cn <= LARGE_MAX_OPERATORS and not capturing
+                   and Lf.stride(3) != 0)
+        if capturing and not all(proven):
+            classes, proven = tuple(range(Cn)), (True,) * Cn
+        reps = sorted(set(classes))
+        if not compare and len(reps) == Cn:
+            Lb, Vb = ops.large_pack_operators(Lf, Vf, planes)
+            return Lb, Vb, classes, None
+        slot = {r: i for i, r in enumerate(reps)}
+        neq = torch.zeros((1,), dtype=torch.int64, device=Lf.device) if compare else None
+        Lb, Vb = ops.large_pack_operators(
+            Lf, Vf, planes, chan_src=reps, chan_rep=[slot[classes[c]] for c in range(Cn)],
+            chan_check=[0 if (classes[c] != c and proven[c]) else 1 for c in range(Cn)], neq=neq)
+        if not compare:
+            return Lb, Vb, classes, None
+        # keyed per device: nn.DataParallel replicas are shallow copies that share this dict, and
+        # each of them runs on a device (and thread) of its own
+        st = self.__dict__.setdefault('_large_fold_state', {}).setdefault((Cn, Lf.device.index), {})
+        host = st.get('host')
+        if host is None:
+            host = st['host'] = torch.zeros((1,), dtype=torch.int64).pin_memory()
+        host.copy_(neq, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        claimed = [c for c in range(Cn) if classes[c] != c and not proven[c]]
+        if not claimed:
+            st['pending'] = (ev, host, classes)   # read at the next call
+            return Lb, Vb, classes, None
+        st['pending'] = None
+
+        def verify():
+            ev.synchronize()
+            bits = int(host.item())
+            ok = not any((bits >> (8 * c + classes[c])) & 1 for c in claimed)
+            if ok:
+                st['guess'] = self._classes_from_bits(bits, classes)
+            else:
+                st['guess'] = tuple(range(Cn))
+            return ok
+        return Lb, Vb, classes, verify
+
+    # -- the node-space term on the nonzeros of L (csrc/conv_sparse.hip) -------------------------
+    # The image kernel reads L once, keeps the nonzeros of channel 0
+    # and reports (a) whether any other channel differs from channel 0 (the fold claim of
+    # `_large_pack`, checked here for all channels at once) and (b) whether a row is too dense for
+    # the gather to beat the stream (when the batch comes from `collate_graph_adjacency`, its K-step
+    # Lanczos pass over L has left that image riding on the tensor: L is read once per batch).
+    # The flags come back through pinned memory behind the layer
+    # launches; a raised flag discards the result, the batch takes the streamed kernels, and the
+    # next `large_sparse_backoff` calls on this device do not try again (twice as many after every
+    # further failure in a row, up to 32 x).
+    large_sparse = os.environ.get('LANCZOSNET_LARGE_SPARSE', '1') != '0'
+    large_head_kernel = os.environ.get('LANCZOSNET_LARGE_HEAD', '1') != '0'
+    large_sparse_backoff = 32
+
+    def _large_sparse_layers(self, node_feat, Lf, Vf, G, planes=1):
+        """-> the last conv layer's state [B,N,128], or None when the batch has to take the
+        streamed kernels (disabled, capturing, N beyond 16-bit columns, or a raised image flag).
+        planes = 1: bf16 values x bf16 features (the streamed bf16 form's products); planes = 2, 3
+        (the split-precision modes): the node-space term in EXACT fp32 — fp32 values x fp32
+        features of lnz_f32_linear — and the lift from `planes` pieces as in the streamed form."""
+        B, N, _, Cn = Lf.shape
+        if not self.large_sparse or N > 65536 or torch.cuda.is_current_stream_capturing():
+            return None
+        st = self.__dict__.setdefault('_large_sparse_state', {}).setdefault(Lf.device.index, {})
+        if st.get('skip', 0) > 0:
+            st['skip'] -= 1
+            return None
+        exact = planes != 1
+        img = ops.attached_sparse_image(Lf)   # left by the collate's Lanczos pass over this very tensor
+        if img is not None and exact and img.values is None:
+            img = None                        # (an image without the unrounded values)
+        st['image_from'] = 'collate' if img is not None else 'forward'
+        if img is None:
+            img = ops.large_sparse_image(Lf, values=exact)
+        host = st.get('host')
+        if host is None:
+            host = st['host'] = torch.zeros((1,), dtype=torch.int32).pin_memory()
+        host.copy_(img.flags, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        Vb = ops.large_pack_vectors(Vf, planes)
+        classes = (0,) * Cn
+        plan = self._plan_large(planes, classes)
+        # (lnz_f32_linear's K: the exact form takes the input columns padded to a multiple of 32)
+        state = input_state(self, node_feat, width=(self.input_dim + 31) // 32 * 32 if exact else None,
+                            as_float=True).contiguous()
+        bufs = [None, None]
+        if not exact:
+            work = ops.large_sparse_work_buffers(B, N, Lf.device)
+            for t, lay in enumerate(plan['conv'][(1, classes)]):
+                state = ops.large_sparse_conv_layer(state, lay['din'], img, Vb, Vf, lay['Wb'], lay['Wt'],
+                                                    G[t] if G is not None else None, lay['bias'], work,
+                                                    relu=True, out=bufs[t & 1])
+                bufs[t & 1] = state
+        else:
+            dev = Lf.device
+            work = (torch.empty((B, N, 128), dtype=torch.float32, device=dev),
+                    torch.zeros((planes, B, 128, 64), dtype=ops.large_plane_dtype(planes), device=dev),
+                    torch.zeros((B, 64, 128), dtype=torch.float32, device=dev))
+            for t, lay in enumerate(plan['conv'][(planes, classes)]):
+                state = ops.large_sparse_conv_layer_f32(state, lay['din'], img, Vb, Vf, lay['Wn32'], lay['Wt'],
+                                                        G[t] if G is not None else None, lay['bias'], work,
+                                                        planes, relu=True, out=bufs[t & 1])
+                bufs[t & 1] = state
+        ev.synchronize()   # the image launch: long finished
+        flags = int(host.item())
+        st['last_flags'] = flags
+        if flags:
+            # (a data set of dense graphs raises it every time: the pause doubles, up to 32 x)
+            st['streak'] = min(st.get('streak', 0) + 1, 6)
+            st['skip'] = self.large_sparse_backoff << (st['streak'] - 1)
+            return None
+        st['streak'] = 0
+        return state
+
+    @torch.no_grad()
+    def _large_graph_forward_hip(self, node_feat, L, D, V, mask, planes=3):
+        """Graphs beyond the 32-node MFMA tile on the hand-written streaming kernels
+        (csrc/conv_large.hip; BASELINE config 5: N = 2048, K = 64, batch 256): the operators are
+        packed once (channel-major bf16 planes, equal channels once — see `_large_pack`), every
+        layer is gemm1 + eigen-space spectral block + streamed conv.  planes = 3: fp32-grade split
+        products (default, the 1e-5 parity mode); planes = 1: plain bf16 operands / fp32
+        accumulate (`gemm_mode = 'bf16'`, config 5's mode)."""
+        S = self.num_scale_long
+        Lf = L if L.dtype == torch.float32 else L.float()
+        Vf = V.float().contiguous()
+        cache = self._plan_large()
+        G = None
+        if S > 0:
+            G = ops.spectral_gains(D, self.long_diffusion_dist, self.num_layer, cache['mlp_pack'])
+        state = self._large_sparse_layers(node_feat, Lf, Vf, G, planes)
+        for attempt in range(2 if state is None else 0):
+            Lb, Vb, classes, verify = self._large_pack(Lf, Vf, planes)
+            plan = self._plan_large(planes, classes)
+            work = ops.large_work_buffers(Lb)
+            state = input_state(self, node_feat, as_float=True).contiguous()
+            bufs = [None, None]
+            for t, lay in enumerate(plan['conv'][(planes, tuple(classes))]):
+                state = ops.large_conv_layer(state, lay['din'], Lb, Vb, Vf, lay['Wb'], lay['Wt'],
+                                             G[t] if G is not None else None, lay['bias'], work,
+                                             relu=True, out=bufs[t & 1])
+                bufs[t & 1] = state
+            if verify is None or verify():
+                break
+            # a folded channel differed in this batch: the guess is dropped, pack every channel
+        if self.large_head_kernel and self.output_dim <= 16 and state.shape[2] == 128:
+            # the readout in one pass over the state (csrc/head_large.hip)
+            return ops.large_head(state, mask, *self._plan_head(cache))
+        return masked_readout(self, state, mask)

@@ -12,6 +12,7 @@ Reference interfaces replaced (paths relative to the reference repo):
 import torch
 
 import os
+import threading
 
 from . import _lib, _torch_ext
 
@@ -52,6 +53,8 @@ class _ExtNamespace(object):
     op = getattr(torch.ops.lanczosnet, self._prefix + name)
 
     def call(*args):
+      if _autograd_kernel[0] is not None and _autograd_kernel[1] != threading.get_ident():
+        _autograd_kernel[0] = None   # a launch from another thread is newer than a backward's note
       try:
         return op(*args)
       except RuntimeError as e:
@@ -83,19 +86,23 @@ NotSupported = _lib.NotSupported
 LnzError = _lib.LnzError
 
 
-_autograd_kernel = [None]
+_autograd_kernel = [None, None]   # a backward launch's kernel, the thread that launched it
 
 
 def last_kernel():
   """lnz_last_kernel(): the kernel (with template arguments) the calling thread's last fused
   forward / input-gradient launch selected.  lnz_last_kernel() is per thread and `loss.backward()`
   launches from autograd's own thread: a backward launch that hands its name over
-  (note_autograd_kernel) is reported here until the next module forward."""
-  return _autograd_kernel[0] or torch.ops.lanczosnet.last_kernel()
+  (note_autograd_kernel) is reported here until another thread calls into the library (every call
+  through `_ext()` / `_abi()` drops a note that is not its own thread's) or the next module forward."""
+  name, ident = _autograd_kernel
+  own = torch.ops.lanczosnet.last_kernel()
+  return own if name is None or ident == threading.get_ident() else name
 
 
 def note_autograd_kernel():
   """Called by a backward launch's wrapper, on the launching thread."""
+  _autograd_kernel[1] = threading.get_ident()
   _autograd_kernel[0] = torch.ops.lanczosnet.last_kernel()
 
 
@@ -1516,6 +1523,7 @@ def lanczosnet_input_grad(plan, Lp, V, G, mask_u8, act, dy, dx0, tiling, row_off
   ops_[_IN['Wp']], ops_[_IN['act']] = plan['Wp_t'], act
   _ext().fused_launch(1, ops_, dims, [int(x) for x in plan['wt_off'][:L]], [],
                       [int(p) for p in plan['short']], None, None, None, dy, dx0, None, None, dy_compact, dbias_part)
+  note_autograd_kernel()   # (launched from autograd's thread: last_kernel() reports it after backward())
 
 
 def lanczosnet_messages(plan, Lp, V, G, mask_u8, act, x0, layer, msg, tiling, row_off=None):

@@ -30,6 +30,8 @@ extern "C" {
  *    entries (lnz_split_laplacian_pack_to, lnz_spectral_gains_rows_split_to), lnz_last_kernel,
  *    lnz_stream_create_cu_masked; the full eigendecomposition (lnz_sym_eigh_topk, _workspace_bytes);
  *    + the wide K-step entry (lnz_lanczos_ritz_kstep_wide, _workspace_bytes: N <= 16384, M <= 256);
+ *    + large graphs from edge lists (lnz_lanczos_ritz_kstep_edges, lnz_lanczos_ritz_kstep_wide_edges,
+ *    lnz_laplacian_l4_edges_image, each with a _workspace_bytes sibling: no N x N array);
  * 6: lnz_forward_args lost Wp16 / w16_off / Wp16_head / Lp16 (gemm_mode 1 is now the split precision
  *    inside the strip kernel: lnz_pack_rows_k8_split; lnz_pack_rows_f16x2 and
  *    lnz_pack_laplacian_f16x2 are gone) and gained dbias_part_cap; + lnz_midgraph_forward,
@@ -371,6 +373,72 @@ int lnz_lanczos_ritz_kstep_image(const float* A, int64_t stride_b, int64_t strid
                                  float* D, float* V, int32_t* info, int32_t* dense_fallback,
                                  uint32_t* conv_entries, float* conv_values, int32_t* conv_counts,
                                  int conv_row_cap, int32_t* conv_flags, lnz_stream_t stream);
+
+/* ---- large graphs from edge lists (csrc/edge_image.hip) ----------------------------------------
+ * The images the K-step recurrence and the sparse conv run on, built from a batch of undirected EDGE
+ * LISTS instead of the dense collated Laplacian: no array of N x N elements is read or written.
+ * Replaces, for unweighted simple graphs with ONE edge type (the reference's graph configuration,
+ * num_edge_type: 1), utils/data_helper.py:92-116,155-156 (normalize_adj / get_laplacian 'L4'),
+ * dataset/get_graph_data.py:61-72 (the offline L4 + eigen pairs of every graph) and the `eigsh`
+ * branch utils/data_helper.py:205-223.
+ *   edges [n_edges][2] int32   local node ids, each undirected edge once, either endpoint order
+ *   edge_off [B + 1] int64     graph b owns edges [edge_off[b], edge_off[b + 1])
+ *   n_nodes [B] int32          rows >= n_nodes[b] are empty
+ * Entry (i, j) = (float)((s_i * 1.0) * s_j), s_i = 1.0 / sqrt((double)deg_i), deg_i = 1 + neighbours
+ * — lnz_laplacian_l4's expression —, the diagonal present in every real row.  The recurrence and the
+ * gather sum a row in ENTRY order, and the dense compaction meets a row's nonzeros in the order of its
+ * vector loads (64 float4s per wave, component by component), so the order is an argument:
+ *   LNZ_EDGE_ORDER_ASCENDING  ascending column (lnz_large_sparse_image's 4-byte form: odd N, any strides)
+ *   LNZ_EDGE_ORDER_PAIR       within every 128 columns the even ones, then the odd ones (the
+ *                             channels-last pair read in place, stride_c = 2: N even / N %% 4 == 0)
+ *   LNZ_EDGE_ORDER_QUAD       within every 256 columns, column %% 4 == 0, then 1, 2, 3 (contiguous rows)
+ * With the order of the dense form it stands in for, an image is bit for bit the one
+ * lnz_lanczos_ritz_kstep_image / lnz_large_sparse_image gathers from the dense L4 of the same
+ * graphs, whatever the order of the edges and of their endpoints (integer atomics only).
+ * status [B] (output): 0, or the OR of 1 = an endpoint outside [0, n_b), 2 = a self loop, 4 = a
+ * duplicate edge, 8 = edge_off[b] .. edge_off[b + 1] is not a range inside the edge array, 16 =
+ * n_nodes[b] outside [0, N].  Checked on the device before any indexed access; such a graph's
+ * outputs are zeros (counts, entries, D, V, info) and nothing is written outside its own slots.
+ * (A duplicate inside a row of more than max(row_cap, conv_row_cap) entries is not looked for: that
+ * graph is reported in `fallback` / conv_flags instead.)
+ * A row of more than row_cap entries is not an error: fallback [B] (optional output) = 1 and the
+ * graph's D, V, info are ZERO — there is no dense A to fall back on; the caller densifies such a
+ * batch.  A row of more than conv_row_cap entries raises conv_flags bit 1 (bit 0 never: both channels
+ * of a one-edge-type L are one operator by construction).
+ * The Ritz pairs are those of lnz_lanczos_ritz_kstep (N <= 2048, K <= M <= 64) /
+ * lnz_lanczos_ritz_kstep_wide (N <= 16384, K <= M <= 256) with LNZ_KSTEP_COMPACT on that image: the
+ * same step kernels, unchanged.  N %% 4 == 0 (pad the batch); row_cap a multiple of 8 in [8, 256];
+ * the conv image is optional (conv_entries NULL: none; else conv_row_cap a multiple of 8 in
+ * [32, 256], conv_values optional).  workspace: 256-B aligned, *_workspace_bytes(...) bytes
+ * (conv_row_cap = 0 without a conv image). */
+#define LNZ_EDGE_ORDER_ASCENDING 0
+#define LNZ_EDGE_ORDER_PAIR 1
+#define LNZ_EDGE_ORDER_QUAD 2
+int64_t lnz_lanczos_ritz_kstep_edges_workspace_bytes(int B, int N, int row_cap, int conv_row_cap);
+int lnz_lanczos_ritz_kstep_edges(const int32_t* edges, int64_t n_edges, const int64_t* edge_off,
+                                 const int32_t* n_nodes, int B, int N, int M, int K, int row_cap,
+                                 int row_order, void* workspace, int64_t workspace_bytes, float* D,
+                                 float* V, int32_t* info, int32_t* fallback, uint32_t* conv_entries,
+                                 float* conv_values, int32_t* conv_counts, int conv_row_cap,
+                                 int conv_order, int32_t* conv_flags, int32_t* status,
+                                 lnz_stream_t stream);
+int64_t lnz_lanczos_ritz_kstep_wide_edges_workspace_bytes(int B, int N, int M, int row_cap,
+                                                          int conv_row_cap);
+int lnz_lanczos_ritz_kstep_wide_edges(const int32_t* edges, int64_t n_edges, const int64_t* edge_off,
+                                      const int32_t* n_nodes, int B, int N, int M, int K, int row_cap,
+                                      int row_order, void* workspace, int64_t workspace_bytes, float* D,
+                                      float* V, int32_t* info, int32_t* fallback, uint32_t* conv_entries,
+                                      float* conv_values, int32_t* conv_counts, int conv_row_cap,
+                                      int conv_order, int32_t* conv_flags, int32_t* status,
+                                      lnz_stream_t stream);
+/* The conv image alone (lnz_large_sparse_image's format), for callers that already hold (D, V): any
+ * N <= 16384; workspace 16-B aligned. */
+int64_t lnz_laplacian_l4_edges_image_workspace_bytes(int B, int N, int conv_row_cap);
+int lnz_laplacian_l4_edges_image(const int32_t* edges, int64_t n_edges, const int64_t* edge_off,
+                                 const int32_t* n_nodes, int B, int N, void* workspace,
+                                 int64_t workspace_bytes, uint32_t* conv_entries, float* conv_values,
+                                 int32_t* conv_counts, int conv_row_cap, int conv_order,
+                                 int32_t* conv_flags, int32_t* status, lnz_stream_t stream);
 
 /* A HIP stream whose kernels run on compute units [first_cu, end_cu) of the current device only
  * (hipExtStreamCreateWithCUMask).  For latency-chain launches that fill a fraction of the chip —

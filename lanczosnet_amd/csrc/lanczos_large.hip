@@ -15,6 +15,7 @@
 // Algorithmic bytes per graph: M * 4 N^2 (A) + basis traffic ~ 4 * 8 N * M(M+1)/2
 // + 4 N K (V) : 1.074 GB + 0.133 GB + 0.5 MB at N = 2048, M = K = 64.
 #include "common.hpp"
+#include "edge_image.hpp"
 #include "ell_image.hpp"
 #include "tql2.hpp"
 
@@ -920,6 +921,60 @@ extern "C" int lnz_lanczos_ritz_kstep_image(const float* A, int64_t stride_b, in
   return kstep_launch(who, A, stride_b, stride_r, stride_c, n_nodes, B, N, M, K, flags, row_cap,
                       workspace, workspace_bytes, D, V, info, dense_fallback,
                       ConvImageOut{conv_entries, conv_values, conv_counts, conv_flags, conv_row_cap}, stream);
+}
+
+// ---- the K-step entry on edge lists: the image comes from csrc/edge_image.hip, no dense A ----------
+// workspace: the layout of LNZ_KSTEP_COMPACT, then the gate words and the builder's scratch
+static int64_t kstep_edges_gate_at(int B, int N, int row_cap) {
+  return align256(kstep_layout(B, N, LNZ_KSTEP_COMPACT, row_cap).total);
+}
+
+extern "C" int64_t lnz_lanczos_ritz_kstep_edges_workspace_bytes(int B, int N, int row_cap, int conv_row_cap) {
+  if (B <= 0 || N <= 0 || row_cap <= 0 || conv_row_cap < 0) return 0;
+  return kstep_edges_gate_at(B, N, row_cap) + align256((int64_t)B * 4) +
+         lnz::edge_scratch_bytes(B, N, lnz::edge_stage_cap(row_cap, conv_row_cap));
+}
+
+extern "C" int lnz_lanczos_ritz_kstep_edges(const int32_t* edges, int64_t n_edges, const int64_t* edge_off,
+                                            const int32_t* n_nodes, int B, int N, int M, int K, int row_cap,
+                                            int row_order, void* workspace, int64_t workspace_bytes, float* D,
+                                            float* V, int32_t* info, int32_t* fallback, uint32_t* conv_entries,
+                                            float* conv_values, int32_t* conv_counts, int conv_row_cap,
+                                            int conv_order, int32_t* conv_flags, int32_t* status,
+                                            lnz_stream_t stream) {
+  const char* who = "lnz_lanczos_ritz_kstep_edges";
+  LNZ_REQUIRE(workspace && D && V && B > 0 && N > 0 && M > 0 && K > 0, LNZ_EINVAL,
+              "%s: bad arguments (workspace, D, V non-null; B=%d N=%d M=%d K=%d >= 1)", who, B, N, M, K);
+  LNZ_REQUIRE(N <= NCH * 256 && M <= MMAX && K <= M, LNZ_ENOTSUP, "%s: N=%d <= 2048, K=%d <= M=%d <= 64 required", who,
+              N, K, M);
+  LNZ_REQUIRE(N % 4 == 0, LNZ_ENOTSUP, "%s: N %% 4 == 0 required (pad the batch)", who);
+  LNZ_REQUIRE(M <= N, LNZ_EINVAL, "%s: M=%d > N=%d", who, M, N);
+  LNZ_REQUIRE(row_cap > 0, LNZ_EINVAL, "%s: row_cap=%d", who, row_cap);
+  const int ccap = conv_entries ? conv_row_cap : 0;
+  const int64_t need = lnz_lanczos_ritz_kstep_edges_workspace_bytes(B, N, row_cap, ccap);
+  LNZ_REQUIRE(workspace_bytes >= need, LNZ_EINVAL, "%s: workspace of %lld bytes, %lld needed", who,
+              (long long)workspace_bytes, (long long)need);
+  LNZ_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, LNZ_EINVAL, "%s: workspace alignment (256 B)", who);
+  const KstepLayout L = kstep_layout(B, N, LNZ_KSTEP_COMPACT, row_cap);
+  char* ws = (char*)workspace;
+  const int64_t gate_at = kstep_edges_gate_at(B, N, row_cap), scratch_at = gate_at + align256((int64_t)B * 4);
+  int32_t* over = fallback ? fallback : (int32_t*)(ws + L.over);
+  int32_t* gate = (int32_t*)(ws + gate_at);
+  const lnz::EdgeBatch g{edges, n_edges, edge_off, n_nodes, B, N};
+  const lnz::EdgeEll ell{(float*)(ws + L.vals), (uint16_t*)(ws + L.cols), (int32_t*)(ws + L.widths),
+                         (int32_t*)(ws + L.rowcnt), over, row_cap, row_order};
+  const lnz::EdgeConv cv{conv_entries, conv_values, conv_counts, conv_flags, ccap, conv_order};
+  const lnz::EdgeRitz rz{D, V, info, K, gate};
+  int rc = lnz::edge_image_build(who, g, ell, cv, rz, ws + scratch_at, workspace_bytes - scratch_at, status,
+                                 (hipStream_t)stream);
+  if (rc != LNZ_OK) return rc;
+  // the steps on the image (MODE 2 reads no A); a graph beyond row_cap or with a status leaves at once
+  const EllImage img = {ell.vals, ell.cols, ell.widths, row_cap};
+  hipLaunchKernelGGL(lanczos_ritz_large_kernel<2>, dim3(B), dim3(TPB), 0, (hipStream_t)stream, (const float*)nullptr,
+                     (int64_t)0, (int64_t)N, N, M, K, (double*)workspace, D, V, info, n_nodes, (const int32_t*)gate, 0,
+                     img);
+  lnz::note_kernel("edge_rows_kernel, lanczos_ritz_large_kernel<2>");
+  return lnz::check_launch(who);
 }
 
 extern "C" int lnz_lanczos_ritz_large(const float* A, int64_t stride_b, int64_t stride_r, int B,

@@ -24,6 +24,7 @@
 // of q from L2 (8 B per entry; q is 128 KiB at N = 16384), and the basis, (j + 1) N 8 B, twice per
 // Gram-Schmidt pass (dots, update).
 #include "common.hpp"
+#include "edge_image.hpp"
 #include "ell_image.hpp"
 #include "tridiag_eig.hpp"
 #include "wave.hpp"
@@ -439,6 +440,10 @@ __global__ __launch_bounds__(WT) void wide_vectors_kernel(Wide p, float* __restr
 
 }  // namespace
 
+static int wide_steps(const char* who, const Layout& L, char* ws, const int32_t* over, const float* A, int64_t stride_b,
+                      int64_t stride_r, bool skip_over, const int32_t* n_nodes, int B, int N, int M, int K, int row_cap,
+                      float* D, float* V, int32_t* info, hipStream_t st);
+
 extern "C" int64_t lnz_lanczos_ritz_kstep_wide_workspace_bytes(int B, int N, int M, int row_cap) {
   if (B <= 0 || N <= 0 || M <= 0 || row_cap <= 0) return 0;
   return layout(B, N, M, row_cap).total;
@@ -495,6 +500,14 @@ extern "C" int lnz_lanczos_ritz_kstep_wide(const float* A, int64_t stride_b, int
                      vals, cols, widths, rowcnt);
   rc = lnz::check_launch(who);
   if (rc != LNZ_OK) return rc;
+  return wide_steps(who, L, ws, over, A, stride_b, stride_r, stride_c != 1, n_nodes, B, N, M, K, row_cap, D, V, info, st);
+}
+
+// ---- the recurrence on the image in the workspace (`over`: the graphs it could not hold) --------------
+static int wide_steps(const char* who, const Layout& L, char* ws, const int32_t* over, const float* A, int64_t stride_b,
+                      int64_t stride_r, bool skip_over, const int32_t* n_nodes, int B, int N, int M, int K, int row_cap,
+                      float* D, float* V, int32_t* info, hipStream_t st) {
+  int rc;
   Wide p;
   p.Q = (double*)(ws + L.Q);
   p.w = (double*)(ws + L.w);
@@ -511,9 +524,9 @@ extern "C" int lnz_lanczos_ritz_kstep_wide(const float* A, int64_t stride_b, int
   p.alive = (int32_t*)(ws + L.alive);
   p.steps = (int32_t*)(ws + L.steps);
   p.over = over;
-  p.vals = vals;
-  p.cols = cols;
-  p.widths = widths;
+  p.vals = (const float*)(ws + L.vals);
+  p.cols = (const uint16_t*)(ws + L.cols);
+  p.widths = (const int32_t*)(ws + L.widths);
   p.n_nodes = n_nodes;
   p.cap = row_cap;
   p.B = B;
@@ -522,7 +535,7 @@ extern "C" int lnz_lanczos_ritz_kstep_wide(const float* A, int64_t stride_b, int
   p.K = K;
   p.nslab = L.nslab;
   p.nchunk = L.nchunk;
-  p.skip_over = stride_c != 1;
+  p.skip_over = skip_over ? 1 : 0;
   const dim3 gs((unsigned)((L.nslab + WT / 64 - 1) / (WT / 64)), (unsigned)B), gc((unsigned)L.nchunk, (unsigned)B);
   hipLaunchKernelGGL(wide_init_kernel, gc, dim3(WT), 0, st, p);
   for (int j = 0; j < M; ++j) {
@@ -541,4 +554,52 @@ extern "C" int lnz_lanczos_ritz_kstep_wide(const float* A, int64_t stride_b, int
                      st, p, D, V, info);
   lnz::note_kernel("lanczos_wide: wide_spmv_kernel, wide_dots_kernel, wide_update_kernel");
   return lnz::check_launch(who);
+}
+
+// ---- the same launches on an image built from edge lists (csrc/edge_image.hip): no dense A ------------
+// workspace: the layout above, then the gate words and the builder's scratch
+extern "C" int64_t lnz_lanczos_ritz_kstep_wide_edges_workspace_bytes(int B, int N, int M, int row_cap,
+                                                                     int conv_row_cap) {
+  if (B <= 0 || N <= 0 || M <= 0 || row_cap <= 0 || conv_row_cap < 0) return 0;
+  return layout(B, N, M, row_cap).total + al256((int64_t)B * 4) +
+         lnz::edge_scratch_bytes(B, N, lnz::edge_stage_cap(row_cap, conv_row_cap));
+}
+
+extern "C" int lnz_lanczos_ritz_kstep_wide_edges(const int32_t* edges, int64_t n_edges, const int64_t* edge_off,
+                                                 const int32_t* n_nodes, int B, int N, int M, int K, int row_cap,
+                                                 int row_order, void* workspace, int64_t workspace_bytes, float* D,
+                                                 float* V, int32_t* info, int32_t* fallback, uint32_t* conv_entries,
+                                                 float* conv_values, int32_t* conv_counts, int conv_row_cap,
+                                                 int conv_order, int32_t* conv_flags, int32_t* status,
+                                                 lnz_stream_t stream) {
+  const char* who = "lnz_lanczos_ritz_kstep_wide_edges";
+  LNZ_REQUIRE(workspace && D && V && B > 0 && N > 0 && M > 0 && K > 0, LNZ_EINVAL,
+              "%s: bad arguments (workspace, D, V non-null; B=%d N=%d M=%d K=%d >= 1)", who, B, N, M, K);
+  LNZ_REQUIRE(N <= MAX_N && M <= MAX_M && K <= M, LNZ_ENOTSUP, "%s: N=%d <= %d, K=%d <= M=%d <= %d required", who, N,
+              MAX_N, K, M, MAX_M);
+  LNZ_REQUIRE(N % 4 == 0, LNZ_ENOTSUP, "%s: N %% 4 == 0 required (pad the batch)", who);
+  LNZ_REQUIRE(M <= N, LNZ_EINVAL, "%s: M=%d > N=%d", who, M, N);
+  LNZ_REQUIRE(B <= 65535, LNZ_EINVAL, "%s: B=%d: at most 65535 graphs per call (the caller chunks)", who, B);
+  LNZ_REQUIRE(row_cap > 0, LNZ_EINVAL, "%s: row_cap=%d", who, row_cap);
+  const int ccap = conv_entries ? conv_row_cap : 0;
+  const int64_t need = lnz_lanczos_ritz_kstep_wide_edges_workspace_bytes(B, N, M, row_cap, ccap);
+  LNZ_REQUIRE(workspace_bytes >= need, LNZ_EINVAL, "%s: workspace of %lld bytes, %lld needed", who,
+              (long long)workspace_bytes, (long long)need);
+  LNZ_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, LNZ_EINVAL, "%s: workspace alignment (256 B)", who);
+  const Layout L = layout(B, N, M, row_cap);
+  char* ws = (char*)workspace;
+  const int64_t scratch_at = L.total + al256((int64_t)B * 4);
+  int32_t* over = fallback ? fallback : (int32_t*)(ws + L.over);
+  int32_t* gate = (int32_t*)(ws + L.total);
+  const lnz::EdgeBatch g{edges, n_edges, edge_off, n_nodes, B, N};
+  const lnz::EdgeEll ell{(float*)(ws + L.vals), (uint16_t*)(ws + L.cols), (int32_t*)(ws + L.widths),
+                         (int32_t*)(ws + L.rowcnt), over, row_cap, row_order};
+  const lnz::EdgeConv cv{conv_entries, conv_values, conv_counts, conv_flags, ccap, conv_order};
+  const lnz::EdgeRitz rz{D, V, info, K, gate};
+  const int rc = lnz::edge_image_build(who, g, ell, cv, rz, ws + scratch_at, workspace_bytes - scratch_at, status,
+                                       (hipStream_t)stream);
+  if (rc != LNZ_OK) return rc;
+  // a graph beyond row_cap or with a status is skipped by every launch (its D, V, info are zero already)
+  return wide_steps(who, L, ws, gate, nullptr, 0, N, true, n_nodes, B, N, M, K, row_cap, D, V, info,
+                    (hipStream_t)stream);
 }

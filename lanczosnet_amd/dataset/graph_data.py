@@ -2,8 +2,8 @@
 `config/graph_lanczos_net.yaml`, pickles written by `dataset/get_graph_data.py:51-92`).
 
 Graphs of 20..100 nodes with float node embeddings `X [n, node_emb_dim]`, ONE edge type and a
-graph-level label `Y [1, graph_emb_dim]`; the model is `LanczosNetGeneral`.  Same two entry points as
-`dataset/qm8.py` here:
+graph-level label `Y [1, graph_emb_dim]`; the model is `LanczosNetGeneral`.  The two entry points of
+`dataset/qm8.py`, and one more for large graphs:
 
 * `collate_graph_preprocessed(items, num_eigs)` — items are the reference's per-graph pickle dicts
   (node_feat, L_multi, L_simple_4, D_simple, V_simple, label); the host-side padding of the
@@ -15,6 +15,10 @@ graph-level label `Y [1, graph_emb_dim]`; the model is `LanczosNetGeneral`.  Sam
   computed ON THE DEVICE.  Batches padded beyond 192 nodes (BASELINE config 5: 2048) get the
   pairs of the K-step recurrence instead (`lnz_lanczos_ritz_kstep`: the reference's
   use_eigen_decomp=False branch, utils/data_helper.py:205-208; announced by a UserWarning).
+
+* `collate_graph_edges(items, num_eigs, device)` — the same batch from EDGE LISTS (`edges [m,2]`): no
+  array of N x N elements on the host or the device, `L` an `ops.SparseLaplacian` (large graphs of one
+  edge type, 192 < N <= 16384; csrc/edge_image.hip).
 
 `GraphData(config, split)` is the class the runner instantiates with
 `eval(config.dataset.loader_name)(config, split=...)` (runner/graph_runner.py:38-40).
@@ -100,6 +104,73 @@ def collate_graph_adjacency(items, num_eigs, device='cuda', model_name='LanczosN
     elif model_name == 'ChebyNet':
         L[:, :, :, 0] = -ops.laplacian(adjs_d, n_nodes, 'L6')[:, :, :, 0]
     out['L'] = L
+    return out
+
+
+def collate_graph_edges(items, num_eigs, device='cuda', lanczos_steps=None):
+    """Raw graphs as EDGE LISTS in, device-resident batch out with no array of N x N elements on the
+    host or the device: items carry `edges [m,2]` (integer local node ids, each undirected edge once,
+    either endpoint order; unweighted simple graphs, ONE edge type — the reference's graph
+    configuration), `node_feat [n,D]`, `label [1,P]`.  Returns the keys of collate_graph_adjacency;
+    `L` is an `ops.SparseLaplacian` (the model's forward takes it; `.to_dense()` is the [B,N,N,2]
+    tensor), D / V the Ritz pairs of the K-step recurrence on its image (ops.lanczos_ritz_edges,
+    replacing utils/data_helper.py:92-116,155-156,205-223 and dataset/get_graph_data.py:61-72).
+    Batches padded to N <= 192 nodes are outside the K-step territory: they are densified and the
+    result is collate_graph_adjacency's for the same graphs.  ValueError for a malformed argument
+    (here) or a graph that is not a simple graph (found on the device)."""
+    if not isinstance(items, (list, tuple)) or len(items) == 0:
+        raise ValueError('collate_graph_edges: a non-empty list of items expected')
+    num_eigs = int(num_eigs or 0)
+    if num_eigs < 0:
+        raise ValueError('collate_graph_edges: num_eigs=%d' % num_eigs)
+    if lanczos_steps is not None and int(lanczos_steps) < num_eigs:
+        raise ValueError('collate_graph_edges: lanczos_steps=%d < num_eigs=%d' % (lanczos_steps, num_eigs))
+    lists = []
+    for b, it in enumerate(items):
+        for key in ('edges', 'node_feat', 'label'):
+            if key not in it:
+                raise ValueError('collate_graph_edges: item %d has no %r' % (b, key))
+        e = np.asarray(it['edges'])
+        if e.size == 0:
+            e = np.zeros((0, 2), dtype=np.int32)
+        if e.ndim != 2 or e.shape[1] != 2:
+            raise ValueError('collate_graph_edges: item %d: edges of shape %s, [m, 2] expected' % (b, e.shape))
+        if not np.issubdtype(e.dtype, np.integer):
+            raise ValueError('collate_graph_edges: item %d: edges of dtype %s, integer node ids expected'
+                             % (b, e.dtype))
+        if np.asarray(it['node_feat']).ndim != 2:
+            raise ValueError('collate_graph_edges: item %d: node_feat [n, D] expected' % b)
+        if e.size and (e.min() < -2**31 or e.max() >= 2**31):
+            raise ValueError('collate_graph_edges: item %d: node ids beyond int32' % b)
+        lists.append(e.astype(np.int32))
+    from .. import ops
+    sizes, B, N, node_feat, mask, label = _pad_common(items)
+    if N > ops.KSTEP_WIDE_MAX_N:
+        raise ValueError('collate_graph_edges: %d nodes: graphs of up to %d nodes are served'
+                         % (N, ops.KSTEP_WIDE_MAX_N))
+    if N <= ops.RITZ_FULL_MAX_N:
+        dense = []
+        for it, e, n in zip(items, lists, sizes):
+            if e.size and (e.min() < 0 or e.max() >= n or (e[:, 0] == e[:, 1]).any()):
+                raise ValueError('collate_graph_edges: an endpoint outside the graph or a self loop')
+            a = np.zeros((n, n, 1), dtype=np.float32)
+            a[e[:, 0], e[:, 1], 0] = 1.0
+            a[e[:, 1], e[:, 0], 0] = 1.0
+            dense.append(dict(adjs=a, node_feat=it['node_feat'], label=it['label']))
+        return collate_graph_adjacency(dense, num_eigs, device=device, lanczos_steps=lanczos_steps)
+    dev = torch.device(device)
+    edge_off = np.zeros((B + 1,), dtype=np.int64)
+    np.cumsum([e.shape[0] for e in lists], out=edge_off[1:])
+    edges = torch.from_numpy(np.concatenate(lists, axis=0)).to(dev)
+    edge_off = torch.from_numpy(edge_off).to(dev)
+    n_nodes = torch.tensor(sizes, dtype=torch.int32, device=dev)
+    out = dict(node_feat=torch.from_numpy(node_feat).to(dev), node_mask=torch.from_numpy(mask).to(dev),
+               label=torch.from_numpy(label).to(dev), n_nodes=n_nodes)
+    if num_eigs:
+        out['D'], out['V'], out['L'] = ops.lanczos_ritz_edges(edges, edge_off, n_nodes, N, num_eigs,
+                                                              lanczos_steps=lanczos_steps)
+    else:
+        out['L'] = ops.sparse_laplacian_from_edges(edges, edge_off, n_nodes, N)
     return out
 
 

@@ -3,6 +3,7 @@ the node-space term on the nonzeros of L (csrc/conv_sparse.hip) with their chann
 sparse-backoff state, and the library-GEMM restatement (hipBLASLt through torch) of everything the
 kernels are not built for.  `_plan_large` is also the cache the 33..128-node plan lives in."""
 import os
+import warnings
 
 import torch
 
@@ -265,6 +266,16 @@ class _LargeMixin:
     # next `large_sparse_backoff` calls on this device do not try again (twice as many after every
     # further failure in a row, up to 32 x).
     large_sparse = os.environ.get('LANCZOSNET_LARGE_SPARSE', '1') != '0'
+
+    def _densify(self, L, why):
+        """A SparseLaplacian batch outside the sparse path: its dense L (`.to_dense()`, the tensor
+        collate_graph_adjacency builds), announced once per module."""
+        if not getattr(self, '_warned_densify', False):
+            warnings.warn('lanczosnet_amd: %s: the SparseLaplacian batch is densified ([B,N,N,2] float32, '
+                          '%.1f MB) and takes the dense route' % (why, L.B * L.N * L.N * 8 / 1e6), UserWarning)
+            self._warned_densify = True
+        return L.to_dense()
+
     large_head_kernel = os.environ.get('LANCZOSNET_LARGE_HEAD', '1') != '0'
     large_sparse_backoff = 32
 
@@ -282,12 +293,16 @@ class _LargeMixin:
             st['skip'] -= 1
             return None
         exact = planes != 1
-        img = ops.attached_sparse_image(Lf)   # left by the collate's Lanczos pass over this very tensor
-        if img is not None and exact and img.values is None:
-            img = None                        # (an image without the unrounded values)
-        st['image_from'] = 'collate' if img is not None else 'forward'
-        if img is None:
-            img = ops.large_sparse_image(Lf, values=exact)
+        if isinstance(Lf, ops.SparseLaplacian):
+            img = Lf.image                        # built from the edge lists: no launch, no dense L
+            st['image_from'] = 'edges'
+        else:
+            img = ops.attached_sparse_image(Lf)   # left by the collate's Lanczos pass over this very tensor
+            if img is not None and exact and img.values is None:
+                img = None                        # (an image without the unrounded values)
+            st['image_from'] = 'collate' if img is not None else 'forward'
+            if img is None:
+                img = ops.large_sparse_image(Lf, values=exact)
         host = st.get('host')
         if host is None:
             host = st['host'] = torch.zeros((1,), dtype=torch.int32).pin_memory()
@@ -345,6 +360,9 @@ class _LargeMixin:
         if S > 0:
             G = ops.spectral_gains(D, self.long_diffusion_dist, self.num_layer, cache['mlp_pack'])
         state = self._large_sparse_layers(node_feat, Lf, Vf, G, planes)
+        if state is None and isinstance(Lf, ops.SparseLaplacian):
+            # (a raised image flag, a pause after one, or the sparse layers switched off)
+            Lf = self._densify(Lf, 'the sparse conv layers do not serve this batch')
         for attempt in range(2 if state is None else 0):
             Lb, Vb, classes, verify = self._large_pack(Lf, Vf, planes)
             plan = self._plan_large(planes, classes)

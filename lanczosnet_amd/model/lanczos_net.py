@@ -327,6 +327,13 @@ class _LanczosNetBase(_SmallMixin, _MidMixin, _LargeMixin, nn.Module):
         N = L.shape[1]
         route = self._route(N, V.shape[2], L.shape[3], self._needs_grad(), drop,
                             torch.cuda.is_current_stream_capturing())
+        if isinstance(L, ops.SparseLaplacian):
+            # the batch of dataset.collate_graph_edges: its image serves the sparse large-graph
+            # layers; every other route reads the dense tensor
+            if L.device != dev:
+                L = L.to(dev)
+            if route != 'large_hip' or torch.cuda.is_current_stream_capturing():
+                L = self._densify(L, "route '%s'" % route)
         if N <= FUSED_MAX_NODES and not route.startswith('fused'):
             self._warn_library_path(drop)
         if route in _TRAIN_FUNCTIONS:

@@ -772,6 +772,184 @@ def large_sparse_image(L, row_cap=None, values=False):
   return LargeSparseImage(entries, counts, flags, cap, vals)
 
 
+# ---- large graphs from edge lists (csrc/edge_image.hip): no N x N tensor ----------------------------
+EDGE_STATUS_REASONS = ((1, 'an endpoint outside [0, n_nodes)'), (2, 'a self loop'), (4, 'a duplicate edge'),
+                       (8, 'edge_off is not monotone inside the edge array'), (16, 'n_nodes outside [0, N]'))
+
+
+EDGE_ORDER_ASCENDING, EDGE_ORDER_PAIR, EDGE_ORDER_QUAD = 0, 1, 2   # LNZ_EDGE_ORDER_*
+
+
+def dense_entry_orders(N):
+  """(row_order, conv_order): the order in which the DENSE route meets a row's nonzeros for a collated
+  L [B,N,N,2] padded to N nodes — the K-step compaction reads the channels-last pair in place when
+  N % 4 == 0 (even columns of every 128 first) and a contiguous copy otherwise (column % 4 classes of
+  every 256); the conv's image kernel reads the pair when N is even and walks column by column when
+  it is odd.  The sums of the recurrence and of the gather run in entry order: with these orders the
+  images from edge lists are the dense route's bit for bit."""
+  return (EDGE_ORDER_PAIR if N % 4 == 0 else EDGE_ORDER_QUAD,
+          EDGE_ORDER_PAIR if N % 2 == 0 else EDGE_ORDER_ASCENDING)
+
+
+class SparseLaplacian:
+  """The collated L [B,N,N,2] of a batch of unweighted simple graphs with one edge type (channel 0 =
+  channel 1 = L4 of the simple graph, dataset/graph_data.py:225-262) WITHOUT its dense form: the
+  edge arrays it was built from (edges [E,2] int32, edge_off [B+1] int64, n_nodes [B] int32) and the
+  large-graph conv's image of its nonzeros (`image`: a LargeSparseImage with `values`).  A plain
+  object of tensors: `.to(device)` moves it, `nn.DataParallel` can scatter what it holds.
+  `shape` / `dtype` / `device` answer like the dense tensor; `.to_dense()` builds it."""
+  __slots__ = ('B', 'N', 'channels', 'n_nodes', 'image', 'edges', 'edge_off')
+
+  def __init__(self, B, N, n_nodes, image, edges, edge_off, channels=2):
+    self.B, self.N, self.channels = int(B), int(N), int(channels)
+    self.n_nodes, self.image, self.edges, self.edge_off = n_nodes, image, edges, edge_off
+
+  shape = property(lambda self: torch.Size((self.B, self.N, self.N, self.channels)))
+  dtype = property(lambda self: torch.float32)
+  device = property(lambda self: self.n_nodes.device)
+
+  def dim(self):
+    return 4
+
+  def to(self, device):
+    device = torch.device(device)
+    if device == self.device:
+      return self
+    mv = lambda t: None if t is None else t.to(device)   # noqa: E731
+    im = self.image
+    img = LargeSparseImage(mv(im.entries), mv(im.counts), mv(im.flags), im.cap, mv(im.values))
+    return SparseLaplacian(self.B, self.N, mv(self.n_nodes), img, mv(self.edges), mv(self.edge_off), self.channels)
+
+  def to_dense(self):
+    """L [B,N,N,2] float32: the adjacency scattered from the edges, then lnz_laplacian_l4 — bit for
+    bit the tensor collate_graph_adjacency builds for the same graphs."""
+    dev, B, N = self.device, self.B, self.N
+    adjs = torch.zeros((B, N, N, self.channels - 1), dtype=torch.float32, device=dev)
+    E = self.edges.shape[0]
+    if E:
+      gid = torch.repeat_interleave(torch.arange(B, device=dev), self.edge_off[1:] - self.edge_off[:-1],
+                                    output_size=E)
+      u, v = self.edges[:, 0].long(), self.edges[:, 1].long()
+      adjs[gid, u, v] = 1.0
+      adjs[gid, v, u] = 1.0
+    return laplacian_l4(adjs, self.n_nodes)
+
+
+def _edge_inputs(edges, edge_off, n_nodes, N):
+  _need_cuda(edges, edge_off, n_nodes)
+  edges = edges.to(torch.int32).contiguous()
+  edge_off = edge_off.to(torch.int64).contiguous()
+  n_nodes = n_nodes.to(torch.int32).contiguous()
+  B = n_nodes.shape[0]
+  if edges.dim() != 2 or edges.shape[1] != 2 or edge_off.shape != (B + 1,) or B < 1:
+    raise ValueError('edges [E,2], edge_off [B+1], n_nodes [B] (B >= 1) expected, got %s, %s, %s'
+                     % (tuple(edges.shape), tuple(edge_off.shape), tuple(n_nodes.shape)))
+  if not 0 < int(N) <= KSTEP_WIDE_MAX_N:
+    raise ValueError('N=%d: graphs from edge lists are padded to 1 .. %d nodes' % (N, KSTEP_WIDE_MAX_N))
+  return edges, edge_off, n_nodes, B
+
+
+def _empty_image(B, N, ccap, dev):
+  return LargeSparseImage(torch.empty((B, N, ccap), dtype=torch.int32, device=dev),
+                          torch.empty((B, N), dtype=torch.int32, device=dev),
+                          torch.empty((1,), dtype=torch.int32, device=dev), ccap,
+                          torch.empty((B, N, ccap), dtype=torch.float32, device=dev))
+
+
+def _raise_edge_status(status, who):
+  """status: host list of the per-graph status words."""
+  for b, st in enumerate(status):
+    if st:
+      why = ', '.join(text for bit, text in EDGE_STATUS_REASONS if st & bit)
+      raise ValueError('%s: graph %d of the batch is not a simple graph inside its slots: %s (status %d)'
+                       % (who, b, why, st))
+
+
+def sparse_laplacian_from_edges(edges, edge_off, n_nodes, N, row_cap=None):
+  """lnz_laplacian_l4_edges_image: the SparseLaplacian of a batch of edge lists (edges [E,2] local
+  node ids, each undirected edge once; edge_off [B+1]; n_nodes [B]) padded to N nodes, for callers
+  that hold (D, V) already.  row_cap: the conv image's row capacity (None = large_sparse_row_cap(N)).
+  One host read (the status words): ValueError for a graph that is not a simple graph."""
+  edges, edge_off, n_nodes, B = _edge_inputs(edges, edge_off, n_nodes, N)
+  N, dev = int(N), n_nodes.device
+  ccap = large_sparse_row_cap(N) if row_cap is None else int(row_cap)
+  img = _empty_image(B, N, ccap, dev)
+  status = torch.empty((B,), dtype=torch.int32, device=dev)
+  need = _abi().laplacian_l4_edges_image_workspace_bytes(B, N, ccap)
+  ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+  with torch.cuda.device(dev):
+    _abi().laplacian_l4_edges_image(edges, edges.shape[0], edge_off, n_nodes, B, N, ws, need, img.entries,
+                                    img.values, img.counts, ccap, dense_entry_orders(N)[1], img.flags, status)
+  _raise_edge_status(status.tolist(), 'sparse_laplacian_from_edges')
+  return SparseLaplacian(B, N, n_nodes, img, edges, edge_off)
+
+
+def lanczos_ritz_edges(edges, edge_off, n_nodes, N, K, lanczos_steps=None, row_cap=None, return_info=False):
+  """lnz_lanczos_ritz_kstep_edges / _wide_edges: the K-step Ritz pairs of lanczos_ritz_kstep AND the
+  SparseLaplacian of a batch of edge lists padded to N nodes (192 < N <= 16384 is the K-step
+  territory; any N >= K works), with no dense tensor: D [B,K], V [B,N,K], SparseLaplacian (+ info).
+  N <= 2048 and M = lanczos_steps (None = K) <= 64: one workgroup per graph; beyond: the wide
+  launches, chunk by chunk under KSTEP_WIDE_WORKSPACE_CAP.  The entries of a row keep the order the
+  dense route would have met them in (dense_entry_orders): D, V and the image are that route's bit for
+  bit.  One host read (status and overflow
+  words): ValueError for a graph that is not a simple graph; a graph with a row beyond row_cap
+  (None = kstep_row_cap) makes the call densify the batch (`.to_dense()`) and take lanczos_ritz_kstep,
+  with a UserWarning — the result is that route's."""
+  edges, edge_off, n_nodes, B = _edge_inputs(edges, edge_off, n_nodes, N)
+  N, K, dev = int(N), int(K), n_nodes.device
+  M = K if lanczos_steps is None else int(lanczos_steps)
+  Np = (N + 3) // 4 * 4
+  if not 0 < K <= M <= min(Np, KSTEP_WIDE_MAX_M):
+    raise _lib.NotSupported(_lib.LNZ_ENOTSUP, 'lanczos_ritz_edges: K=%d <= M=%d <= %d Lanczos steps (and M <= N=%d) '
+                            'required' % (K, M, KSTEP_WIDE_MAX_M, N))
+  cap = int(row_cap if row_cap is not None else kstep_row_cap(Np))
+  ccap = large_sparse_row_cap(N)
+  E = edges.shape[0]
+  row_order, conv_order = dense_entry_orders(N)
+  img = _empty_image(B, Np, ccap, dev)
+  D = torch.empty((B, K), dtype=torch.float32, device=dev)
+  V = torch.empty((B, Np, K), dtype=torch.float32, device=dev)
+  info = torch.empty((B,), dtype=torch.int32, device=dev)
+  words = torch.empty((2, B), dtype=torch.int32, device=dev)   # status, overflow
+  status, over = words[0], words[1]
+  with torch.cuda.device(dev):
+    if Np <= KSTEP_MAX_N and M <= KSTEP_MAX_M:
+      need = _abi().lanczos_ritz_kstep_edges_workspace_bytes(B, Np, cap, ccap)
+      ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+      _abi().lanczos_ritz_kstep_edges(edges, E, edge_off, n_nodes, B, Np, M, K, cap, row_order, ws, need, D, V, info,
+                                      over, img.entries, img.values, img.counts, ccap, conv_order, img.flags, status)
+    else:
+      size = lambda n: _abi().lanczos_ritz_kstep_wide_edges_workspace_bytes(n, Np, M, cap, ccap)   # noqa: E731
+      chunk = max(1, min(B, KSTEP_WIDE_WORKSPACE_CAP // size(1), 65535))
+      while chunk > 1 and size(chunk) > KSTEP_WIDE_WORKSPACE_CAP:   # (arrays rounded to 256 bytes one by one)
+        chunk -= 1
+      need = size(chunk)
+      ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+      img.flags.zero_()
+      flags = torch.empty((1,), dtype=torch.int32, device=dev)   # (every call zeroes its flag word)
+      for c0 in range(0, B, chunk):
+        c1 = min(B, c0 + chunk)
+        _abi().lanczos_ritz_kstep_wide_edges(edges, E, edge_off[c0:c1 + 1], n_nodes[c0:c1], c1 - c0, Np, M, K, cap,
+                                             row_order, ws, need, D[c0:c1], V[c0:c1], info[c0:c1], over[c0:c1],
+                                             img.entries[c0:c1], img.values[c0:c1], img.counts[c0:c1], ccap,
+                                             conv_order, flags, status[c0:c1])
+        img.flags.bitwise_or_(flags)
+  host = words.tolist()   # the one host read of this path
+  _raise_edge_status(host[0], 'lanczos_ritz_edges')
+  if Np != N:
+    V = V[:, :N, :].contiguous()
+    img = LargeSparseImage(img.entries[:, :N].contiguous(), img.counts[:, :N].contiguous(), img.flags, ccap,
+                           img.values[:, :N].contiguous())
+  sl = SparseLaplacian(B, N, n_nodes, img, edges, edge_off)
+  if any(host[1]):
+    import warnings
+    warnings.warn('lanczos_ritz_edges: graph %d has a row of more than %d entries (the image\'s row capacity): '
+                  'the batch is densified and takes lanczos_ritz_kstep' % (host[1].index(1), cap), UserWarning,
+                  stacklevel=2)
+    D, V, info = lanczos_ritz_kstep(sl.to_dense()[..., 0], n_nodes, M, K, row_cap=row_cap, return_info=True)
+  return (D, V, sl, info) if return_info else (D, V, sl)
+
+
 def large_pack_vectors(V, planes=1):
   """lnz_large_pack_vectors: V [B,N,K] fp32 -> Vb [planes,B,RT,4,64,8] (see large_pack_operators)."""
   _need_cuda(V)

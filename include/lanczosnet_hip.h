@@ -254,6 +254,34 @@ int lnz_large_spectral_gemm1_rows(const float* X, int ldx, int din, const float*
 int lnz_large_sparse_conv_f32(const uint32_t* entries, const float* values, const int32_t* counts,
                               int row_cap, const float* Zf, int B, int N, int relu, float* X,
                               lnz_stream_t stream);
+/* Several operators on the nonzeros: a batch with num_edge_type >= 2, whose collated L [B,N,N,E+1] holds
+ * L4 of the simple graph and of every edge type alone (dataset/get_graph_data.py:60-72), and the
+ * node-space term  sum_c L_c (X W_c^T)  of model/lanczos_net_general.py:157-182 on R = E + 1 = 2 .. 8
+ * images, CHANNEL MAJOR: entries / values [R][B][N][row_cap], counts [R][B][N], each channel in
+ * lnz_large_sparse_image's row format.
+ *   lnz_large_sparse_image_channels   one pass over a dense L [B,N,N,C] (C <= 8, any strides): image c
+ *                            is bit for bit what lnz_large_sparse_image writes for the slice
+ *                            L[..., c:c+1] (ascending columns); flags: bit 1 (a row of some channel
+ *                            beyond row_cap) only.
+ *   lnz_large_sparse_conv_channels    X[r] = act( X[r] + sum_c sum_k value_c[r][k] Z_c[column_c[r][k]] ),
+ *                            channels ascending, entries in entry order, ONE fp32 accumulator: a
+ *                            fixed function of the images.  Z CLASS MAJOR [R][B][N][128] bf16
+ *                            (lnz_large_gemm1_rows once per channel on that channel's fragments).
+ *   lnz_large_sparse_conv_channels_f32  the same in exact fp32: values x Zf [R][B][N][128] fp32
+ *                            (lnz_f32_linear once per channel).
+ * row_cap a multiple of 8, >= 32; N <= 65536; X 8-byte aligned.  A layer = the one-operator layer with
+ * R feature launches and this gather (lnz_large_spectral, lnz_large_conv with C = 0 unchanged).  R = 1:
+ * lnz_large_sparse_conv / _f32. */
+int lnz_large_sparse_image_channels(const float* L, int64_t stride_b, int64_t stride_r, int64_t stride_c,
+                                    int64_t stride_ch, int B, int N, int C, int row_cap,
+                                    uint32_t* entries, float* values, int32_t* counts, int32_t* flags,
+                                    lnz_stream_t stream);
+int lnz_large_sparse_conv_channels(const uint32_t* entries, const int32_t* counts, int row_cap,
+                                   const uint16_t* Z, int B, int N, int R, int relu, float* X,
+                                   lnz_stream_t stream);
+int lnz_large_sparse_conv_channels_f32(const uint32_t* entries, const float* values,
+                                       const int32_t* counts, int row_cap, const float* Zf, int B, int N,
+                                       int R, int relu, float* X, lnz_stream_t stream);
 
 /* ---- R6 standalone: batched symmetric tridiagonal eigensolver --------------------------------
  * The step the reference leaves to LAPACK (inside np.linalg.eigh, utils/data_helper.py:201) /
@@ -439,6 +467,28 @@ int lnz_laplacian_l4_edges_image(const int32_t* edges, int64_t n_edges, const in
                                  int64_t workspace_bytes, uint32_t* conv_entries, float* conv_values,
                                  int32_t* conv_counts, int conv_row_cap, int conv_order,
                                  int32_t* conv_flags, int32_t* status, lnz_stream_t stream);
+/* The conv images of a TYPED batch (num_edge_type = E in 2 .. 7: E + 1 <= 8 operator channels), replacing
+ * utils/data_helper.py:92-116,155-156,261-293 and dataset/get_graph_data.py:60-72 for unweighted simple
+ * graphs whose every node pair carries at most one edge, of one type: edge_type [n_edges] int32 in
+ * [0, E) beside `edges`.  Channel 0 = all neighbours + the diagonal (the image lnz_laplacian_l4_edges_image
+ * builds for the same edge set), channel 1 + e = the type-e neighbours + the diagonal with
+ * deg = 1 + the node's type-e neighbours (a live node without a type-e edge: the single entry (i, 1.0f));
+ * CHANNEL MAJOR conv_entries / conv_values [E+1][B][N][conv_row_cap], conv_counts [E+1][B][N], every
+ * channel in LNZ_EDGE_ORDER_ASCENDING — bit for bit what lnz_large_sparse_image writes for the slice
+ * L[..., c:c+1] of the dense lnz_laplacian_l4 tensor.  status as above, plus 32 = an edge type outside
+ * [0, E); the same pair listed twice, with equal or different types, is status 4.  conv_flags bit 1 is
+ * decided on channel 0.  Integer atomics only; every word is a function of the typed edge SET.  The Ritz
+ * pairs of such a batch are those of channel 0: lnz_lanczos_ritz_kstep_edges / _wide_edges on `edges`
+ * alone (conv_entries NULL, row_order LNZ_EDGE_ORDER_QUAD: the dense route copies L[..., 0] of an
+ * [B,N,N,E+1] tensor to contiguous rows).  workspace 16-B aligned. */
+int64_t lnz_laplacian_l4_typed_edges_images_workspace_bytes(int B, int N, int num_edge_type,
+                                                            int conv_row_cap);
+int lnz_laplacian_l4_typed_edges_images(const int32_t* edges, const int32_t* edge_type, int64_t n_edges,
+                                        const int64_t* edge_off, const int32_t* n_nodes, int B, int N,
+                                        int num_edge_type, void* workspace, int64_t workspace_bytes,
+                                        uint32_t* conv_entries, float* conv_values, int32_t* conv_counts,
+                                        int conv_row_cap, int32_t* conv_flags, int32_t* status,
+                                        lnz_stream_t stream);
 
 /* A HIP stream whose kernels run on compute units [first_cu, end_cu) of the current device only
  * (hipExtStreamCreateWithCUMask).  For latency-chain launches that fill a fraction of the chip —

@@ -75,6 +75,12 @@ SIGNATURES = {
     'lnz_lanczos_ritz_kstep_wide_edges': (C.c_int, [_P, _L, _P, _P, _I, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P]),
     'lnz_laplacian_l4_edges_image_workspace_bytes': (C.c_int64, [_I, _I, _I]),
     'lnz_laplacian_l4_edges_image': (C.c_int, [_P, _L, _P, _P, _I, _I, _P, _L, _P, _P, _P, _I, _I, _P, _P, _P]),
+    'lnz_laplacian_l4_typed_edges_images_workspace_bytes': (C.c_int64, [_I, _I, _I, _I]),
+    'lnz_laplacian_l4_typed_edges_images': (C.c_int, [_P, _P, _L, _P, _P, _I, _I, _I, _P, _L, _P, _P, _P, _I, _P, _P,
+                                                      _P]),
+    'lnz_large_sparse_image_channels': (C.c_int, [_P, _L, _L, _L, _L, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    'lnz_large_sparse_conv_channels': (C.c_int, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P]),
+    'lnz_large_sparse_conv_channels_f32': (C.c_int, [_P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P]),
     'lnz_sym_eigh_topk_workspace_bytes': (C.c_int64, [_I, _I, _I]),
     'lnz_sym_eigh_topk': (C.c_int, [_P, _L, _L, _L, _P, _I, _I, _I, _P, _L, _P, _P, _P, _P]),
     'lnz_stream_create_cu_masked': (C.c_int, [_I, _I, _P]),

@@ -27,6 +27,9 @@
 // — the streamed form's products (bf16 x bf16, fp32 accumulate) without the zeros, in entry order.
 // (The same image falls out of the K-step Lanczos entry's own pass over L: lnz_lanczos_ritz_kstep_image,
 // csrc/lanczos_large.hip — the collated Laplacian is then read from HBM once per batch.)
+// Several DISTINCT operators (two or more edge types): one image per channel
+// (lnz_large_sparse_image_channels, or csrc/edge_image.hip from typed edge lists) and the gather over all
+// of them, lnz_large_sparse_conv_channels[_f32] — the second half of this file.
 #include "common.hpp"
 
 #include <type_traits>
@@ -319,6 +322,221 @@ __global__ __launch_bounds__(64 * WAVES) void sparse_conv_f32_kernel(
   }
 }
 
+
+// ==== several operators (a typed batch: channel 0 = the simple graph, channel 1 + e = edge type e alone,
+// dataset/get_graph_data.py:60-72; the node-space term sum_c L_c (X W_c^T) of
+// model/lanczos_net_general.py:179) ==================================================================
+constexpr int MAXR = 8;   // LARGE_MAX_OPERATORS
+
+// ---- images of all C channels in ONE pass over L: one wave per row, ascending columns, 4-byte loads at
+// the given strides (the channels of a column sit next to each other: every line of the row is fetched
+// from HBM once and serves all channels).  Image c [c][B][N][cap] is, bit for bit, what
+// sparse_image_kernel<0> writes for the one-channel slice L[..., c:c+1]; flags: bit 1 only.
+__global__ __launch_bounds__(256) void sparse_image_channels_kernel(
+    const float* __restrict__ L, int64_t sb, int64_t sr, int64_t sc, int64_t sch, int B, int N, int C,
+    int cap, unsigned* __restrict__ ent, float* __restrict__ vals, int32_t* __restrict__ counts,
+    int32_t* __restrict__ flags) {
+  const int lane = threadIdx.x & 63;
+  const int64_t rows = (int64_t)B * N;
+  const int64_t rid = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (rid >= rows) return;
+  const int b = (int)(rid / N), r = (int)(rid - (int64_t)b * N);
+  const float* Lr = L + (int64_t)b * sb + (int64_t)r * sr;
+  bool over = false;
+  for (int c = 0; c < C; ++c) {
+    const float* Lc = Lr + (int64_t)c * sch;
+    unsigned* oe = ent + ((int64_t)c * rows + rid) * cap;
+    float* ov = vals ? vals + ((int64_t)c * rows + rid) * cap : nullptr;
+    int k = 0;   // entries of this row and channel so far (wave-uniform)
+    for (int c0 = 0; c0 < N; c0 += 64 * 8) {
+      float x[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int col = c0 + 64 * u + lane;
+        x[u] = col < N ? Lc[(int64_t)col * sc] : 0.0f;
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const bool nz = x[u] != 0.0f;   // (a NaN is kept)
+        const unsigned long long m = __ballot(nz);
+        if (m == 0ull) continue;
+        const int pos = k + lane_rank(m);
+        if (nz && pos < cap) {
+          oe[pos] = pack_entry(x[u], c0 + 64 * u + lane);
+          if (ov) ov[pos] = x[u];
+        }
+        k += __popcll(m);
+      }
+    }
+    const int cnt = k < cap ? k : cap;
+    const int cnt8 = (cnt + 7) & ~7;
+    if (cnt + lane < cnt8) {
+      oe[cnt + lane] = 0u;
+      if (ov) ov[cnt + lane] = 0.0f;
+    }
+    if (lane == 0) counts[(int64_t)c * rows + rid] = cnt;
+    over |= k > cap;
+  }
+  if (lane == 0 && over) atomicOr(flags, 2);
+}
+
+// ---- conv: X[r][:] = act( X[r][:] + sum_c sum_k value_c[r][k] Z_c[column_c[r][k]][:] ), R = 2 .. 8 ----
+// The schedule of sparse_conv_kernel with the (row, channel) pairs of a wave's eight rows as its sequence:
+// lane q = R rr + c holds the count of pair q (at most 64 pairs), the entries of pair q + 1 are requested
+// while pair q is gathered, channels ascending and entries in entry order into ONE accumulator per row —
+// the result is a fixed function of the images.  Images [R][B][N][cap], counts [R][B][N], Z CLASS MAJOR
+// [R][B][N][128] (lnz_large_gemm1_rows once per channel): a graph's R feature blocks are R buffers of
+// N x 256 B, the descriptor rebuilt per pair from scalars.
+__global__ __launch_bounds__(64 * WAVES) void sparse_conv_channels_kernel(
+    const unsigned* __restrict__ ent, const int32_t* __restrict__ counts, int cap,
+    const u16* __restrict__ Z, int B, int N, int R, int tiles, int relu, float* __restrict__ X) {
+  const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
+  const int b = xcd + 8 * (seq / tiles), tile = seq % tiles;
+  if (b >= B) return;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r0 = tile * TILE_ROWS + wave * ROWS_PER_WAVE;
+  if (r0 >= N) return;
+  const int nr = min(ROWS_PER_WAVE, N - r0), nq = nr * R;   // (ROWS_PER_WAVE * MAXR <= 64)
+  const int64_t rows = (int64_t)B * N, row0 = (int64_t)b * N + r0;
+  const int cv = lane < nq ? counts[(int64_t)(lane % R) * rows + row0 + lane / R] : 0;
+  const u16* Zb = Z + (int64_t)b * N * DH;
+  const unsigned zoff = 4u * lane;
+  auto entries = [&](const int rr, const int c, const int k0, const int cnt8) -> unsigned {
+    return k0 + lane < cnt8 ? ent[((int64_t)c * rows + row0 + rr) * cap + k0 + lane] : 0u;
+  };
+  int cnt8n = (__builtin_amdgcn_readlane(cv, 0) + GS - 1) & ~(GS - 1);
+  unsigned en = entries(0, 0, 0, cnt8n);
+  f32x2 acc = {0.0f, 0.0f};
+  int rr = 0, c = 0;
+  for (int q = 0; q < nq; ++q) {
+    const int cnt8 = cnt8n;
+    unsigned e = en;
+    float* xr = X + (row0 + rr) * DH + 2 * lane;
+    if (c == 0) acc = *reinterpret_cast<const f32x2*>(xr);
+    const int cn = c + 1 < R ? c + 1 : 0, rn = c + 1 < R ? rr : rr + 1;
+    if (q + 1 < nq) {   // (uniform) the next pair's entries
+      cnt8n = (__builtin_amdgcn_readlane(cv, q + 1) + GS - 1) & ~(GS - 1);
+      en = entries(rn, cn, 0, cnt8n);
+    }
+    const __amdgpu_buffer_rsrc_t z_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<u16*>(Zb + (int64_t)c * rows * DH), 0, (unsigned)N * DH * 2, 0x00020000);
+    for (int k0 = 0; k0 < cnt8; k0 += 64) {
+      if (k0 > 0) e = entries(rr, c, k0, cnt8);   // (rows of more than 64 entries)
+      const int m = min(64, cnt8 - k0);
+      for (int k = 0; k < m; k += 32) {
+        auto turn = [&](auto nc) {   // (one uniform decision, then a straight line: see sparse_conv_kernel)
+          constexpr int n = decltype(nc)::value;
+          unsigned z[n];
+          float s[n];
+#pragma unroll
+          for (int u = 0; u < n; ++u) {
+            const unsigned se = (unsigned)__builtin_amdgcn_readlane((int)e, k + u);
+            s[u] = __uint_as_float(se & 0xffff0000u);
+            z[u] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(z_rsrc, zoff, (se & 0xffffu) * (DH * 2), 0);
+          }
+#pragma unroll
+          for (int u = 0; u < n; ++u) {
+            acc[0] = fmaf(s[u], __uint_as_float(z[u] << 16), acc[0]);
+            acc[1] = fmaf(s[u], __uint_as_float(z[u] & 0xffff0000u), acc[1]);
+          }
+        };
+        switch (min(32, m - k) / GS) {   // (m - k is a multiple of GS)
+#define LNZ_TURN(q) case q: if constexpr (q * GS <= 32) turn(std::integral_constant<int, (q * GS <= 32 ? q * GS : 32)>{}); break;
+          LNZ_TURN(1) LNZ_TURN(2) LNZ_TURN(3) LNZ_TURN(4) LNZ_TURN(5) LNZ_TURN(6) LNZ_TURN(7) LNZ_TURN(8)
+#undef LNZ_TURN
+          default: break;
+        }
+      }
+    }
+    if (cn == 0) {   // the row's last channel
+      if (relu) {
+        acc[0] = acc[0] > 0.0f ? acc[0] : 0.0f;
+        acc[1] = acc[1] > 0.0f ? acc[1] : 0.0f;
+      }
+      *reinterpret_cast<f32x2*>(xr) = acc;
+    }
+    rr = rn;
+    c = cn;
+  }
+}
+
+// ---- the same in exact fp32: values [R][B][N][cap] fp32, Zf CLASS MAJOR [R][B][N][128] fp32 ------------
+__global__ __launch_bounds__(64 * WAVES) void sparse_conv_channels_f32_kernel(
+    const unsigned* __restrict__ ent, const float* __restrict__ vals, const int32_t* __restrict__ counts,
+    int cap, const float* __restrict__ Zf, int B, int N, int R, int tiles, int relu, float* __restrict__ X) {
+  const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
+  const int b = xcd + 8 * (seq / tiles), tile = seq % tiles;
+  if (b >= B) return;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r0 = tile * TILE_ROWS + wave * ROWS_PER_WAVE;
+  if (r0 >= N) return;
+  const int nr = min(ROWS_PER_WAVE, N - r0), nq = nr * R;
+  const int64_t rows = (int64_t)B * N, row0 = (int64_t)b * N + r0;
+  const int cv = lane < nq ? counts[(int64_t)(lane % R) * rows + row0 + lane / R] : 0;
+  const float* Zb = Zf + (int64_t)b * N * DH;
+  const unsigned zoff = 8u * lane;
+  auto entries = [&](const int rr, const int c, const int k0, const int cnt8, unsigned& e, float& v) {
+    const bool in = k0 + lane < cnt8;
+    const int64_t o = ((int64_t)c * rows + row0 + rr) * cap + k0 + lane;
+    e = in ? ent[o] : 0u;
+    v = in ? vals[o] : 0.0f;
+  };
+  int cnt8n = (__builtin_amdgcn_readlane(cv, 0) + 7) & ~7;
+  unsigned en;
+  float vn;
+  entries(0, 0, 0, cnt8n, en, vn);
+  f32x2 acc = {0.0f, 0.0f};
+  int rr = 0, c = 0;
+  for (int q = 0; q < nq; ++q) {
+    const int cnt8 = cnt8n;
+    unsigned e = en;
+    float v = vn;
+    float* xr = X + (row0 + rr) * DH + 2 * lane;
+    if (c == 0) acc = *reinterpret_cast<const f32x2*>(xr);
+    const int cn = c + 1 < R ? c + 1 : 0, rn = c + 1 < R ? rr : rr + 1;
+    if (q + 1 < nq) {   // (uniform) the next pair's entries
+      cnt8n = (__builtin_amdgcn_readlane(cv, q + 1) + 7) & ~7;
+      entries(rn, cn, 0, cnt8n, en, vn);
+    }
+    const __amdgpu_buffer_rsrc_t z_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(Zb + (int64_t)c * rows * DH), 0, (unsigned)N * DH * 4, 0x00020000);
+    for (int k0 = 0; k0 < cnt8; k0 += 64) {
+      if (k0 > 0) entries(rr, c, k0, cnt8, e, v);   // (rows of more than 64 entries)
+      const int m = min(64, cnt8 - k0);
+      for (int k = 0; k < m; k += 16) {
+        auto turn = [&](auto nc) {
+          constexpr int n = decltype(nc)::value;
+          f32x2 z[n];
+          float s[n];
+#pragma unroll
+          for (int u = 0; u < n; ++u) {
+            const unsigned col = (unsigned)__builtin_amdgcn_readlane((int)e, k + u) & 0xffffu;
+            s[u] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k + u));
+            z[u] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(z_rsrc, zoff, col * (DH * 4), 0));
+          }
+#pragma unroll
+          for (int u = 0; u < n; ++u) {
+            acc[0] = fmaf(s[u], z[u][0], acc[0]);
+            acc[1] = fmaf(s[u], z[u][1], acc[1]);
+          }
+        };
+        if (m - k > 8) turn(std::integral_constant<int, 16>{});
+        else turn(std::integral_constant<int, 8>{});
+      }
+    }
+    if (cn == 0) {
+      if (relu) {
+        acc[0] = acc[0] > 0.0f ? acc[0] : 0.0f;
+        acc[1] = acc[1] > 0.0f ? acc[1] : 0.0f;
+      }
+      *reinterpret_cast<f32x2*>(xr) = acc;
+    }
+    rr = rn;
+    c = cn;
+  }
+}
+static_assert(ROWS_PER_WAVE * MAXR <= 64, "a wave's (row, channel) pairs: one count per lane");
+
 }  // namespace
 
 extern "C" int lnz_large_sparse_image(const float* L, int64_t stride_b, int64_t stride_r,
@@ -386,4 +604,68 @@ extern "C" int lnz_large_sparse_conv_f32(const uint32_t* entries, const float* v
                      (hipStream_t)stream, entries, values, counts, row_cap, Zf, B, N, tiles, relu, X);
   lnz::note_kernel("sparse_conv_f32_kernel");
   return lnz::check_launch("lnz_large_sparse_conv_f32");
+}
+
+extern "C" int lnz_large_sparse_image_channels(const float* L, int64_t stride_b, int64_t stride_r,
+                                               int64_t stride_c, int64_t stride_ch, int B, int N, int C,
+                                               int row_cap, uint32_t* entries, float* values,
+                                               int32_t* counts, int32_t* flags, lnz_stream_t stream) {
+  LNZ_REQUIRE(L && entries && counts && flags && B > 0 && N > 0 && C > 0, LNZ_EINVAL,
+              "lnz_large_sparse_image_channels: bad arguments (B=%d N=%d C=%d)", B, N, C);
+  LNZ_REQUIRE(C <= MAXR, LNZ_ENOTSUP, "lnz_large_sparse_image_channels: C=%d > %d operator channels", C, MAXR);
+  LNZ_REQUIRE(N <= 65536, LNZ_ENOTSUP, "lnz_large_sparse_image_channels: N=%d > 65536 (16-bit columns)", N);
+  LNZ_REQUIRE(row_cap >= 32 && row_cap % 8 == 0, LNZ_EINVAL,
+              "lnz_large_sparse_image_channels: row_cap=%d must be a multiple of 8, at least 32", row_cap);
+  const int64_t rows = (int64_t)B * N;
+  LNZ_REQUIRE((rows + 3) / 4 <= 0x7fffffffll, LNZ_ENOTSUP, "lnz_large_sparse_image_channels: B x N too large");
+  hipStream_t s = (hipStream_t)stream;
+  LNZ_REQUIRE(hipMemsetAsync(flags, 0, sizeof(int32_t), s) == hipSuccess, LNZ_ELAUNCH,
+              "lnz_large_sparse_image_channels: hipMemsetAsync failed");
+  hipLaunchKernelGGL(sparse_image_channels_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, L, stride_b,
+                     stride_r, stride_c, stride_ch, B, N, C, row_cap, entries, values, counts, flags);
+  lnz::note_kernel("sparse_image_channels_kernel");
+  return lnz::check_launch("lnz_large_sparse_image_channels");
+}
+
+extern "C" int lnz_large_sparse_conv_channels(const uint32_t* entries, const int32_t* counts, int row_cap,
+                                              const uint16_t* Z, int B, int N, int R, int relu, float* X,
+                                              lnz_stream_t stream) {
+  LNZ_REQUIRE(entries && counts && Z && X && B > 0 && N > 0, LNZ_EINVAL,
+              "lnz_large_sparse_conv_channels: bad arguments");
+  LNZ_REQUIRE(R >= 2 && R <= MAXR, LNZ_ENOTSUP,
+              "lnz_large_sparse_conv_channels: R=%d: 2 .. %d operators (one: lnz_large_sparse_conv)", R, MAXR);
+  LNZ_REQUIRE(N <= 65536, LNZ_ENOTSUP, "lnz_large_sparse_conv_channels: N=%d > 65536 (16-bit columns)", N);
+  LNZ_REQUIRE(row_cap >= 32 && row_cap % 8 == 0, LNZ_EINVAL,
+              "lnz_large_sparse_conv_channels: row_cap=%d must be a multiple of 8, at least 32", row_cap);
+  LNZ_REQUIRE((((uintptr_t)X) & 7) == 0 && (((uintptr_t)Z) & 3) == 0, LNZ_EINVAL,
+              "lnz_large_sparse_conv_channels: X must be 8-byte, Z 4-byte aligned");
+  const int tiles = (N + TILE_ROWS - 1) / TILE_ROWS;
+  const int64_t grid = (int64_t)8 * tiles * ((B + 7) / 8);
+  LNZ_REQUIRE(grid <= 0x7fffffffll, LNZ_ENOTSUP, "lnz_large_sparse_conv_channels: B x N too large");
+  hipLaunchKernelGGL(sparse_conv_channels_kernel, dim3((unsigned)grid), dim3(64 * WAVES), 0,
+                     (hipStream_t)stream, entries, counts, row_cap, Z, B, N, R, tiles, relu, X);
+  lnz::note_kernel("sparse_conv_channels_kernel");
+  return lnz::check_launch("lnz_large_sparse_conv_channels");
+}
+
+extern "C" int lnz_large_sparse_conv_channels_f32(const uint32_t* entries, const float* values,
+                                                  const int32_t* counts, int row_cap, const float* Zf, int B,
+                                                  int N, int R, int relu, float* X, lnz_stream_t stream) {
+  LNZ_REQUIRE(entries && values && counts && Zf && X && B > 0 && N > 0, LNZ_EINVAL,
+              "lnz_large_sparse_conv_channels_f32: bad arguments");
+  LNZ_REQUIRE(R >= 2 && R <= MAXR, LNZ_ENOTSUP,
+              "lnz_large_sparse_conv_channels_f32: R=%d: 2 .. %d operators (one: lnz_large_sparse_conv_f32)", R, MAXR);
+  LNZ_REQUIRE(row_cap >= 32 && row_cap % 8 == 0, LNZ_EINVAL,
+              "lnz_large_sparse_conv_channels_f32: row_cap=%d must be a multiple of 8, at least 32", row_cap);
+  LNZ_REQUIRE((((uintptr_t)X) & 7) == 0 && (((uintptr_t)Zf) & 7) == 0, LNZ_EINVAL,
+              "lnz_large_sparse_conv_channels_f32: X / Zf must be 8-byte aligned");
+  LNZ_REQUIRE(N <= 65536 && (int64_t)N * DH * 4 <= 0x7fffffffll, LNZ_ENOTSUP,
+              "lnz_large_sparse_conv_channels_f32: N=%d too large", N);
+  const int tiles = (N + TILE_ROWS - 1) / TILE_ROWS;
+  const int64_t grid = (int64_t)8 * tiles * ((B + 7) / 8);
+  LNZ_REQUIRE(grid <= 0x7fffffffll, LNZ_ENOTSUP, "lnz_large_sparse_conv_channels_f32: B x N too large");
+  hipLaunchKernelGGL(sparse_conv_channels_f32_kernel, dim3((unsigned)grid), dim3(64 * WAVES), 0,
+                     (hipStream_t)stream, entries, values, counts, row_cap, Zf, B, N, R, tiles, relu, X);
+  lnz::note_kernel("sparse_conv_channels_f32_kernel");
+  return lnz::check_launch("lnz_large_sparse_conv_channels_f32");
 }

@@ -17,6 +17,8 @@
 //            and the gate word of the Ritz launch raised
 // Only integer atomics, and every stored word is a function of the edge SET: the order of the edges
 // and of the endpoints changes which staging slot a column lands in, and the ranking undoes that.
+// Typed batches (edge_type [n_edges] in [0, E), E = 2 .. 7; dataset/get_graph_data.py:60-72): the same four
+// launches write one conv image per operator channel — see edge_typed_rows_kernel below.
 #include "edge_image.hpp"
 #include "ell_image.hpp"
 
@@ -216,6 +218,193 @@ __global__ __launch_bounds__(256) void edge_finish_kernel(int B, int N, int nsla
   }
 }
 
+
+// ---- typed batches: E + 1 conv images (channel 0 = every neighbour, channel 1 + e = the type-e neighbours,
+// each with the diagonal and its OWN degrees: L4 of that channel's graph alone, laplacian.hip:44-79), every
+// channel in ascending column order — the order the 4-byte form of sparse_image_kernel meets a row of a
+// one-channel strided slice L[..., c:c+1] in.  The same four launches; next to the cursor the scatter keeps
+// per-type neighbour counts (integer atomicAdd), next to a staged column its type.
+constexpr int kDiagType = 15;   // (the diagonal's mark in the rows kernel's list: a member of every channel)
+
+__global__ __launch_bounds__(256) void edge_typed_init_kernel(int B, int N, int E, int32_t* __restrict__ cursor,
+                                                              int32_t* __restrict__ tcount,
+                                                              int32_t* __restrict__ status,
+                                                              int32_t* __restrict__ flags) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t < (int64_t)B * N) cursor[t] = 0;
+  if (t < (int64_t)B * N * E) tcount[t] = 0;
+  if (t < B) status[t] = 0;
+  if (t == 0) flags[0] = 0;
+}
+
+__global__ __launch_bounds__(256) void edge_typed_scatter_kernel(EdgeBatch g, const int32_t* __restrict__ edge_type,
+                                                                 int E, int scap, int32_t* __restrict__ cursor,
+                                                                 int32_t* __restrict__ tcount,
+                                                                 uint16_t* __restrict__ stage,
+                                                                 uint8_t* __restrict__ tstage,
+                                                                 int32_t* __restrict__ status) {
+  const int b = blockIdx.y;
+  const int64_t lo = g.edge_off[b], hi = g.edge_off[b + 1];
+  const int n = g.n_nodes[b];
+  const bool bad_off = lo < 0 || hi < lo || hi > g.n_edges, bad_n = n < 0 || n > g.N;
+  if (bad_off || bad_n) {
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+      atomicOr(status + b, (bad_off ? lnz::kEdgeOffsets : 0) | (bad_n ? lnz::kEdgeNodes : 0));
+    return;
+  }
+  const int2* ev = reinterpret_cast<const int2*>(g.edges);
+  const int64_t row0 = (int64_t)b * g.N;
+  for (int64_t e = lo + (int64_t)blockIdx.x * 256 + threadIdx.x; e < hi; e += (int64_t)gridDim.x * 256) {
+    const int2 uv = ev[e];
+    const int ty = edge_type[e];
+    int why = 0;
+    if (uv.x < 0 || uv.x >= n || uv.y < 0 || uv.y >= n) why |= lnz::kEdgeEndpoint;
+    else if (uv.x == uv.y) why |= lnz::kEdgeSelfLoop;
+    if (ty < 0 || ty >= E) why |= lnz::kEdgeType;
+    if (why) {   // (nothing of this edge is used as an index)
+      atomicOr(status + b, why);
+      continue;
+    }
+    const int su = atomicAdd(cursor + row0 + uv.x, 1);
+    if (su < scap - 1) {
+      stage[(row0 + uv.x) * scap + su] = (uint16_t)uv.y;
+      tstage[(row0 + uv.x) * scap + su] = (uint8_t)ty;
+    }
+    atomicAdd(tcount + (row0 + uv.x) * E + ty, 1);
+    const int sv = atomicAdd(cursor + row0 + uv.y, 1);
+    if (sv < scap - 1) {
+      stage[(row0 + uv.y) * scap + sv] = (uint16_t)uv.x;
+      tstage[(row0 + uv.y) * scap + sv] = (uint8_t)ty;
+    }
+    atomicAdd(tcount + (row0 + uv.y) * E + ty, 1);
+  }
+}
+
+// One wave per row, as edge_rows_kernel: every staged entry is ranked twice in ascending column order, among
+// all of the row's entries (channel 0) and among those of its own type and the diagonal (channel 1 + type);
+// the diagonal's rank in channel 1 + e is the number of type-e neighbours below the row.  (scap == cv.cap)
+__global__ __launch_bounds__(256) void edge_typed_rows_kernel(EdgeBatch g, int E, int scap,
+                                                              const int32_t* __restrict__ cursor,
+                                                              const int32_t* __restrict__ tcount,
+                                                              const uint16_t* __restrict__ stage,
+                                                              const uint8_t* __restrict__ tstage,
+                                                              lnz::EdgeConvChannels cv, int32_t* __restrict__ status) {
+  __shared__ int list[4][lnz::kEdgeMaxCap];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t rid = (int64_t)blockIdx.x * 4 + wave;
+  const int64_t rows = (int64_t)g.B * g.N;
+  const bool valid = rid < rows;
+  const int b = valid ? (int)(rid / g.N) : 0, r = valid ? (int)(rid - (int64_t)b * g.N) : 0;
+  const bool live = valid && status[b] == 0 && r < g.n_nodes[b];
+  const int nnb = live ? cursor[rid] : 0;
+  const int m = live ? min(nnb, scap - 1) : 0;           // staged neighbours
+  const int items = live ? m + 1 : 0;
+  int col[4], typ[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int t = lane + 64 * u;
+    col[u] = t < m ? (int)stage[rid * scap + t] : r;
+    typ[u] = t < m ? (int)tstage[rid * scap + t] : kDiagType;
+    if (t < items) list[wave][t] = col[u] | (typ[u] << 16);
+  }
+  __syncthreads();
+  int rank0[4] = {0, 0, 0, 0}, rankt[4] = {0, 0, 0, 0};
+  bool dup = false;
+  for (int j = 0; j < items; ++j) {
+    const int x = list[wave][j];   // (a broadcast read)
+    const int xc = x & 0xffff, xt = x >> 16;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int t = lane + 64 * u;
+      const bool less = xc < col[u] || (xc == col[u] && j < t);
+      rank0[u] += less ? 1 : 0;
+      rankt[u] += (less && (xt == typ[u] || xt == kDiagType)) ? 1 : 0;
+      dup |= t < items && xc == col[u] && j != t;
+    }
+  }
+  if (!valid) return;   // (no barrier below)
+  // channel 0: every entry, the degrees of the simple graph
+  {
+    unsigned* ce = cv.ent + rid * cv.cap;
+    float* cvv = cv.vals ? cv.vals + rid * cv.cap : nullptr;
+    const double si = 1.0 / sqrt((double)(nnb + 1));
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int t = lane + 64 * u;
+      if (t >= items) continue;
+      const int c = col[u], pos = rank0[u];
+      const int dc = c == r ? nnb : cursor[(int64_t)b * g.N + c];   // (c < n_b: checked before it was staged)
+      const float v = (float)((si * 1.0) * (1.0 / sqrt((double)(dc + 1))));
+      if (pos < cv.cap) {
+        ce[pos] = conv_entry(v, c);
+        if (cvv) cvv[pos] = v;
+      }
+    }
+    const int k = live ? nnb + 1 : 0, c = k < cv.cap ? k : cv.cap;
+    if (c + lane < ((c + 7) & ~7)) {   // (the conv walks whole groups of eight)
+      ce[c + lane] = 0u;
+      if (cvv) cvv[c + lane] = 0.f;
+    }
+    if (lane == 0) {
+      cv.counts[rid] = c;
+      if (k > cv.cap) atomicOr(cv.flags, 2);
+    }
+  }
+  // channel 1 + e: the staged type-e entries and the diagonal, the degrees of the type-e graph
+  for (int e = 0; e < E; ++e) {
+    int ke = live ? 1 : 0, below = 0;
+    bool in[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      in[u] = lane + 64 * u < m && typ[u] == e;
+      ke += __popcll(__ballot(in[u]));
+      below += __popcll(__ballot(in[u] && col[u] < r));
+    }
+    const int64_t at = ((int64_t)(1 + e) * rows + rid) * cv.cap;
+    unsigned* ce = cv.ent + at;
+    float* cvv = cv.vals ? cv.vals + at : nullptr;
+    const int de = live ? tcount[rid * E + e] : 0;
+    const double si = 1.0 / sqrt((double)(de + 1));
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (!in[u]) continue;
+      const int c = col[u], pos = rankt[u];
+      const int dc = tcount[((int64_t)b * g.N + c) * E + e];
+      const float v = (float)((si * 1.0) * (1.0 / sqrt((double)(dc + 1))));
+      if (pos < cv.cap) {
+        ce[pos] = conv_entry(v, c);
+        if (cvv) cvv[pos] = v;
+      }
+    }
+    if (live && lane == 0 && below < cv.cap) {   // (a live node with no type-e edge: the single entry (i, 1.0f))
+      const float v = (float)((si * 1.0) * si);
+      ce[below] = conv_entry(v, r);
+      if (cvv) cvv[below] = v;
+    }
+    const int c = ke < cv.cap ? ke : cv.cap;
+    if (c + lane < ((c + 7) & ~7)) {
+      ce[c + lane] = 0u;
+      if (cvv) cvv[c + lane] = 0.f;
+    }
+    if (lane == 0) cv.counts[(int64_t)(1 + e) * rows + rid] = c;
+  }
+  if (__ballot(dup) != 0ull && lane == 0) atomicOr(status + b, lnz::kEdgeDuplicate);
+}
+
+// One workgroup per (graph, channel): a graph with a non-zero status has its rows emptied in every channel.
+__global__ __launch_bounds__(256) void edge_typed_finish_kernel(int B, int N, lnz::EdgeConvChannels cv,
+                                                                const int32_t* __restrict__ status) {
+  const int b = blockIdx.x, c = blockIdx.y, t = threadIdx.x;
+  if (status[b] == 0) return;
+  const int64_t row0 = ((int64_t)c * B + b) * N;
+  for (int i = t; i < N; i += 256) cv.counts[row0 + i] = 0;
+  const int64_t words = (int64_t)N * cv.cap, at = row0 * cv.cap;
+  for (int64_t i = t; i < words; i += 256) {
+    cv.ent[at + i] = 0u;
+    if (cv.vals) cv.vals[at + i] = 0.f;
+  }
+}
+
 }  // namespace
 
 int64_t lnz::edge_scratch_bytes(int B, int N, int stage_cap) {
@@ -283,5 +472,70 @@ extern "C" int lnz_laplacian_l4_edges_image(const int32_t* edges, int64_t n_edge
   const EdgeRitz norz{nullptr, nullptr, nullptr, 0, nullptr};
   const int rc = lnz::edge_image_build(who, g, noell, cv, norz, workspace, workspace_bytes, status, (hipStream_t)stream);
   if (rc == LNZ_OK) lnz::note_kernel("edge_rows_kernel");
+  return rc;
+}
+
+// ---- the conv images of a typed batch --------------------------------------------------------------------
+int64_t lnz::edge_typed_scratch_bytes(int B, int N, int E, int cap) {
+  const int64_t rows = (int64_t)B * N;
+  return al256(rows * 4) + al256(rows * E * 4) + al256(rows * cap * 2) + al256(rows * cap);
+}
+
+int lnz::edge_typed_image_build(const char* who, const EdgeBatch& g, const int32_t* edge_type, int E,
+                                const EdgeConvChannels& cv, void* scratch, int64_t scratch_bytes, int32_t* status,
+                                hipStream_t stream) {
+  LNZ_REQUIRE(g.edge_off && g.n_nodes && status && scratch && g.B > 0 && g.N > 0 && g.n_edges >= 0 &&
+                  ((g.edges && edge_type) || g.n_edges == 0),
+              LNZ_EINVAL,
+              "%s: bad arguments (edges, edge_type, edge_off, n_nodes, status, workspace non-null; B=%d N=%d >= 1)", who,
+              g.B, g.N);
+  LNZ_REQUIRE(E >= 2 && E <= kEdgeMaxTypes, LNZ_ENOTSUP,
+              "%s: num_edge_type=%d: 2 .. %d edge types (one type: the untyped entries)", who, E, kEdgeMaxTypes);
+  LNZ_REQUIRE(g.N <= kEdgeMaxN && g.B <= 65535, LNZ_ENOTSUP, "%s: N=%d <= %d nodes, B=%d <= 65535 graphs per call", who,
+              g.N, kEdgeMaxN, g.B);
+  LNZ_REQUIRE((reinterpret_cast<uintptr_t>(g.edges) & 7) == 0 && (reinterpret_cast<uintptr_t>(edge_type) & 3) == 0 &&
+                  (reinterpret_cast<uintptr_t>(scratch) & 15) == 0,
+              LNZ_EINVAL, "%s: edges must be 8-byte, edge_type 4-byte, the workspace 16-byte aligned", who);
+  LNZ_REQUIRE(cv.ent && cv.counts && cv.flags && cv.cap >= 32 && cv.cap % 8 == 0 && cv.cap <= kEdgeMaxCap, LNZ_EINVAL,
+              "%s: conv image outputs (conv_row_cap=%d: a multiple of 8 in [32, %d])", who, cv.cap, kEdgeMaxCap);
+  const int64_t need = edge_typed_scratch_bytes(g.B, g.N, E, cv.cap);
+  LNZ_REQUIRE(scratch_bytes >= need, LNZ_EINVAL, "%s: workspace of %lld bytes, %lld needed", who,
+              (long long)scratch_bytes, (long long)need);
+  const int64_t rows = (int64_t)g.B * g.N;
+  char* ws = (char*)scratch;
+  int32_t* cursor = (int32_t*)ws;
+  int32_t* tcount = (int32_t*)(ws + al256(rows * 4));
+  uint16_t* stage = (uint16_t*)(ws + al256(rows * 4) + al256(rows * E * 4));
+  uint8_t* tstage = (uint8_t*)(ws + al256(rows * 4) + al256(rows * E * 4) + al256(rows * cv.cap * 2));
+  hipLaunchKernelGGL(edge_typed_init_kernel, dim3((unsigned)((rows * E + 255) / 256)), dim3(256), 0, stream, g.B, g.N, E,
+                     cursor, tcount, status, cv.flags);
+  const int64_t chunks = std::min<int64_t>(256, std::max<int64_t>(1, (g.n_edges / g.B + 1023) / 1024));
+  hipLaunchKernelGGL(edge_typed_scatter_kernel, dim3((unsigned)chunks, (unsigned)g.B), dim3(256), 0, stream, g, edge_type,
+                     E, cv.cap, cursor, tcount, stage, tstage, status);
+  hipLaunchKernelGGL(edge_typed_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, g, E, cv.cap, cursor,
+                     tcount, stage, tstage, cv, status);
+  hipLaunchKernelGGL(edge_typed_finish_kernel, dim3((unsigned)g.B, (unsigned)(E + 1)), dim3(256), 0, stream, g.B, g.N, cv,
+                     status);
+  return lnz::check_launch(who);
+}
+
+extern "C" int64_t lnz_laplacian_l4_typed_edges_images_workspace_bytes(int B, int N, int num_edge_type,
+                                                                       int conv_row_cap) {
+  if (B <= 0 || N <= 0 || num_edge_type <= 0 || conv_row_cap <= 0) return 0;
+  return lnz::edge_typed_scratch_bytes(B, N, num_edge_type, conv_row_cap);
+}
+
+extern "C" int lnz_laplacian_l4_typed_edges_images(const int32_t* edges, const int32_t* edge_type, int64_t n_edges,
+                                                   const int64_t* edge_off, const int32_t* n_nodes, int B, int N,
+                                                   int num_edge_type, void* workspace, int64_t workspace_bytes,
+                                                   uint32_t* conv_entries, float* conv_values, int32_t* conv_counts,
+                                                   int conv_row_cap, int32_t* conv_flags, int32_t* status,
+                                                   lnz_stream_t stream) {
+  const char* who = "lnz_laplacian_l4_typed_edges_images";
+  const EdgeBatch g{edges, n_edges, edge_off, n_nodes, B, N};
+  const lnz::EdgeConvChannels cv{conv_entries, conv_values, conv_counts, conv_flags, conv_row_cap};
+  const int rc = lnz::edge_typed_image_build(who, g, edge_type, num_edge_type, cv, workspace, workspace_bytes, status,
+                                             (hipStream_t)stream);
+  if (rc == LNZ_OK) lnz::note_kernel("edge_typed_rows_kernel");
   return rc;
 }

@@ -13,6 +13,7 @@ constexpr int kEdgeSelfLoop = 2;    // an edge (i, i)
 constexpr int kEdgeDuplicate = 4;   // an edge listed twice (either orientation)
 constexpr int kEdgeOffsets = 8;     // edge_off[b] .. edge_off[b + 1] is not a range inside the edge array
 constexpr int kEdgeNodes = 16;      // n_nodes[b] outside [0, N]
+constexpr int kEdgeType = 32;       // (typed batches) an edge type outside [0, E)
 constexpr int kEdgeMaxCap = 256;    // row capacities served (a wave ranks 4 entries per lane)
 constexpr int kEdgeMaxN = 16384;
 
@@ -57,5 +58,25 @@ inline int edge_stage_cap(int row_cap, int conv_row_cap) { return row_cap > conv
 int edge_image_build(const char* who, const EdgeBatch& g, const EdgeEll& ell, const EdgeConv& cv,
                      const EdgeRitz& rz, void* scratch, int64_t scratch_bytes, int32_t* status,
                      hipStream_t stream);
+
+// ---- typed batches: edge_type [n_edges] in [0, E), one conv image per operator channel ----------------
+constexpr int kEdgeMaxTypes = 7;    // E + 1 <= 8 operator channels (LARGE_MAX_OPERATORS)
+
+struct EdgeConvChannels {    // E + 1 conv images, channel major, each in EdgeConv's row format
+  uint32_t* ent;             // [E + 1][B][N][cap]
+  float* vals;               // [E + 1][B][N][cap], optional
+  int32_t* counts;           // [E + 1][B][N]
+  int32_t* flags;            // one word: bit 1 = a row of channel 0 beyond `cap` (the others are subsets + diagonal)
+  int cap;
+};
+
+// cursor [B][N] int32 + per-type neighbour counts [B][N][E] int32 + staged columns [B][N][cap] u16 + staged
+// types [B][N][cap] u8
+int64_t edge_typed_scratch_bytes(int B, int N, int E, int cap);
+
+// Four launches on `stream`: init, scatter, rows, finish.  Every channel in ascending column order.
+int edge_typed_image_build(const char* who, const EdgeBatch& g, const int32_t* edge_type, int E,
+                           const EdgeConvChannels& cv, void* scratch, int64_t scratch_bytes, int32_t* status,
+                           hipStream_t stream);
 
 }  // namespace lnz

@@ -107,7 +107,7 @@ def collate_graph_adjacency(items, num_eigs, device='cuda', model_name='LanczosN
     return out
 
 
-def collate_graph_edges(items, num_eigs, device='cuda', lanczos_steps=None):
+def collate_graph_edges(items, num_eigs, device='cuda', lanczos_steps=None, num_edge_type=1):
     """Raw graphs as EDGE LISTS in, device-resident batch out with no array of N x N elements on the
     host or the device: items carry `edges [m,2]` (integer local node ids, each undirected edge once,
     either endpoint order; unweighted simple graphs, ONE edge type — the reference's graph
@@ -117,7 +117,15 @@ def collate_graph_edges(items, num_eigs, device='cuda', lanczos_steps=None):
     replacing utils/data_helper.py:92-116,155-156,205-223 and dataset/get_graph_data.py:61-72).
     Batches padded to N <= 192 nodes are outside the K-step territory: they are densified and the
     result is collate_graph_adjacency's for the same graphs.  ValueError for a malformed argument
-    (here) or a graph that is not a simple graph (found on the device)."""
+    (here) or a graph that is not a simple graph (found on the device).
+    num_edge_type = E >= 2 (at most 7): every item also carries `edge_type [m]`, integers in [0, E), one
+    type per edge (a node pair carries at most one edge; pairs with two bond types stay with
+    collate_graph_adjacency).  `L` then has E + 1 channels (channel 0 the simple graph, channel 1 + e
+    edge type e alone, dataset/get_graph_data.py:60-72) and carries one sparse image per channel; D / V
+    are channel 0's.  num_edge_type = 1: an `edge_type` key, if present, must be all zeros."""
+    num_edge_type = int(num_edge_type)
+    if not 1 <= num_edge_type <= 7:
+        raise ValueError('collate_graph_edges: num_edge_type=%d: 1 .. 7 edge types are served' % num_edge_type)
     if not isinstance(items, (list, tuple)) or len(items) == 0:
         raise ValueError('collate_graph_edges: a non-empty list of items expected')
     num_eigs = int(num_eigs or 0)
@@ -125,7 +133,7 @@ def collate_graph_edges(items, num_eigs, device='cuda', lanczos_steps=None):
         raise ValueError('collate_graph_edges: num_eigs=%d' % num_eigs)
     if lanczos_steps is not None and int(lanczos_steps) < num_eigs:
         raise ValueError('collate_graph_edges: lanczos_steps=%d < num_eigs=%d' % (lanczos_steps, num_eigs))
-    lists = []
+    lists, types = [], []
     for b, it in enumerate(items):
         for key in ('edges', 'node_feat', 'label'):
             if key not in it:
@@ -143,6 +151,22 @@ def collate_graph_edges(items, num_eigs, device='cuda', lanczos_steps=None):
         if e.size and (e.min() < -2**31 or e.max() >= 2**31):
             raise ValueError('collate_graph_edges: item %d: node ids beyond int32' % b)
         lists.append(e.astype(np.int32))
+        if num_edge_type > 1 or 'edge_type' in it:
+            if 'edge_type' not in it:
+                raise ValueError('collate_graph_edges: item %d has no %r (num_edge_type=%d)'
+                                 % (b, 'edge_type', num_edge_type))
+            ty = np.asarray(it['edge_type'])
+            if ty.size == 0:
+                ty = np.zeros((0,), dtype=np.int32)
+            if ty.ndim != 1 or ty.shape[0] != lists[-1].shape[0]:
+                raise ValueError('collate_graph_edges: item %d: edge_type of shape %s, [%d] expected'
+                                 % (b, ty.shape, lists[-1].shape[0]))
+            if not np.issubdtype(ty.dtype, np.integer):
+                raise ValueError('collate_graph_edges: item %d: edge_type of dtype %s, integers expected'
+                                 % (b, ty.dtype))
+            if ty.size and (ty.min() < 0 or ty.max() >= num_edge_type):
+                raise ValueError('collate_graph_edges: item %d: an edge type outside [0, %d)' % (b, num_edge_type))
+            types.append(ty.astype(np.int32))
     from .. import ops
     sizes, B, N, node_feat, mask, label = _pad_common(items)
     if N > ops.KSTEP_WIDE_MAX_N:
@@ -153,9 +177,10 @@ def collate_graph_edges(items, num_eigs, device='cuda', lanczos_steps=None):
         for it, e, n in zip(items, lists, sizes):
             if e.size and (e.min() < 0 or e.max() >= n or (e[:, 0] == e[:, 1]).any()):
                 raise ValueError('collate_graph_edges: an endpoint outside the graph or a self loop')
-            a = np.zeros((n, n, 1), dtype=np.float32)
-            a[e[:, 0], e[:, 1], 0] = 1.0
-            a[e[:, 1], e[:, 0], 0] = 1.0
+            a = np.zeros((n, n, num_edge_type), dtype=np.float32)
+            ty = types[len(dense)] if num_edge_type > 1 else 0
+            a[e[:, 0], e[:, 1], ty] = 1.0
+            a[e[:, 1], e[:, 0], ty] = 1.0
             dense.append(dict(adjs=a, node_feat=it['node_feat'], label=it['label']))
         return collate_graph_adjacency(dense, num_eigs, device=device, lanczos_steps=lanczos_steps)
     dev = torch.device(device)
@@ -166,11 +191,14 @@ def collate_graph_edges(items, num_eigs, device='cuda', lanczos_steps=None):
     n_nodes = torch.tensor(sizes, dtype=torch.int32, device=dev)
     out = dict(node_feat=torch.from_numpy(node_feat).to(dev), node_mask=torch.from_numpy(mask).to(dev),
                label=torch.from_numpy(label).to(dev), n_nodes=n_nodes)
+    typed = {}
+    if num_edge_type > 1:
+        typed = dict(edge_type=torch.from_numpy(np.concatenate(types, axis=0)).to(dev), num_edge_type=num_edge_type)
     if num_eigs:
         out['D'], out['V'], out['L'] = ops.lanczos_ritz_edges(edges, edge_off, n_nodes, N, num_eigs,
-                                                              lanczos_steps=lanczos_steps)
+                                                              lanczos_steps=lanczos_steps, **typed)
     else:
-        out['L'] = ops.sparse_laplacian_from_edges(edges, edge_off, n_nodes, N)
+        out['L'] = ops.sparse_laplacian_from_edges(edges, edge_off, n_nodes, N, **typed)
     return out
 
 

@@ -132,8 +132,12 @@ class _LargeMixin:
                 d32 = (d_in + 31) // 32 * 32
                 Wn32 = torch.nn.functional.pad(Wn[:, 0, :d_in], (0, d32 - d_in)).contiguous() \
                     if len(reps) == 1 else None
+                # several operator classes: their fp32 blocks stacked [R * 128, d32], NOT summed
+                # (lnz_large_sparse_conv_channels_f32: one lnz_f32_linear per channel)
+                Wn32s = torch.nn.functional.pad(Wn[:, :, :d_in].permute(1, 0, 2).reshape(len(reps) * dout, d_in),
+                                                (0, d32 - d_in)).contiguous() if len(reps) > 1 else None
                 layers.append(dict(Wb=Wb, Wt=Wt, bias=self.filter[t].bias.detach().float().contiguous(),
-                                   din=d_in, Wn32=Wn32))
+                                   din=d_in, Wn32=Wn32, Wn32s=Wn32s))
             cache['conv'][key] = layers
         return cache
 
@@ -266,6 +270,13 @@ class _LargeMixin:
     # next `large_sparse_backoff` calls on this device do not try again (twice as many after every
     # further failure in a row, up to 32 x).
     large_sparse = os.environ.get('LANCZOSNET_LARGE_SPARSE', '1') != '0'
+    # A dense L with SEVERAL distinct operator channels (two or more edge types): 'one' claims one
+    # operator class, finds the claim refuted (flag bit 0) and backs off to the streamed kernels;
+    # 'each' (or LANCZOSNET_LARGE_SPARSE_CHANNELS=each) reads L once into one image per channel
+    # (lnz_large_sparse_image_channels) and gathers over all of them (lnz_large_sparse_conv_channels).
+    # A typed SparseLaplacian (collate_graph_edges with num_edge_type >= 2) carries those images and
+    # takes that gather whatever this says.
+    large_sparse_channels = os.environ.get('LANCZOSNET_LARGE_SPARSE_CHANNELS', 'one')
 
     def _densify(self, L, why):
         """A SparseLaplacian batch outside the sparse path: its dense L (`.to_dense()`, the tensor
@@ -293,9 +304,18 @@ class _LargeMixin:
             st['skip'] -= 1
             return None
         exact = planes != 1
-        if isinstance(Lf, ops.SparseLaplacian):
+        if self.large_sparse_channels not in ('one', 'each'):
+            raise ValueError("large_sparse_channels is 'one' or 'each', got %r" % (self.large_sparse_channels,))
+        imgs = None                               # the images of several operators
+        if isinstance(Lf, ops.SparseLaplacian) and Lf.images is not None:
+            img = imgs = Lf.images                # a typed batch: one image per channel, from the edge lists
+            st['image_from'] = 'edges'
+        elif isinstance(Lf, ops.SparseLaplacian):
             img = Lf.image                        # built from the edge lists: no launch, no dense L
             st['image_from'] = 'edges'
+        elif self.large_sparse_channels == 'each' and 1 < Cn <= LARGE_MAX_OPERATORS and Lf.stride(3) != 0:
+            img = imgs = ops.large_sparse_image_channels(Lf)
+            st['image_from'] = 'forward'
         else:
             img = ops.attached_sparse_image(Lf)   # left by the collate's Lanczos pass over this very tensor
             if img is not None and exact and img.values is None:
@@ -310,13 +330,31 @@ class _LargeMixin:
         ev = torch.cuda.Event()
         ev.record()
         Vb = ops.large_pack_vectors(Vf, planes)
-        classes = (0,) * Cn
+        classes = (0,) * Cn if imgs is None else tuple(range(Cn))
         plan = self._plan_large(planes, classes)
         # (lnz_f32_linear's K: the exact form takes the input columns padded to a multiple of 32)
         state = input_state(self, node_feat, width=(self.input_dim + 31) // 32 * 32 if exact else None,
                             as_float=True).contiguous()
         bufs = [None, None]
-        if not exact:
+        if imgs is not None:
+            dev = Lf.device
+            if not exact:
+                work = ops.large_sparse_channels_work_buffers(Cn, B, N, dev)
+            else:
+                work = (torch.empty((Cn, B, N, 128), dtype=torch.float32, device=dev),
+                        torch.zeros((planes, B, 128, 64), dtype=ops.large_plane_dtype(planes), device=dev),
+                        torch.zeros((B, 64, 128), dtype=torch.float32, device=dev))
+            for t, lay in enumerate(plan['conv'][(planes, classes)]):
+                Gt = G[t] if G is not None else None
+                if not exact:
+                    state = ops.large_sparse_conv_layer_channels(state, lay['din'], imgs, Vb, Vf, lay['Wb'], lay['Wt'],
+                                                                 Gt, lay['bias'], work, relu=True, out=bufs[t & 1])
+                else:
+                    state = ops.large_sparse_conv_layer_channels_f32(state, lay['din'], imgs, Vb, Vf, lay['Wn32s'],
+                                                                     lay['Wt'], Gt, lay['bias'], work, planes,
+                                                                     relu=True, out=bufs[t & 1])
+                bufs[t & 1] = state
+        elif not exact:
             work = ops.large_sparse_work_buffers(B, N, Lf.device)
             for t, lay in enumerate(plan['conv'][(1, classes)]):
                 state = ops.large_sparse_conv_layer(state, lay['din'], img, Vb, Vf, lay['Wb'], lay['Wt'],

@@ -330,6 +330,9 @@ class _LanczosNetBase(_SmallMixin, _MidMixin, _LargeMixin, nn.Module):
         if isinstance(L, ops.SparseLaplacian):
             # the batch of dataset.collate_graph_edges: its image serves the sparse large-graph
             # layers; every other route reads the dense tensor
+            if L.channels != self.num_edgetype + 1:
+                raise ValueError('the SparseLaplacian batch has %d operator channels (num_edge_type = %d), the '
+                                 'model num_edgetype + 1 = %d' % (L.channels, L.channels - 1, self.num_edgetype + 1))
             if L.device != dev:
                 L = L.to(dev)
             if route != 'large_hip' or torch.cuda.is_current_stream_capturing():

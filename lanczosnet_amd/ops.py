@@ -772,9 +772,53 @@ def large_sparse_image(L, row_cap=None, values=False):
   return LargeSparseImage(entries, counts, flags, cap, vals)
 
 
+class LargeSparseImages:
+  """The images of R operator channels, CHANNEL MAJOR (lnz_large_sparse_image_channels,
+  lnz_laplacian_l4_typed_edges_images): entries [R,B,N,cap] int32, values [R,B,N,cap] fp32 (or None),
+  counts [R,B,N], flags (one int32 on the device: bit 1 = a row overflowed `cap`; non-zero = the images
+  must not be used).  `.channel(c)` is channel c as a LargeSparseImage (views, the shared flag word)."""
+  __slots__ = ('entries', 'counts', 'flags', 'cap', 'R', 'B', 'N', 'values')
+
+  def __init__(self, entries, counts, flags, cap, values=None):
+    self.entries, self.counts, self.flags, self.cap, self.values = entries, counts, flags, cap, values
+    self.R, self.B, self.N = counts.shape
+
+  def channel(self, c):
+    return LargeSparseImage(self.entries[c], self.counts[c], self.flags, self.cap,
+                            None if self.values is None else self.values[c])
+
+  def to(self, device):
+    mv = lambda t: None if t is None else t.to(device)   # noqa: E731
+    return LargeSparseImages(mv(self.entries), mv(self.counts), mv(self.flags), self.cap, mv(self.values))
+
+
+def _empty_images(R, B, N, cap, dev, values=True):
+  return LargeSparseImages(torch.empty((R, B, N, cap), dtype=torch.int32, device=dev),
+                           torch.empty((R, B, N), dtype=torch.int32, device=dev),
+                           torch.empty((1,), dtype=torch.int32, device=dev), cap,
+                           torch.empty((R, B, N, cap), dtype=torch.float32, device=dev) if values else None)
+
+
+def large_sparse_image_channels(L, row_cap=None, values=True):
+  """lnz_large_sparse_image_channels on the current stream: L [B,N,N,C] fp32 (any strides, C <= 8) read
+  once -> the LargeSparseImages of all C channels; image c is bit for bit large_sparse_image(L[..., c:c+1])."""
+  _need_cuda(L)
+  assert L.dim() == 4 and L.dtype == torch.float32
+  B, N, _, Cn = L.shape
+  cap = large_sparse_row_cap(N) if row_cap is None else int(row_cap)
+  imgs = _empty_images(Cn, B, N, cap, L.device, values)
+  sb, sr, sc, sch = L.stride()
+  with torch.cuda.device(L.device):
+    _abi().large_sparse_image_channels(L, sb, sr, sc, sch, B, N, Cn, cap, imgs.entries, imgs.values, imgs.counts,
+                                       imgs.flags)
+  return imgs
+
+
 # ---- large graphs from edge lists (csrc/edge_image.hip): no N x N tensor ----------------------------
 EDGE_STATUS_REASONS = ((1, 'an endpoint outside [0, n_nodes)'), (2, 'a self loop'), (4, 'a duplicate edge'),
                        (8, 'edge_off is not monotone inside the edge array'), (16, 'n_nodes outside [0, N]'))
+# (typed batches, lnz_laplacian_l4_typed_edges_images, add one)
+EDGE_TYPED_STATUS_REASONS = EDGE_STATUS_REASONS + ((32, 'an edge type outside [0, num_edge_type)'),)
 
 
 EDGE_ORDER_ASCENDING, EDGE_ORDER_PAIR, EDGE_ORDER_QUAD = 0, 1, 2   # LNZ_EDGE_ORDER_*
@@ -792,17 +836,20 @@ def dense_entry_orders(N):
 
 
 class SparseLaplacian:
-  """The collated L [B,N,N,2] of a batch of unweighted simple graphs with one edge type (channel 0 =
-  channel 1 = L4 of the simple graph, dataset/graph_data.py:225-262) WITHOUT its dense form: the
-  edge arrays it was built from (edges [E,2] int32, edge_off [B+1] int64, n_nodes [B] int32) and the
-  large-graph conv's image of its nonzeros (`image`: a LargeSparseImage with `values`).  A plain
+  """The collated L [B,N,N,E+1] of a batch of unweighted simple graphs (channel 0 = L4 of the simple
+  graph, channel 1 + e = L4 of edge type e alone, dataset/graph_data.py:225-262) WITHOUT its dense form:
+  the edge arrays it was built from (edges [m,2] int32, edge_off [B+1] int64, n_nodes [B] int32, and
+  for E >= 2 edge_type [m] int32) and the large-graph conv's image of its nonzeros (`image`: channel
+  0's LargeSparseImage with `values`; with one edge type both channels are that operator).  E >= 2:
+  `images` holds all E + 1 channels (a LargeSparseImages; `image` is its channel 0), else None.  A plain
   object of tensors: `.to(device)` moves it, `nn.DataParallel` can scatter what it holds.
   `shape` / `dtype` / `device` answer like the dense tensor; `.to_dense()` builds it."""
-  __slots__ = ('B', 'N', 'channels', 'n_nodes', 'image', 'edges', 'edge_off')
+  __slots__ = ('B', 'N', 'channels', 'n_nodes', 'image', 'edges', 'edge_off', 'edge_type', 'images')
 
-  def __init__(self, B, N, n_nodes, image, edges, edge_off, channels=2):
+  def __init__(self, B, N, n_nodes, image, edges, edge_off, channels=2, edge_type=None, images=None):
     self.B, self.N, self.channels = int(B), int(N), int(channels)
     self.n_nodes, self.image, self.edges, self.edge_off = n_nodes, image, edges, edge_off
+    self.edge_type, self.images = edge_type, images
 
   shape = property(lambda self: torch.Size((self.B, self.N, self.N, self.channels)))
   dtype = property(lambda self: torch.float32)
@@ -816,23 +863,44 @@ class SparseLaplacian:
     if device == self.device:
       return self
     mv = lambda t: None if t is None else t.to(device)   # noqa: E731
-    im = self.image
-    img = LargeSparseImage(mv(im.entries), mv(im.counts), mv(im.flags), im.cap, mv(im.values))
-    return SparseLaplacian(self.B, self.N, mv(self.n_nodes), img, mv(self.edges), mv(self.edge_off), self.channels)
+    if self.images is not None:
+      imgs = self.images.to(device)
+      img = imgs.channel(0)
+    else:
+      im, imgs = self.image, None
+      img = LargeSparseImage(mv(im.entries), mv(im.counts), mv(im.flags), im.cap, mv(im.values))
+    return SparseLaplacian(self.B, self.N, mv(self.n_nodes), img, mv(self.edges), mv(self.edge_off), self.channels,
+                           mv(self.edge_type), imgs)
 
   def to_dense(self):
-    """L [B,N,N,2] float32: the adjacency scattered from the edges, then lnz_laplacian_l4 — bit for
-    bit the tensor collate_graph_adjacency builds for the same graphs."""
+    """L [B,N,N,E+1] float32: the adjacency scattered from the edges, then lnz_laplacian_l4 — bit for
+    bit the tensor collate_graph_adjacency builds for the same graphs.  Typed batches: the adjacency is
+    [B,N,N,E], served while (E + 1) N <= 8192 (lnz_laplacian_l4 holds the degrees of every channel in
+    LDS); NotSupported beyond."""
     dev, B, N = self.device, self.B, self.N
+    typed = self.edge_type is not None
+    if typed and self.channels * N > LAPLACIAN_MAX_CHANNEL_NODES:
+      raise _lib.NotSupported(_lib.LNZ_ENOTSUP, 'SparseLaplacian.to_dense: %d channels x %d nodes = %d > %d (the '
+                              'limit of lnz_laplacian_l4): a typed batch of this size has no dense form'
+                              % (self.channels, N, self.channels * N, LAPLACIAN_MAX_CHANNEL_NODES))
     adjs = torch.zeros((B, N, N, self.channels - 1), dtype=torch.float32, device=dev)
     E = self.edges.shape[0]
     if E:
       gid = torch.repeat_interleave(torch.arange(B, device=dev), self.edge_off[1:] - self.edge_off[:-1],
                                     output_size=E)
       u, v = self.edges[:, 0].long(), self.edges[:, 1].long()
-      adjs[gid, u, v] = 1.0
-      adjs[gid, v, u] = 1.0
+      if typed:
+        t = self.edge_type.long()
+        adjs[gid, u, v, t] = 1.0
+        adjs[gid, v, u, t] = 1.0
+      else:
+        adjs[gid, u, v] = 1.0
+        adjs[gid, v, u] = 1.0
     return laplacian_l4(adjs, self.n_nodes)
+
+
+LAPLACIAN_MAX_CHANNEL_NODES = 8192   # lnz_laplacian_l4: (E + 1) N degrees in 64 KB of LDS
+EDGE_MAX_TYPES = 7                   # E + 1 <= 8 operator channels (LARGE_MAX_OPERATORS)
 
 
 def _edge_inputs(edges, edge_off, n_nodes, N):
@@ -860,19 +928,61 @@ def _raise_edge_status(status, who):
   """status: host list of the per-graph status words."""
   for b, st in enumerate(status):
     if st:
-      why = ', '.join(text for bit, text in EDGE_STATUS_REASONS if st & bit)
+      why = ', '.join(text for bit, text in EDGE_TYPED_STATUS_REASONS if st & bit)
       raise ValueError('%s: graph %d of the batch is not a simple graph inside its slots: %s (status %d)'
                        % (who, b, why, st))
 
 
-def sparse_laplacian_from_edges(edges, edge_off, n_nodes, N, row_cap=None):
+def _edge_types(edge_type, num_edge_type, edges, who):
+  """-> (E, edge_type int32 or None).  One edge type: the types (when given) must all be 0 and the call
+  is the untyped one."""
+  E = int(num_edge_type)
+  if not 1 <= E <= EDGE_MAX_TYPES:
+    raise ValueError('%s: num_edge_type=%d: 1 .. %d edge types are served' % (who, E, EDGE_MAX_TYPES))
+  if edge_type is None:
+    if E > 1:
+      raise ValueError('%s: num_edge_type=%d needs edge_type [m]' % (who, E))
+    return 1, None
+  _need_cuda(edge_type)
+  if edge_type.dim() != 1 or edge_type.shape[0] != edges.shape[0] or edge_type.dtype.is_floating_point or \
+      edge_type.dtype == torch.bool:
+    raise ValueError('%s: edge_type [%d] of integers expected, got %s %s'
+                     % (who, edges.shape[0], tuple(edge_type.shape), edge_type.dtype))
+  if E == 1:
+    if bool((edge_type != 0).any()):
+      raise ValueError('%s: num_edge_type=1: every edge type must be 0' % who)
+    return 1, None
+  return E, edge_type.to(torch.int32).contiguous()
+
+
+def _typed_images(edges, edge_type, edge_off, n_nodes, B, N, E, ccap):
+  """lnz_laplacian_l4_typed_edges_images -> (LargeSparseImages of the E + 1 channels, status [B] on the device)."""
+  dev = n_nodes.device
+  imgs = _empty_images(E + 1, B, N, ccap, dev)
+  status = torch.empty((B,), dtype=torch.int32, device=dev)
+  need = _abi().laplacian_l4_typed_edges_images_workspace_bytes(B, N, E, ccap)
+  ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+  with torch.cuda.device(dev):
+    _abi().laplacian_l4_typed_edges_images(edges, edge_type, edges.shape[0], edge_off, n_nodes, B, N, E, ws, need,
+                                           imgs.entries, imgs.values, imgs.counts, ccap, imgs.flags, status)
+  return imgs, status
+
+
+def sparse_laplacian_from_edges(edges, edge_off, n_nodes, N, row_cap=None, edge_type=None, num_edge_type=1):
   """lnz_laplacian_l4_edges_image: the SparseLaplacian of a batch of edge lists (edges [E,2] local
   node ids, each undirected edge once; edge_off [B+1]; n_nodes [B]) padded to N nodes, for callers
   that hold (D, V) already.  row_cap: the conv image's row capacity (None = large_sparse_row_cap(N)).
+  num_edge_type >= 2 with edge_type [m] in [0, num_edge_type): lnz_laplacian_l4_typed_edges_images, one
+  image per operator channel (`.images`).
   One host read (the status words): ValueError for a graph that is not a simple graph."""
   edges, edge_off, n_nodes, B = _edge_inputs(edges, edge_off, n_nodes, N)
+  E, edge_type = _edge_types(edge_type, num_edge_type, edges, 'sparse_laplacian_from_edges')
   N, dev = int(N), n_nodes.device
   ccap = large_sparse_row_cap(N) if row_cap is None else int(row_cap)
+  if E > 1:
+    imgs, status = _typed_images(edges, edge_type, edge_off, n_nodes, B, N, E, ccap)
+    _raise_edge_status(status.tolist(), 'sparse_laplacian_from_edges')
+    return SparseLaplacian(B, N, n_nodes, imgs.channel(0), edges, edge_off, E + 1, edge_type, imgs)
   img = _empty_image(B, N, ccap, dev)
   status = torch.empty((B,), dtype=torch.int32, device=dev)
   need = _abi().laplacian_l4_edges_image_workspace_bytes(B, N, ccap)
@@ -884,7 +994,8 @@ def sparse_laplacian_from_edges(edges, edge_off, n_nodes, N, row_cap=None):
   return SparseLaplacian(B, N, n_nodes, img, edges, edge_off)
 
 
-def lanczos_ritz_edges(edges, edge_off, n_nodes, N, K, lanczos_steps=None, row_cap=None, return_info=False):
+def lanczos_ritz_edges(edges, edge_off, n_nodes, N, K, lanczos_steps=None, row_cap=None, return_info=False,
+                       edge_type=None, num_edge_type=1):
   """lnz_lanczos_ritz_kstep_edges / _wide_edges: the K-step Ritz pairs of lanczos_ritz_kstep AND the
   SparseLaplacian of a batch of edge lists padded to N nodes (192 < N <= 16384 is the K-step
   territory; any N >= K works), with no dense tensor: D [B,K], V [B,N,K], SparseLaplacian (+ info).
@@ -894,8 +1005,14 @@ def lanczos_ritz_edges(edges, edge_off, n_nodes, N, K, lanczos_steps=None, row_c
   bit.  One host read (status and overflow
   words): ValueError for a graph that is not a simple graph; a graph with a row beyond row_cap
   (None = kstep_row_cap) makes the call densify the batch (`.to_dense()`) and take lanczos_ritz_kstep,
-  with a UserWarning — the result is that route's."""
+  with a UserWarning — the result is that route's.
+  num_edge_type >= 2 with edge_type [m] in [0, num_edge_type): the pairs are those of channel 0 (the
+  simple graph; its rows in LNZ_EDGE_ORDER_QUAD, the order lanczos_ritz_kstep meets them in after its
+  contiguous copy of L[..., 0]) and the SparseLaplacian carries the E + 1 conv images of
+  lnz_laplacian_l4_typed_edges_images, each in ascending column order."""
   edges, edge_off, n_nodes, B = _edge_inputs(edges, edge_off, n_nodes, N)
+  Et, edge_type = _edge_types(edge_type, num_edge_type, edges, 'lanczos_ritz_edges')
+  typed = Et > 1
   N, K, dev = int(N), int(K), n_nodes.device
   M = K if lanczos_steps is None else int(lanczos_steps)
   Np = (N + 3) // 4 * 4
@@ -906,41 +1023,62 @@ def lanczos_ritz_edges(edges, edge_off, n_nodes, N, K, lanczos_steps=None, row_c
   ccap = large_sparse_row_cap(N)
   E = edges.shape[0]
   row_order, conv_order = dense_entry_orders(N)
-  img = _empty_image(B, Np, ccap, dev)
+  if typed:
+    # channel 0 alone goes through the Ritz launches (no conv image there); the typed build writes all E + 1
+    row_order = EDGE_ORDER_QUAD
+    imgs, tstatus = _typed_images(edges, edge_type, edge_off, n_nodes, B, N, Et, ccap)
+    img, ccap_call = None, 0
+    c_ent = c_val = c_cnt = c_flags = None
+  else:
+    img, ccap_call = _empty_image(B, Np, ccap, dev), ccap
+    c_ent, c_val, c_cnt, c_flags = img.entries, img.values, img.counts, img.flags
   D = torch.empty((B, K), dtype=torch.float32, device=dev)
   V = torch.empty((B, Np, K), dtype=torch.float32, device=dev)
   info = torch.empty((B,), dtype=torch.int32, device=dev)
-  words = torch.empty((2, B), dtype=torch.int32, device=dev)   # status, overflow
+  words = torch.empty((3 if typed else 2, B), dtype=torch.int32, device=dev)   # status, overflow(, typed status)
   status, over = words[0], words[1]
+  sl_ = lambda t, c0, c1: None if t is None else t[c0:c1]   # noqa: E731
   with torch.cuda.device(dev):
     if Np <= KSTEP_MAX_N and M <= KSTEP_MAX_M:
-      need = _abi().lanczos_ritz_kstep_edges_workspace_bytes(B, Np, cap, ccap)
+      need = _abi().lanczos_ritz_kstep_edges_workspace_bytes(B, Np, cap, ccap_call)
       ws = torch.empty((need,), dtype=torch.uint8, device=dev)
       _abi().lanczos_ritz_kstep_edges(edges, E, edge_off, n_nodes, B, Np, M, K, cap, row_order, ws, need, D, V, info,
-                                      over, img.entries, img.values, img.counts, ccap, conv_order, img.flags, status)
+                                      over, c_ent, c_val, c_cnt, ccap_call, conv_order, c_flags, status)
     else:
-      size = lambda n: _abi().lanczos_ritz_kstep_wide_edges_workspace_bytes(n, Np, M, cap, ccap)   # noqa: E731
+      size = lambda n: _abi().lanczos_ritz_kstep_wide_edges_workspace_bytes(n, Np, M, cap, ccap_call)   # noqa: E731
       chunk = max(1, min(B, KSTEP_WIDE_WORKSPACE_CAP // size(1), 65535))
       while chunk > 1 and size(chunk) > KSTEP_WIDE_WORKSPACE_CAP:   # (arrays rounded to 256 bytes one by one)
         chunk -= 1
       need = size(chunk)
       ws = torch.empty((need,), dtype=torch.uint8, device=dev)
-      img.flags.zero_()
-      flags = torch.empty((1,), dtype=torch.int32, device=dev)   # (every call zeroes its flag word)
+      flags = None
+      if not typed:
+        img.flags.zero_()
+        flags = torch.empty((1,), dtype=torch.int32, device=dev)   # (every call zeroes its flag word)
       for c0 in range(0, B, chunk):
         c1 = min(B, c0 + chunk)
         _abi().lanczos_ritz_kstep_wide_edges(edges, E, edge_off[c0:c1 + 1], n_nodes[c0:c1], c1 - c0, Np, M, K, cap,
                                              row_order, ws, need, D[c0:c1], V[c0:c1], info[c0:c1], over[c0:c1],
-                                             img.entries[c0:c1], img.values[c0:c1], img.counts[c0:c1], ccap,
+                                             sl_(c_ent, c0, c1), sl_(c_val, c0, c1), sl_(c_cnt, c0, c1), ccap_call,
                                              conv_order, flags, status[c0:c1])
-        img.flags.bitwise_or_(flags)
+        if not typed:
+          img.flags.bitwise_or_(flags)
+    if typed:
+      words[2].copy_(tstatus)
   host = words.tolist()   # the one host read of this path
-  _raise_edge_status(host[0], 'lanczos_ritz_edges')
+  if typed:
+    _raise_edge_status([a | b for a, b in zip(host[0], host[2])], 'lanczos_ritz_edges')
+  else:
+    _raise_edge_status(host[0], 'lanczos_ritz_edges')
   if Np != N:
     V = V[:, :N, :].contiguous()
-    img = LargeSparseImage(img.entries[:, :N].contiguous(), img.counts[:, :N].contiguous(), img.flags, ccap,
-                           img.values[:, :N].contiguous())
-  sl = SparseLaplacian(B, N, n_nodes, img, edges, edge_off)
+    if not typed:
+      img = LargeSparseImage(img.entries[:, :N].contiguous(), img.counts[:, :N].contiguous(), img.flags, ccap,
+                             img.values[:, :N].contiguous())
+  if typed:
+    sl = SparseLaplacian(B, N, n_nodes, imgs.channel(0), edges, edge_off, Et + 1, edge_type, imgs)
+  else:
+    sl = SparseLaplacian(B, N, n_nodes, img, edges, edge_off)
   if any(host[1]):
     import warnings
     warnings.warn('lanczos_ritz_edges: graph %d has a row of more than %d entries (the image\'s row capacity): '
@@ -1042,6 +1180,70 @@ def large_sparse_conv_layer_f32(X, din, img, Vb, V, Wn, Wt, G, bias, work, plane
       abi.large_spectral(X, ldx, din, V, G, Wt, B, N, K, S, planes, Ybuf, Tt)
     abi.large_conv(None, Vb, None, Tt, bias, B, N, 0, planes, 0, out)
     abi.large_sparse_conv_f32(img.entries, img.values, img.counts, img.cap, Zf, B, N, int(bool(relu)), out)
+  return out
+
+
+def large_sparse_channels_work_buffers(R, B, N, device):
+  """(Z, Tt, Ybuf) of large_sparse_conv_layer_channels: Z [R,B,N,128] bf16 (CLASS MAJOR: one
+  lnz_large_gemm1_rows per channel), Tt [1,B,128,64] bf16 and Ybuf [B,64,128] fp32, both zero."""
+  Z = torch.empty((R, B, N, 128), dtype=torch.bfloat16, device=device)
+  Tt = torch.zeros((1, B, 128, 64), dtype=torch.bfloat16, device=device)
+  Ybuf = torch.zeros((B, 64, 128), dtype=torch.float32, device=device)
+  return Z, Tt, Ybuf
+
+
+def large_sparse_conv_layer_channels(X, din, imgs, Vb, V, Wf, Wt, G, bias, work, relu=True, out=None):
+  """large_sparse_conv_layer for R = 2 .. 8 operators: the node-space term sum_c L_c (X W_c^T) on the
+  LargeSparseImages `imgs` (lnz_large_sparse_conv_channels).  Wf [1,R,4,dinp/16,64,8]: the one-plane
+  fragments of the R channels' weight blocks, NOT summed (large_weight_fragments); work from
+  large_sparse_channels_work_buffers().  The spectral block and the lift are the one-operator layer's."""
+  Z, Tt, Ybuf = work
+  _need_cuda(X, imgs.entries, Vb, Wf, bias, Z, Tt)
+  R, B, N = imgs.R, imgs.B, imgs.N
+  assert X.dtype == torch.float32 and X.is_contiguous() and X.shape[0] == B and X.shape[1] == N
+  assert Vb.shape[0] == 1 and Wf.shape[0] == 1 and Wf.shape[1] == R and Wf.is_contiguous()
+  assert tuple(Z.shape) == (R, B, N, 128) and Z.is_contiguous()
+  if out is None:
+    out = torch.empty((B, N, 128), dtype=torch.float32, device=X.device)
+  with torch.cuda.device(X.device):
+    abi = _abi()
+    for c in range(R):
+      abi.large_gemm1_rows(X, X.shape[2], din, Wf[:, c], B, N, Z[c])
+    if G is not None:
+      K, S = V.shape[2], G.shape[1]
+      assert V.dtype == torch.float32 and V.is_contiguous()
+      assert G.is_contiguous() and G.dtype == torch.float32 and tuple(G.shape) == (B, S, K)
+      abi.large_spectral(X, X.shape[2], din, V, G, Wt, B, N, K, S, 1, Ybuf, Tt)
+    abi.large_conv(None, Vb, None, Tt, bias, B, N, 0, 1, 0, out)
+    abi.large_sparse_conv_channels(imgs.entries, imgs.counts, imgs.cap, Z, B, N, R, int(bool(relu)), out)
+  return out
+
+
+def large_sparse_conv_layer_channels_f32(X, din, imgs, Vb, V, Wn, Wt, G, bias, work, planes, relu=True, out=None):
+  """large_sparse_conv_layer_f32 for R = 2 .. 8 operators (lnz_large_sparse_conv_channels_f32): Wn
+  [R*128, ldx] fp32, the channels' weight blocks stacked (zero padded columns); imgs with `values`;
+  work = (Zf [R,B,N,128] fp32 CLASS MAJOR — lnz_f32_linear once per channel —, Tt [planes,B,128,64], Ybuf)."""
+  Zf, Tt, Ybuf = work
+  _need_cuda(X, imgs.entries, imgs.values, Vb, Wn, bias, Zf, Tt)
+  R, B, N = imgs.R, imgs.B, imgs.N
+  ldx = X.shape[2]
+  assert X.dtype == torch.float32 and X.is_contiguous() and X.shape[0] == B and X.shape[1] == N
+  assert ldx % 32 == 0 and tuple(Wn.shape) == (R * 128, ldx) and Vb.shape[0] == planes == Tt.shape[0]
+  assert tuple(Zf.shape) == (R, B, N, 128) and Zf.is_contiguous()
+  if out is None:
+    out = torch.empty((B, N, 128), dtype=torch.float32, device=X.device)
+  for c in range(R):
+    f32_linear(X.view(B * N, ldx), Wn[128 * c:128 * (c + 1)], out=Zf[c].view(B * N, 128))
+  with torch.cuda.device(X.device):
+    abi = _abi()
+    if G is not None:
+      K, S = V.shape[2], G.shape[1]
+      assert V.dtype == torch.float32 and V.is_contiguous()
+      assert G.is_contiguous() and G.dtype == torch.float32 and tuple(G.shape) == (B, S, K)
+      abi.large_spectral(X, ldx, din, V, G, Wt, B, N, K, S, planes, Ybuf, Tt)
+    abi.large_conv(None, Vb, None, Tt, bias, B, N, 0, planes, 0, out)
+    abi.large_sparse_conv_channels_f32(imgs.entries, imgs.values, imgs.counts, imgs.cap, Zf, B, N, R,
+                                       int(bool(relu)), out)
   return out
 
 

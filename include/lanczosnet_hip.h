@@ -32,6 +32,8 @@ extern "C" {
  *    + the wide K-step entry (lnz_lanczos_ritz_kstep_wide, _workspace_bytes: N <= 16384, M <= 256);
  *    + large graphs from edge lists (lnz_lanczos_ritz_kstep_edges, lnz_lanczos_ritz_kstep_wide_edges,
  *    lnz_laplacian_l4_edges_image, each with a _workspace_bytes sibling: no N x N array);
+ *    + the backward of the one-operator sparse large-graph layer (lnz_large_grad_project,
+ *    lnz_large_grad_spectral, lnz_large_grad_input: additive, the version stays);
  * 6: lnz_forward_args lost Wp16 / w16_off / Wp16_head / Lp16 (gemm_mode 1 is now the split precision
  *    inside the strip kernel: lnz_pack_rows_k8_split; lnz_pack_rows_f16x2 and
  *    lnz_pack_laplacian_f16x2 are gone) and gained dbias_part_cap; + lnz_midgraph_forward,
@@ -254,6 +256,32 @@ int lnz_large_spectral_gemm1_rows(const float* X, int ldx, int din, const float*
 int lnz_large_sparse_conv_f32(const uint32_t* entries, const float* values, const int32_t* counts,
                               int row_cap, const float* Zf, int B, int N, int relu, float* X,
                               lnz_stream_t stream);
+/* The backward of that exact-fp32 layer for ONE symmetric operator (an undirected simple graph's L4
+ * given as its image: L^T = L), X' = relu( L Z + V T + b ), Z = X Wn^T, Y = V^T X, T = sum_s
+ * diag(g_s) Y W_s^T, from the gradient dX' of its output (model/lanczos_net_general.py:157-182 under
+ * runner/graph_runner.py's loss.backward()).  All fp32, K <= 64, S <= 16, hidden width 128.
+ *   lnz_large_grad_project   dX [B,N,128] in place: dP = dX' * (Xout > 0), rows >= n_nodes[b] (NULL:
+ *                            N) exactly zero whatever they held; db [B,128] = the graph's column sums of
+ *                            dP; A [B,K,128] = V^T dP on v_mfma_f32_16x16x4_f32.  part: workspace of
+ *                            B * ceil(N / 256) * 65 * 128 floats (per 256-row chunk a partial of A and
+ *                            of db, added in ascending chunk order by a second launch: no atomics, the
+ *                            same bits every time).
+ *   (dZ = L dP is lnz_large_sparse_conv_f32 with relu = 0 onto a zeroed buffer.)
+ *   lnz_large_grad_spectral  one workgroup per graph.  A [B,K,128], Y [B,K,ldy] (first d columns), G
+ *                            [B,S,K], W [128][ldw]: the mix weight, long-scale block s in columns
+ *                            [s d, s d + d).  With U_s = A W_s:  dG [B,K,S] (may be NULL) = <U_s[k],
+ *                            Y[k]> = sum_o A[k][o] (Y W_s^T)[k][o];  Q [B,K,S,d] = g_s[k] Y[k];
+ *                            dY [B,K,128] = sum_s g_s[k] U_s[k] (columns >= d zero).
+ *   lnz_large_grad_input     dX [B,N,128] = dZ Wn + V dY, one fp32 MFMA GEMM over the depth 128 + K:
+ *                            dZ [B,N,128], Wn [128][128] (Wn[o][i], columns >= d zero), V [B,N,K], dY
+ *                            [B,K,128] (K = 0: V, dY may be NULL); columns >= d of dX are written zero.
+ *                            dX must not alias dZ. */
+int lnz_large_grad_project(float* dX, const float* Xout, const float* V, const int32_t* n_nodes, int B,
+                           int N, int K, float* part, float* A, float* db, lnz_stream_t stream);
+int lnz_large_grad_spectral(const float* A, const float* Y, int ldy, const float* G, const float* W, int ldw,
+                            int B, int K, int S, int d, float* dG, float* Q, float* dY, lnz_stream_t stream);
+int lnz_large_grad_input(const float* dZ, const float* Wn, const float* V, const float* dY, int B, int N,
+                         int K, int d, float* dX, lnz_stream_t stream);
 /* Several operators on the nonzeros: a batch with num_edge_type >= 2, whose collated L [B,N,N,E+1] holds
  * L4 of the simple graph and of every edge type alone (dataset/get_graph_data.py:60-72), and the
  * node-space term  sum_c L_c (X W_c^T)  of model/lanczos_net_general.py:157-182 on R = E + 1 = 2 .. 8

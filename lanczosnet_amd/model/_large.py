@@ -1,14 +1,17 @@
 """Graphs beyond the 32-node MFMA tile: the hand-written streaming kernels (csrc/conv_large.hip),
 the node-space term on the nonzeros of L (csrc/conv_sparse.hip) with their channel-fold and
 sparse-backoff state, and the library-GEMM restatement (hipBLASLt through torch) of everything the
-kernels are not built for.  `_plan_large` is also the cache the 33..128-node plan lives in."""
+kernels are not built for.  `_plan_large` is also the cache the 33..128-node plan lives in.
+`_LargeSparseFusedFunction`: the opt-in HIP backward of the exact-fp32 sparse layers for edge-list batches
+(csrc/conv_sparse_grad.hip)."""
 import os
 import warnings
 
 import torch
 
 from .. import ops
-from ._common import (LARGE_MAX_K, LARGE_MAX_OPERATORS, head_params, input_state, masked_readout,
+from ._common import (LARGE_MAX_K, LARGE_MAX_OPERATORS, _spectral_mlp_param_grads, _tn_split_k, embedding_grad,
+                      head_params, input_state, masked_readout, param_grad_tuple, scatter_head_grads,
                       spectral_mlp_operands)
 
 
@@ -18,6 +21,10 @@ class _LargeMixin:
     large_split_planes = int(os.environ.get('LANCZOSNET_LARGE_PLANES', '3'))
     # lnz_spectral_gains / lnz_pack_spectral_mlp_layers: csrc/gains_body.hpp SMAX
     gains_kernel_max_scales = 16
+    # edge-list batches (an untyped SparseLaplacian) in training: 'hip' = the backward on the sparse image
+    # (_LargeSparseFusedFunction, csrc/conv_sparse_grad.hip), 'torch' (default) = densify + autograd
+    # through `_torch_forward`.  Opt-in: its step time is recorded, not yet a reason
+    large_backward_impl = os.environ.get('LANCZOSNET_LARGE_BACKWARD', 'torch')
 
     @torch.no_grad()
     def _torch_gains(self, D):
@@ -156,6 +163,29 @@ class _LargeMixin:
         return (self._strip_widths_ok() and self.num_scale_short == 0 and K <= LARGE_MAX_K
                 and channels <= LARGE_MAX_OPERATORS
                 and self.num_scale_long <= self.gains_kernel_max_scales)
+
+    def _large_backward_supported(self, K, channels):
+        """The HIP backward of the exact-fp32 sparse layers (lnz_large_grad_project / _spectral / _input):
+        the envelope of `_large_hip_supported` in a split-precision mode (the node-space term exact
+        fp32), the reference's channel order, diagonal gains; selected by `large_backward_impl ==
+        'hip'` where `backward_impl` asks for HIP at all.  WHAT the batch is (one operator given as a
+        clean sparse image) is `_route`'s `sparse_one_operator`."""
+        return (self.large_backward_impl == 'hip' and self.backward_impl == 'hip'
+                and self._large_hip_supported(K, channels) and self.gemm_mode != 'bf16'
+                and self.large_split_planes != 1 and self.large_sparse
+                and self._channel_order() is None and self.filter_kind == 0)
+
+    def _sparse_one_operator(self, L, drop, capturing):
+        """`_route`'s `sparse_one_operator` for this call: L is an untyped SparseLaplacian (one edge
+        type: two channels that are ONE operator) whose image carries its fp32 values and raised no
+        flag.  The flag word is read here — the image was built at collate time, the wait is on
+        finished work — and only where the answer can matter."""
+        if not (isinstance(L, ops.SparseLaplacian) and L.images is None and L.channels == 2
+                and L.image is not None and L.image.values is not None and L.N <= 65536):
+            return False
+        if drop or capturing or not self._needs_grad() or not self._large_backward_supported(0, L.channels):
+            return False
+        return int(L.image.flags.item()) == 0
 
     # -- channel folding of the large-graph path ------------------------------------------------
     # With one edge type (config/graph_lanczos_net.yaml:14) the collated L carries the SAME operator
@@ -419,3 +449,105 @@ class _LargeMixin:
             # the readout in one pass over the state (csrc/head_large.hip)
             return ops.large_head(state, mask, *self._plan_head(cache))
         return masked_readout(self, state, mask)
+
+
+class _LargeSparseFusedFunction(torch.autograd.Function):
+    """Training an edge-list batch (an untyped SparseLaplacian: ONE symmetric operator as its sparse
+    image) through the HIP kernels, with no dense L.
+
+    forward: spectral gains + ops.large_sparse_conv_layer_f32 per layer — the launches of
+    `_large_sparse_layers` on the same operands, so the score is the inference route's bit for bit —
+    each layer into its own slice of ONE [num_layer, B, N, 128] buffer, then the readout.
+    backward, last layer first: lnz_large_grad_project (dP, db, A = V^T dP), the forward's gather on dP
+    (dZ = L dP = L^T dP), lnz_large_grad_spectral (dG, Q, dY; Y = V^T X recomputed by one library
+    GEMM), library GEMMs for dWn = dZ^T X and dW_s = A^T Q_s, lnz_large_grad_input (dX = dZ Wn + V dY);
+    the head by autograd on the stored last state; lnz_spectral_mlp_grad; lnz_embedding_grad.
+    Inputs L, D, V, mask, node features are data: no gradient."""
+
+    @staticmethod
+    def forward(ctx, module, node_feat, L, D, V, mask, *params):
+        m = module
+        S, planes = m.num_scale_long, m.large_split_planes
+        B, N = L.B, L.N
+        dev = V.device
+        Vf = V.float().contiguous()
+        cache = m._plan_large()
+        G = None
+        if S > 0:
+            G = ops.spectral_gains(D, m.long_diffusion_dist, m.num_layer, cache['mlp_pack'])
+        img = L.image
+        Vb = ops.large_pack_vectors(Vf, planes)
+        classes = (0,) * L.channels
+        plan = m._plan_large(planes, classes)
+        X0 = input_state(m, node_feat, width=(m.input_dim + 31) // 32 * 32, as_float=True).contiguous()
+        work = (torch.empty((B, N, 128), dtype=torch.float32, device=dev),
+                torch.zeros((planes, B, 128, 64), dtype=ops.large_plane_dtype(planes), device=dev),
+                torch.zeros((B, 64, 128), dtype=torch.float32, device=dev))
+        Xs = torch.empty((m.num_layer, B, N, 128), dtype=torch.float32, device=dev)
+        state = X0
+        for t, lay in enumerate(plan['conv'][(planes, classes)]):
+            state = ops.large_sparse_conv_layer_f32(state, lay['din'], img, Vb, Vf, lay['Wn32'], lay['Wt'],
+                                                    G[t] if G is not None else None, lay['bias'], work,
+                                                    planes, relu=True, out=Xs[t])
+        mask_u8 = mask.to(torch.uint8).contiguous()
+        if m.large_head_kernel and m.output_dim <= 16:
+            score = ops.large_head(state, mask_u8, *m._plan_head(cache))
+        else:
+            score = masked_readout(m, state, mask)
+        ctx.module, ctx.image, ctx.has_gains = m, img, G is not None
+        ctx.save_for_backward(node_feat, X0, D, Vf, mask_u8, L.n_nodes, Xs, *([G] if G is not None else []))
+        return score
+
+    @staticmethod
+    def backward(ctx, grad_score):
+        m, img = ctx.module, ctx.image
+        node_feat, X0, D, V, mask_u8, n_nodes, Xs = ctx.saved_tensors[:7]
+        G = ctx.saved_tensors[7] if ctx.has_gains else None
+        Lnum, B, N, _ = Xs.shape
+        K, S, C = V.shape[2], m.num_scale_long, 2
+        dev = Xs.device
+        grads = {}
+        # ---- head (model/lanczos_net.py:185-194): autograd on the stored last state
+        Whead, bhead = m._plan_head(m._plan_large())
+        with torch.enable_grad():
+            XL = Xs[-1].detach().requires_grad_(True)
+            Wh = Whead.detach().requires_grad_(True)
+            bh = bhead.detach().requires_grad_(True)
+            dXL, dWh, dbh = torch.autograd.grad(masked_readout(m, XL, mask_u8, stacked=(Wh, bh)),
+                                                [XL, Wh, bh], grad_score.contiguous())
+        scatter_head_grads(m, grads, dWh, dbh)
+        g = dXL.contiguous()            # dX' of the layer at hand; lnz_large_grad_project masks it in place
+        dZ = torch.empty_like(g)
+        Vt = V.transpose(1, 2)
+        dGs = []
+        for t in range(Lnum - 1, -1, -1):
+            X = X0 if t == 0 else Xs[t - 1]
+            d = m.input_dim if t == 0 else 128
+            W = m.filter[t].weight.detach().float().contiguous()      # [128, (S + 2) d]
+            A, dbg = ops.large_grad_project(g, Xs[t], V, n_nodes)     # g is dP from here on
+            dZ.zero_()
+            with torch.cuda.device(dev):
+                ops._abi().large_sparse_conv_f32(img.entries, img.values, img.counts, img.cap, g, B, N, 0, dZ)
+            dWn = _tn_split_k(dZ.view(B * N, 128), X.view(B * N, X.shape[2]))[:, :d]
+            blocks = [dWn] * C
+            dY = None
+            if S > 0:
+                Y = torch.bmm(Vt, X)                                  # V^T X  [B, K, ldx]
+                dG, Q, dY = ops.large_grad_spectral(A, Y, G[t], W, d, want_dgains=m._has_mlp())
+                dWl = A.view(B * K, 128).t() @ Q.view(B * K, S * d)
+                blocks = list(dWl.view(128, S, d).unbind(1)) + blocks
+                if dG is not None:
+                    dGs.append(dG)
+            grads[id(m.filter[t].weight)] = torch.stack(blocks, dim=1).reshape(128, -1)
+            grads[id(m.filter[t].bias)] = dbg.sum(dim=0)
+            if t > 0 or not m.general:
+                Wv = W.view(128, S + C, d)
+                Wn = torch.nn.functional.pad(Wv[:, S] + Wv[:, S + 1], (0, 128 - d)).contiguous()
+                ops.large_grad_input(dZ, Wn, V if S > 0 else None, dY, d, out=g)
+        # ---- spectral filter MLPs from dG [L, B K, S]
+        if dGs:
+            _spectral_mlp_param_grads(m, grads, D, torch.stack(dGs[::-1]).view(Lnum, B * K, S))
+        # ---- embedding rows
+        if not m.general:
+            grads[id(m.embedding.weight)] = embedding_grad(m, node_feat, g, N, m.input_dim)
+        return param_grad_tuple(m, grads, 6)

@@ -1183,6 +1183,71 @@ def large_sparse_conv_layer_f32(X, din, img, Vb, V, Wn, Wt, G, bias, work, plane
   return out
 
 
+# ---- the backward of large_sparse_conv_layer_f32 for ONE symmetric operator (csrc/conv_sparse_grad.hip) --
+LARGE_GRAD_CHUNK = 256   # rows of a graph per workgroup of lnz_large_grad_project
+
+
+def large_grad_project(dX, Xout, V, n_nodes=None):
+  """lnz_large_grad_project: dX [B,N,128] IN PLACE -> dP = dX * (Xout > 0), rows at or beyond
+  n_nodes[b] exactly zero whatever they held; returns (A [B,K,128] = V^T dP, db [B,128] = the graphs'
+  column sums of dP).  Fixed summation order: the same bits every time."""
+  _need_cuda(dX, Xout, V, n_nodes)
+  B, N, K = V.shape
+  assert dX.dtype == Xout.dtype == V.dtype == torch.float32
+  assert dX.is_contiguous() and Xout.is_contiguous() and V.is_contiguous()
+  assert tuple(dX.shape) == tuple(Xout.shape) == (B, N, 128)
+  dev = dX.device
+  if n_nodes is not None:
+    n_nodes = n_nodes.to(torch.int32).contiguous()
+    assert tuple(n_nodes.shape) == (B,)
+  chunks = (N + LARGE_GRAD_CHUNK - 1) // LARGE_GRAD_CHUNK
+  part = torch.empty((B, chunks, 65, 128), dtype=torch.float32, device=dev)
+  A = torch.empty((B, K, 128), dtype=torch.float32, device=dev)
+  db = torch.empty((B, 128), dtype=torch.float32, device=dev)
+  with torch.cuda.device(dev):
+    _abi().large_grad_project(dX, Xout, V, n_nodes, B, N, K, part, A, db)
+  return A, db
+
+
+def large_grad_spectral(A, Y, G, W, d, want_dgains=True):
+  """lnz_large_grad_spectral: A [B,K,128], Y [B,K,>= d] = V^T X, G [B,S,K], W [128, >= S d] the mix
+  weight (long-scale block s in columns [s d, s d + d)) -> (dG [B,K,S] or None, Q [B,K,S,d] =
+  g_s[k] Y[k], dY [B,K,128] = sum_s g_s[k] (A W_s)[k], columns >= d zero)."""
+  _need_cuda(A, Y, G, W)
+  B, K, _ = A.shape
+  S = G.shape[1]
+  assert A.dtype == Y.dtype == G.dtype == W.dtype == torch.float32
+  assert A.is_contiguous() and Y.is_contiguous() and G.is_contiguous() and W.is_contiguous()
+  assert A.shape[2] == 128 and tuple(Y.shape[:2]) == (B, K) and tuple(G.shape) == (B, S, K) and W.shape[0] == 128
+  dev = A.device
+  dG = torch.empty((B, K, S), dtype=torch.float32, device=dev) if want_dgains else None
+  Q = torch.empty((B, K, S, d), dtype=torch.float32, device=dev)
+  dY = torch.empty((B, K, 128), dtype=torch.float32, device=dev)
+  with torch.cuda.device(dev):
+    _abi().large_grad_spectral(A, Y, Y.shape[2], G, W, W.shape[1], B, K, S, d, dG, Q, dY)
+  return dG, Q, dY
+
+
+def large_grad_input(dZ, Wn, V, dY, d, out):
+  """lnz_large_grad_input: out [B,N,128] = dZ Wn + V dY in one exact-fp32 MFMA launch (dZ [B,N,128],
+  Wn [128,128] with columns >= d zero, V [B,N,K], dY [B,K,128]; V = dY = None: no long scales);
+  columns >= d of `out` are written zero.  `out` must not be dZ.  Names itself to last_kernel()."""
+  _need_cuda(dZ, Wn, V, dY, out)
+  B, N, _ = dZ.shape
+  K = 0 if dY is None else dY.shape[1]
+  assert dZ.dtype == Wn.dtype == out.dtype == torch.float32
+  assert dZ.is_contiguous() and Wn.is_contiguous() and out.is_contiguous()
+  assert tuple(out.shape) == tuple(dZ.shape) == (B, N, 128) and tuple(Wn.shape) == (128, 128)
+  assert out.data_ptr() != dZ.data_ptr()
+  if K:
+    assert V.dtype == dY.dtype == torch.float32 and V.is_contiguous() and dY.is_contiguous()
+    assert tuple(V.shape) == (B, N, K) and tuple(dY.shape) == (B, K, 128)
+  with torch.cuda.device(dZ.device):
+    _abi().large_grad_input(dZ, Wn, V if K else None, dY, B, N, K, d, out)
+  note_autograd_kernel()
+  return out
+
+
 def large_sparse_channels_work_buffers(R, B, N, device):
   """(Z, Tt, Ybuf) of large_sparse_conv_layer_channels: Z [R,B,N,128] bf16 (CLASS MAJOR: one
   lnz_large_gemm1_rows per channel), Tt [1,B,128,64] bf16 and Ybuf [B,64,128] fp32, both zero."""

@@ -1,0 +1,135 @@
+#!/usr/bin/env python
+"""One training step (forward + backward + Adam) of LanczosNetGeneral on large graphs from edge lists,
+on the MI355X: the densify + autograd route (`large_backward_impl = 'torch'`, the default) against the
+opt-in HIP backward on the sparse image (`'hip'`: `_LargeSparseFusedFunction`, csrc/conv_sparse_grad.hip;
+DESIGN.md §4.9c), in the same run on the same batch.
+
+Shapes: BASELINE config 5's graphs from edge lists (B 256, N 2048, G(n, 0.01), K 64, 7 x 128 — the
+generator of tools/bench_edge_collate.py) and the wide corner (B 4, N 8192, M 128, K 64), which has no
+dense form: the torch route is recorded there with its error, not skipped silently.
+Per shape and route, warm: step_ms min / median / max over `--windows` windows of `--steps` steps (device
+events around a window; the cyclic collector is collected and frozen outside the windows, as in
+tools/bench_train_step.py) and peak_bytes = torch.cuda.max_memory_allocated above the resident batch,
+parameters and optimizer state.
+
+    python tools/bench_large_train_step.py [--shapes config5,wide] [--windows 3] [--steps 2] [--batch B]
+                                           [--out profiles/large_train_step.json]
+"""
+import argparse
+import gc
+import json
+import os
+import sys
+import warnings
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+  sys.path.insert(0, ROOT)
+
+from tools.bench_edge_collate import SHAPES, gnp_edges, stats  # noqa: E402
+
+
+def net_for(K, dev, impl):
+  import torch
+  import oracle
+  from lanczosnet_amd.model import LanczosNetGeneral
+  from lanczosnet_amd.utils.arg_helper import make_model_config
+  cfg = dict(num_bond_type=1, short_diffusion_dist=[], long_diffusion_dist=[1, 2, 3, 5, 7, 10, 20, 30], num_eig_vec=K,
+             spectral_filter_kind='MLP', input_dim=10, hidden_dim=[128] * 7, output_dim=2, num_layer=7, num_atom=0)
+  P = oracle.make_lanczosnet_params(cfg, 17, general=True)
+  net = LanczosNetGeneral(make_model_config(cfg, general=True)).train()
+  net.load_state_dict({k: torch.from_numpy(v) for k, v in P.items()})
+  net = net.to(dev)
+  net.gemm_mode = 'fp32'
+  net.large_backward_impl = impl
+  return net
+
+
+def route(impl, b, K, dev, windows, steps):
+  """-> the record of one route on the resident batch `b`: one warm step, then the timed windows."""
+  import torch
+  from lanczosnet_amd import ops
+  net = net_for(K, dev, impl)
+  opt = torch.optim.Adam(net.parameters(), lr=1e-4)
+
+  def step():
+    opt.zero_grad(set_to_none=True)
+    _, loss = net(b['node_feat'], b['L'], b['D'], b['V'], label=b['label'], mask=b['node_mask'])
+    loss.backward()
+    opt.step()
+    return loss
+  loss = step()   # (code objects, plans, the allocator, Adam's state)
+  torch.cuda.synchronize()
+  out = dict(backward_kernel=ops.last_kernel(), first_loss=float(loss))
+  torch.cuda.empty_cache()
+  torch.cuda.reset_peak_memory_stats()
+  base = torch.cuda.memory_allocated()
+  gc.collect()
+  gc.freeze()
+  ms = []
+  for _ in range(windows):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(steps):
+      loss = step()
+    e1.record()
+    torch.cuda.synchronize()
+    ms.append(e0.elapsed_time(e1) / steps)
+  gc.unfreeze()
+  out.update(step_ms=stats(ms), windows_ms=[round(x, 4) for x in ms], steps_per_window=steps,
+             peak_bytes=int(torch.cuda.max_memory_allocated() - base), last_loss=float(loss))
+  return out
+
+
+def main():
+  ap = argparse.ArgumentParser()
+  ap.add_argument('--shapes', default='config5,wide')
+  ap.add_argument('--windows', type=int, default=3)
+  ap.add_argument('--steps', type=int, default=2)
+  ap.add_argument('--batch', type=int, default=0, help="override B (0: the shape's own)")
+  ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'large_train_step.json'))
+  args = ap.parse_args()
+  import torch
+  if not torch.cuda.is_available():
+    raise SystemExit('bench_large_train_step: needs the MI355X (no CPU fallback)')
+  from lanczosnet_amd.dataset import collate_graph_edges
+  dev = 'cuda:0'
+  result = dict(device=torch.cuda.get_device_name(0), windows=args.windows, workload='LanczosNetGeneral 7 x 128, '
+                'eight long scales, train step (fwd + bwd + Adam), graphs from edge lists', shapes={})
+  warnings.simplefilter('ignore')
+  for name in args.shapes.split(','):
+    s = dict(SHAPES[name])
+    if args.batch:
+      s['B'] = args.batch
+    rs = np.random.RandomState(5)
+    graphs = [gnp_edges(s['N'], s['p'], rs) for _ in range(s['B'])]
+    items = [dict(edges=g, node_feat=rs.randn(s['N'], 10).astype(np.float32), label=rs.randn(1, 2)) for g in graphs]
+    rec = dict(s, edges_per_graph=int(np.mean([g.shape[0] for g in graphs])),
+               dense_L_bytes=int(s['B'] * s['N'] * s['N'] * 8))
+    b = collate_graph_edges(items, s['K'], device=dev, lanczos_steps=s['M'])
+    rec['image_flags'] = int(b['L'].image.flags.item())
+    for impl in ('torch', 'hip'):
+      try:
+        rec['large_backward_' + impl] = route(impl, b, s['K'], dev, args.windows, args.steps)
+      except Exception as e:   # noqa: BLE001  (recorded: the densify route does not reach every shape)
+        gc.unfreeze()
+        rec['large_backward_' + impl] = dict(error='%s: %s' % (type(e).__name__, str(e).splitlines()[0][:300]))
+      torch.cuda.empty_cache()
+    t, h = rec['large_backward_torch'], rec['large_backward_hip']
+    if 'step_ms' in t and 'step_ms' in h:
+      rec['hip_over_torch'] = dict(step_ms=round(h['step_ms']['median'] / t['step_ms']['median'], 4),
+                                   peak_bytes=round(h['peak_bytes'] / t['peak_bytes'], 4))
+    result['shapes'][name] = rec
+    print(json.dumps({name: rec}))
+    del b
+  os.makedirs(os.path.dirname(args.out), exist_ok=True)
+  with open(args.out, 'w') as f:
+    json.dump(result, f, indent=1, sort_keys=True)
+    f.write('\n')
+  print('wrote', args.out)
+
+
+if __name__ == '__main__':
+  main()

@@ -29,8 +29,10 @@
 // csrc/lanczos_large.hip — the collated Laplacian is then read from HBM once per batch.)
 // Several DISTINCT operators (two or more edge types): one image per channel
 // (lnz_large_sparse_image_channels, or csrc/edge_image.hip from typed edge lists) and the gather over all
-// of them, lnz_large_sparse_conv_channels[_f32] — the second half of this file.
+// of them, lnz_large_sparse_conv_channels[_f32] — the same gather kernel over (row, channel) pairs.
+// The image's format (entry packing, lane rank, row padding): csrc/conv_image.hpp.
 #include "common.hpp"
+#include "conv_image.hpp"
 
 #include <type_traits>
 
@@ -57,15 +59,51 @@ constexpr int GS = LNZ_SPARSE_GS;
 static_assert(GS == 4 || GS == 8, "the image pads rows to multiples of 8; a turn is at most 8 groups");
 constexpr int ROWS_PER_WAVE = LNZ_SPARSE_ROWS_PER_WAVE, WAVES = LNZ_SPARSE_WAVES, TILE_ROWS = ROWS_PER_WAVE * WAVES;
 
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-// bf16(value) << 16 | column; round to nearest even (v_cvt_pk_bf16_f32), as conv_large.hip's pack
-__device__ inline unsigned pack_entry(float v, int col) {
-  const bf16x2 p = __builtin_convertvector(f32x2{v, 0.0f}, bf16x2);
-  return ((unsigned)__builtin_bit_cast(u16, p[0]) << 16) | (unsigned)col;
+constexpr int MAXR = 8;   // LARGE_MAX_OPERATORS
+static_assert(ROWS_PER_WAVE * MAXR <= 64, "a wave's (row, channel) pairs: one count per lane");
+
+// the wave's nonzeros among v (one column per lane) go behind the row's k entries, in lane order
+__device__ inline void place_nonzeros(const float v, const int col, int& k, const int cap, unsigned* oe, float* ov) {
+  const bool nz = v != 0.0f;   // (a NaN is kept)
+  const unsigned long long m = __ballot(nz);
+  if (m == 0ull) return;
+  const int pos = k + lane_rank(m);
+  if (nz && pos < cap) {
+    oe[pos] = conv_entry(v, col);
+    if (ov) ov[pos] = v;
+  }
+  k += __popcll(m);
 }
 
-__device__ inline int lane_rank(unsigned long long m) {  // set bits of m below this lane
-  return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+// One row of one channel at 4-byte loads and the given column stride, ascending columns -> the row's
+// number of nonzeros (those beyond cap are counted, not kept).  COMPARE: channels 1 .. nchk - 1 (sch
+// apart) are read next to it and `differ` is raised in a lane that saw one differ from this channel.
+template <bool COMPARE>
+__device__ inline int strided_row_scan(const float* Lr, const int64_t sc, const int64_t sch, const int nchk,
+                                       const int N, const int cap, unsigned* oe, float* ov, bool& differ) {
+  const int lane = threadIdx.x & 63;
+  int k = 0;   // entries of this row so far (wave-uniform)
+  for (int c0 = 0; c0 < N; c0 += 64 * 8) {
+    float x[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int col = c0 + 64 * u + lane;
+      x[u] = col < N ? Lr[(int64_t)col * sc] : 0.0f;
+    }
+    if constexpr (COMPARE) {
+      for (int c = 1; c < nchk; ++c) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int col = c0 + 64 * u + lane;
+          const float y = col < N ? Lr[(int64_t)col * sc + (int64_t)c * sch] : 0.0f;
+          differ |= x[u] != y;
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) place_nonzeros(x[u], c0 + 64 * u + lane, k, cap, oe, ov);
+  }
+  return k;
 }
 
 // ---- image: one wavefront per row ---------------------------------------------------------------
@@ -87,17 +125,7 @@ __global__ __launch_bounds__(256) void sparse_image_kernel(
   float* ov = vals ? vals + rid * cap : nullptr;   // (the exact-fp32 form's values, optional)
   int k = 0;            // entries of this row so far (wave-uniform)
   bool differ = false;  // a channel differs from channel 0 in this lane's columns
-  auto place = [&](const float v, const int col) {
-    const bool nz = v != 0.0f;   // (a NaN is kept)
-    const unsigned long long m = __ballot(nz);
-    if (m == 0ull) return;
-    const int pos = k + lane_rank(m);
-    if (nz && pos < cap) {
-      oe[pos] = pack_entry(v, col);
-      if (ov) ov[pos] = v;
-    }
-    k += __popcll(m);
-  };
+  auto place = [&](const float v, const int col) { place_nonzeros(v, col, k, cap, oe, ov); };
   if constexpr (FORM == 1) {
     const f32x4* src = reinterpret_cast<const f32x4*>(Lr);
     const int nq = N >> 2;   // (N is a multiple of 4 in this form)
@@ -138,31 +166,10 @@ __global__ __launch_bounds__(256) void sparse_image_kernel(
     }
   } else {
     const int nchk = sch == 0 ? 1 : C;   // (a zero channel stride: one operator by construction)
-    for (int c0 = 0; c0 < N; c0 += 64 * 8) {
-      float x[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int col = c0 + 64 * u + lane;
-        x[u] = col < N ? Lr[(int64_t)col * sc] : 0.0f;
-      }
-      for (int c = 1; c < nchk; ++c) {
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int col = c0 + 64 * u + lane;
-          const float y = col < N ? Lr[(int64_t)col * sc + (int64_t)c * sch] : 0.0f;
-          differ |= x[u] != y;
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) place(x[u], c0 + 64 * u + lane);
-    }
+    k = strided_row_scan<true>(Lr, sc, sch, nchk, N, cap, oe, ov, differ);
   }
   const int cnt = k < cap ? k : cap;
-  const int cnt8 = (cnt + 7) & ~7;   // (cap is a multiple of 8) the conv walks whole groups of eight
-  if (cnt + lane < cnt8) {
-    oe[cnt + lane] = 0u;
-    if (ov) ov[cnt + lane] = 0.0f;
-  }
+  conv_pad_row(oe, ov, cnt, lane);
   const bool any_differ = __ballot(differ) != 0ull;
   if (lane == 0) {
     counts[rid] = cnt;
@@ -171,7 +178,37 @@ __global__ __launch_bounds__(256) void sparse_image_kernel(
   }
 }
 
-// ---- conv: X[r][:] = act( X[r][:] + sum_k value[r][k] Z[column[r][k]][:] ) ---------------------
+// ---- images of all C channels in ONE pass over L (several DISTINCT operators: a typed batch, channel 0 =
+// the simple graph, channel 1 + e = edge type e alone, dataset/get_graph_data.py:60-72): one wave per row,
+// ascending columns, 4-byte loads at the given strides (the channels of a column sit next to each other:
+// every line of the row is fetched from HBM once and serves all channels).  Image c [c][B][N][cap] is, bit
+// for bit, what sparse_image_kernel<0> writes for the one-channel slice L[..., c:c+1] — the same row scan,
+// without the compare; flags: bit 1 only.
+__global__ __launch_bounds__(256) void sparse_image_channels_kernel(
+    const float* __restrict__ L, int64_t sb, int64_t sr, int64_t sc, int64_t sch, int B, int N, int C,
+    int cap, unsigned* __restrict__ ent, float* __restrict__ vals, int32_t* __restrict__ counts,
+    int32_t* __restrict__ flags) {
+  const int lane = threadIdx.x & 63;
+  const int64_t rows = (int64_t)B * N;
+  const int64_t rid = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (rid >= rows) return;
+  const int b = (int)(rid / N), r = (int)(rid - (int64_t)b * N);
+  const float* Lr = L + (int64_t)b * sb + (int64_t)r * sr;
+  bool over = false, differ = false;   // (differ: never raised here)
+  for (int c = 0; c < C; ++c) {
+    unsigned* oe = ent + ((int64_t)c * rows + rid) * cap;
+    float* ov = vals ? vals + ((int64_t)c * rows + rid) * cap : nullptr;
+    const int k = strided_row_scan<false>(Lr + (int64_t)c * sch, sc, 0, 1, N, cap, oe, ov, differ);
+    const int cnt = k < cap ? k : cap;
+    conv_pad_row(oe, ov, cnt, lane);
+    if (lane == 0) counts[(int64_t)c * rows + rid] = cnt;
+    over |= k > cap;
+  }
+  if (lane == 0 && over) atomicOr(flags, 2);
+}
+
+// ---- conv: X[r][:] = act( X[r][:] + sum_c sum_k value_c[r][k] Z_c[column_c[r][k]][:] ), R = 1 .. 8 ----
+// (the node-space term sum_c L_c (X W_c^T) of model/lanczos_net_general.py:179; R = 1: one operator)
 // Workgroup = 32 rows of one graph (4 waves x 8 rows: 0.276 ms; x 16: 0.288, x 32: 0.340 — fewer
 // graphs share an L2 at a time); blockIdx -> (graph, tile) deals the tiles
 // of a graph to ONE XCD (workgroup i runs on XCD i % 8), whose L2 then holds the graph's Z (512
@@ -184,212 +221,105 @@ __global__ __launch_bounds__(256) void sparse_image_kernel(
 // instructions per entry and 8 -> 32 gathers in flight changed nothing; a form with a feature
 // quarter of Z staged in LDS and ds_bpermute broadcasts was issue bound at 0.32 ms; the lift V T in
 // vector FMAs inside this kernel, T in LDS, cost 0.25 ms against the 0.08 ms of the MFMA launch).
-__global__ __launch_bounds__(64 * WAVES) void sparse_conv_kernel(
-    const unsigned* __restrict__ ent, const int32_t* __restrict__ counts, int cap,
-    const u16* __restrict__ Z, int B, int N, int tiles, int relu, float* __restrict__ X) {
-  const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
-  const int b = xcd + 8 * (seq / tiles), tile = seq % tiles;
-  if (b >= B) return;
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int r0 = tile * TILE_ROWS + wave * ROWS_PER_WAVE;
-  if (r0 >= N) return;
-  const int nr = min(ROWS_PER_WAVE, N - r0);
-  const int64_t row0 = (int64_t)b * N + r0;
-  const int cv = lane < nr ? counts[row0 + lane] : 0;
-  // the graph's Z as a buffer: dword `lane` of a node's 256 B = features 2 lane, 2 lane + 1
-  const __amdgpu_buffer_rsrc_t z_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<u16*>(Z + (int64_t)b * N * DH), 0, (unsigned)N * DH * 2, 0x00020000);
-  const unsigned zoff = 4u * lane;
-  auto entries = [&](const int rr, const int k0, const int cnt8) -> unsigned {
-    return k0 + lane < cnt8 ? ent[(row0 + rr) * cap + k0 + lane] : 0u;
-  };
-  int cnt8n = (__builtin_amdgcn_readlane(cv, 0) + GS - 1) & ~(GS - 1);
-  unsigned en = entries(0, 0, cnt8n);
-  for (int rr = 0; rr < nr; ++rr) {
-    const int cnt8 = cnt8n;
-    unsigned e = en;
-    float* xr = X + (row0 + rr) * DH + 2 * lane;
-    f32x2 acc = *reinterpret_cast<const f32x2*>(xr);
-    if (rr + 1 < nr) {   // (uniform) the next row's entries
-      cnt8n = (__builtin_amdgcn_readlane(cv, rr + 1) + GS - 1) & ~(GS - 1);
-      en = entries(rr + 1, 0, cnt8n);
+//
+// What differs between the two element types of the gather, and nothing else:
+//   GatherBf16  the value rides in the entry (bf16(value) << 16 | column), Z [..][N][128] bf16: a lane's
+//               dword = features 2 lane, 2 lane + 1; counts rounded up to GS, turns of GS .. 32 entries.
+//   GatherF32   the split-precision modes' node-space term in EXACT fp32: the unrounded values beside the
+//               entries, Zf [..][N][128] fp32 (= lnz_f32_linear's X W^T): a lane's dwordx2, 512 B through
+//               the L2 -> L1 path per nonzero (twice the bf16 form's), no unpacking; counts rounded up to
+//               8 (whatever GS is), turns of 8 or 16 entries.
+// A turn is ONE uniform decision followed by a straight line of gathers and their FMAs (a test per group
+// of eight was a point the loads behind it waited at).
+struct GatherBf16 {
+  typedef u16 T;
+  struct Entry { unsigned e; };
+  static constexpr int TURN = 32;
+  static __device__ __forceinline__ int round_up(const int cnt) { return (cnt + GS - 1) & ~(GS - 1); }
+  static __device__ __forceinline__ Entry load(const unsigned* ent, const float*, const int64_t o, const bool in) {
+    return Entry{in ? ent[o] : 0u};
+  }
+  template <int n>
+  static __device__ __forceinline__ void turn(const __amdgpu_buffer_rsrc_t z, const unsigned zoff, const Entry en,
+                                              const int k, f32x2& acc) {
+    unsigned g[n];
+    float s[n];
+#pragma unroll
+    for (int u = 0; u < n; ++u) {
+      const unsigned se = (unsigned)__builtin_amdgcn_readlane((int)en.e, k + u);
+      s[u] = __uint_as_float(se & 0xffff0000u);
+      g[u] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(z, zoff, (se & 0xffffu) * (DH * 2), 0);
     }
-    for (int k0 = 0; k0 < cnt8; k0 += 64) {
-      if (k0 > 0) e = entries(rr, k0, cnt8);   // (rows of more than 64 entries)
-      const int m = min(64, cnt8 - k0);
-      for (int k = 0; k < m; k += 32) {
-        // ONE uniform decision per turn, then a straight line of 8, 16, 24 or 32 gathers and their
-        // FMAs (a test per group of eight was a point the loads behind it waited at)
-        auto turn = [&](auto nc) {
-          constexpr int n = decltype(nc)::value;
-          unsigned z[n];
-          float s[n];
 #pragma unroll
-          for (int u = 0; u < n; ++u) {
-            const unsigned se = (unsigned)__builtin_amdgcn_readlane((int)e, k + u);
-            s[u] = __uint_as_float(se & 0xffff0000u);
-            z[u] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(z_rsrc, zoff, (se & 0xffffu) * (DH * 2), 0);
-          }
-#pragma unroll
-          for (int u = 0; u < n; ++u) {
-            acc[0] = fmaf(s[u], __uint_as_float(z[u] << 16), acc[0]);
-            acc[1] = fmaf(s[u], __uint_as_float(z[u] & 0xffff0000u), acc[1]);
-          }
-        };
-        switch (min(32, m - k) / GS) {   // (m - k is a multiple of GS)
-#define LNZ_TURN(q) case q: if constexpr (q * GS <= 32) turn(std::integral_constant<int, (q * GS <= 32 ? q * GS : 32)>{}); break;
-          LNZ_TURN(1) LNZ_TURN(2) LNZ_TURN(3) LNZ_TURN(4) LNZ_TURN(5) LNZ_TURN(6) LNZ_TURN(7) LNZ_TURN(8)
+    for (int u = 0; u < n; ++u) {
+      acc[0] = fmaf(s[u], __uint_as_float(g[u] << 16), acc[0]);
+      acc[1] = fmaf(s[u], __uint_as_float(g[u] & 0xffff0000u), acc[1]);
+    }
+  }
+  // entries k .. of the lanes' `left` (> 0, a multiple of GS), TURN of them at most
+  static __device__ __forceinline__ void turns(const __amdgpu_buffer_rsrc_t z, const unsigned zoff, const Entry en,
+                                               const int k, const int left, f32x2& acc) {
+    switch (min(32, left) / GS) {
+#define LNZ_TURN(q) case q: if constexpr (q * GS <= 32) turn<(q * GS <= 32 ? q * GS : 32)>(z, zoff, en, k, acc); break;
+      LNZ_TURN(1) LNZ_TURN(2) LNZ_TURN(3) LNZ_TURN(4) LNZ_TURN(5) LNZ_TURN(6) LNZ_TURN(7) LNZ_TURN(8)
 #undef LNZ_TURN
-          default: break;
-        }
-      }
+      default: break;
     }
-    if (relu) {
-      acc[0] = acc[0] > 0.0f ? acc[0] : 0.0f;
-      acc[1] = acc[1] > 0.0f ? acc[1] : 0.0f;
-    }
-    *reinterpret_cast<f32x2*>(xr) = acc;
   }
-}
+};
 
-// ---- the same in exact fp32 (the split-precision modes' node-space term): fp32 values x fp32
-// features, Zf [B][N][128] fp32 (= lnz_f32_linear's X W^T), a lane's dwordx2 = features 2 lane,
-// 2 lane + 1: 512 B through the L2 -> L1 path per nonzero (twice the bf16 form's), no unpacking.
-__global__ __launch_bounds__(64 * WAVES) void sparse_conv_f32_kernel(
+struct GatherF32 {
+  typedef float T;
+  struct Entry { unsigned e; float v; };
+  static constexpr int TURN = 16;
+  static __device__ __forceinline__ int round_up(const int cnt) { return (cnt + 7) & ~7; }
+  static __device__ __forceinline__ Entry load(const unsigned* ent, const float* vals, const int64_t o, const bool in) {
+    Entry en = {0u, 0.0f};
+    if (in) {   // (both loads behind ONE test)
+      en.e = ent[o];
+      en.v = vals[o];
+    }
+    return en;
+  }
+  template <int n>
+  static __device__ __forceinline__ void turn(const __amdgpu_buffer_rsrc_t z, const unsigned zoff, const Entry en,
+                                              const int k, f32x2& acc) {
+    f32x2 g[n];
+    float s[n];
+#pragma unroll
+    for (int u = 0; u < n; ++u) {
+      const unsigned col = (unsigned)__builtin_amdgcn_readlane((int)en.e, k + u) & 0xffffu;
+      s[u] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(en.v), k + u));
+      g[u] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(z, zoff, col * (DH * 4), 0));
+    }
+#pragma unroll
+    for (int u = 0; u < n; ++u) {
+      acc[0] = fmaf(s[u], g[u][0], acc[0]);
+      acc[1] = fmaf(s[u], g[u][1], acc[1]);
+    }
+  }
+  static __device__ __forceinline__ void turns(const __amdgpu_buffer_rsrc_t z, const unsigned zoff, const Entry en,
+                                               const int k, const int left, f32x2& acc) {
+    if (left > 8) turn<16>(z, zoff, en, k, acc);
+    else turn<8>(z, zoff, en, k, acc);
+  }
+};
+
+// The schedule, once: the (row, channel) pairs of a wave's eight rows are its sequence — lane q = R rr + c
+// holds the count of pair q (at most 64 pairs), the entries of pair q + 1 are requested while pair q is
+// gathered, channels ascending and entries in entry order into ONE accumulator per row (X read at c == 0,
+// written behind the last channel): the result is a fixed function of the images.  Images [R][B][N][cap],
+// counts [R][B][N], Z CLASS MAJOR [R][B][N][128] (one GEMM1 per channel): a graph's R feature blocks are R
+// buffers of N rows, the descriptor rebuilt per pair from scalars.  MULTI = false: R = 1 at compile time
+// — the pairs are the rows, the channel and the per-pair descriptor fold away.
+template <class Elem, bool MULTI>
+__global__ __launch_bounds__(64 * WAVES) void sparse_gather_kernel(
     const unsigned* __restrict__ ent, const float* __restrict__ vals, const int32_t* __restrict__ counts,
-    int cap, const float* __restrict__ Zf, int B, int N, int tiles, int relu, float* __restrict__ X) {
-  const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
-  const int b = xcd + 8 * (seq / tiles), tile = seq % tiles;
-  if (b >= B) return;
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int r0 = tile * TILE_ROWS + wave * ROWS_PER_WAVE;
-  if (r0 >= N) return;
-  const int nr = min(ROWS_PER_WAVE, N - r0);
-  const int64_t row0 = (int64_t)b * N + r0;
-  const int cv = lane < nr ? counts[row0 + lane] : 0;
-  const __amdgpu_buffer_rsrc_t z_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(Zf + (int64_t)b * N * DH), 0, (unsigned)N * DH * 4, 0x00020000);
-  const unsigned zoff = 8u * lane;
-  auto entries = [&](const int rr, const int k0, const int cnt8, unsigned& e, float& v) {
-    const bool in = k0 + lane < cnt8;
-    const int64_t o = (row0 + rr) * cap + k0 + lane;
-    e = in ? ent[o] : 0u;
-    v = in ? vals[o] : 0.0f;
-  };
-  int cnt8n = (__builtin_amdgcn_readlane(cv, 0) + 7) & ~7;
-  unsigned en;
-  float vn;
-  entries(0, 0, cnt8n, en, vn);
-  for (int rr = 0; rr < nr; ++rr) {
-    const int cnt8 = cnt8n;
-    unsigned e = en;
-    float v = vn;
-    float* xr = X + (row0 + rr) * DH + 2 * lane;
-    f32x2 acc = *reinterpret_cast<const f32x2*>(xr);
-    if (rr + 1 < nr) {   // (uniform) the next row's entries
-      cnt8n = (__builtin_amdgcn_readlane(cv, rr + 1) + 7) & ~7;
-      entries(rr + 1, 0, cnt8n, en, vn);
-    }
-    for (int k0 = 0; k0 < cnt8; k0 += 64) {
-      if (k0 > 0) entries(rr, k0, cnt8, e, v);   // (rows of more than 64 entries)
-      const int m = min(64, cnt8 - k0);
-      for (int k = 0; k < m; k += 16) {
-        auto turn = [&](auto nc) {   // (one uniform decision, then a straight line: see the bf16 form)
-          constexpr int n = decltype(nc)::value;
-          f32x2 z[n];
-          float s[n];
-#pragma unroll
-          for (int u = 0; u < n; ++u) {
-            const unsigned col = (unsigned)__builtin_amdgcn_readlane((int)e, k + u) & 0xffffu;
-            s[u] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k + u));
-            z[u] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(z_rsrc, zoff, col * (DH * 4), 0));
-          }
-#pragma unroll
-          for (int u = 0; u < n; ++u) {
-            acc[0] = fmaf(s[u], z[u][0], acc[0]);
-            acc[1] = fmaf(s[u], z[u][1], acc[1]);
-          }
-        };
-        if (m - k > 8) turn(std::integral_constant<int, 16>{});
-        else turn(std::integral_constant<int, 8>{});
-      }
-    }
-    if (relu) {
-      acc[0] = acc[0] > 0.0f ? acc[0] : 0.0f;
-      acc[1] = acc[1] > 0.0f ? acc[1] : 0.0f;
-    }
-    *reinterpret_cast<f32x2*>(xr) = acc;
-  }
-}
-
-
-// ==== several operators (a typed batch: channel 0 = the simple graph, channel 1 + e = edge type e alone,
-// dataset/get_graph_data.py:60-72; the node-space term sum_c L_c (X W_c^T) of
-// model/lanczos_net_general.py:179) ==================================================================
-constexpr int MAXR = 8;   // LARGE_MAX_OPERATORS
-
-// ---- images of all C channels in ONE pass over L: one wave per row, ascending columns, 4-byte loads at
-// the given strides (the channels of a column sit next to each other: every line of the row is fetched
-// from HBM once and serves all channels).  Image c [c][B][N][cap] is, bit for bit, what
-// sparse_image_kernel<0> writes for the one-channel slice L[..., c:c+1]; flags: bit 1 only.
-__global__ __launch_bounds__(256) void sparse_image_channels_kernel(
-    const float* __restrict__ L, int64_t sb, int64_t sr, int64_t sc, int64_t sch, int B, int N, int C,
-    int cap, unsigned* __restrict__ ent, float* __restrict__ vals, int32_t* __restrict__ counts,
-    int32_t* __restrict__ flags) {
-  const int lane = threadIdx.x & 63;
-  const int64_t rows = (int64_t)B * N;
-  const int64_t rid = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (rid >= rows) return;
-  const int b = (int)(rid / N), r = (int)(rid - (int64_t)b * N);
-  const float* Lr = L + (int64_t)b * sb + (int64_t)r * sr;
-  bool over = false;
-  for (int c = 0; c < C; ++c) {
-    const float* Lc = Lr + (int64_t)c * sch;
-    unsigned* oe = ent + ((int64_t)c * rows + rid) * cap;
-    float* ov = vals ? vals + ((int64_t)c * rows + rid) * cap : nullptr;
-    int k = 0;   // entries of this row and channel so far (wave-uniform)
-    for (int c0 = 0; c0 < N; c0 += 64 * 8) {
-      float x[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int col = c0 + 64 * u + lane;
-        x[u] = col < N ? Lc[(int64_t)col * sc] : 0.0f;
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const bool nz = x[u] != 0.0f;   // (a NaN is kept)
-        const unsigned long long m = __ballot(nz);
-        if (m == 0ull) continue;
-        const int pos = k + lane_rank(m);
-        if (nz && pos < cap) {
-          oe[pos] = pack_entry(x[u], c0 + 64 * u + lane);
-          if (ov) ov[pos] = x[u];
-        }
-        k += __popcll(m);
-      }
-    }
-    const int cnt = k < cap ? k : cap;
-    const int cnt8 = (cnt + 7) & ~7;
-    if (cnt + lane < cnt8) {
-      oe[cnt + lane] = 0u;
-      if (ov) ov[cnt + lane] = 0.0f;
-    }
-    if (lane == 0) counts[(int64_t)c * rows + rid] = cnt;
-    over |= k > cap;
-  }
-  if (lane == 0 && over) atomicOr(flags, 2);
-}
-
-// ---- conv: X[r][:] = act( X[r][:] + sum_c sum_k value_c[r][k] Z_c[column_c[r][k]][:] ), R = 2 .. 8 ----
-// The schedule of sparse_conv_kernel with the (row, channel) pairs of a wave's eight rows as its sequence:
-// lane q = R rr + c holds the count of pair q (at most 64 pairs), the entries of pair q + 1 are requested
-// while pair q is gathered, channels ascending and entries in entry order into ONE accumulator per row —
-// the result is a fixed function of the images.  Images [R][B][N][cap], counts [R][B][N], Z CLASS MAJOR
-// [R][B][N][128] (lnz_large_gemm1_rows once per channel): a graph's R feature blocks are R buffers of
-// N x 256 B, the descriptor rebuilt per pair from scalars.
-__global__ __launch_bounds__(64 * WAVES) void sparse_conv_channels_kernel(
-    const unsigned* __restrict__ ent, const int32_t* __restrict__ counts, int cap,
-    const u16* __restrict__ Z, int B, int N, int R, int tiles, int relu, float* __restrict__ X) {
+    int cap, const typename Elem::T* __restrict__ Z, int B, int N, int operators, int tiles, int relu,
+    float* __restrict__ X) {
+  typedef typename Elem::T T;
+  typedef typename Elem::Entry Entry;
+  const int R = MULTI ? operators : 1;
   const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
   const int b = xcd + 8 * (seq / tiles), tile = seq % tiles;
   if (b >= B) return;
@@ -399,54 +329,32 @@ __global__ __launch_bounds__(64 * WAVES) void sparse_conv_channels_kernel(
   const int nr = min(ROWS_PER_WAVE, N - r0), nq = nr * R;   // (ROWS_PER_WAVE * MAXR <= 64)
   const int64_t rows = (int64_t)B * N, row0 = (int64_t)b * N + r0;
   const int cv = lane < nq ? counts[(int64_t)(lane % R) * rows + row0 + lane / R] : 0;
-  const u16* Zb = Z + (int64_t)b * N * DH;
-  const unsigned zoff = 4u * lane;
-  auto entries = [&](const int rr, const int c, const int k0, const int cnt8) -> unsigned {
-    return k0 + lane < cnt8 ? ent[((int64_t)c * rows + row0 + rr) * cap + k0 + lane] : 0u;
+  // the graph's Z as a buffer: a lane's two features of a node's 128
+  const T* Zb = Z + (int64_t)b * N * DH;
+  const unsigned zoff = (unsigned)(2 * sizeof(T)) * lane;
+  auto entries = [&](const int rr, const int c, const int k0, const int cnt8) -> Entry {
+    return Elem::load(ent, vals, ((int64_t)c * rows + row0 + rr) * cap + k0 + lane, k0 + lane < cnt8);
   };
-  int cnt8n = (__builtin_amdgcn_readlane(cv, 0) + GS - 1) & ~(GS - 1);
-  unsigned en = entries(0, 0, 0, cnt8n);
+  int cnt8n = Elem::round_up(__builtin_amdgcn_readlane(cv, 0));
+  Entry en = entries(0, 0, 0, cnt8n);
   f32x2 acc = {0.0f, 0.0f};
   int rr = 0, c = 0;
   for (int q = 0; q < nq; ++q) {
     const int cnt8 = cnt8n;
-    unsigned e = en;
+    Entry e = en;
     float* xr = X + (row0 + rr) * DH + 2 * lane;
     if (c == 0) acc = *reinterpret_cast<const f32x2*>(xr);
     const int cn = c + 1 < R ? c + 1 : 0, rn = c + 1 < R ? rr : rr + 1;
     if (q + 1 < nq) {   // (uniform) the next pair's entries
-      cnt8n = (__builtin_amdgcn_readlane(cv, q + 1) + GS - 1) & ~(GS - 1);
+      cnt8n = Elem::round_up(__builtin_amdgcn_readlane(cv, q + 1));
       en = entries(rn, cn, 0, cnt8n);
     }
     const __amdgpu_buffer_rsrc_t z_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<u16*>(Zb + (int64_t)c * rows * DH), 0, (unsigned)N * DH * 2, 0x00020000);
+        const_cast<T*>(Zb + (int64_t)c * rows * DH), 0, (unsigned)N * DH * (unsigned)sizeof(T), 0x00020000);
     for (int k0 = 0; k0 < cnt8; k0 += 64) {
       if (k0 > 0) e = entries(rr, c, k0, cnt8);   // (rows of more than 64 entries)
       const int m = min(64, cnt8 - k0);
-      for (int k = 0; k < m; k += 32) {
-        auto turn = [&](auto nc) {   // (one uniform decision, then a straight line: see sparse_conv_kernel)
-          constexpr int n = decltype(nc)::value;
-          unsigned z[n];
-          float s[n];
-#pragma unroll
-          for (int u = 0; u < n; ++u) {
-            const unsigned se = (unsigned)__builtin_amdgcn_readlane((int)e, k + u);
-            s[u] = __uint_as_float(se & 0xffff0000u);
-            z[u] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(z_rsrc, zoff, (se & 0xffffu) * (DH * 2), 0);
-          }
-#pragma unroll
-          for (int u = 0; u < n; ++u) {
-            acc[0] = fmaf(s[u], __uint_as_float(z[u] << 16), acc[0]);
-            acc[1] = fmaf(s[u], __uint_as_float(z[u] & 0xffff0000u), acc[1]);
-          }
-        };
-        switch (min(32, m - k) / GS) {   // (m - k is a multiple of GS)
-#define LNZ_TURN(q) case q: if constexpr (q * GS <= 32) turn(std::integral_constant<int, (q * GS <= 32 ? q * GS : 32)>{}); break;
-          LNZ_TURN(1) LNZ_TURN(2) LNZ_TURN(3) LNZ_TURN(4) LNZ_TURN(5) LNZ_TURN(6) LNZ_TURN(7) LNZ_TURN(8)
-#undef LNZ_TURN
-          default: break;
-        }
-      }
+      for (int k = 0; k < m; k += Elem::TURN) Elem::turns(z_rsrc, zoff, e, k, m - k, acc);
     }
     if (cn == 0) {   // the row's last channel
       if (relu) {
@@ -460,82 +368,40 @@ __global__ __launch_bounds__(64 * WAVES) void sparse_conv_channels_kernel(
   }
 }
 
-// ---- the same in exact fp32: values [R][B][N][cap] fp32, Zf CLASS MAJOR [R][B][N][128] fp32 ------------
-__global__ __launch_bounds__(64 * WAVES) void sparse_conv_channels_f32_kernel(
-    const unsigned* __restrict__ ent, const float* __restrict__ vals, const int32_t* __restrict__ counts,
-    int cap, const float* __restrict__ Zf, int B, int N, int R, int tiles, int relu, float* __restrict__ X) {
-  const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
-  const int b = xcd + 8 * (seq / tiles), tile = seq % tiles;
-  if (b >= B) return;
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int r0 = tile * TILE_ROWS + wave * ROWS_PER_WAVE;
-  if (r0 >= N) return;
-  const int nr = min(ROWS_PER_WAVE, N - r0), nq = nr * R;
-  const int64_t rows = (int64_t)B * N, row0 = (int64_t)b * N + r0;
-  const int cv = lane < nq ? counts[(int64_t)(lane % R) * rows + row0 + lane / R] : 0;
-  const float* Zb = Zf + (int64_t)b * N * DH;
-  const unsigned zoff = 8u * lane;
-  auto entries = [&](const int rr, const int c, const int k0, const int cnt8, unsigned& e, float& v) {
-    const bool in = k0 + lane < cnt8;
-    const int64_t o = ((int64_t)c * rows + row0 + rr) * cap + k0 + lane;
-    e = in ? ent[o] : 0u;
-    v = in ? vals[o] : 0.0f;
-  };
-  int cnt8n = (__builtin_amdgcn_readlane(cv, 0) + 7) & ~7;
-  unsigned en;
-  float vn;
-  entries(0, 0, 0, cnt8n, en, vn);
-  f32x2 acc = {0.0f, 0.0f};
-  int rr = 0, c = 0;
-  for (int q = 0; q < nq; ++q) {
-    const int cnt8 = cnt8n;
-    unsigned e = en;
-    float v = vn;
-    float* xr = X + (row0 + rr) * DH + 2 * lane;
-    if (c == 0) acc = *reinterpret_cast<const f32x2*>(xr);
-    const int cn = c + 1 < R ? c + 1 : 0, rn = c + 1 < R ? rr : rr + 1;
-    if (q + 1 < nq) {   // (uniform) the next pair's entries
-      cnt8n = (__builtin_amdgcn_readlane(cv, q + 1) + 7) & ~7;
-      entries(rn, cn, 0, cnt8n, en, vn);
-    }
-    const __amdgpu_buffer_rsrc_t z_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(Zb + (int64_t)c * rows * DH), 0, (unsigned)N * DH * 4, 0x00020000);
-    for (int k0 = 0; k0 < cnt8; k0 += 64) {
-      if (k0 > 0) entries(rr, c, k0, cnt8, e, v);   // (rows of more than 64 entries)
-      const int m = min(64, cnt8 - k0);
-      for (int k = 0; k < m; k += 16) {
-        auto turn = [&](auto nc) {
-          constexpr int n = decltype(nc)::value;
-          f32x2 z[n];
-          float s[n];
-#pragma unroll
-          for (int u = 0; u < n; ++u) {
-            const unsigned col = (unsigned)__builtin_amdgcn_readlane((int)e, k + u) & 0xffffu;
-            s[u] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k + u));
-            z[u] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(z_rsrc, zoff, col * (DH * 4), 0));
-          }
-#pragma unroll
-          for (int u = 0; u < n; ++u) {
-            acc[0] = fmaf(s[u], z[u][0], acc[0]);
-            acc[1] = fmaf(s[u], z[u][1], acc[1]);
-          }
-        };
-        if (m - k > 8) turn(std::integral_constant<int, 16>{});
-        else turn(std::integral_constant<int, 8>{});
-      }
-    }
-    if (cn == 0) {
-      if (relu) {
-        acc[0] = acc[0] > 0.0f ? acc[0] : 0.0f;
-        acc[1] = acc[1] > 0.0f ? acc[1] : 0.0f;
-      }
-      *reinterpret_cast<f32x2*>(xr) = acc;
-    }
-    rr = rn;
-    c = cn;
+// The four gather entries: `who` = the entry's name, whose kernel is named after it (lnz_last_kernel():
+// sparse_conv[_channels][_f32]_kernel).  MULTI: R = 2 .. MAXR operators; otherwise R = 1.
+template <class Elem, bool MULTI>
+int launch_gather(const char* who, const uint32_t* entries, const float* values, const int32_t* counts, int row_cap,
+                  const typename Elem::T* Z, int B, int N, int R, int relu, float* X, lnz_stream_t stream) {
+  constexpr bool F32 = std::is_same<Elem, GatherF32>::value;
+  LNZ_REQUIRE(entries && (values || !F32) && counts && Z && X && B > 0 && N > 0, LNZ_EINVAL, "%s: bad arguments", who);
+  if (MULTI)
+    LNZ_REQUIRE(R >= 2 && R <= MAXR, LNZ_ENOTSUP, "%s: R=%d: 2 .. %d operators (one: lnz_large_sparse_conv%s)", who, R,
+                MAXR, F32 ? "_f32" : "");
+  if (MULTI && !F32) LNZ_REQUIRE(N <= 65536, LNZ_ENOTSUP, "%s: N=%d > 65536 (16-bit columns)", who, N);
+  LNZ_REQUIRE(row_cap >= 32 && row_cap % 8 == 0, LNZ_EINVAL, "%s: row_cap=%d must be a multiple of 8, at least 32", who,
+              row_cap);
+  if (F32) {
+    LNZ_REQUIRE((((uintptr_t)X) & 7) == 0 && (((uintptr_t)Z) & 7) == 0, LNZ_EINVAL,
+                "%s: X / Zf must be 8-byte aligned", who);
+    if (MULTI)
+      LNZ_REQUIRE(N <= 65536 && (int64_t)N * DH * 4 <= 0x7fffffffll, LNZ_ENOTSUP, "%s: N=%d too large", who, N);
+    else
+      LNZ_REQUIRE((int64_t)N * DH * 4 <= 0x7fffffffll, LNZ_ENOTSUP, "%s: N too large", who);
+  } else if (MULTI) {
+    LNZ_REQUIRE((((uintptr_t)X) & 7) == 0 && (((uintptr_t)Z) & 3) == 0, LNZ_EINVAL,
+                "%s: X must be 8-byte, Z 4-byte aligned", who);
+  } else {
+    LNZ_REQUIRE((((uintptr_t)X) & 7) == 0, LNZ_EINVAL, "%s: X must be 8-byte aligned", who);
   }
+  const int tiles = (N + TILE_ROWS - 1) / TILE_ROWS;
+  const int64_t grid = (int64_t)8 * tiles * ((B + 7) / 8);
+  LNZ_REQUIRE(grid <= 0x7fffffffll, LNZ_ENOTSUP, "%s: B x N too large", who);
+  hipLaunchKernelGGL((sparse_gather_kernel<Elem, MULTI>), dim3((unsigned)grid), dim3(64 * WAVES), 0,
+                     (hipStream_t)stream, entries, values, counts, row_cap, Z, B, N, R, tiles, relu, X);
+  lnz::note_kernel("%s_kernel", who + sizeof("lnz_large_") - 1);
+  return lnz::check_launch(who);
 }
-static_assert(ROWS_PER_WAVE * MAXR <= 64, "a wave's (row, channel) pairs: one count per lane");
 
 }  // namespace
 
@@ -570,42 +436,6 @@ extern "C" int lnz_large_sparse_image(const float* L, int64_t stride_b, int64_t 
   return lnz::check_launch("lnz_large_sparse_image");
 }
 
-extern "C" int lnz_large_sparse_conv(const uint32_t* entries, const int32_t* counts, int row_cap,
-                                     const uint16_t* Z, int B, int N, int relu, float* X,
-                                     lnz_stream_t stream) {
-  LNZ_REQUIRE(entries && counts && Z && X && B > 0 && N > 0, LNZ_EINVAL,
-              "lnz_large_sparse_conv: bad arguments");
-  LNZ_REQUIRE(row_cap >= 32 && row_cap % 8 == 0, LNZ_EINVAL,
-              "lnz_large_sparse_conv: row_cap=%d must be a multiple of 8, at least 32", row_cap);
-  LNZ_REQUIRE((((uintptr_t)X) & 7) == 0, LNZ_EINVAL, "lnz_large_sparse_conv: X must be 8-byte aligned");
-  const int tiles = (N + TILE_ROWS - 1) / TILE_ROWS;
-  const int64_t grid = (int64_t)8 * tiles * ((B + 7) / 8);
-  LNZ_REQUIRE(grid <= 0x7fffffffll, LNZ_ENOTSUP, "lnz_large_sparse_conv: B x N too large");
-  hipLaunchKernelGGL(sparse_conv_kernel, dim3((unsigned)grid), dim3(64 * WAVES), 0,
-                     (hipStream_t)stream, entries, counts, row_cap, Z, B, N, tiles, relu, X);
-  lnz::note_kernel("sparse_conv_kernel");
-  return lnz::check_launch("lnz_large_sparse_conv");
-}
-
-extern "C" int lnz_large_sparse_conv_f32(const uint32_t* entries, const float* values,
-                                         const int32_t* counts, int row_cap, const float* Zf, int B,
-                                         int N, int relu, float* X, lnz_stream_t stream) {
-  LNZ_REQUIRE(entries && values && counts && Zf && X && B > 0 && N > 0, LNZ_EINVAL,
-              "lnz_large_sparse_conv_f32: bad arguments");
-  LNZ_REQUIRE(row_cap >= 32 && row_cap % 8 == 0, LNZ_EINVAL,
-              "lnz_large_sparse_conv_f32: row_cap=%d must be a multiple of 8, at least 32", row_cap);
-  LNZ_REQUIRE((((uintptr_t)X) & 7) == 0 && (((uintptr_t)Zf) & 7) == 0, LNZ_EINVAL,
-              "lnz_large_sparse_conv_f32: X / Zf must be 8-byte aligned");
-  LNZ_REQUIRE((int64_t)N * DH * 4 <= 0x7fffffffll, LNZ_ENOTSUP, "lnz_large_sparse_conv_f32: N too large");
-  const int tiles = (N + TILE_ROWS - 1) / TILE_ROWS;
-  const int64_t grid = (int64_t)8 * tiles * ((B + 7) / 8);
-  LNZ_REQUIRE(grid <= 0x7fffffffll, LNZ_ENOTSUP, "lnz_large_sparse_conv_f32: B x N too large");
-  hipLaunchKernelGGL(sparse_conv_f32_kernel, dim3((unsigned)grid), dim3(64 * WAVES), 0,
-                     (hipStream_t)stream, entries, values, counts, row_cap, Zf, B, N, tiles, relu, X);
-  lnz::note_kernel("sparse_conv_f32_kernel");
-  return lnz::check_launch("lnz_large_sparse_conv_f32");
-}
-
 extern "C" int lnz_large_sparse_image_channels(const float* L, int64_t stride_b, int64_t stride_r,
                                                int64_t stride_c, int64_t stride_ch, int B, int N, int C,
                                                int row_cap, uint32_t* entries, float* values,
@@ -627,45 +457,30 @@ extern "C" int lnz_large_sparse_image_channels(const float* L, int64_t stride_b,
   return lnz::check_launch("lnz_large_sparse_image_channels");
 }
 
+extern "C" int lnz_large_sparse_conv(const uint32_t* entries, const int32_t* counts, int row_cap,
+                                     const uint16_t* Z, int B, int N, int relu, float* X,
+                                     lnz_stream_t stream) {
+  return launch_gather<GatherBf16, false>("lnz_large_sparse_conv", entries, nullptr, counts, row_cap, Z, B, N, 1, relu,
+                                          X, stream);
+}
+
+extern "C" int lnz_large_sparse_conv_f32(const uint32_t* entries, const float* values,
+                                         const int32_t* counts, int row_cap, const float* Zf, int B,
+                                         int N, int relu, float* X, lnz_stream_t stream) {
+  return launch_gather<GatherF32, false>("lnz_large_sparse_conv_f32", entries, values, counts, row_cap, Zf, B, N, 1,
+                                         relu, X, stream);
+}
+
 extern "C" int lnz_large_sparse_conv_channels(const uint32_t* entries, const int32_t* counts, int row_cap,
                                               const uint16_t* Z, int B, int N, int R, int relu, float* X,
                                               lnz_stream_t stream) {
-  LNZ_REQUIRE(entries && counts && Z && X && B > 0 && N > 0, LNZ_EINVAL,
-              "lnz_large_sparse_conv_channels: bad arguments");
-  LNZ_REQUIRE(R >= 2 && R <= MAXR, LNZ_ENOTSUP,
-              "lnz_large_sparse_conv_channels: R=%d: 2 .. %d operators (one: lnz_large_sparse_conv)", R, MAXR);
-  LNZ_REQUIRE(N <= 65536, LNZ_ENOTSUP, "lnz_large_sparse_conv_channels: N=%d > 65536 (16-bit columns)", N);
-  LNZ_REQUIRE(row_cap >= 32 && row_cap % 8 == 0, LNZ_EINVAL,
-              "lnz_large_sparse_conv_channels: row_cap=%d must be a multiple of 8, at least 32", row_cap);
-  LNZ_REQUIRE((((uintptr_t)X) & 7) == 0 && (((uintptr_t)Z) & 3) == 0, LNZ_EINVAL,
-              "lnz_large_sparse_conv_channels: X must be 8-byte, Z 4-byte aligned");
-  const int tiles = (N + TILE_ROWS - 1) / TILE_ROWS;
-  const int64_t grid = (int64_t)8 * tiles * ((B + 7) / 8);
-  LNZ_REQUIRE(grid <= 0x7fffffffll, LNZ_ENOTSUP, "lnz_large_sparse_conv_channels: B x N too large");
-  hipLaunchKernelGGL(sparse_conv_channels_kernel, dim3((unsigned)grid), dim3(64 * WAVES), 0,
-                     (hipStream_t)stream, entries, counts, row_cap, Z, B, N, R, tiles, relu, X);
-  lnz::note_kernel("sparse_conv_channels_kernel");
-  return lnz::check_launch("lnz_large_sparse_conv_channels");
+  return launch_gather<GatherBf16, true>("lnz_large_sparse_conv_channels", entries, nullptr, counts, row_cap, Z, B, N,
+                                         R, relu, X, stream);
 }
 
 extern "C" int lnz_large_sparse_conv_channels_f32(const uint32_t* entries, const float* values,
                                                   const int32_t* counts, int row_cap, const float* Zf, int B,
                                                   int N, int R, int relu, float* X, lnz_stream_t stream) {
-  LNZ_REQUIRE(entries && values && counts && Zf && X && B > 0 && N > 0, LNZ_EINVAL,
-              "lnz_large_sparse_conv_channels_f32: bad arguments");
-  LNZ_REQUIRE(R >= 2 && R <= MAXR, LNZ_ENOTSUP,
-              "lnz_large_sparse_conv_channels_f32: R=%d: 2 .. %d operators (one: lnz_large_sparse_conv_f32)", R, MAXR);
-  LNZ_REQUIRE(row_cap >= 32 && row_cap % 8 == 0, LNZ_EINVAL,
-              "lnz_large_sparse_conv_channels_f32: row_cap=%d must be a multiple of 8, at least 32", row_cap);
-  LNZ_REQUIRE((((uintptr_t)X) & 7) == 0 && (((uintptr_t)Zf) & 7) == 0, LNZ_EINVAL,
-              "lnz_large_sparse_conv_channels_f32: X / Zf must be 8-byte aligned");
-  LNZ_REQUIRE(N <= 65536 && (int64_t)N * DH * 4 <= 0x7fffffffll, LNZ_ENOTSUP,
-              "lnz_large_sparse_conv_channels_f32: N=%d too large", N);
-  const int tiles = (N + TILE_ROWS - 1) / TILE_ROWS;
-  const int64_t grid = (int64_t)8 * tiles * ((B + 7) / 8);
-  LNZ_REQUIRE(grid <= 0x7fffffffll, LNZ_ENOTSUP, "lnz_large_sparse_conv_channels_f32: B x N too large");
-  hipLaunchKernelGGL(sparse_conv_channels_f32_kernel, dim3((unsigned)grid), dim3(64 * WAVES), 0,
-                     (hipStream_t)stream, entries, values, counts, row_cap, Zf, B, N, R, tiles, relu, X);
-  lnz::note_kernel("sparse_conv_channels_f32_kernel");
-  return lnz::check_launch("lnz_large_sparse_conv_channels_f32");
+  return launch_gather<GatherF32, true>("lnz_large_sparse_conv_channels_f32", entries, values, counts, row_cap, Zf, B,
+                                        N, R, relu, X, stream);
 }

@@ -171,10 +171,7 @@ __global__ __launch_bounds__(256) void edge_rows_kernel(EdgeBatch g, int scap, c
   if (!valid) return;
   if (ce) {
     const int c = k < cv.cap ? k : cv.cap;
-    if (c + lane < ((c + 7) & ~7)) {   // (the conv walks whole groups of eight)
-      ce[c + lane] = 0u;
-      if (cvv) cvv[c + lane] = 0.f;
-    }
+    conv_pad_row(ce, cvv, c, lane);
     if (lane == 0) {
       cv.counts[rid] = c;
       if (k > cv.cap) atomicOr(cv.flags, 2);
@@ -341,10 +338,7 @@ __global__ __launch_bounds__(256) void edge_typed_rows_kernel(EdgeBatch g, int E
       }
     }
     const int k = live ? nnb + 1 : 0, c = k < cv.cap ? k : cv.cap;
-    if (c + lane < ((c + 7) & ~7)) {   // (the conv walks whole groups of eight)
-      ce[c + lane] = 0u;
-      if (cvv) cvv[c + lane] = 0.f;
-    }
+    conv_pad_row(ce, cvv, c, lane);
     if (lane == 0) {
       cv.counts[rid] = c;
       if (k > cv.cap) atomicOr(cv.flags, 2);
@@ -382,10 +376,7 @@ __global__ __launch_bounds__(256) void edge_typed_rows_kernel(EdgeBatch g, int E
       if (cvv) cvv[below] = v;
     }
     const int c = ke < cv.cap ? ke : cv.cap;
-    if (c + lane < ((c + 7) & ~7)) {
-      ce[c + lane] = 0u;
-      if (cvv) cvv[c + lane] = 0.f;
-    }
+    conv_pad_row(ce, cvv, c, lane);
     if (lane == 0) cv.counts[(int64_t)(1 + e) * rows + rid] = c;
   }
   if (__ballot(dup) != 0ull && lane == 0) atomicOr(status + b, lnz::kEdgeDuplicate);

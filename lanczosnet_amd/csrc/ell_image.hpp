@@ -3,6 +3,7 @@
 // workgroups).  One implementation, included by both.
 #pragma once
 #include "common.hpp"
+#include "conv_image.hpp"
 
 // A (16.8 MB per graph at N = 2048, re-streamed every Lanczos step) never survives in a cache
 // until its next use: non-temporal loads leave L2 / Infinity Cache to the fp64 Krylov basis.
@@ -52,12 +53,6 @@ struct ConvImageOut {
   int32_t* flags;
   int cap;
 };
-typedef __bf16 lnz_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float lnz_f32x2 __attribute__((ext_vector_type(2)));
-__device__ inline unsigned conv_entry(float v, int col) {   // (= conv_sparse.hip pack_entry: round to nearest even)
-  const lnz_bf16x2 p = __builtin_convertvector(lnz_f32x2{v, 0.0f}, lnz_bf16x2);
-  return ((unsigned)__builtin_bit_cast(unsigned short, p[0]) << 16) | (unsigned)col;
-}
 
 template <bool PAIR>
 __global__ __launch_bounds__(256) void ell_compact_rows_kernel(
@@ -81,7 +76,7 @@ __global__ __launch_bounds__(256) void ell_compact_rows_kernel(
     const bool nz = v != 0.f;
     const unsigned long long m = __ballot(nz);
     if (m == 0ull) return;
-    const int pos = k + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+    const int pos = k + lane_rank(m);
     if (nz && pos < cap) {
       vs[(int64_t)pos * 64] = v;
       cs[(int64_t)pos * 64] = (uint16_t)col;
@@ -119,10 +114,7 @@ __global__ __launch_bounds__(256) void ell_compact_rows_kernel(
   }
   if (ce) {
     const int c = k < cv.cap ? k : cv.cap;
-    if (c + lane < ((c + 7) & ~7)) {   // (the conv walks whole groups of eight)
-      ce[c + lane] = 0u;
-      if (cvv) cvv[c + lane] = 0.f;
-    }
+    conv_pad_row(ce, cvv, c, lane);
     const bool any_differ = __ballot(differ) != 0ull;
     if (lane == 0) {
       cv.counts[rid] = c;

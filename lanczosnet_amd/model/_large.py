@@ -366,41 +366,13 @@ class _LargeMixin:
         state = input_state(self, node_feat, width=(self.input_dim + 31) // 32 * 32 if exact else None,
                             as_float=True).contiguous()
         bufs = [None, None]
-        if imgs is not None:
-            dev = Lf.device
-            if not exact:
-                work = ops.large_sparse_channels_work_buffers(Cn, B, N, dev)
-            else:
-                work = (torch.empty((Cn, B, N, 128), dtype=torch.float32, device=dev),
-                        torch.zeros((planes, B, 128, 64), dtype=ops.large_plane_dtype(planes), device=dev),
-                        torch.zeros((B, 64, 128), dtype=torch.float32, device=dev))
-            for t, lay in enumerate(plan['conv'][(planes, classes)]):
-                Gt = G[t] if G is not None else None
-                if not exact:
-                    state = ops.large_sparse_conv_layer_channels(state, lay['din'], imgs, Vb, Vf, lay['Wb'], lay['Wt'],
-                                                                 Gt, lay['bias'], work, relu=True, out=bufs[t & 1])
-                else:
-                    state = ops.large_sparse_conv_layer_channels_f32(state, lay['din'], imgs, Vb, Vf, lay['Wn32s'],
-                                                                     lay['Wt'], Gt, lay['bias'], work, planes,
-                                                                     relu=True, out=bufs[t & 1])
-                bufs[t & 1] = state
-        elif not exact:
-            work = ops.large_sparse_work_buffers(B, N, Lf.device)
-            for t, lay in enumerate(plan['conv'][(1, classes)]):
-                state = ops.large_sparse_conv_layer(state, lay['din'], img, Vb, Vf, lay['Wb'], lay['Wt'],
-                                                    G[t] if G is not None else None, lay['bias'], work,
-                                                    relu=True, out=bufs[t & 1])
-                bufs[t & 1] = state
-        else:
-            dev = Lf.device
-            work = (torch.empty((B, N, 128), dtype=torch.float32, device=dev),
-                    torch.zeros((planes, B, 128, 64), dtype=ops.large_plane_dtype(planes), device=dev),
-                    torch.zeros((B, 64, 128), dtype=torch.float32, device=dev))
-            for t, lay in enumerate(plan['conv'][(planes, classes)]):
-                state = ops.large_sparse_conv_layer_f32(state, lay['din'], img, Vb, Vf, lay['Wn32'], lay['Wt'],
-                                                        G[t] if G is not None else None, lay['bias'], work,
-                                                        planes, relu=True, out=bufs[t & 1])
-                bufs[t & 1] = state
+        work = ops.large_sparse_work_buffers(B, N, Lf.device, R=None if imgs is None else Cn, planes=planes)
+        weight = 'Wb' if not exact else 'Wn32' if imgs is None else 'Wn32s'
+        for t, lay in enumerate(plan['conv'][(planes, classes)]):
+            state = ops.large_sparse_conv_layer(state, lay['din'], img, Vb, Vf, lay[weight], lay['Wt'],
+                                                G[t] if G is not None else None, lay['bias'], work,
+                                                planes, relu=True, out=bufs[t & 1])
+            bufs[t & 1] = state
         ev.synchronize()   # the image launch: long finished
         flags = int(host.item())
         st['last_flags'] = flags
@@ -455,7 +427,7 @@ class _LargeSparseFusedFunction(torch.autograd.Function):
     """Training an edge-list batch (an untyped SparseLaplacian: ONE symmetric operator as its sparse
     image) through the HIP kernels, with no dense L.
 
-    forward: spectral gains + ops.large_sparse_conv_layer_f32 per layer — the launches of
+    forward: spectral gains + the exact ops.large_sparse_conv_layer per layer — the launches of
     `_large_sparse_layers` on the same operands, so the score is the inference route's bit for bit —
     each layer into its own slice of ONE [num_layer, B, N, 128] buffer, then the readout.
     backward, last layer first: lnz_large_grad_project (dP, db, A = V^T dP), the forward's gather on dP
@@ -480,15 +452,13 @@ class _LargeSparseFusedFunction(torch.autograd.Function):
         classes = (0,) * L.channels
         plan = m._plan_large(planes, classes)
         X0 = input_state(m, node_feat, width=(m.input_dim + 31) // 32 * 32, as_float=True).contiguous()
-        work = (torch.empty((B, N, 128), dtype=torch.float32, device=dev),
-                torch.zeros((planes, B, 128, 64), dtype=ops.large_plane_dtype(planes), device=dev),
-                torch.zeros((B, 64, 128), dtype=torch.float32, device=dev))
+        work = ops.large_sparse_work_buffers(B, N, dev, planes=planes)
         Xs = torch.empty((m.num_layer, B, N, 128), dtype=torch.float32, device=dev)
         state = X0
         for t, lay in enumerate(plan['conv'][(planes, classes)]):
-            state = ops.large_sparse_conv_layer_f32(state, lay['din'], img, Vb, Vf, lay['Wn32'], lay['Wt'],
-                                                    G[t] if G is not None else None, lay['bias'], work,
-                                                    planes, relu=True, out=Xs[t])
+            state = ops.large_sparse_conv_layer(state, lay['din'], img, Vb, Vf, lay['Wn32'], lay['Wt'],
+                                                G[t] if G is not None else None, lay['bias'], work,
+                                                planes, relu=True, out=Xs[t])
         mask_u8 = mask.to(torch.uint8).contiguous()
         if m.large_head_kernel and m.output_dim <= 16:
             score = ops.large_head(state, mask_u8, *m._plan_head(cache))

@@ -1115,75 +1115,78 @@ def large_head(X, mask_u8, Whead, bhead):
 _FUSED_PROJECT_GEMM1 = os.environ.get('LNZ_FUSED_PROJECT_GEMM1', '1') != '0'
 
 
-def large_sparse_work_buffers(B, N, device):
-  """(Z, Tt, Ybuf) of large_sparse_conv_layer: Z [B,N,128] bf16, Tt [1,B,128,64] bf16 (zero: stays
-  zero without long scales), Ybuf [B,64,128] fp32 (zero; the spectral kernels keep it zero)."""
-  Z = torch.empty((B, N, 128), dtype=torch.bfloat16, device=device)
-  Tt = torch.zeros((1, B, 128, 64), dtype=torch.bfloat16, device=device)
+def large_sparse_work_buffers(B, N, device, R=None, planes=1):
+  """(Z, Tt, Ybuf) of large_sparse_conv_layer: Z [B,N,128] — [R,B,N,128] CLASS MAJOR for the R images of
+  a LargeSparseImages: one GEMM1 per channel — bf16 (planes = 1) or fp32 (the exact form), Tt
+  [planes,B,128,64] in the planes' dtype (zero: stays zero without long scales), Ybuf [B,64,128] fp32
+  (zero; the spectral kernels keep it zero)."""
+  Z = torch.empty((B, N, 128) if R is None else (R, B, N, 128),
+                  dtype=torch.bfloat16 if planes == 1 else torch.float32, device=device)
+  Tt = torch.zeros((planes, B, 128, 64), dtype=large_plane_dtype(planes), device=device)
   Ybuf = torch.zeros((B, 64, 128), dtype=torch.float32, device=device)
   return Z, Tt, Ybuf
 
 
-def large_sparse_conv_layer(X, din, img, Vb, V, Wf, Wt, G, bias, work, relu=True, out=None):
-  """One conv layer with the node-space term on the sparse image: lnz_large_gemm1_rows +
-  lnz_large_spectral + lnz_large_conv (C = 0: the lift + bias) + lnz_large_sparse_conv.  X [B,N,ldx]
-  fp32 (first `din` columns are the layer input); Vb = large_pack_vectors(V); V [B,N,K] fp32; Wf: the
-  one-channel, one-plane fragments of the summed weight blocks (large_weight_fragments); Wt / G as
-  large_conv_layer; work from large_sparse_work_buffers().  Returns X' [B,N,128]."""
+def large_sparse_conv_layer(X, din, img, Vb, V, W, Wt, G, bias, work, planes=1, relu=True, out=None):
+  """One conv layer with the node-space term on the sparse image: GEMM1 (once per operator) +
+  lnz_large_spectral + lnz_large_conv (C = 0: the lift from `planes` pieces + bias) + the gather.  X
+  [B,N,ldx] fp32 (first `din` columns are the layer input); img: a LargeSparseImage, or the
+  LargeSparseImages of R = 2 .. 8 operators (the node-space term sum_c L_c (X W_c^T)); Vb =
+  large_pack_vectors(V, planes); V [B,N,K] fp32; Wt / G as large_conv_layer; work from
+  large_sparse_work_buffers().  Returns X' [B,N,128].
+  planes = 1: bf16 values x bf16 features (lnz_large_gemm1_rows + lnz_large_sparse_conv[_channels]); W =
+  the one-plane fragments of the weight blocks (large_weight_fragments): one channel, summed — for several
+  images [1,R,4,dinp/16,64,8], the R channels' blocks, NOT summed.
+  planes = 2, 3 (the split-precision modes): the node-space term in EXACT fp32 (lnz_f32_linear +
+  lnz_large_sparse_conv[_channels]_f32) on an image with `values`; ldx a multiple of 32 (columns >= din
+  zero); W [128, ldx] fp32, the class's summed weight blocks, zero padded — for several images
+  [R*128, ldx], the channels' blocks stacked."""
   Z, Tt, Ybuf = work
-  _need_cuda(X, img.entries, Vb, Wf, bias, Z, Tt)
-  B, N = img.B, img.N
-  assert X.dtype == torch.float32 and X.is_contiguous() and X.shape[0] == B and X.shape[1] == N
-  assert Vb.shape[0] == 1 and Wf.shape[0] == 1 and Wf.shape[1] == 1
-  if out is None:
-    out = torch.empty((B, N, 128), dtype=torch.float32, device=X.device)
-  with torch.cuda.device(X.device):
-    abi = _abi()
-    if G is not None:
-      K, S = V.shape[2], G.shape[1]
-      assert V.dtype == torch.float32 and V.is_contiguous()
-      assert G.is_contiguous() and G.dtype == torch.float32 and tuple(G.shape) == (B, S, K)
-      if _FUSED_PROJECT_GEMM1:
-        abi.large_spectral_gemm1_rows(X, X.shape[2], din, V, G, Wt, Wf, B, N, K, S, Ybuf, Tt, Z)
-      else:
-        abi.large_gemm1_rows(X, X.shape[2], din, Wf, B, N, Z)
-        abi.large_spectral(X, X.shape[2], din, V, G, Wt, B, N, K, S, 1, Ybuf, Tt)
-    else:
-      abi.large_gemm1_rows(X, X.shape[2], din, Wf, B, N, Z)
-    abi.large_conv(None, Vb, None, Tt, bias, B, N, 0, 1, 0, out)
-    abi.large_sparse_conv(img.entries, img.counts, img.cap, Z, B, N, int(bool(relu)), out)
-  return out
-
-
-def large_sparse_conv_layer_f32(X, din, img, Vb, V, Wn, Wt, G, bias, work, planes, relu=True, out=None):
-  """The split-precision modes' layer with the node-space term in EXACT fp32 on the sparse image:
-  lnz_f32_linear (Zf = X Wn^T) + lnz_large_spectral + lnz_large_conv (C = 0: the lift, `planes`
-  pieces) + lnz_large_sparse_conv_f32.  X [B,N,ldx] fp32 with ldx a multiple of 32 (columns >= din
-  zero); Wn [128, ldx] fp32 (the class's summed weight blocks, zero padded); Vb =
-  large_pack_vectors(V, planes); img with `values`; work = (Zf [B,N,128] fp32, Tt [planes,B,128,64],
-  Ybuf)."""
-  Zf, Tt, Ybuf = work
-  _need_cuda(X, img.entries, img.values, Vb, Wn, bias, Zf, Tt)
-  B, N = img.B, img.N
+  multi = isinstance(img, LargeSparseImages)
+  R, B, N = (img.R if multi else 1), img.B, img.N
   ldx = X.shape[2]
+  exact = planes != 1
+  _need_cuda(X, img.entries, Vb, W, bias, Z, Tt, *([img.values] if exact else []))
   assert X.dtype == torch.float32 and X.is_contiguous() and X.shape[0] == B and X.shape[1] == N
-  assert ldx % 32 == 0 and tuple(Wn.shape) == (128, ldx) and Vb.shape[0] == planes == Tt.shape[0]
+  if exact:
+    assert ldx % 32 == 0 and tuple(W.shape) == (R * 128, ldx) and Vb.shape[0] == planes == Tt.shape[0]
+  else:
+    assert Vb.shape[0] == 1 and W.shape[0] == 1 and W.shape[1] == R
+  if multi:
+    assert tuple(Z.shape) == (R, B, N, 128) and Z.is_contiguous() and (exact or W.is_contiguous())
   if out is None:
     out = torch.empty((B, N, 128), dtype=torch.float32, device=X.device)
-  f32_linear(X.view(B * N, ldx), Wn, out=Zf.view(B * N, 128))
+  if G is not None:
+    K, S = V.shape[2], G.shape[1]
+    assert V.dtype == torch.float32 and V.is_contiguous()
+    assert G.is_contiguous() and G.dtype == torch.float32 and tuple(G.shape) == (B, S, K)
+  Zc = Z if multi else Z[None]   # (one block per operator)
+  relu = int(bool(relu))
   with torch.cuda.device(X.device):
     abi = _abi()
-    if G is not None:
-      K, S = V.shape[2], G.shape[1]
-      assert V.dtype == torch.float32 and V.is_contiguous()
-      assert G.is_contiguous() and G.dtype == torch.float32 and tuple(G.shape) == (B, S, K)
-      abi.large_spectral(X, ldx, din, V, G, Wt, B, N, K, S, planes, Ybuf, Tt)
+    if G is not None and _FUSED_PROJECT_GEMM1 and not exact and not multi:
+      abi.large_spectral_gemm1_rows(X, ldx, din, V, G, Wt, W, B, N, K, S, Ybuf, Tt, Z)
+    else:
+      for c in range(R):
+        if exact:
+          f32_linear(X.view(B * N, ldx), W[128 * c:128 * (c + 1)], out=Zc[c].view(B * N, 128))
+        else:
+          abi.large_gemm1_rows(X, ldx, din, W[:, c], B, N, Zc[c])
+      if G is not None:
+        abi.large_spectral(X, ldx, din, V, G, Wt, B, N, K, S, planes, Ybuf, Tt)
     abi.large_conv(None, Vb, None, Tt, bias, B, N, 0, planes, 0, out)
-    abi.large_sparse_conv_f32(img.entries, img.values, img.counts, img.cap, Zf, B, N, int(bool(relu)), out)
+    if multi and exact:
+      abi.large_sparse_conv_channels_f32(img.entries, img.values, img.counts, img.cap, Z, B, N, R, relu, out)
+    elif multi:
+      abi.large_sparse_conv_channels(img.entries, img.counts, img.cap, Z, B, N, R, relu, out)
+    elif exact:
+      abi.large_sparse_conv_f32(img.entries, img.values, img.counts, img.cap, Z, B, N, relu, out)
+    else:
+      abi.large_sparse_conv(img.entries, img.counts, img.cap, Z, B, N, relu, out)
   return out
 
 
-# ---- the backward of large_sparse_conv_layer_f32 for ONE symmetric operator (csrc/conv_sparse_grad.hip) --
+# ---- the backward of the exact large_sparse_conv_layer for ONE symmetric operator (csrc/conv_sparse_grad.hip) --
 LARGE_GRAD_CHUNK = 256   # rows of a graph per workgroup of lnz_large_grad_project
 
 
@@ -1245,70 +1248,6 @@ def large_grad_input(dZ, Wn, V, dY, d, out):
   with torch.cuda.device(dZ.device):
     _abi().large_grad_input(dZ, Wn, V if K else None, dY, B, N, K, d, out)
   note_autograd_kernel()
-  return out
-
-
-def large_sparse_channels_work_buffers(R, B, N, device):
-  """(Z, Tt, Ybuf) of large_sparse_conv_layer_channels: Z [R,B,N,128] bf16 (CLASS MAJOR: one
-  lnz_large_gemm1_rows per channel), Tt [1,B,128,64] bf16 and Ybuf [B,64,128] fp32, both zero."""
-  Z = torch.empty((R, B, N, 128), dtype=torch.bfloat16, device=device)
-  Tt = torch.zeros((1, B, 128, 64), dtype=torch.bfloat16, device=device)
-  Ybuf = torch.zeros((B, 64, 128), dtype=torch.float32, device=device)
-  return Z, Tt, Ybuf
-
-
-def large_sparse_conv_layer_channels(X, din, imgs, Vb, V, Wf, Wt, G, bias, work, relu=True, out=None):
-  """large_sparse_conv_layer for R = 2 .. 8 operators: the node-space term sum_c L_c (X W_c^T) on the
-  LargeSparseImages `imgs` (lnz_large_sparse_conv_channels).  Wf [1,R,4,dinp/16,64,8]: the one-plane
-  fragments of the R channels' weight blocks, NOT summed (large_weight_fragments); work from
-  large_sparse_channels_work_buffers().  The spectral block and the lift are the one-operator layer's."""
-  Z, Tt, Ybuf = work
-  _need_cuda(X, imgs.entries, Vb, Wf, bias, Z, Tt)
-  R, B, N = imgs.R, imgs.B, imgs.N
-  assert X.dtype == torch.float32 and X.is_contiguous() and X.shape[0] == B and X.shape[1] == N
-  assert Vb.shape[0] == 1 and Wf.shape[0] == 1 and Wf.shape[1] == R and Wf.is_contiguous()
-  assert tuple(Z.shape) == (R, B, N, 128) and Z.is_contiguous()
-  if out is None:
-    out = torch.empty((B, N, 128), dtype=torch.float32, device=X.device)
-  with torch.cuda.device(X.device):
-    abi = _abi()
-    for c in range(R):
-      abi.large_gemm1_rows(X, X.shape[2], din, Wf[:, c], B, N, Z[c])
-    if G is not None:
-      K, S = V.shape[2], G.shape[1]
-      assert V.dtype == torch.float32 and V.is_contiguous()
-      assert G.is_contiguous() and G.dtype == torch.float32 and tuple(G.shape) == (B, S, K)
-      abi.large_spectral(X, X.shape[2], din, V, G, Wt, B, N, K, S, 1, Ybuf, Tt)
-    abi.large_conv(None, Vb, None, Tt, bias, B, N, 0, 1, 0, out)
-    abi.large_sparse_conv_channels(imgs.entries, imgs.counts, imgs.cap, Z, B, N, R, int(bool(relu)), out)
-  return out
-
-
-def large_sparse_conv_layer_channels_f32(X, din, imgs, Vb, V, Wn, Wt, G, bias, work, planes, relu=True, out=None):
-  """large_sparse_conv_layer_f32 for R = 2 .. 8 operators (lnz_large_sparse_conv_channels_f32): Wn
-  [R*128, ldx] fp32, the channels' weight blocks stacked (zero padded columns); imgs with `values`;
-  work = (Zf [R,B,N,128] fp32 CLASS MAJOR — lnz_f32_linear once per channel —, Tt [planes,B,128,64], Ybuf)."""
-  Zf, Tt, Ybuf = work
-  _need_cuda(X, imgs.entries, imgs.values, Vb, Wn, bias, Zf, Tt)
-  R, B, N = imgs.R, imgs.B, imgs.N
-  ldx = X.shape[2]
-  assert X.dtype == torch.float32 and X.is_contiguous() and X.shape[0] == B and X.shape[1] == N
-  assert ldx % 32 == 0 and tuple(Wn.shape) == (R * 128, ldx) and Vb.shape[0] == planes == Tt.shape[0]
-  assert tuple(Zf.shape) == (R, B, N, 128) and Zf.is_contiguous()
-  if out is None:
-    out = torch.empty((B, N, 128), dtype=torch.float32, device=X.device)
-  for c in range(R):
-    f32_linear(X.view(B * N, ldx), Wn[128 * c:128 * (c + 1)], out=Zf[c].view(B * N, 128))
-  with torch.cuda.device(X.device):
-    abi = _abi()
-    if G is not None:
-      K, S = V.shape[2], G.shape[1]
-      assert V.dtype == torch.float32 and V.is_contiguous()
-      assert G.is_contiguous() and G.dtype == torch.float32 and tuple(G.shape) == (B, S, K)
-      abi.large_spectral(X, ldx, din, V, G, Wt, B, N, K, S, planes, Ybuf, Tt)
-    abi.large_conv(None, Vb, None, Tt, bias, B, N, 0, planes, 0, out)
-    abi.large_sparse_conv_channels_f32(imgs.entries, imgs.values, imgs.counts, imgs.cap, Zf, B, N, R,
-                                       int(bool(relu)), out)
   return out
 
 

@@ -239,6 +239,30 @@ def gather_case(cap=GATHER_CAP, exact=True):
   return dict(L=L.astype(np.float32), Z=Z.astype(np.float32), X0=X0.astype(np.float32), plan=plan)
 
 
+@functools.lru_cache(maxsize=None)
+def gather_channels_case(cap, R):
+  """R operators from gather_case(cap, exact=False): channel c of L [B,N,N,R] is the case's L with the
+  graphs rotated by c, L[(b + c) % B] — every graph walks its waves in another order, so the R rows of a
+  (row, channel) group have other lengths —; Z [R,B,N,128]: R different blocks (the case's Z, its nodes
+  rotated by 3 c, the sign flipped for odd c: still bf16 numbers); plan [R,B,N]; X0 as the case's."""
+  case = gather_case(cap, False)
+  B = GATHER_B
+  assert 2 <= R <= 8 and R < B
+  rot = [[(b + c) % B for b in range(B)] for c in range(R)]
+  L = np.stack([case['L'][rot[c]] for c in range(R)], axis=3)
+  plan = np.stack([case['plan'][rot[c]] for c in range(R)], axis=0)
+  Z = np.stack([np.roll(case['Z'], 3 * c, axis=1) * (-1.0 if c & 1 else 1.0) for c in range(R)], axis=0)
+  # the preconditions: no row beyond cap (the images raise no flag), the plan is the rotated plan, no two
+  # channels of a graph share their lengths or their features
+  assert plan.max() == cap and np.array_equal((L != 0).sum(axis=2).transpose(2, 0, 1), plan)
+  for c in range(1, R):
+    for d in range(c):
+      assert not np.array_equal(Z[c], Z[d])
+      assert all(not np.array_equal(plan[c, b], plan[d, b]) for b in range(B))
+  assert is_bf16(Z)
+  return dict(L=np.ascontiguousarray(L, np.float32), Z=np.ascontiguousarray(Z, np.float32), X0=case['X0'], plan=plan)
+
+
 def gather_reference(L64, Z64, X064, relu):
   """(float64 result, per-element bound 2 (n + 1) 2^-24 (|x0| + sum |v z|)): a chain of n fp32 FMAs,
   the standard running-error bound, doubled"""

@@ -282,16 +282,19 @@ def _image(case, cap, channels=2):
   return img
 
 
-def _gather(img, Z, X0, relu, f32):
-  """the ABI entry on given Z (bf16) / Zf (fp32) and a non-zero X (accumulated in place)"""
+def _gather_into(out, img, Z, relu, f32):
   B, N = img.B, img.N
-  out = _dev(X0).clone()
   abi = ops._abi()
   if f32:
     abi.large_sparse_conv_f32(img.entries, img.values, img.counts, img.cap, Z, B, N, int(relu), out)
   else:
     abi.large_sparse_conv(img.entries, img.counts, img.cap, Z, B, N, int(relu), out)
   return out
+
+
+def _gather(img, Z, X0, relu, f32):
+  """the ABI entry on given Z (bf16) / Zf (fp32) and a non-zero X (accumulated in place)"""
+  return _gather_into(_dev(X0).clone(), img, Z, relu, f32)
 
 
 def _z_operand(Z, f32):
@@ -343,7 +346,8 @@ def test_image_row_of_exactly_cap_entries_is_kept_and_cap_plus_one_is_flagged():
 @pytest.mark.parametrize('f32', [False, True], ids=['sparse_conv', 'sparse_conv_f32'])
 def test_gathers_keep_graphs_apart(f32):
   """One graph's Z rows non-finite: every other graph's output is bit for bit what it is without
-  (the per-graph buffer bounds and the graph map of the second dealing round)."""
+  (the per-graph buffer bounds and the graph map of the second dealing round) — one operator, then
+  R = 3 with ONE channel's block of that graph non-finite."""
   case = fx.gather_case(128, False)
   img = _image(case, 128)
   base = _gather(img, _z_operand(case['Z'], f32), case['X0'], 0, f32)   # (no ReLU: it would clear a NaN)
@@ -355,6 +359,68 @@ def test_gathers_keep_graphs_apart(f32):
   assert torch.equal(got[others], base[others]) and torch.isfinite(got[others]).all()
   empty = torch.from_numpy(case['plan'][1] == 0).to(DEV)
   assert torch.equal(got[1][empty], base[1][empty]) and not torch.isfinite(got[1][~empty]).any()
+  # R = 3 operators: the Z block of ONE graph in ONE channel (the per-pair buffer and its bounds)
+  R, g, ch = 3, 1, 2
+  case = fx.gather_channels_case(128, R)
+  imgs = _images(case, 128)
+  base = _gather_channels(imgs, _z_operand(case['Z'], f32), case['X0'], 0, f32)
+  Zp = case['Z'].copy()
+  Zp[ch, g] = np.nan
+  Zp[ch, g, ::2] = np.inf
+  got = _gather_channels(imgs, _z_operand(Zp, f32), case['X0'], 0, f32)
+  assert torch.equal(got[others], base[others]) and torch.isfinite(got[others]).all()
+  empty = torch.from_numpy(case['plan'][ch, g] == 0).to(DEV)
+  assert torch.equal(got[g][empty], base[g][empty]) and not torch.isfinite(got[g][~empty]).any()
+
+
+def _images(case, cap):
+  imgs = ops.large_sparse_image_channels(_dev(case['L']), cap, values=True)
+  assert int(imgs.flags.item()) == 0   # (the inputs: no row of the plan beyond the capacity, test_large_edges_cpu.py)
+  assert np.array_equal(imgs.counts.cpu().numpy(), case['plan'])
+  return imgs
+
+
+def _gather_channels(imgs, Z, X0, relu, f32):
+  """the channel ABI entry on class-major Z [R,B,N,128] and a non-zero X (accumulated in place)"""
+  R, B, N = imgs.R, imgs.B, imgs.N
+  out = _dev(X0).clone()
+  abi = ops._abi()
+  if f32:
+    abi.large_sparse_conv_channels_f32(imgs.entries, imgs.values, imgs.counts, imgs.cap, Z, B, N, R, int(relu), out)
+  else:
+    abi.large_sparse_conv_channels(imgs.entries, imgs.counts, imgs.cap, Z, B, N, R, int(relu), out)
+  return out
+
+
+@pytest.mark.parametrize('f32', [False, True], ids=['sparse_conv_channels', 'sparse_conv_channels_f32'])
+@pytest.mark.parametrize('R', [2, 3, 8])
+@pytest.mark.parametrize('cap', [128, None], ids=['cap128', 'default_cap32'])
+def test_channel_gathers_equal_chained_one_operator_gathers(cap, R, f32):
+  """The gather over R operators is R one-operator gathers chained through X: the same fp32 FMA
+  sequence (channels ascending, entries in entry order, one accumulator per row) with a store and a
+  reload between channels, the activation on the last one — EQUAL bits, no tolerance.  The gather
+  case's B = 10, N = 133 with channel c = the graphs rotated by c (other row lengths in every channel
+  of a row), R different Z blocks; R = 3: lane % R with no power of two, R = 8: 64 (row, channel)
+  pairs.  The channel images: no flag, the rotated plan's counts, and on the live entries the bits of
+  the one-operator image of each channel alone."""
+  rcap = ops.large_sparse_row_cap(fx.GATHER_N) if cap is None else cap
+  case = fx.gather_channels_case(rcap, R)
+  imgs = _images(case, cap)
+  L = _dev(case['L'])
+  for c in range(R):
+    one = ops.large_sparse_image(L[..., c:c + 1], cap, values=True)
+    assert int(one.flags.item()) == 0 and torch.equal(one.counts, imgs.counts[c])
+    keep = torch.arange(rcap, device=DEV)[None, None, :] < ((one.counts + 7) // 8 * 8)[:, :, None]
+    assert torch.equal(imgs.entries[c][keep], one.entries[keep])
+    assert torch.equal(imgs.values[c][keep], one.values[keep])
+  Z = _z_operand(case['Z'], f32)
+  for relu in (0, 1):
+    got = _gather_channels(imgs, Z, case['X0'], relu, f32)
+    assert ops.last_kernel() == ('sparse_conv_channels_f32_kernel' if f32 else 'sparse_conv_channels_kernel')
+    chained = _dev(case['X0']).clone()
+    for c in range(R):
+      _gather_into(chained, imgs.channel(c), Z[c], relu if c == R - 1 else 0, f32)
+    assert torch.equal(got, chained) and not torch.equal(got, _dev(case['X0']))
 
 
 @pytest.mark.parametrize('f32', [False, True], ids=['sparse_conv', 'sparse_conv_f32'])

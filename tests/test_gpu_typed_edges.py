@@ -265,19 +265,19 @@ def test_channels_layer_matches_the_streamed_layer_and_fp64(name, K, din, S):
     # test_sparse_layer_matches_the_streamed_layer_and_fp64)
     dwork = ops.large_work_buffers(Lb)
     dense = ops.large_conv_layer(Xd, din, Lb, Vb, Vd, Wf, Wt, Gd, bd, dwork, relu=relu)
-    swork = ops.large_sparse_channels_work_buffers(R, B, N, DEV)
+    swork = ops.large_sparse_work_buffers(B, N, DEV, R=R)
     swork[1].copy_(dwork[1])
-    sparse = ops.large_sparse_conv_layer_channels(Xd, din, imgs, Vb1, Vd, Wf, None, None, bd, swork, relu=relu)
+    sparse = ops.large_sparse_conv_layer(Xd, din, imgs, Vb1, Vd, Wf, None, None, bd, swork, relu=relu)
     assert ops.last_kernel() == 'sparse_conv_channels_kernel'
     err = _rel(sparse, dense)
     print('%s bf16 relu %d: against the streamed layer %.2e' % (name, relu, err))
     assert err <= 1e-5
   # without long scales, against the launch's own Z in fp64
   A = L.cpu().numpy()
-  work0 = ops.large_sparse_channels_work_buffers(R, B, N, DEV)
-  sparse0 = ops.large_sparse_conv_layer_channels(Xd, din, imgs, Vb1, Vd, Wf, None, None, bd, work0)
-  again0 = ops.large_sparse_conv_layer_channels(Xd, din, imgs, Vb1, Vd, Wf, None, None, bd,
-                                                ops.large_sparse_channels_work_buffers(R, B, N, DEV))
+  work0 = ops.large_sparse_work_buffers(B, N, DEV, R=R)
+  sparse0 = ops.large_sparse_conv_layer(Xd, din, imgs, Vb1, Vd, Wf, None, None, bd, work0)
+  again0 = ops.large_sparse_conv_layer(Xd, din, imgs, Vb1, Vd, Wf, None, None, bd,
+                                       ops.large_sparse_work_buffers(B, N, DEV, R=R))
   assert torch.equal(sparse0, again0)
   Zdev = work0[0].float().cpu().numpy().astype(np.float64)
   ref0 = sum(np.einsum('bnm,bmo->bno', _bf16(A[..., c]).astype(np.float64), Zdev[c]) for c in range(R)) + bias
@@ -292,12 +292,10 @@ def test_channels_layer_matches_the_streamed_layer_and_fp64(name, K, din, S):
   Vb3 = ops.large_pack_vectors(Vd, 3)
 
   def work32():
-    return (torch.empty((R, B, N, 128), dtype=torch.float32, device=DEV),
-            torch.zeros((3, B, 128, 64), dtype=ops.large_plane_dtype(3), device=DEV),
-            torch.zeros((B, 64, 128), dtype=torch.float32, device=DEV))
-  s32 = ops.large_sparse_conv_layer_channels_f32(X32, din, imgs, Vb3, Vd, Wn32, None, None, bd, work32(), 3)
+    return ops.large_sparse_work_buffers(B, N, DEV, R=R, planes=3)
+  s32 = ops.large_sparse_conv_layer(X32, din, imgs, Vb3, Vd, Wn32, None, None, bd, work32(), 3)
   assert ops.last_kernel() == 'sparse_conv_channels_f32_kernel'
-  t32 = ops.large_sparse_conv_layer_channels_f32(X32, din, imgs, Vb3, Vd, Wn32, None, None, bd, work32(), 3)
+  t32 = ops.large_sparse_conv_layer(X32, din, imgs, Vb3, Vd, Wn32, None, None, bd, work32(), 3)
   assert torch.equal(s32, t32)
   Z64 = np.einsum('bnd,ocd->cbno', X.astype(np.float64), W[:, S:].astype(np.float64))
   ref32 = sum(np.einsum('bnm,bmo->bno', A[..., c].astype(np.float64), Z64[c]) for c in range(R)) + bias

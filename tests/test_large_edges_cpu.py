@@ -38,6 +38,17 @@ def test_gather_plan_holds_every_row_length_in_every_graph():
   assert fx.GATHER_N % 32 == 5   # the last tile: one wave with five rows
 
 
+def test_channel_gather_case_rotates_the_plan_and_stays_within_the_row_capacity():
+  """(the case asserts its own preconditions) no row of any channel beyond cap: the images of
+  test_channel_gathers_equal_chained_one_operator_gathers raise no flag because of their INPUTS"""
+  for cap in (128, 32):
+    for R in (2, 3, 8):
+      case = fx.gather_channels_case(cap, R)
+      assert case['L'].shape == (fx.GATHER_B, fx.GATHER_N, fx.GATHER_N, R) and case['plan'].max() == cap
+      assert np.array_equal(case['plan'][1, 0], fx.gather_row_plan(cap)[1])
+  assert fx.GATHER_B > 8   # the second dealing round
+
+
 def test_bf16_round_is_round_to_nearest_even():
   x = np.array([1.0, 1.00390625, 1.01171875, 257.0, 259.0, -3.0, 0.0], np.float32)   # ties at 1 + 2^-8 k
   np.testing.assert_array_equal(fx.bf16_round(x), [1.0, 1.0, 1.015625, 256.0, 260.0, -3.0, 0.0])

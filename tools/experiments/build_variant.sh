@@ -4,10 +4,11 @@
 # extension binds to it as well).
 #   tools/experiments/build_variant.sh conv_strip.hip phases:"-DLNZ_STRIP_PHASES" ...
 #   -> tools/experiments/_variants/liblnz_<source stem>_<name>.so
+# REPLACES=<stem>: the source stands in for csrc/<stem>.hip under another file name (an earlier commit's copy).
 set -e
 cd "$(dirname "$0")/../../lanczosnet_amd/csrc"
 SRC=$1; shift
-STEM=${SRC%.hip}
+STEM=${REPLACES:-${SRC%.hip}}
 OUT=../../tools/experiments/_variants
 mkdir -p $OUT
 OBJS=$(ls *.o | grep -v "^$STEM.o$")

@@ -341,9 +341,12 @@ extern "C" int lnz_ada_t_powers(const float* T, int B, int K, const int32_t* dis
   for (int i = 0; i < 16; ++i) {
     d.v[i] = i < S ? dist_host[i] : -1;
     if (i < S && dist_host[i] > pmax) pmax = dist_host[i];
+    // every exponent, not only the largest: a slot whose exponent the loop never reaches stays unwritten
+    LNZ_REQUIRE(i >= S || (dist_host[i] >= 1 && dist_host[i] <= 4096), LNZ_EINVAL,
+                "lnz_ada_t_powers: bad exponents (dist[%d]=%d, 1 .. 4096)", i, i < S ? dist_host[i] : 0);
   }
-  LNZ_REQUIRE(pmax >= 1 && pmax <= 4096, LNZ_EINVAL, "lnz_ada_t_powers: bad exponents");
-  size_t lds = (size_t)3 * K * K * sizeof(double);
+  size_t lds = (size_t)3 * K * K * sizeof(double);   // 96 KiB at K = 64: beyond 64 KiB from K = 53
+  LNZ_DYNAMIC_LDS(ada_t_powers_kernel, lds, "ada_lanczos.hip");
   hipLaunchKernelGGL(ada_t_powers_kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, T, K, d, S,
                      pmax, Tcat);
   return lnz::check_launch("lnz_ada_t_powers");

@@ -483,13 +483,17 @@ __global__ __launch_bounds__(256) void ada_t_powers_f64_backward_kernel(
 
 }  // namespace
 
+// the largest exponent, or 0 when ANY exponent of the list lies outside 1 .. 4096 (a slot whose
+// exponent the kernels' loop never reaches would stay unwritten)
 static int pow_args(const int32_t* dist_host, int S, PowArr64* d) {
   int pmax = 0;
+  bool ok = true;
   for (int i = 0; i < 16; ++i) {
     d->v[i] = i < S ? dist_host[i] : -1;
     if (i < S && dist_host[i] > pmax) pmax = dist_host[i];
+    if (i < S && (dist_host[i] < 1 || dist_host[i] > 4096)) ok = false;
   }
-  return pmax;
+  return ok ? pmax : 0;
 }
 
 extern "C" int64_t lnz_ada_laplacian_f64_state_doubles(int B, int N) {
@@ -530,7 +534,7 @@ extern "C" int lnz_ada_t_powers_f64(const double* T, int B, int K, const int32_t
   LNZ_REQUIRE(S <= 16 && K <= 64, LNZ_ENOTSUP, "lnz_ada_t_powers_f64: S=%d K=%d out of range", S, K);
   PowArr64 d;
   const int pmax = pow_args(dist_host, S, &d);
-  LNZ_REQUIRE(pmax >= 1 && pmax <= 4096, LNZ_EINVAL, "lnz_ada_t_powers_f64: bad exponents");
+  LNZ_REQUIRE(pmax >= 1, LNZ_EINVAL, "lnz_ada_t_powers_f64: bad exponents (every one of 1 .. 4096)");
   const size_t lds = (size_t)3 * K * K * sizeof(double);
   LNZ_DYNAMIC_LDS(ada_t_powers_f64_forward_kernel, lds, "ada_lanczos_grad.hip");
   hipLaunchKernelGGL(ada_t_powers_f64_forward_kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, T, K, d,
@@ -546,7 +550,7 @@ extern "C" int lnz_ada_t_powers_f64_backward(const double* T, int B, int K, cons
   LNZ_REQUIRE(S <= 16 && K <= 64, LNZ_ENOTSUP, "lnz_ada_t_powers_f64_backward: S=%d K=%d out of range", S, K);
   PowArr64 d;
   const int pmax = pow_args(dist_host, S, &d);
-  LNZ_REQUIRE(pmax >= 1 && pmax <= 4096, LNZ_EINVAL, "lnz_ada_t_powers_f64_backward: bad exponents");
+  LNZ_REQUIRE(pmax >= 1, LNZ_EINVAL, "lnz_ada_t_powers_f64_backward: bad exponents (every one of 1 .. 4096)");
   const size_t lds = (size_t)5 * K * K * sizeof(double);
   LNZ_DYNAMIC_LDS(ada_t_powers_f64_backward_kernel, lds, "ada_lanczos_grad.hip");
   hipLaunchKernelGGL(ada_t_powers_f64_backward_kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, T, K, d,

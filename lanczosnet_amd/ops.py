@@ -2052,16 +2052,26 @@ def ada_graph_laplacian_f64_backward(saved, dLe):
   return dX
 
 
+def _power_list(dist, who):
+  """The exponents as ints; every one of 1 .. 4096 (the launchers refuse the same list: this keeps
+  a bad exponent from sizing a buffer first)."""
+  darr = [int(x) for x in dist]
+  bad = [x for x in darr if x < 1 or x > 4096]
+  if bad or not darr:
+    raise _lib.LnzError(_lib.LNZ_EINVAL, '%s: bad exponents %r (every one of 1 .. 4096)' % (who, darr))
+  return darr
+
+
 def ada_t_powers_f64(T, dist):
   """lnz_ada_t_powers_f64: T [B,K,K] fp64 -> (Tcat [B, K, S*K] fp32, saved powers)."""
   _need_cuda(T)
   assert T.dtype == torch.float64 and T.is_contiguous()
   B, K, _ = T.shape
   S = len(dist)
-  pmax = max(int(x) for x in dist)
+  darr = _power_list(dist, 'ada_t_powers_f64')
+  pmax = max(darr)
   out = torch.empty((B, K, S * K), dtype=torch.float32, device=T.device)
   P = torch.empty((B, pmax, K, K), dtype=torch.float64, device=T.device)
-  darr = [int(x) for x in dist]
   with torch.cuda.device(T.device):
     _abi().ada_t_powers_f64(T, B, K, darr, S, out, P)
   return out, (T, P, tuple(int(x) for x in dist))

@@ -64,6 +64,21 @@ def test_argument_validation_without_gpu():
   assert lib.lnz_lanczosnet_forward(C.byref(a), null) == _lib.LNZ_ENOTSUP
   with pytest.raises(_lib.NotSupported):
     _lib.check(_lib.LNZ_ENOTSUP)
+  # the three T-powers launchers check EVERY exponent (1 .. 4096), not only the largest: a slot
+  # whose exponent the kernel's loop never reaches would be returned unwritten
+  for dist in ([5, 0, 7], [-1, 3], [0], [1, 4097], [4097]):
+    d = (C.c_int32 * len(dist))(*dist)
+    dp = C.cast(d, C.c_void_p)
+    assert lib.lnz_ada_t_powers(one, 1, 4, d, len(dist), one, null) == _lib.LNZ_EINVAL, dist
+    assert b'bad exponents' in lib.lnz_last_error()
+    assert lib.lnz_ada_t_powers_f64(one, 1, 4, dp, len(dist), one, one, null) == _lib.LNZ_EINVAL, dist
+    assert b'bad exponents' in lib.lnz_last_error()
+    assert lib.lnz_ada_t_powers_f64_backward(one, 1, 4, dp, len(dist), one, one, one, null) == \
+        _lib.LNZ_EINVAL, dist
+    assert b'bad exponents' in lib.lnz_last_error()
+  d17 = (C.c_int32 * 17)(*range(1, 18))
+  assert lib.lnz_ada_t_powers(one, 1, 4, d17, 17, one, null) == _lib.LNZ_ENOTSUP
+  assert lib.lnz_ada_t_powers(one, 1, 65, d17, 16, one, null) == _lib.LNZ_ENOTSUP
   assert lib.lnz_packed_rows_k8_size(128, 1920) == 128 * 1920
   assert lib.lnz_packed_rows_k8_size(17, 20) == 32 * 24
 

@@ -34,6 +34,8 @@ extern "C" {
  *    lnz_laplacian_l4_edges_image, each with a _workspace_bytes sibling: no N x N array);
  *    + the backward of the one-operator sparse large-graph layer (lnz_large_grad_project,
  *    lnz_large_grad_spectral, lnz_large_grad_input: additive, the version stays);
+ *    + the same backward over R = 2 .. 8 operator channels of a typed batch (lnz_large_sparse_conv_split_f32,
+ *    lnz_large_grad_input_channels: additive, the version stays);
  * 6: lnz_forward_args lost Wp16 / w16_off / Wp16_head / Lp16 (gemm_mode 1 is now the split precision
  *    inside the strip kernel: lnz_pack_rows_k8_split; lnz_pack_rows_f16x2 and
  *    lnz_pack_laplacian_f16x2 are gone) and gained dbias_part_cap; + lnz_midgraph_forward,
@@ -310,6 +312,25 @@ int lnz_large_sparse_conv_channels(const uint32_t* entries, const int32_t* count
 int lnz_large_sparse_conv_channels_f32(const uint32_t* entries, const float* values,
                                        const int32_t* counts, int row_cap, const float* Zf, int B, int N,
                                        int R, int relu, float* X, lnz_stream_t stream);
+/* The backward of that exact-fp32 layer over the R = E + 1 channels, every L_c symmetric (the L4 of an undirected
+ * graph with its own degrees):  X' = relu( sum_c L_c Z_c + V T + b ),  Z_c = X Wn_c^T.  With dP of
+ * lnz_large_grad_project:  dZ_c = L_c dP,  dWn_c = dZ_c^T X,  dX = sum_c dZ_c Wn_c + V dY; db, A, dG, Q, dY as
+ * for one operator (lnz_large_grad_project, lnz_large_grad_spectral).
+ *   lnz_large_sparse_conv_split_f32   dZ [R][B][N][128] fp32: dZ[c] = L_c P for ONE source P [B][N][128]
+ *                            fp32 and the R images (channel major, with values).  The same gather kernel in
+ *                            the same (row, channel) order; dZ is overwritten, never read, no activation:
+ *                            channel c's block is bit for bit lnz_large_sparse_conv_f32 of image c with
+ *                            relu = 0 onto zeros.  R = 2 .. 8; P, dZ 8-byte aligned, dZ not P.
+ *   lnz_large_grad_input_channels     dX [B,N,128] = sum_c dZ_c Wn_c + V dY, one fp32 MFMA GEMM over the depth
+ *                            R 128 + K in ascending order: dZ [R][B][N][128], Wn [R][128][128] (Wn[c][o][i],
+ *                            columns >= d zero), V [B,N,K], dY [B,K,128] (K = 0: V, dY may be NULL); columns
+ *                            >= d of dX are written zero.  1 <= R <= 8 (R = 1: the bits of
+ *                            lnz_large_grad_input), K <= 64, d <= 128.  dX must not alias dZ. */
+int lnz_large_sparse_conv_split_f32(const uint32_t* entries, const float* values, const int32_t* counts,
+                                    int row_cap, const float* P, int B, int N, int R, float* dZ,
+                                    lnz_stream_t stream);
+int lnz_large_grad_input_channels(const float* dZ, const float* Wn, const float* V, const float* dY, int B,
+                                  int N, int K, int R, int d, float* dX, lnz_stream_t stream);
 
 /* ---- R6 standalone: batched symmetric tridiagonal eigensolver --------------------------------
  * The step the reference leaves to LAPACK (inside np.linalg.eigh, utils/data_helper.py:201) /

@@ -312,7 +312,11 @@ struct GatherF32 {
 // counts [R][B][N], Z CLASS MAJOR [R][B][N][128] (one GEMM1 per channel): a graph's R feature blocks are R
 // buffers of N rows, the descriptor rebuilt per pair from scalars.  MULTI = false: R = 1 at compile time
 // — the pairs are the rows, the channel and the per-pair descriptor fold away.
-template <class Elem, bool MULTI>
+// SPLIT (the backward's dZ_c = L_c dP, csrc/conv_sparse_grad.hip): the same pairs over ONE source — every
+// channel reads the graph's Z [B][N][128] — and one result per pair: the accumulator starts at zero and is
+// stored into channel c's block of X [R][B][N][128] behind the pair's own entries (X is written, never
+// read; no activation).  Channel c's block is, bit for bit, the R = 1 gather of image c onto zeros.
+template <class Elem, bool MULTI, bool SPLIT = false>
 __global__ __launch_bounds__(64 * WAVES) void sparse_gather_kernel(
     const unsigned* __restrict__ ent, const float* __restrict__ vals, const int32_t* __restrict__ counts,
     int cap, const typename Elem::T* __restrict__ Z, int B, int N, int operators, int tiles, int relu,
@@ -342,22 +346,23 @@ __global__ __launch_bounds__(64 * WAVES) void sparse_gather_kernel(
   for (int q = 0; q < nq; ++q) {
     const int cnt8 = cnt8n;
     Entry e = en;
-    float* xr = X + (row0 + rr) * DH + 2 * lane;
-    if (c == 0) acc = *reinterpret_cast<const f32x2*>(xr);
+    float* xr = X + ((SPLIT ? (int64_t)c * rows : 0) + row0 + rr) * DH + 2 * lane;
+    if constexpr (SPLIT) acc = f32x2{0.0f, 0.0f};
+    else if (c == 0) acc = *reinterpret_cast<const f32x2*>(xr);
     const int cn = c + 1 < R ? c + 1 : 0, rn = c + 1 < R ? rr : rr + 1;
     if (q + 1 < nq) {   // (uniform) the next pair's entries
       cnt8n = Elem::round_up(__builtin_amdgcn_readlane(cv, q + 1));
       en = entries(rn, cn, 0, cnt8n);
     }
     const __amdgpu_buffer_rsrc_t z_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<T*>(Zb + (int64_t)c * rows * DH), 0, (unsigned)N * DH * (unsigned)sizeof(T), 0x00020000);
+        const_cast<T*>(Zb + (SPLIT ? 0 : (int64_t)c * rows * DH)), 0, (unsigned)N * DH * (unsigned)sizeof(T), 0x00020000);
     for (int k0 = 0; k0 < cnt8; k0 += 64) {
       if (k0 > 0) e = entries(rr, c, k0, cnt8);   // (rows of more than 64 entries)
       const int m = min(64, cnt8 - k0);
       for (int k = 0; k < m; k += Elem::TURN) Elem::turns(z_rsrc, zoff, e, k, m - k, acc);
     }
-    if (cn == 0) {   // the row's last channel
-      if (relu) {
+    if (SPLIT || cn == 0) {   // the row's last channel (SPLIT: every pair)
+      if (!SPLIT && relu) {
         acc[0] = acc[0] > 0.0f ? acc[0] : 0.0f;
         acc[1] = acc[1] > 0.0f ? acc[1] : 0.0f;
       }
@@ -368,13 +373,15 @@ __global__ __launch_bounds__(64 * WAVES) void sparse_gather_kernel(
   }
 }
 
-// The four gather entries: `who` = the entry's name, whose kernel is named after it (lnz_last_kernel():
-// sparse_conv[_channels][_f32]_kernel).  MULTI: R = 2 .. MAXR operators; otherwise R = 1.
-template <class Elem, bool MULTI>
+// The gather entries: `who` = the entry's name, whose kernel is named after it (lnz_last_kernel():
+// sparse_conv[_channels | _split][_f32]_kernel).  MULTI: R = 2 .. MAXR operators; otherwise R = 1.  SPLIT: Z is
+// the one source [B][N][128], X the R results [R][B][N][128].
+template <class Elem, bool MULTI, bool SPLIT = false>
 int launch_gather(const char* who, const uint32_t* entries, const float* values, const int32_t* counts, int row_cap,
                   const typename Elem::T* Z, int B, int N, int R, int relu, float* X, lnz_stream_t stream) {
   constexpr bool F32 = std::is_same<Elem, GatherF32>::value;
   LNZ_REQUIRE(entries && (values || !F32) && counts && Z && X && B > 0 && N > 0, LNZ_EINVAL, "%s: bad arguments", who);
+  if (SPLIT) LNZ_REQUIRE((const void*)Z != (const void*)X, LNZ_EINVAL, "%s: the results must not alias the source", who);
   if (MULTI)
     LNZ_REQUIRE(R >= 2 && R <= MAXR, LNZ_ENOTSUP, "%s: R=%d: 2 .. %d operators (one: lnz_large_sparse_conv%s)", who, R,
                 MAXR, F32 ? "_f32" : "");
@@ -397,7 +404,7 @@ int launch_gather(const char* who, const uint32_t* entries, const float* values,
   const int tiles = (N + TILE_ROWS - 1) / TILE_ROWS;
   const int64_t grid = (int64_t)8 * tiles * ((B + 7) / 8);
   LNZ_REQUIRE(grid <= 0x7fffffffll, LNZ_ENOTSUP, "%s: B x N too large", who);
-  hipLaunchKernelGGL((sparse_gather_kernel<Elem, MULTI>), dim3((unsigned)grid), dim3(64 * WAVES), 0,
+  hipLaunchKernelGGL((sparse_gather_kernel<Elem, MULTI, SPLIT>), dim3((unsigned)grid), dim3(64 * WAVES), 0,
                      (hipStream_t)stream, entries, values, counts, row_cap, Z, B, N, R, tiles, relu, X);
   lnz::note_kernel("%s_kernel", who + sizeof("lnz_large_") - 1);
   return lnz::check_launch(who);
@@ -483,4 +490,11 @@ extern "C" int lnz_large_sparse_conv_channels_f32(const uint32_t* entries, const
                                                   int N, int R, int relu, float* X, lnz_stream_t stream) {
   return launch_gather<GatherF32, true>("lnz_large_sparse_conv_channels_f32", entries, values, counts, row_cap, Zf, B,
                                         N, R, relu, X, stream);
+}
+
+extern "C" int lnz_large_sparse_conv_split_f32(const uint32_t* entries, const float* values,
+                                               const int32_t* counts, int row_cap, const float* P, int B,
+                                               int N, int R, float* dZ, lnz_stream_t stream) {
+  return launch_gather<GatherF32, true, true>("lnz_large_sparse_conv_split_f32", entries, values, counts, row_cap, P, B,
+                                              N, R, 0, dZ, stream);
 }

@@ -19,6 +19,11 @@
 //                            operand rows are per graph, written at leading dimension 128 (columns
 //                            beyond the layer's input width zero) — the next layer's dX'.
 //
+// R = 2 .. 8 symmetric operators (a typed batch, `_LargeTypedSparseFusedFunction`):  X' = relu( sum_c
+// L_c Z_c + V T + b ),  Z_c = X Wn_c^T.  dZ_c = L_c dP is lnz_large_sparse_conv_split_f32 (csrc/conv_sparse.hip: R
+// results gathered from one source), dWn_c = dZ_c^T X one library GEMM per block, and
+//   lnz_large_grad_input_channels   dX = sum_c dZ_c Wn_c + V dY: the same GEMM over the depth R 128 + K.
+//
 // MFMA operand maps (v_mfma_f32_16x16x4_f32): lane l holds A[i = l & 15][k = l >> 4] and
 // B[k = l >> 4][j = l & 15]; C/D register j of lane l is row 4 (l >> 4) + j, column l & 15.  The LDS
 // tiles are padded so that a wave's ds_read_b32 of either operand is conflict free (32 lanes per LDS
@@ -33,6 +38,7 @@ namespace {
 constexpr int DH = 128;          // hidden width
 constexpr int KMAX = 64;         // LARGE_MAX_K
 constexpr int SMAX = 16;         // gains_kernel_max_scales
+constexpr int RMAX = 8;          // LARGE_MAX_OPERATORS
 constexpr int CHUNK = 256;       // rows of a graph per workgroup of the projection
 constexpr int STEP = 32;         // ... staged in LDS at a time
 constexpr int PART_ROWS = KMAX + 1;   // a chunk's partial: 64 rows of A, then the bias row
@@ -305,6 +311,97 @@ __global__ __launch_bounds__(256) void large_grad_input_kernel(
     }
 }
 
+// ---- dX = sum_c dZ_c Wn_c + V dY over R operator channels: 64 rows of one graph per workgroup -------
+// (the typed batch's layer, X' = relu( sum_c L_c Z_c + V T + b ), Z_c = X Wn_c^T: `_LargeTypedSparseFusedFunction`,
+// DESIGN.md §4.9d.)  The kernel above with the depth R 128 + K: the row tile [64][R 128 + K] does not fit LDS at
+// R = 8, so the [64][128] tile of dZ_c is restaged once per channel — requested from memory before the
+// previous channel's MFMAs, written to LDS behind them — and the V tile is staged once, in the same padded rows
+// (row stride 2 mod 32: the A operand's ds_read_b32 stays conflict free).  The second operand is read in place
+// with the same look-ahead: Wn [R][128][128] is ONE matrix of R 128 rows (row 128 c + o = Wn_c[o]), then the K
+// rows of the graph's dY.  Ascending depth into one accumulator per column tile: R = 1 gives the bits of
+// large_grad_input_kernel.
+__global__ __launch_bounds__(256) void large_grad_input_channels_kernel(
+    const float* __restrict__ dZ, const float* __restrict__ Wn, const float* __restrict__ V,
+    const float* __restrict__ dY, int B, int N, int K, int R, int d, float* __restrict__ dX) {
+  __shared__ float sT[IN_ROWS][ST_LD];
+  const int b = blockIdx.y, r0 = blockIdx.x * IN_ROWS;
+  const int t = threadIdx.x, lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int li = lane & 15, lk = lane >> 4;
+  const int Kp = (K + 3) & ~3;
+  const int64_t rows = (int64_t)B * N;
+  f32x4 z[8];   // the next channel's tile of dZ, on its way
+  auto fetch = [&](const int c) {
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int idx = t + 256 * u, row = idx >> 5, c4 = idx & 31, r = r0 + row;
+      z[u] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      if (r < N) z[u] = *reinterpret_cast<const f32x4*>(dZ + ((int64_t)c * rows + (int64_t)b * N + r) * DH + 4 * c4);
+    }
+  };
+  fetch(0);
+  for (int idx = t; idx < IN_ROWS * Kp; idx += 256) {
+    const int row = idx / Kp, k = idx - row * Kp, r = r0 + row;
+    sT[row][DH + k] = (r < N && k < K) ? V[((int64_t)b * N + r) * K + k] : 0.0f;
+  }
+  const int nct = (d + 15) >> 4;
+  f32x4 acc[8];
+#pragma unroll
+  for (int ct = 0; ct < 8; ++ct) acc[ct] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  // depth index dep < R 128: row dep of the stacked Wn; R 128 + k: row k of the graph's dY (k >= K: padding,
+  // zero).  The look-ahead runs across the channel seams: the operand rows do not wait for the restaging.
+  const int RD = R * DH;
+  auto load = [&](float (&v)[8], const int k0) {
+    const int dep = k0 + lk;
+    const float* p = nullptr;
+    if (dep < RD) p = Wn + (int64_t)dep * DH + li;
+    else if (dep - RD < K) p = dY + ((int64_t)b * K + (dep - RD)) * DH + li;
+#pragma unroll
+    for (int ct = 0; ct < 8; ++ct) v[ct] = (p && ct < nct) ? p[ct * 16] : 0.0f;
+  };
+  constexpr int PF = 2;
+  float cur[PF][8], nxt[PF][8];
+#pragma unroll
+  for (int u = 0; u < PF; ++u) load(cur[u], 4 * u);
+  // one turn of 4 PF depth steps: operand rows g0 .., the A operand from columns a0 .. of the tile, `n` live
+  auto turn = [&](const int g0, const int a0, const int n) {
+#pragma unroll
+    for (int u = 0; u < PF; ++u) load(nxt[u], g0 + 4 * PF + 4 * u);
+#pragma unroll
+    for (int u = 0; u < PF; ++u) {
+      if (4 * u < n) {   // (uniform; n is a multiple of 4)
+        const float a = sT[16 * w + li][a0 + 4 * u + lk];
+#pragma unroll
+        for (int ct = 0; ct < 8; ++ct)
+          if (ct < nct) acc[ct] = mfma16(a, cur[u][ct], acc[ct]);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < PF; ++u)
+#pragma unroll
+      for (int ct = 0; ct < 8; ++ct) cur[u][ct] = nxt[u][ct];
+  };
+  for (int c = 0; c < R; ++c) {
+    if (c > 0) __syncthreads();   // every wave is done with channel c - 1's tile
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int idx = t + 256 * u, row = idx >> 5, c4 = idx & 31;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) sT[row][4 * c4 + e] = z[u][e];
+    }
+    __syncthreads();
+    if (c + 1 < R) fetch(c + 1);
+    for (int k0 = 0; k0 < DH; k0 += 4 * PF) turn(c * DH + k0, k0, DH - k0);
+  }
+  for (int k0 = 0; k0 < Kp; k0 += 4 * PF) turn(RD + k0, DH + k0, Kp - k0);
+#pragma unroll
+  for (int ct = 0; ct < 8; ++ct)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int r = r0 + 16 * w + 4 * lk + j;
+      if (r < N) dX[((int64_t)b * N + r) * DH + ct * 16 + li] = ct * 16 + li < d ? acc[ct][j] : 0.0f;
+    }
+}
+
 }  // namespace
 
 extern "C" int lnz_large_grad_project(float* dX, const float* Xout, const float* V, const int32_t* n_nodes,
@@ -351,4 +448,23 @@ extern "C" int lnz_large_grad_input(const float* dZ, const float* Wn, const floa
                      0, (hipStream_t)stream, dZ, Wn, V, dY, N, K, d, dX);
   lnz::note_kernel("large_grad_input_kernel");
   return lnz::check_launch("lnz_large_grad_input");
+}
+
+extern "C" int lnz_large_grad_input_channels(const float* dZ, const float* Wn, const float* V, const float* dY,
+                                             int B, int N, int K, int R, int d, float* dX, lnz_stream_t stream) {
+  LNZ_REQUIRE(dZ && Wn && dX && dZ != dX && B > 0 && N > 0, LNZ_EINVAL,
+              "lnz_large_grad_input_channels: bad arguments (B=%d N=%d; dX must not alias dZ)", B, N);
+  LNZ_REQUIRE(R >= 1 && R <= RMAX && K >= 0 && K <= KMAX && d >= 1 && d <= DH, LNZ_ENOTSUP,
+              "lnz_large_grad_input_channels: R=%d K=%d d=%d: 1 <= R <= %d, K <= %d, 1 <= d <= %d", R, K, d, RMAX,
+              KMAX, DH);
+  LNZ_REQUIRE(K == 0 || (V && dY), LNZ_EINVAL, "lnz_large_grad_input_channels: K=%d needs V and dY", K);
+  LNZ_REQUIRE(B <= 65535, LNZ_ENOTSUP, "lnz_large_grad_input_channels: B=%d > 65535 graphs", B);
+  const uintptr_t block = (uintptr_t)B * N * DH * sizeof(float), z0 = (uintptr_t)dZ, x0 = (uintptr_t)dX;
+  LNZ_REQUIRE(x0 + block <= z0 || z0 + (uintptr_t)R * block <= x0, LNZ_EINVAL,
+              "lnz_large_grad_input_channels: dX must not alias any channel of dZ");
+  LNZ_REQUIRE((((uintptr_t)dZ) & 15) == 0, LNZ_EINVAL, "lnz_large_grad_input_channels: dZ must be 16-byte aligned");
+  hipLaunchKernelGGL(large_grad_input_channels_kernel, dim3((unsigned)((N + IN_ROWS - 1) / IN_ROWS), (unsigned)B),
+                     dim3(256), 0, (hipStream_t)stream, dZ, Wn, V, dY, B, N, K, R, d, dX);
+  lnz::note_kernel("large_grad_input_channels_kernel");
+  return lnz::check_launch("lnz_large_grad_input_channels");
 }

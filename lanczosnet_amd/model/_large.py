@@ -3,7 +3,8 @@ the node-space term on the nonzeros of L (csrc/conv_sparse.hip) with their chann
 sparse-backoff state, and the library-GEMM restatement (hipBLASLt through torch) of everything the
 kernels are not built for.  `_plan_large` is also the cache the 33..128-node plan lives in.
 `_LargeSparseFusedFunction`: the opt-in HIP backward of the exact-fp32 sparse layers for edge-list batches
-(csrc/conv_sparse_grad.hip)."""
+(csrc/conv_sparse_grad.hip); `_LargeTypedSparseFusedFunction`: the same for typed batches —
+R = 3 .. 8 distinct operator channels, one sparse image each."""
 import os
 import warnings
 
@@ -25,6 +26,10 @@ class _LargeMixin:
     # (_LargeSparseFusedFunction, csrc/conv_sparse_grad.hip), 'torch' (default) = densify + autograd
     # through `_torch_forward`.  Opt-in: its step time is recorded, not yet a reason
     large_backward_impl = os.environ.get('LANCZOSNET_LARGE_BACKWARD', 'torch')
+    # typed edge-list batches (a SparseLaplacian with `images`: two or more edge types) in training: 'hip' =
+    # the backward over the channels' images (_LargeTypedSparseFusedFunction), 'torch'
+    # (default) = densify + autograd.  A switch of its own: each governs its own kind of batch
+    large_typed_backward_impl = os.environ.get('LANCZOSNET_LARGE_BACKWARD_TYPED', 'torch')
 
     @torch.no_grad()
     def _torch_gains(self, D):
@@ -170,10 +175,21 @@ class _LargeMixin:
         fp32), the reference's channel order, diagonal gains; selected by `large_backward_impl ==
         'hip'` where `backward_impl` asks for HIP at all.  WHAT the batch is (one operator given as a
         clean sparse image) is `_route`'s `sparse_one_operator`."""
-        return (self.large_backward_impl == 'hip' and self.backward_impl == 'hip'
+        return self.large_backward_impl == 'hip' and self._large_backward_envelope(K, channels)
+
+    def _large_backward_envelope(self, K, channels):
+        """What the HIP backwards on sparse images share, whichever switch selects them."""
+        return (self.backward_impl == 'hip'
                 and self._large_hip_supported(K, channels) and self.gemm_mode != 'bf16'
                 and self.large_split_planes != 1 and self.large_sparse
                 and self._channel_order() is None and self.filter_kind == 0)
+
+    def _large_typed_backward_supported(self, K, channels):
+        """The HIP backward over the R = 3 .. 8 operator channels of a typed batch (lnz_large_sparse_conv_split_f32,
+        lnz_large_grad_input_channels): `_large_backward_envelope`, selected by `large_typed_backward_impl == 'hip'`.
+        WHAT the batch is (clean images with their fp32 values) is `_route`'s `sparse_typed_operators`."""
+        return (self.large_typed_backward_impl == 'hip' and 3 <= channels <= LARGE_MAX_OPERATORS
+                and self._large_backward_envelope(K, channels))
 
     def _sparse_one_operator(self, L, drop, capturing):
         """`_route`'s `sparse_one_operator` for this call: L is an untyped SparseLaplacian (one edge
@@ -186,6 +202,17 @@ class _LargeMixin:
         if drop or capturing or not self._needs_grad() or not self._large_backward_supported(0, L.channels):
             return False
         return int(L.image.flags.item()) == 0
+
+    def _sparse_typed_operators(self, L, drop, capturing):
+        """`_route`'s `sparse_typed_operators` for this call: L is a typed SparseLaplacian (two or more edge
+        types: R = 3 .. 8 distinct operators) whose images carry their fp32 values and raised no flag.  The flag
+        word is read last, and only where the answer can matter."""
+        if not (isinstance(L, ops.SparseLaplacian) and L.images is not None
+                and 3 <= L.channels <= LARGE_MAX_OPERATORS and L.images.values is not None and L.N <= 65536):
+            return False
+        if drop or capturing or not self._needs_grad() or not self._large_typed_backward_supported(0, L.channels):
+            return False
+        return int(L.images.flags.item()) == 0
 
     # -- channel folding of the large-graph path ------------------------------------------------
     # With one edge type (config/graph_lanczos_net.yaml:14) the collated L carries the SAME operator
@@ -514,6 +541,102 @@ class _LargeSparseFusedFunction(torch.autograd.Function):
                 Wv = W.view(128, S + C, d)
                 Wn = torch.nn.functional.pad(Wv[:, S] + Wv[:, S + 1], (0, 128 - d)).contiguous()
                 ops.large_grad_input(dZ, Wn, V if S > 0 else None, dY, d, out=g)
+        # ---- spectral filter MLPs from dG [L, B K, S]
+        if dGs:
+            _spectral_mlp_param_grads(m, grads, D, torch.stack(dGs[::-1]).view(Lnum, B * K, S))
+        # ---- embedding rows
+        if not m.general:
+            grads[id(m.embedding.weight)] = embedding_grad(m, node_feat, g, N, m.input_dim)
+        return param_grad_tuple(m, grads, 6)
+
+
+class _LargeTypedSparseFusedFunction(torch.autograd.Function):
+    """Training a TYPED edge-list batch (a SparseLaplacian with `images`: R = E + 1 = 3 .. 8 symmetric operators,
+    one sparse image each) through the HIP kernels, with no dense L.
+
+    forward: the launches of `_large_sparse_layers` for a typed batch (one lnz_f32_linear per channel on the
+    stacked weight blocks, lnz_large_sparse_conv_channels_f32), each layer into its slice of ONE [num_layer, B,
+    N, 128] buffer, then the readout: the score is the inference route's.
+    backward, last layer first: lnz_large_grad_project; lnz_large_sparse_conv_split_f32 (dZ_c = L_c dP, R results
+    from one source); library GEMMs dWn_c = dZ_c^T X, one per channel block; lnz_large_grad_spectral and dW_s as for
+    one operator; lnz_large_grad_input_channels (dX = sum_c dZ_c Wn_c + V dY).  Head, filter MLPs and embedding
+    rows as `_LargeSparseFusedFunction`."""
+
+    @staticmethod
+    def forward(ctx, module, node_feat, L, D, V, mask, *params):
+        m = module
+        S, planes = m.num_scale_long, m.large_split_planes
+        B, N, R = L.B, L.N, L.channels
+        dev = V.device
+        Vf = V.float().contiguous()
+        cache = m._plan_large()
+        G = None
+        if S > 0:
+            G = ops.spectral_gains(D, m.long_diffusion_dist, m.num_layer, cache['mlp_pack'])
+        imgs = L.images
+        Vb = ops.large_pack_vectors(Vf, planes)
+        classes = tuple(range(R))
+        plan = m._plan_large(planes, classes)
+        X0 = input_state(m, node_feat, width=(m.input_dim + 31) // 32 * 32, as_float=True).contiguous()
+        work = ops.large_sparse_work_buffers(B, N, dev, R=R, planes=planes)
+        Xs = torch.empty((m.num_layer, B, N, 128), dtype=torch.float32, device=dev)
+        state = X0
+        for t, lay in enumerate(plan['conv'][(planes, classes)]):
+            state = ops.large_sparse_conv_layer(state, lay['din'], imgs, Vb, Vf, lay['Wn32s'], lay['Wt'],
+                                                G[t] if G is not None else None, lay['bias'], work,
+                                                planes, relu=True, out=Xs[t])
+        mask_u8 = mask.to(torch.uint8).contiguous()
+        if m.large_head_kernel and m.output_dim <= 16:
+            score = ops.large_head(state, mask_u8, *m._plan_head(cache))
+        else:
+            score = masked_readout(m, state, mask)
+        # (the [R, B, N, 128] feature buffer of the forward is the backward's dZ: no allocation of its own)
+        ctx.module, ctx.images, ctx.has_gains, ctx.dZ = m, imgs, G is not None, work[0]
+        ctx.save_for_backward(node_feat, X0, D, Vf, mask_u8, L.n_nodes, Xs, *([G] if G is not None else []))
+        return score
+
+    @staticmethod
+    def backward(ctx, grad_score):
+        m, imgs = ctx.module, ctx.images
+        node_feat, X0, D, V, mask_u8, n_nodes, Xs = ctx.saved_tensors[:7]
+        G = ctx.saved_tensors[7] if ctx.has_gains else None
+        Lnum, B, N, _ = Xs.shape
+        K, S, R = V.shape[2], m.num_scale_long, imgs.R
+        grads = {}
+        # ---- head (model/lanczos_net.py:185-194): autograd on the stored last state
+        Whead, bhead = m._plan_head(m._plan_large())
+        with torch.enable_grad():
+            XL = Xs[-1].detach().requires_grad_(True)
+            Wh = Whead.detach().requires_grad_(True)
+            bh = bhead.detach().requires_grad_(True)
+            dXL, dWh, dbh = torch.autograd.grad(masked_readout(m, XL, mask_u8, stacked=(Wh, bh)),
+                                                [XL, Wh, bh], grad_score.contiguous())
+        scatter_head_grads(m, grads, dWh, dbh)
+        g = dXL.contiguous()            # dX' of the layer at hand; lnz_large_grad_project masks it in place
+        dZ = ctx.dZ
+        Vt = V.transpose(1, 2)
+        dGs = []
+        for t in range(Lnum - 1, -1, -1):
+            X = X0 if t == 0 else Xs[t - 1]
+            d = m.input_dim if t == 0 else 128
+            W = m.filter[t].weight.detach().float().contiguous()      # [128, (S + R) d]
+            A, dbg = ops.large_grad_project(g, Xs[t], V, n_nodes)     # g is dP from here on
+            ops.large_sparse_conv_split(imgs, g, out=dZ)              # dZ[c] = L_c dP
+            Xr = X.view(B * N, X.shape[2])
+            blocks = [_tn_split_k(dZ[c].view(B * N, 128), Xr)[:, :d] for c in range(R)]
+            dY = None
+            if S > 0:
+                Y = torch.bmm(Vt, X)                                  # V^T X  [B, K, ldx]
+                dG, Q, dY = ops.large_grad_spectral(A, Y, G[t], W, d, want_dgains=m._has_mlp())
+                dWl = A.view(B * K, 128).t() @ Q.view(B * K, S * d)
+                blocks = list(dWl.view(128, S, d).unbind(1)) + blocks
+                if dG is not None:
+                    dGs.append(dG)
+            grads[id(m.filter[t].weight)] = torch.stack(blocks, dim=1).reshape(128, -1)
+            grads[id(m.filter[t].bias)] = dbg.sum(dim=0)
+            if t > 0 or not m.general:
+                Wn = torch.nn.functional.pad(W.view(128, S + R, d)[:, S:].permute(1, 0, 2), (0, 128 - d)).contiguous()
+                ops.large_grad_input_channels(dZ, Wn, V if S > 0 else None, dY, d, out=g)
         # ---- spectral filter MLPs from dG [L, B K, S]
         if dGs:
             _spectral_mlp_param_grads(m, grads, D, torch.stack(dGs[::-1]).view(Lnum, B * K, S))

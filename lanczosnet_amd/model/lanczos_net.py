@@ -18,7 +18,8 @@ same math (`_torch_forward`) — still GPU only; there is no CPU path.  Graphs o
 a HIP backward of their own (`_MidGraphFusedFunction`, csrc/conv_mid_grad.hip),
 opt-in through `mid_backward_impl`; edge-list batches beyond that (an untyped `ops.SparseLaplacian`) have
 one on their sparse image (`_LargeSparseFusedFunction`, csrc/conv_sparse_grad.hip), opt-in
-through `large_backward_impl`.
+through `large_backward_impl`; typed ones (two or more edge types) through `large_typed_backward_impl`
+(`_LargeTypedSparseFusedFunction`).
 
 One regime per module: `_small` (<= 32 nodes, the fused kernels), `_mid` (33..128 nodes, one launch),
 `_large` (beyond: streamed and sparse kernels, library GEMMs), `_ada` (AdaLanczosNet); `_common`
@@ -35,7 +36,7 @@ from .. import ops
 from ..utils.data_helper import check_dist
 from ._common import (FUSED_MAX_NODES, FUSED_WIDTHS, MAX_CHANNELS, MAX_INPUT_DIM, MAX_SHORT_SCALES,
                       STRIP_MAX_LONG_SCALES, STRIP_WIDTH, _opt, input_state, masked_readout)
-from ._large import _LargeMixin, _LargeSparseFusedFunction
+from ._large import _LargeMixin, _LargeSparseFusedFunction, _LargeTypedSparseFusedFunction
 from ._mid import _MidGraphFusedFunction, _MidMixin
 from ._small import _LanczosNetFunction, _LanczosNetFusedFunction, _SmallMixin
 
@@ -43,7 +44,8 @@ __all__ = ['LanczosNet', 'LanczosNetGeneral', 'AdaLanczosNet']
 
 # the routes of `_LanczosNetBase._route` that train through an autograd.Function of their own
 _TRAIN_FUNCTIONS = {'fused_train_hip': _LanczosNetFusedFunction, 'fused_train_torch': _LanczosNetFunction,
-                    'mid_train_hip': _MidGraphFusedFunction, 'large_train_hip': _LargeSparseFusedFunction}
+                    'mid_train_hip': _MidGraphFusedFunction, 'large_train_hip': _LargeSparseFusedFunction,
+                    'large_typed_train_hip': _LargeTypedSparseFusedFunction}
 
 
 class _LanczosNetBase(_SmallMixin, _MidMixin, _LargeMixin, nn.Module):
@@ -221,12 +223,14 @@ class _LanczosNetBase(_SmallMixin, _MidMixin, _LargeMixin, nn.Module):
         return (set(self.hidden_dim[:self.num_layer]) == {STRIP_WIDTH}
                 and self.input_dim <= MAX_INPUT_DIM)
 
-    def _route(self, N, K, channels, needs_grad, drop, capturing, sparse_one_operator=False):
+    def _route(self, N, K, channels, needs_grad, drop, capturing, sparse_one_operator=False,
+               sparse_typed_operators=False):
         """The path `forward` takes for graphs of N nodes, K Ritz pairs and `channels` operator
         channels (needs_grad: `_needs_grad()`; drop: dropout > 0 in training; capturing: the
         current stream is being captured into a HIP graph; sparse_one_operator: L is an untyped
         SparseLaplacian — one operator as a sparse image with its fp32 values — and the image raised
-        no flag).  No GPU needed to ask.
+        no flag; sparse_typed_operators: L is a typed SparseLaplacian — `channels` = 3 .. 8 distinct operators,
+        one sparse image each with its fp32 values — and the images raised no flag).  No GPU needed to ask.
           'fused'              <= 32 nodes: the fused MFMA kernels (`_hip_forward`)
           'fused_train_hip'    ... training, HIP backward (`_LanczosNetFusedFunction`)
           'fused_train_torch'  ... training, backward through `_torch_forward` (`_LanczosNetFunction`)
@@ -234,6 +238,8 @@ class _LanczosNetBase(_SmallMixin, _MidMixin, _LargeMixin, nn.Module):
           'mid_train_hip'      ... training, opted in (`_MidGraphFusedFunction`)
           'large_hip'          > 32 nodes: the streamed / sparse kernels (`_large_graph_forward_hip`)
           'large_train_hip'    ... an edge-list batch in training, opted in (`_LargeSparseFusedFunction`)
+          'large_typed_train_hip'  ... a typed edge-list batch in training, opted in
+                               (`_LargeTypedSparseFusedFunction`)
           'library'            > 32 nodes or an architecture outside the fused kernels, inference:
                                hipBLASLt conv + HIP spectral gains (`_large_graph_forward`)
           'torch'              gradients or dropout outside the kernels: `_torch_forward`"""
@@ -247,6 +253,9 @@ class _LanczosNetBase(_SmallMixin, _MidMixin, _LargeMixin, nn.Module):
         if (needs_grad and not drop and not capturing and sparse_one_operator and N > FUSED_MAX_NODES
                 and self._large_backward_supported(K, channels)):
             return 'large_train_hip'
+        if (needs_grad and not drop and not capturing and sparse_typed_operators and N > FUSED_MAX_NODES
+                and self._large_typed_backward_supported(K, channels)):
+            return 'large_typed_train_hip'
         if needs_grad or drop:
             return 'torch'
         if self._mid_hip_supported(N, K, channels):
@@ -335,7 +344,8 @@ class _LanczosNetBase(_SmallMixin, _MidMixin, _LargeMixin, nn.Module):
         N = L.shape[1]
         capturing = torch.cuda.is_current_stream_capturing()
         route = self._route(N, V.shape[2], L.shape[3], self._needs_grad(), drop, capturing,
-                            sparse_one_operator=self._sparse_one_operator(L, drop, capturing))
+                            sparse_one_operator=self._sparse_one_operator(L, drop, capturing),
+                            sparse_typed_operators=self._sparse_typed_operators(L, drop, capturing))
         if isinstance(L, ops.SparseLaplacian):
             # the batch of dataset.collate_graph_edges: its image serves the sparse large-graph
             # layers; every other route reads the dense tensor
@@ -344,7 +354,7 @@ class _LanczosNetBase(_SmallMixin, _MidMixin, _LargeMixin, nn.Module):
                                  'model num_edgetype + 1 = %d' % (L.channels, L.channels - 1, self.num_edgetype + 1))
             if L.device != dev:
                 L = L.to(dev)
-            if route not in ('large_hip', 'large_train_hip') or capturing:
+            if route not in ('large_hip', 'large_train_hip', 'large_typed_train_hip') or capturing:
                 L = self._densify(L, "route '%s'" % route)
         if N <= FUSED_MAX_NODES and not route.startswith('fused'):
             self._warn_library_path(drop)

@@ -1251,6 +1251,47 @@ def large_grad_input(dZ, Wn, V, dY, d, out):
   return out
 
 
+# ---- the same backward over the R operator channels of a typed batch ----------------------
+def large_sparse_conv_split(imgs, P, out=None):
+  """lnz_large_sparse_conv_split_f32: out [R,B,N,128] with out[c] = L_c P for the R = 2 .. 8 images of a
+  LargeSparseImages (with `values`) and ONE source P [B,N,128] fp32 — the backward's dZ_c = L_c dP (every L_c
+  symmetric).  `out` is overwritten, never read; out[c] is bit for bit the one-operator gather of image c onto
+  zeros."""
+  assert isinstance(imgs, LargeSparseImages) and imgs.values is not None
+  R, B, N = imgs.R, imgs.B, imgs.N
+  _need_cuda(imgs.entries, imgs.values, imgs.counts, P, out)
+  assert P.dtype == torch.float32 and P.is_contiguous() and tuple(P.shape) == (B, N, 128)
+  assert imgs.entries.is_contiguous() and imgs.values.is_contiguous() and imgs.counts.is_contiguous()
+  if out is None:
+    out = torch.empty((R, B, N, 128), dtype=torch.float32, device=P.device)
+  assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (R, B, N, 128)
+  assert out.data_ptr() != P.data_ptr()
+  with torch.cuda.device(P.device):
+    _abi().large_sparse_conv_split_f32(imgs.entries, imgs.values, imgs.counts, imgs.cap, P, B, N, R, out)
+  return out
+
+
+def large_grad_input_channels(dZ, Wn, V, dY, d, out):
+  """lnz_large_grad_input_channels: out [B,N,128] = sum_c dZ[c] Wn[c] + V dY in one exact-fp32 MFMA launch
+  (dZ [R,B,N,128], Wn [R,128,128] with columns >= d zero, V [B,N,K], dY [B,K,128]; V = dY = None: no long
+  scales); columns >= d of `out` are written zero.  `out` must not be (part of) dZ.  Names itself to
+  last_kernel()."""
+  _need_cuda(dZ, Wn, V, dY, out)
+  R, B, N, _ = dZ.shape
+  K = 0 if dY is None else dY.shape[1]
+  assert dZ.dtype == Wn.dtype == out.dtype == torch.float32
+  assert dZ.is_contiguous() and Wn.is_contiguous() and out.is_contiguous()
+  assert tuple(dZ.shape) == (R, B, N, 128) and tuple(out.shape) == (B, N, 128) and tuple(Wn.shape) == (R, 128, 128)
+  assert not dZ.data_ptr() <= out.data_ptr() < dZ.data_ptr() + dZ.numel() * 4
+  if K:
+    assert V.dtype == dY.dtype == torch.float32 and V.is_contiguous() and dY.is_contiguous()
+    assert tuple(V.shape) == (B, N, K) and tuple(dY.shape) == (B, K, 128)
+  with torch.cuda.device(dZ.device):
+    _abi().large_grad_input_channels(dZ, Wn, V if K else None, dY if K else None, B, N, K, R, d, out)
+  note_autograd_kernel()
+  return out
+
+
 # ------------------------------------------------------------------------------------- packing
 def pack_rows_k8(W):
   """[rows, cols] -> MFMA fragment order (see include/lanczosnet_hip.h)."""

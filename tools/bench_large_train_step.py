@@ -12,8 +12,14 @@ events around a window; the cyclic collector is collected and frozen outside the
 tools/bench_train_step.py) and peak_bytes = torch.cuda.max_memory_allocated above the resident batch,
 parameters and optimizer state.
 
-    python tools/bench_large_train_step.py [--shapes config5,wide] [--windows 3] [--steps 2] [--batch B]
-                                           [--out profiles/large_train_step.json]
+TYPED shapes (`typed`: config 5's graphs, `typed_wide`: the wide corner — (E + 1) N beyond `to_dense`'s limit, the
+switch on only —, each with two edge types drawn per edge): the same two routes under the typed switch
+(`large_typed_backward_impl`: `_LargeTypedSparseFusedFunction`), and one layer's split gather
+(lnz_large_sparse_conv_split_f32) beside R launches of lnz_large_sparse_conv_f32 onto zeroed buffers on the same
+operands.  They are written to profiles/large_typed_train_step.json.
+
+    python tools/bench_large_train_step.py [--shapes config5,wide | typed,typed_wide] [--windows 3] [--steps 2]
+                                           [--batch B] [--out profiles/large[_typed]_train_step.json]
 """
 import argparse
 import gc
@@ -31,27 +37,67 @@ if ROOT not in sys.path:
 from tools.bench_edge_collate import SHAPES, gnp_edges, stats  # noqa: E402
 
 
-def net_for(K, dev, impl):
+TYPED = {'typed': 'config5', 'typed_wide': 'wide'}   # typed shape -> the graphs it types
+TYPED_E = 2
+
+
+def net_for(K, dev, impl, E=1):
   import torch
   import oracle
   from lanczosnet_amd.model import LanczosNetGeneral
   from lanczosnet_amd.utils.arg_helper import make_model_config
-  cfg = dict(num_bond_type=1, short_diffusion_dist=[], long_diffusion_dist=[1, 2, 3, 5, 7, 10, 20, 30], num_eig_vec=K,
+  cfg = dict(num_bond_type=E, short_diffusion_dist=[], long_diffusion_dist=[1, 2, 3, 5, 7, 10, 20, 30], num_eig_vec=K,
              spectral_filter_kind='MLP', input_dim=10, hidden_dim=[128] * 7, output_dim=2, num_layer=7, num_atom=0)
   P = oracle.make_lanczosnet_params(cfg, 17, general=True)
   net = LanczosNetGeneral(make_model_config(cfg, general=True)).train()
   net.load_state_dict({k: torch.from_numpy(v) for k, v in P.items()})
   net = net.to(dev)
   net.gemm_mode = 'fp32'
-  net.large_backward_impl = impl
+  net.large_backward_impl = impl if E == 1 else 'torch'
+  net.large_typed_backward_impl = impl if E > 1 else 'torch'
   return net
 
 
-def route(impl, b, K, dev, windows, steps):
+def gather_record(imgs, reps=10):
+  """One layer's dZ_c = L_c dP for all R channels: the split gather against R one-operator gathers onto zeroed
+  buffers (the zero fill inside the timed region: it is part of that composition), the same operands."""
+  import torch
+  from lanczosnet_amd import ops
+  R, B, N = imgs.R, imgs.B, imgs.N
+  P = torch.randn((B, N, 128), device=imgs.entries.device)
+  out, ref = torch.empty((R, B, N, 128), device=P.device), torch.empty((R, B, N, 128), device=P.device)
+  chans = [imgs.channel(c) for c in range(R)]
+
+  def split():
+    ops.large_sparse_conv_split(imgs, P, out=out)
+
+  def composed():
+    ref.zero_()
+    for c, im in enumerate(chans):
+      ops._abi().large_sparse_conv_f32(im.entries, im.values, im.counts, im.cap, P, B, N, 0, ref[c])
+  rec = {}
+  for name, fn in (('split_gather_ms', split), ('r_launches_onto_zeros_ms', composed)):
+    fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+      e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+      e0.record()
+      fn()
+      e1.record()
+      torch.cuda.synchronize()
+      ms.append(e0.elapsed_time(e1))
+    rec[name] = stats([round(x, 4) for x in ms])
+  rec['same_bits'] = bool(torch.equal(out, ref))
+  rec['split_over_r_launches'] = round(rec['split_gather_ms']['median'] / rec['r_launches_onto_zeros_ms']['median'], 4)
+  return rec
+
+
+def route(impl, b, K, dev, windows, steps, E=1):
   """-> the record of one route on the resident batch `b`: one warm step, then the timed windows."""
   import torch
   from lanczosnet_amd import ops
-  net = net_for(K, dev, impl)
+  net = net_for(K, dev, impl, E)
   opt = torch.optim.Adam(net.parameters(), lr=1e-4)
 
   def step():
@@ -89,8 +135,14 @@ def main():
   ap.add_argument('--windows', type=int, default=3)
   ap.add_argument('--steps', type=int, default=2)
   ap.add_argument('--batch', type=int, default=0, help="override B (0: the shape's own)")
-  ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'large_train_step.json'))
+  ap.add_argument('--out', default=None)
   args = ap.parse_args()
+  names = args.shapes.split(',')
+  if len({n in TYPED for n in names}) != 1:
+    raise SystemExit('bench_large_train_step: typed and untyped shapes go to files of their own: one kind per run')
+  typed = names[0] in TYPED
+  if args.out is None:
+    args.out = os.path.join(ROOT, 'profiles', 'large_typed_train_step.json' if typed else 'large_train_step.json')
   import torch
   if not torch.cuda.is_available():
     raise SystemExit('bench_large_train_step: needs the MI355X (no CPU fallback)')
@@ -99,25 +151,33 @@ def main():
   result = dict(device=torch.cuda.get_device_name(0), windows=args.windows, workload='LanczosNetGeneral 7 x 128, '
                 'eight long scales, train step (fwd + bwd + Adam), graphs from edge lists', shapes={})
   warnings.simplefilter('ignore')
-  for name in args.shapes.split(','):
-    s = dict(SHAPES[name])
+  for name in names:
+    s = dict(SHAPES[TYPED.get(name, name)])
+    E = TYPED_E if typed else 1
     if args.batch:
       s['B'] = args.batch
     rs = np.random.RandomState(5)
     graphs = [gnp_edges(s['N'], s['p'], rs) for _ in range(s['B'])]
     items = [dict(edges=g, node_feat=rs.randn(s['N'], 10).astype(np.float32), label=rs.randn(1, 2)) for g in graphs]
     rec = dict(s, edges_per_graph=int(np.mean([g.shape[0] for g in graphs])),
-               dense_L_bytes=int(s['B'] * s['N'] * s['N'] * 8))
-    b = collate_graph_edges(items, s['K'], device=dev, lanczos_steps=s['M'])
+               dense_L_bytes=int(s['B'] * s['N'] * s['N'] * 4 * (E + 1)))
+    if typed:
+      for it, g in zip(items, graphs):
+        it['edge_type'] = rs.randint(0, E, size=g.shape[0])
+      rec['num_edge_type'] = E
+    b = collate_graph_edges(items, s['K'], device=dev, lanczos_steps=s['M'], num_edge_type=E)
     rec['image_flags'] = int(b['L'].image.flags.item())
-    for impl in ('torch', 'hip'):
+    if typed:
+      rec['gather'] = gather_record(b['L'].images)
+    impls = ('hip',) if name == 'typed_wide' else ('torch', 'hip')
+    for impl in impls:
       try:
-        rec['large_backward_' + impl] = route(impl, b, s['K'], dev, args.windows, args.steps)
+        rec['large_backward_' + impl] = route(impl, b, s['K'], dev, args.windows, args.steps, E)
       except Exception as e:   # noqa: BLE001  (recorded: the densify route does not reach every shape)
         gc.unfreeze()
         rec['large_backward_' + impl] = dict(error='%s: %s' % (type(e).__name__, str(e).splitlines()[0][:300]))
       torch.cuda.empty_cache()
-    t, h = rec['large_backward_torch'], rec['large_backward_hip']
+    t, h = rec.get('large_backward_torch', {}), rec['large_backward_hip']
     if 'step_ms' in t and 'step_ms' in h:
       rec['hip_over_torch'] = dict(step_ms=round(h['step_ms']['median'] / t['step_ms']['median'], 4),
                                    peak_bytes=round(h['peak_bytes'] / t['peak_bytes'], 4))

@@ -36,6 +36,8 @@ extern "C" {
  *    lnz_large_grad_spectral, lnz_large_grad_input: additive, the version stays);
  *    + the same backward over R = 2 .. 8 operator channels of a typed batch (lnz_large_sparse_conv_split_f32,
  *    lnz_large_grad_input_channels: additive, the version stays);
+ *    + the symmetry check of a sparse image (lnz_large_sparse_image_symmetry: what lets a dense collated batch
+ *    take that backward; additive, the version stays);
  * 6: lnz_forward_args lost Wp16 / w16_off / Wp16_head / Lp16 (gemm_mode 1 is now the split precision
  *    inside the strip kernel: lnz_pack_rows_k8_split; lnz_pack_rows_f16x2 and
  *    lnz_pack_laplacian_f16x2 are gone) and gained dbias_part_cap; + lnz_midgraph_forward,
@@ -331,6 +333,20 @@ int lnz_large_sparse_conv_split_f32(const uint32_t* entries, const float* values
                                     lnz_stream_t stream);
 int lnz_large_grad_input_channels(const float* dZ, const float* Wn, const float* V, const float* dY, int B,
                                   int N, int K, int R, int d, float* dX, lnz_stream_t stream);
+/* That backward forms dZ = L dP for L^T dP: it asks for symmetric operators.  An image from an edge list is
+ * symmetric by construction; of an image built from a caller's tensor this entry says so:
+ *   lnz_large_sparse_image_symmetry   entries / values / counts: a one-operator image (R = 1) or R channel-major
+ *                            images [R][B][N][row_cap]; values required.  status [R * B] int32, cleared by the
+ *                            call; word r B + b: bit 0 = an entry (i, j, v) of graph b, channel r, has no entry with
+ *                            column i in row j; bit 1 = the mirror's value is not v — they match when the signs
+ *                            agree and the bit patterns, as integers, differ by at most 1 (one fp32 ulp: an L built
+ *                            in float64 and cast can round (s_i a) s_j and (s_j a) s_i one ulp apart).  A row's
+ *                            padding is not an entry, a diagonal entry is its own mirror; rows are searched (entry
+ *                            order is not ascending).  Counts are clamped to row_cap and columns >= N never
+ *                            followed: safe on an image whose flags are raised (the result is then meaningless).
+ *                            R <= 8, N <= 65536, row_cap a multiple of 8, >= 32.  A fixed function of the image. */
+int lnz_large_sparse_image_symmetry(const uint32_t* entries, const float* values, const int32_t* counts,
+                                    int row_cap, int R, int B, int N, int32_t* status, lnz_stream_t stream);
 
 /* ---- R6 standalone: batched symmetric tridiagonal eigensolver --------------------------------
  * The step the reference leaves to LAPACK (inside np.linalg.eigh, utils/data_helper.py:201) /

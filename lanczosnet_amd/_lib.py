@@ -104,6 +104,7 @@ SIGNATURES = {
     'lnz_large_grad_input': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     'lnz_large_sparse_conv_split_f32': (C.c_int, [_P, _P, _P, _I, _P, _I, _I, _I, _P, _P]),
     'lnz_large_grad_input_channels': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    'lnz_large_sparse_image_symmetry': (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     'lnz_large_pack_vectors': (C.c_int, [_P, _I, _I, _I, _I, _P, _P]),
     'lnz_large_gemm1_rows': (C.c_int, [_P, _I, _I, _P, _I, _I, _P, _P]),
     'lnz_large_sparse_conv': (C.c_int, [_P, _P, _I, _P, _I, _I, _I, _P, _P]),

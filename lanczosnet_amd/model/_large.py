@@ -4,15 +4,17 @@ sparse-backoff state, and the library-GEMM restatement (hipBLASLt through torch)
 kernels are not built for.  `_plan_large` is also the cache the 33..128-node plan lives in.
 `_LargeSparseFusedFunction`: the opt-in HIP backward of the exact-fp32 sparse layers for edge-list batches
 (csrc/conv_sparse_grad.hip); `_LargeTypedSparseFusedFunction`: the same for typed batches —
-R = 3 .. 8 distinct operator channels, one sparse image each."""
+R = 3 .. 8 distinct operator channels, one sparse image each.  A DENSE collated L beyond 128
+nodes reaches the same two Functions through `_dense_operators`: its image(s), and the symmetry check that an
+edge list does not need (csrc/sparse_symmetry.hip)."""
 import os
 import warnings
 
 import torch
 
 from .. import ops
-from ._common import (LARGE_MAX_K, LARGE_MAX_OPERATORS, _spectral_mlp_param_grads, _tn_split_k, embedding_grad,
-                      head_params, input_state, masked_readout, param_grad_tuple, scatter_head_grads,
+from ._common import (LARGE_MAX_K, LARGE_MAX_OPERATORS, MID_MAX_NODES, _spectral_mlp_param_grads, _tn_split_k,
+                      embedding_grad, head_params, input_state, masked_readout, param_grad_tuple, scatter_head_grads,
                       spectral_mlp_operands)
 
 
@@ -30,6 +32,11 @@ class _LargeMixin:
     # the backward over the channels' images (_LargeTypedSparseFusedFunction), 'torch'
     # (default) = densify + autograd.  A switch of its own: each governs its own kind of batch
     large_typed_backward_impl = os.environ.get('LANCZOSNET_LARGE_BACKWARD_TYPED', 'torch')
+    # DENSE collated batches (a float32 L [B,N,N,E+1] tensor: GraphData.collate_fn, collate_graph_adjacency)
+    # beyond 128 nodes in training: 'hip' = the same backward on the sparse image(s) of the tensor, where the
+    # operators are symmetric (lnz_large_sparse_image_symmetry), 'torch' (default) = autograd
+    # through `_torch_forward`.  It governs dense tensors only; the two switches above govern theirs
+    large_dense_backward_impl = os.environ.get('LANCZOSNET_LARGE_BACKWARD_DENSE', 'torch')
 
     @torch.no_grad()
     def _torch_gains(self, D):
@@ -213,6 +220,96 @@ class _LargeMixin:
         if drop or capturing or not self._needs_grad() or not self._large_typed_backward_supported(0, L.channels):
             return False
         return int(L.images.flags.item()) == 0
+
+    def _large_dense_backward_supported(self, K, channels):
+        """The HIP backward for a dense collated L: `_large_backward_envelope`, selected by
+        `large_dense_backward_impl == 'hip'`.  WHAT the tensor is (symmetric operators as clean sparse images) is
+        `_route`'s `dense_one_operator` / `dense_channel_operators`."""
+        return self.large_dense_backward_impl == 'hip' and self._large_backward_envelope(K, channels)
+
+    def _dense_operators(self, L, K, drop, capturing):
+        """`_route`'s `dense_one_operator` ('one') / `dense_channel_operators` ('each') for this call, or None.
+        L is a dense float32 tensor on the device, beyond 128 nodes, whose operator channels are
+          'one'   ONE operator class — every channel equals channel 0: the reference's single-edge-type collate or
+                  a zero-stride expanded view — or
+          'each'  3 .. 8 distinct channels under `large_sparse_channels == 'each'`,
+        every operator SYMMETRIC (the backward forms L dP for L^T dP) and no image flag raised.  The image is the
+        one riding on L where it carries values, else it is built here and left riding on L (the Function does
+        not build it twice); the symmetry status and the flag word come back through pinned memory behind ONE
+        event.  Asked only where the answer can matter (switch on, envelope met); the verdict stays on the image
+        object, so a tensor that is reused asks once.  A refusal (channels differ under 'one', a row beyond
+        row_cap, an asymmetric operator) warns once per module and pauses the question for `large_sparse_backoff`
+        dense batches on this device, twice as many after every further refusal in a row."""
+        if self.large_dense_backward_impl != 'hip' or drop or capturing or not self._needs_grad():
+            return None
+        if isinstance(L, ops.SparseLaplacian) or not isinstance(L, torch.Tensor):
+            return None
+        if L.dim() != 4 or L.dtype != torch.float32 or not L.is_cuda:
+            return None
+        B, N, _, Cn = L.shape
+        if N <= MID_MAX_NODES or N > 65536 or Cn != self.num_edgetype + 1 \
+                or not self._large_dense_backward_supported(K, Cn):
+            return None
+        if self.large_sparse_channels not in ('one', 'each'):
+            raise ValueError("large_sparse_channels is 'one' or 'each', got %r" % (self.large_sparse_channels,))
+        kind = 'each' if (self.large_sparse_channels == 'each' and 3 <= Cn <= LARGE_MAX_OPERATORS
+                          and L.stride(3) != 0) else 'one'
+        img = ops.attached_sparse_images(L) if kind == 'each' else ops.attached_sparse_image(L)
+        if img is not None and img.values is None:
+            img = None
+        if img is not None and img.symmetric is not None:
+            return kind if img.symmetric else None
+        st = self.__dict__.setdefault('_large_dense_state', {}).setdefault(L.device.index, {})
+        if st.get('skip', 0) > 0:
+            st['skip'] -= 1
+            return None
+        st['image_from'] = 'collate' if img is not None else 'module'
+        if img is None and kind == 'each':
+            img = ops.large_sparse_image_channels(L)
+            ops.attach_sparse_images(L, img)
+        elif img is None:
+            img = ops.large_sparse_image(L, values=True)
+            ops.attach_sparse_image(L, img)
+        R = Cn if kind == 'each' else 1
+        host = st.get('host')
+        if host is None or host.numel() != 1 + R * B:
+            host = st['host'] = torch.zeros((1 + R * B,), dtype=torch.int32).pin_memory()
+        status = ops.large_sparse_image_symmetry(img)
+        host[:1].copy_(img.flags, non_blocking=True)
+        host[1:].copy_(status, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        ev.synchronize()
+        words = host.tolist()
+        flags, status = words[0], words[1:]
+        st['last_flags'], st['last_status'] = flags, status
+        img.symmetric = flags == 0 and not any(status)
+        if img.symmetric:
+            st['streak'] = 0
+            return kind
+        st['streak'] = min(st.get('streak', 0) + 1, 6)
+        st['skip'] = self.large_sparse_backoff << (st['streak'] - 1)
+        if not getattr(self, '_warned_dense_refusal', False):
+            self._warned_dense_refusal = True
+            warnings.warn("lanczosnet_amd: large_dense_backward_impl = 'hip': %s; the dense batch trains through "
+                          "the torch route, and the next %d dense batches on this device are not examined"
+                          % (self._dense_refusal(L, img, flags, status), st['skip']), UserWarning)
+        return None
+
+    @staticmethod
+    def _dense_refusal(L, img, flags, status):
+        """The first offending graph and the reason, for the warning (once per module: it may look at L)."""
+        B, cap = L.shape[0], img.cap
+        if flags & 2:
+            first = next((b for b in range(B) if int((L[b] != 0).sum(dim=1).max()) > cap), None)
+            return 'graph %s has a row of more than row_cap = %d nonzeros' % (first, cap)
+        if flags & 1:
+            first = next((b for b in range(B) if not bool((L[b] == L[b][..., :1]).all())), None)
+            return ("the operator channels of graph %s differ (large_sparse_channels = 'each' serves 3 .. %d "
+                    "distinct channels)" % (first, LARGE_MAX_OPERATORS))
+        w = next(i for i, x in enumerate(status) if x)
+        why = ' and '.join(text for bit, text in ops.SYMMETRY_REASONS if status[w] & bit)
+        return 'graph %d (operator channel %d) is not symmetric: %s' % (w % B, w // B, why)
 
     # -- channel folding of the large-graph path ------------------------------------------------
     # With one edge type (config/graph_lanczos_net.yaml:14) the collated L carries the SAME operator
@@ -450,6 +547,21 @@ class _LargeMixin:
         return masked_readout(self, state, mask)
 
 
+class _DenseBatch:
+    """What the two Functions below read of a batch — B, N, channels, image / images, n_nodes — for a dense
+    collated L whose image(s) `_dense_operators` left riding on it.  n_nodes is None: the mask need not be a
+    prefix, and rows outside it get an exactly zero gradient from the masked readout (from then on they receive
+    gradient only through L and V, as autograd computes it)."""
+    __slots__ = ('B', 'N', 'channels', 'image', 'images', 'n_nodes')
+
+    def __init__(self, L, each):
+        self.B, self.N, self.channels = L.shape[0], L.shape[1], L.shape[3]
+        self.images = ops.attached_sparse_images(L) if each else None
+        self.image = self.images.channel(0) if each else ops.attached_sparse_image(L)
+        self.n_nodes = None
+        assert self.image is not None and self.image.values is not None
+
+
 class _LargeSparseFusedFunction(torch.autograd.Function):
     """Training an edge-list batch (an untyped SparseLaplacian: ONE symmetric operator as its sparse
     image) through the HIP kernels, with no dense L.
@@ -491,7 +603,7 @@ class _LargeSparseFusedFunction(torch.autograd.Function):
             score = ops.large_head(state, mask_u8, *m._plan_head(cache))
         else:
             score = masked_readout(m, state, mask)
-        ctx.module, ctx.image, ctx.has_gains = m, img, G is not None
+        ctx.module, ctx.image, ctx.has_gains, ctx.channels = m, img, G is not None, L.channels
         ctx.save_for_backward(node_feat, X0, D, Vf, mask_u8, L.n_nodes, Xs, *([G] if G is not None else []))
         return score
 
@@ -501,7 +613,7 @@ class _LargeSparseFusedFunction(torch.autograd.Function):
         node_feat, X0, D, V, mask_u8, n_nodes, Xs = ctx.saved_tensors[:7]
         G = ctx.saved_tensors[7] if ctx.has_gains else None
         Lnum, B, N, _ = Xs.shape
-        K, S, C = V.shape[2], m.num_scale_long, 2
+        K, S, C = V.shape[2], m.num_scale_long, ctx.channels   # (C channels that are ONE operator: 2 from edge lists)
         dev = Xs.device
         grads = {}
         # ---- head (model/lanczos_net.py:185-194): autograd on the stored last state
@@ -539,7 +651,10 @@ class _LargeSparseFusedFunction(torch.autograd.Function):
             grads[id(m.filter[t].bias)] = dbg.sum(dim=0)
             if t > 0 or not m.general:
                 Wv = W.view(128, S + C, d)
-                Wn = torch.nn.functional.pad(Wv[:, S] + Wv[:, S + 1], (0, 128 - d)).contiguous()
+                Wsum = Wv[:, S]
+                for c in range(1, C):
+                    Wsum = Wsum + Wv[:, S + c]
+                Wn = torch.nn.functional.pad(Wsum, (0, 128 - d)).contiguous()
                 ops.large_grad_input(dZ, Wn, V if S > 0 else None, dY, d, out=g)
         # ---- spectral filter MLPs from dG [L, B K, S]
         if dGs:

@@ -19,7 +19,9 @@ a HIP backward of their own (`_MidGraphFusedFunction`, csrc/conv_mid_grad.hip; D
 opt-in through `mid_backward_impl`; edge-list batches beyond that (an untyped `ops.SparseLaplacian`) have
 one on their sparse image (`_LargeSparseFusedFunction`, csrc/conv_sparse_grad.hip), opt-in
 through `large_backward_impl`; typed ones (two or more edge types) through `large_typed_backward_impl`
-(`_LargeTypedSparseFusedFunction`).
+(`_LargeTypedSparseFusedFunction`); a DENSE collated `L` beyond 128 nodes whose operators are
+symmetric takes the same two Functions on the image(s) of the tensor, opt-in through `large_dense_backward_impl`
+(DESIGN.md §4.9e).
 
 One regime per module: `_small` (<= 32 nodes, the fused kernels), `_mid` (33..128 nodes, one launch),
 `_large` (beyond: streamed and sparse kernels, library GEMMs), `_ada` (AdaLanczosNet); `_common`
@@ -34,9 +36,9 @@ import torch.nn as nn
 
 from .. import ops
 from ..utils.data_helper import check_dist
-from ._common import (FUSED_MAX_NODES, FUSED_WIDTHS, MAX_CHANNELS, MAX_INPUT_DIM, MAX_SHORT_SCALES,
-                      STRIP_MAX_LONG_SCALES, STRIP_WIDTH, _opt, input_state, masked_readout)
-from ._large import _LargeMixin, _LargeSparseFusedFunction, _LargeTypedSparseFusedFunction
+from ._common import (FUSED_MAX_NODES, FUSED_WIDTHS, LARGE_MAX_OPERATORS, MAX_CHANNELS, MAX_INPUT_DIM,
+                      MAX_SHORT_SCALES, MID_MAX_NODES, STRIP_MAX_LONG_SCALES, STRIP_WIDTH, _opt, input_state, masked_readout)
+from ._large import _DenseBatch, _LargeMixin, _LargeSparseFusedFunction, _LargeTypedSparseFusedFunction
 from ._mid import _MidGraphFusedFunction, _MidMixin
 from ._small import _LanczosNetFunction, _LanczosNetFusedFunction, _SmallMixin
 
@@ -45,7 +47,10 @@ __all__ = ['LanczosNet', 'LanczosNetGeneral', 'AdaLanczosNet']
 # the routes of `_LanczosNetBase._route` that train through an autograd.Function of their own
 _TRAIN_FUNCTIONS = {'fused_train_hip': _LanczosNetFusedFunction, 'fused_train_torch': _LanczosNetFunction,
                     'mid_train_hip': _MidGraphFusedFunction, 'large_train_hip': _LargeSparseFusedFunction,
-                    'large_typed_train_hip': _LargeTypedSparseFusedFunction}
+                    'large_typed_train_hip': _LargeTypedSparseFusedFunction,
+                    'large_dense_train_hip': _LargeSparseFusedFunction,
+                    'large_dense_channels_train_hip': _LargeTypedSparseFusedFunction}
+_DENSE_TRAIN_ROUTES = ('large_dense_train_hip', 'large_dense_channels_train_hip')
 
 
 class _LanczosNetBase(_SmallMixin, _MidMixin, _LargeMixin, nn.Module):
@@ -224,13 +229,16 @@ class _LanczosNetBase(_SmallMixin, _MidMixin, _LargeMixin, nn.Module):
                 and self.input_dim <= MAX_INPUT_DIM)
 
     def _route(self, N, K, channels, needs_grad, drop, capturing, sparse_one_operator=False,
-               sparse_typed_operators=False):
+               sparse_typed_operators=False, *, dense_one_operator=False, dense_channel_operators=False):
         """The path `forward` takes for graphs of N nodes, K Ritz pairs and `channels` operator
         channels (needs_grad: `_needs_grad()`; drop: dropout > 0 in training; capturing: the
         current stream is being captured into a HIP graph; sparse_one_operator: L is an untyped
         SparseLaplacian — one operator as a sparse image with its fp32 values — and the image raised
         no flag; sparse_typed_operators: L is a typed SparseLaplacian — `channels` = 3 .. 8 distinct operators,
-        one sparse image each with its fp32 values — and the images raised no flag).  No GPU needed to ask.
+        one sparse image each with its fp32 values — and the images raised no flag; dense_one_operator: L is a dense
+        float32 tensor on the device whose channels are ONE symmetric operator, its clean image with values riding
+        on it; dense_channel_operators: ... whose 3 .. 8 channels are distinct symmetric operators under
+        `large_sparse_channels == 'each'`, their images riding on it — `_dense_operators`).  No GPU needed to ask.
           'fused'              <= 32 nodes: the fused MFMA kernels (`_hip_forward`)
           'fused_train_hip'    ... training, HIP backward (`_LanczosNetFusedFunction`)
           'fused_train_torch'  ... training, backward through `_torch_forward` (`_LanczosNetFunction`)
@@ -240,6 +248,10 @@ class _LanczosNetBase(_SmallMixin, _MidMixin, _LargeMixin, nn.Module):
           'large_train_hip'    ... an edge-list batch in training, opted in (`_LargeSparseFusedFunction`)
           'large_typed_train_hip'  ... a typed edge-list batch in training, opted in
                                (`_LargeTypedSparseFusedFunction`)
+          'large_dense_train_hip'  > 128 nodes: a dense L of one symmetric operator class in training, opted in
+                               (`_LargeSparseFusedFunction` on the tensor's image)
+          'large_dense_channels_train_hip'  ... of 3 .. 8 distinct symmetric channels, opted in
+                               (`_LargeTypedSparseFusedFunction` on the tensor's images)
           'library'            > 32 nodes or an architecture outside the fused kernels, inference:
                                hipBLASLt conv + HIP spectral gains (`_large_graph_forward`)
           'torch'              gradients or dropout outside the kernels: `_torch_forward`"""
@@ -256,6 +268,13 @@ class _LanczosNetBase(_SmallMixin, _MidMixin, _LargeMixin, nn.Module):
         if (needs_grad and not drop and not capturing and sparse_typed_operators and N > FUSED_MAX_NODES
                 and self._large_typed_backward_supported(K, channels)):
             return 'large_typed_train_hip'
+        if (needs_grad and not drop and not capturing and N > MID_MAX_NODES
+                and (dense_one_operator or dense_channel_operators)
+                and self._large_dense_backward_supported(K, channels)):
+            if dense_one_operator:
+                return 'large_dense_train_hip'
+            if self.large_sparse_channels == 'each' and 3 <= channels <= LARGE_MAX_OPERATORS:
+                return 'large_dense_channels_train_hip'
         if needs_grad or drop:
             return 'torch'
         if self._mid_hip_supported(N, K, channels):
@@ -343,9 +362,11 @@ class _LanczosNetBase(_SmallMixin, _MidMixin, _LargeMixin, nn.Module):
         ops.forget_autograd_kernel()   # (last_kernel(): the previous step's backward is history)
         N = L.shape[1]
         capturing = torch.cuda.is_current_stream_capturing()
+        dense = self._dense_operators(L, V.shape[2], drop, capturing)
         route = self._route(N, V.shape[2], L.shape[3], self._needs_grad(), drop, capturing,
                             sparse_one_operator=self._sparse_one_operator(L, drop, capturing),
-                            sparse_typed_operators=self._sparse_typed_operators(L, drop, capturing))
+                            sparse_typed_operators=self._sparse_typed_operators(L, drop, capturing),
+                            dense_one_operator=dense == 'one', dense_channel_operators=dense == 'each')
         if isinstance(L, ops.SparseLaplacian):
             # the batch of dataset.collate_graph_edges: its image serves the sparse large-graph
             # layers; every other route reads the dense tensor
@@ -358,6 +379,9 @@ class _LanczosNetBase(_SmallMixin, _MidMixin, _LargeMixin, nn.Module):
                 L = self._densify(L, "route '%s'" % route)
         if N <= FUSED_MAX_NODES and not route.startswith('fused'):
             self._warn_library_path(drop)
+        if route in _DENSE_TRAIN_ROUTES:
+            # (the two Functions read the image(s) `_dense_operators` left riding on the tensor)
+            L = _DenseBatch(L, each=route == 'large_dense_channels_train_hip')
         if route in _TRAIN_FUNCTIONS:
             # forward = HIP kernels keeping their states (runner/qm8_runner.py:216-248); backward =
             # HIP kernels + library GEMMs where built, else autograd through a torch recomputation

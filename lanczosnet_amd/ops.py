@@ -687,10 +687,11 @@ class LargeSparseImage:
   int32 = bf16(value) << 16 | column, counts [B,N], flags (one int32 on the device: bit 0 = a
   channel differs from channel 0, bit 1 = a row overflowed `cap`; non-zero = the image must not be
   used)."""
-  __slots__ = ('entries', 'counts', 'flags', 'cap', 'B', 'N', 'version', 'values')
+  __slots__ = ('entries', 'counts', 'flags', 'cap', 'B', 'N', 'version', 'values', 'symmetric')
 
   def __init__(self, entries, counts, flags, cap, values=None):
     self.entries, self.counts, self.flags, self.cap = entries, counts, flags, cap
+    self.symmetric = None   # the verdict of large_sparse_image_symmetry + flags, once somebody asked (a bool)
     self.values = values   # [B,N,cap] fp32: the unrounded entries (the exact-fp32 form), or None
     self.B, self.N = counts.shape
     self.version = None   # the source tensor's version counter when the image rides on it (attach_sparse_image)
@@ -702,6 +703,21 @@ def attach_sparse_image(L, img):
   of L (`.to()`, `.clone()`, a DataParallel scatter) does not carry it."""
   img.version = L._version
   L._lnz_sparse_image = img
+
+
+def attach_sparse_images(L, imgs):
+  """The same for the per-channel images of a dense L with distinct channels (large_sparse_image_channels)."""
+  imgs.version = L._version
+  L._lnz_sparse_images = imgs
+
+
+def attached_sparse_images(L):
+  """The per-channel images riding on L (attach_sparse_images), or None when there are none or L changed since."""
+  imgs = getattr(L, '_lnz_sparse_images', None)
+  if imgs is None or imgs.version != L._version or (imgs.B, imgs.N, imgs.R) != (L.shape[0], L.shape[1], L.shape[3]) \
+      or imgs.entries.device != L.device:
+    return None
+  return imgs
 
 
 def attached_sparse_image(L):
@@ -777,10 +793,12 @@ class LargeSparseImages:
   lnz_laplacian_l4_typed_edges_images): entries [R,B,N,cap] int32, values [R,B,N,cap] fp32 (or None),
   counts [R,B,N], flags (one int32 on the device: bit 1 = a row overflowed `cap`; non-zero = the images
   must not be used).  `.channel(c)` is channel c as a LargeSparseImage (views, the shared flag word)."""
-  __slots__ = ('entries', 'counts', 'flags', 'cap', 'R', 'B', 'N', 'values')
+  __slots__ = ('entries', 'counts', 'flags', 'cap', 'R', 'B', 'N', 'values', 'version', 'symmetric')
 
   def __init__(self, entries, counts, flags, cap, values=None):
     self.entries, self.counts, self.flags, self.cap, self.values = entries, counts, flags, cap, values
+    self.version = None     # the source tensor's version counter when the images ride on it (attach_sparse_images)
+    self.symmetric = None   # as LargeSparseImage.symmetric
     self.R, self.B, self.N = counts.shape
 
   def channel(self, c):
@@ -812,6 +830,31 @@ def large_sparse_image_channels(L, row_cap=None, values=True):
     _abi().large_sparse_image_channels(L, sb, sr, sc, sch, B, N, Cn, cap, imgs.entries, imgs.values, imgs.counts,
                                        imgs.flags)
   return imgs
+
+
+SYMMETRY_REASONS = ((1, 'an entry (i, j) without an entry (j, i)'),
+                    (2, 'entries (i, j) and (j, i) more than one fp32 ulp apart'))
+
+
+def large_sparse_image_symmetry(img, out=None):
+  """lnz_large_sparse_image_symmetry on the current stream: img a LargeSparseImage or LargeSparseImages WITH
+  `values` -> status [R*B] int32 on the device (R = 1 for one image), word r B + b: bit 0 = an entry (i, j, v) of
+  graph b, channel r, has no entry with column i in row j; bit 1 = its mirror's value differs from v by more than
+  one fp32 ulp (SYMMETRY_REASONS).  All zero: every operator of the image is symmetric.  Safe (and meaningless) on
+  an image whose flags are raised."""
+  if img.values is None:
+    raise ValueError('large_sparse_image_symmetry: the image carries no fp32 values')
+  R = img.R if isinstance(img, LargeSparseImages) else 1
+  B, N = img.B, img.N
+  _need_cuda(img.entries, img.values, img.counts, out)
+  assert img.entries.is_contiguous() and img.values.is_contiguous() and img.counts.is_contiguous()
+  assert img.entries.shape[-1] == img.values.shape[-1] == img.cap
+  if out is None:
+    out = torch.empty((R * B,), dtype=torch.int32, device=img.entries.device)
+  assert out.dtype == torch.int32 and out.is_contiguous() and out.numel() == R * B
+  with torch.cuda.device(img.entries.device):
+    _abi().large_sparse_image_symmetry(img.entries, img.values, img.counts, img.cap, R, B, N, out)
+  return out
 
 
 # ---- large graphs from edge lists (csrc/edge_image.hip): no N x N tensor ----------------------------

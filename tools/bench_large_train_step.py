@@ -18,8 +18,13 @@ switch on only —, each with two edge types drawn per edge): the same two route
 (lnz_large_sparse_conv_split_f32) beside R launches of lnz_large_sparse_conv_f32 onto zeroed buffers on the same
 operands.  They are written to profiles/large_typed_train_step.json.
 
-    python tools/bench_large_train_step.py [--shapes config5,wide | typed,typed_wide] [--windows 3] [--steps 2]
-                                           [--batch B] [--out profiles/large[_typed]_train_step.json]
+DENSE shape (`dense`: config 5's graphs through `collate_graph_adjacency`, L a [B,N,N,2] float32 tensor): the dense
+switch (`large_dense_backward_impl`) off — the parent's route, bit for bit: the yardstick — and on,
+in the same run on the same batch; the image pass's and the symmetry kernel's own times from device events; and
+the edge-list HIP step of the same graphs beside them.  Written to profiles/large_dense_train_step.json.
+
+    python tools/bench_large_train_step.py [--shapes config5,wide | typed,typed_wide | dense] [--windows 3]
+                                           [--steps 2] [--batch B] [--out profiles/large[_typed|_dense]_train_step.json]
 """
 import argparse
 import gc
@@ -41,7 +46,7 @@ TYPED = {'typed': 'config5', 'typed_wide': 'wide'}   # typed shape -> the graphs
 TYPED_E = 2
 
 
-def net_for(K, dev, impl, E=1):
+def net_for(K, dev, impl, E=1, dense=False):
   import torch
   import oracle
   from lanczosnet_amd.model import LanczosNetGeneral
@@ -53,8 +58,9 @@ def net_for(K, dev, impl, E=1):
   net.load_state_dict({k: torch.from_numpy(v) for k, v in P.items()})
   net = net.to(dev)
   net.gemm_mode = 'fp32'
-  net.large_backward_impl = impl if E == 1 else 'torch'
-  net.large_typed_backward_impl = impl if E > 1 else 'torch'
+  net.large_backward_impl = impl if E == 1 and not dense else 'torch'
+  net.large_typed_backward_impl = impl if E > 1 and not dense else 'torch'
+  net.large_dense_backward_impl = impl if dense else 'torch'
   return net
 
 
@@ -93,11 +99,11 @@ def gather_record(imgs, reps=10):
   return rec
 
 
-def route(impl, b, K, dev, windows, steps, E=1):
+def route(impl, b, K, dev, windows, steps, E=1, dense=False):
   """-> the record of one route on the resident batch `b`: one warm step, then the timed windows."""
   import torch
   from lanczosnet_amd import ops
-  net = net_for(K, dev, impl, E)
+  net = net_for(K, dev, impl, E, dense)
   opt = torch.optim.Adam(net.parameters(), lr=1e-4)
 
   def step():
@@ -129,6 +135,75 @@ def route(impl, b, K, dev, windows, steps, E=1):
   return out
 
 
+def timed(fn, reps=10):
+  """ms of fn() from device events around each of `reps` calls, after one warm call."""
+  import torch
+  fn()
+  torch.cuda.synchronize()
+  ms = []
+  for _ in range(reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    torch.cuda.synchronize()
+    ms.append(round(e0.elapsed_time(e1), 4))
+  return stats(ms)
+
+
+def dense_shape(s, args, dev):
+  """config 5's graphs as the dense collate's batch: switch off / on, the two kernels alone, the edge-list step."""
+  import torch
+  from lanczosnet_amd import ops
+  from lanczosnet_amd.dataset import collate_graph_adjacency, collate_graph_edges
+  rs = np.random.RandomState(5)
+  N = s['N']
+  graphs = [gnp_edges(N, s['p'], rs) for _ in range(s['B'])]
+  feats = [(rs.randn(N, 10).astype(np.float32), rs.randn(1, 2)) for _ in graphs]
+  rec = dict(s, edges_per_graph=int(np.mean([g.shape[0] for g in graphs])), dense_L_bytes=int(s['B'] * N * N * 4 * 2))
+
+  def adjacency(g):
+    A = np.zeros((N, N, 1), np.float32)
+    A[g[:, 0], g[:, 1], 0] = 1.0
+    A[g[:, 1], g[:, 0], 0] = 1.0
+    return A
+  b = collate_graph_adjacency([dict(adjs=adjacency(g), node_feat=x, label=y) for g, (x, y) in zip(graphs, feats)],
+                              s['K'], device=dev, lanczos_steps=s['M'])
+  L = b['L']
+  riding = ops.attached_sparse_image(L)
+  rec['image_rides_on_L'] = riding is not None and riding.values is not None
+  # the two kernels alone, on this batch
+  out = {}
+
+  def image():
+    out['img'] = ops.large_sparse_image(L, values=True)
+
+  def check():
+    out['status'] = ops.large_sparse_image_symmetry(out['img'])
+  rec['image_pass_ms'] = timed(image)
+  rec['symmetry_ms'] = timed(check)
+  img, status = out['img'], out['status']
+  rec['image_flags'] = int(img.flags.item())
+  rec['status_nonzero_words'] = int((status != 0).sum().item())
+  rec['image_entries'] = int(img.counts.sum().item())
+  rec['row_cap'] = img.cap
+  del out, img, status
+  torch.cuda.empty_cache()
+  for impl in ('torch', 'hip'):
+    rec['large_dense_backward_' + impl] = route(impl, b, s['K'], dev, args.windows, args.steps, dense=True)
+    torch.cuda.empty_cache()
+  del b, L, riding
+  torch.cuda.empty_cache()
+  be = collate_graph_edges([dict(edges=g, node_feat=x, label=y) for g, (x, y) in zip(graphs, feats)], s['K'],
+                           device=dev, lanczos_steps=s['M'])
+  rec['edge_list_backward_hip'] = route('hip', be, s['K'], dev, args.windows, args.steps)
+  t, h, e = (rec[k] for k in ('large_dense_backward_torch', 'large_dense_backward_hip', 'edge_list_backward_hip'))
+  rec['hip_over_torch'] = dict(step_ms=round(h['step_ms']['median'] / t['step_ms']['median'], 4),
+                               peak_bytes=round(h['peak_bytes'] / t['peak_bytes'], 4))
+  rec['dense_hip_minus_edge_list_hip_ms'] = round(h['step_ms']['median'] - e['step_ms']['median'], 4)
+  return rec
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--shapes', default='config5,wide')
@@ -138,11 +213,13 @@ def main():
   ap.add_argument('--out', default=None)
   args = ap.parse_args()
   names = args.shapes.split(',')
-  if len({n in TYPED for n in names}) != 1:
-    raise SystemExit('bench_large_train_step: typed and untyped shapes go to files of their own: one kind per run')
-  typed = names[0] in TYPED
+  kinds = {'typed' if n in TYPED else 'dense' if n == 'dense' else 'plain' for n in names}
+  if len(kinds) != 1:
+    raise SystemExit('bench_large_train_step: typed, dense and untyped shapes go to files of their own: one kind per run')
+  typed, dense = kinds == {'typed'}, kinds == {'dense'}
   if args.out is None:
-    args.out = os.path.join(ROOT, 'profiles', 'large_typed_train_step.json' if typed else 'large_train_step.json')
+    args.out = os.path.join(ROOT, 'profiles', 'large_typed_train_step.json' if typed else
+                            'large_dense_train_step.json' if dense else 'large_train_step.json')
   import torch
   if not torch.cuda.is_available():
     raise SystemExit('bench_large_train_step: needs the MI355X (no CPU fallback)')
@@ -151,11 +228,17 @@ def main():
   result = dict(device=torch.cuda.get_device_name(0), windows=args.windows, workload='LanczosNetGeneral 7 x 128, '
                 'eight long scales, train step (fwd + bwd + Adam), graphs from edge lists', shapes={})
   warnings.simplefilter('ignore')
+  if dense:
+    result['workload'] += ' and as the dense collated L'
   for name in names:
-    s = dict(SHAPES[TYPED.get(name, name)])
+    s = dict(SHAPES[TYPED.get(name, 'config5' if dense else name)])
     E = TYPED_E if typed else 1
     if args.batch:
       s['B'] = args.batch
+    if dense:
+      result['shapes'][name] = rec = dense_shape(s, args, dev)
+      print(json.dumps({name: rec}))
+      continue
     rs = np.random.RandomState(5)
     graphs = [gnp_edges(s['N'], s['p'], rs) for _ in range(s['B'])]
     items = [dict(edges=g, node_feat=rs.randn(s['N'], 10).astype(np.float32), label=rs.randn(1, 2)) for g in graphs]

@@ -38,6 +38,8 @@ extern "C" {
  *    lnz_large_grad_input_channels: additive, the version stays);
  *    + the symmetry check of a sparse image (lnz_large_sparse_image_symmetry: what lets a dense collated batch
  *    take that backward; additive, the version stays);
+ *    + the GAT baseline's attention and readout (lnz_gat_attention, lnz_gat_readout: additive, the version
+ *    stays);
  * 6: lnz_forward_args lost Wp16 / w16_off / Wp16_head / Lp16 (gemm_mode 1 is now the split precision
  *    inside the strip kernel: lnz_pack_rows_k8_split; lnz_pack_rows_f16x2 and
  *    lnz_pack_laplacian_f16x2 are gone) and gained dbias_part_cap; + lnz_midgraph_forward,
@@ -1084,6 +1086,35 @@ int lnz_f32_linear(const float* x, int ldx, const float* w, int ldw, const float
                    int M, int N, int K, float* out, int ldo, float* partials, lnz_stream_t stream);
 int lnz_f32_linear_splits(int M, int N, int K);
 int64_t lnz_f32_linear_workspace_floats(int M, int N, int K);
+
+/* ---- the GAT baseline (model/gat.py, config/qm8_gat.yaml): attention and readout --------------
+ * One layer's dense additive attention for all C channels x H heads (replaces model/gat.py:153-175;
+ * the projection :150-152 is ONE lnz_f32_linear on the stacked weight [C H Dh, Din]).  Block
+ * c H + h of Dh columns of Wh [B N, ldw] is head h of channel c; per block
+ *   s1 = Wh a1 + b1, s2 = Wh a2 + b2                                   (att_net_1 / att_net_2)
+ *   e[i][j] = leaky_relu(s1[i] + s2[j], 0.2) + L[b, i, j, c]
+ *   att[:, j] = softmax over the row index i, per column j             (F.softmax(.., dim=1), :158-160)
+ *   out[i] = sum_j att[i][j] Wh[j] + bias ;  ELU if `elu`             (:166-175)
+ * written to the same block of out [B N, ldo].  L (element (b, i, j, c) at b stride_b + i stride_r +
+ * j stride_c + c stride_ch floats, strides >= 0: a sliced or expanded view is read in place) is ADDED
+ * to the logits, it masks nothing — all N rows and columns of the padded batch take part, there is no
+ * node count.  a1, a2, bias [C H][Dh], b1, b2 [C H]; `bias` is what the caller resolved (the
+ * reference's aliased list reads bias_{h}_{C-1}_{t} for every channel).  out must not alias Wh.
+ * 1 <= N <= 32, C <= 8, H <= 16, Dh a multiple of 4 and <= 32, ldw / ldo multiples of 4 (LNZ_ENOTSUP
+ * otherwise); Wh, bias, out 16-byte aligned.  Column maximum subtracted, full-precision expf / expm1f,
+ * every sum in a fixed order: bit-reproducible.  One workgroup per (molecule, channel), 40 KB of LDS. */
+int lnz_gat_attention(const float* Wh, int ldw, const float* L, int64_t stride_b, int64_t stride_r,
+                      int64_t stride_c, int64_t stride_ch, const float* a1, const float* b1,
+                      const float* a2, const float* b2, const float* bias, int B, int N, int C, int H,
+                      int Dh, int elu, float* out, int ldo, lnz_stream_t stream);
+/* The last layer's head mean and the gated masked-mean readout in one launch (replaces
+ * model/gat.py:177-196): x[i] = (1 / CH) sum of the CH blocks of Dh columns of Hlast [B N, ld], blocks
+ * ascending; y[i] = (Wo x[i] + bo) * sigmoid(wg x[i] + bg); score [B, P] = mean of y over the rows with
+ * mask != 0 (mask [B, N] u8; NULL: all N rows).  No masked row: NaN, like the reference's empty mean.
+ * Wo [P][Dh], bo [P], wg [Dh], bg [1].  N <= 32, Dh <= 32, P <= 16 (LNZ_ENOTSUP otherwise). */
+int lnz_gat_readout(const float* Hlast, int ld, const uint8_t* mask, const float* Wo, const float* bo,
+                    const float* wg, const float* bg, int B, int N, int CH, int Dh, int P, float* score,
+                    lnz_stream_t stream);
 
 
 /* ---- next row (SURVEY.md 8f rank 1 + 3): device-side collate from a packed molecule shard ----

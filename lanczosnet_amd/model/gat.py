@@ -1,0 +1,260 @@
+"""`GAT` (reference `model/gat.py:8-201`, `config/qm8_gat.yaml`) on the hand-written attention and
+readout kernels (csrc/gat.hip).
+
+Same constructor keys, `forward(node_feat, L, label=None, mask=None)`, `state_dict` keys and shapes,
+`named_parameters()` order (the root module's `bias_*` first) and `_init_param` draws as the
+reference, so `from model import *` picks the class up by name and a reference checkpoint loads
+unchanged.  Four properties of the reference are reproduced, not fixed:
+`L` is ADDED to the logits (every padded row and column takes part; the mask enters only the final
+mean), the softmax runs over the ROW index per column, every channel of a layer reads the bias of
+the LAST channel (`bias_{h}_{E}_{t}`; the others are registered, saved and never read), and the
+parameter order above.
+
+Route 'gat_hip' (inference, and training calls that need no gradient): per layer ONE `f32_linear`
+launch on the weight stack [C H Dh, Din], then `gat_attention`; `gat_readout` after the last layer.
+Everything else — gradients, dropout in training, shapes outside the kernels — takes 'gat_torch', a
+device-side differentiable torch restatement, with one UserWarning per module that names the reason.
+There is no CPU path and no HIP backward.
+"""
+import warnings
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .. import ops
+from ._common import _opt
+
+__all__ = ['GAT']
+
+# the envelope of route 'gat_hip' beyond the kernels' own (ops.GAT_MAX_*): lnz_f32_linear's K, and the
+# widths one stacked launch was sized for
+GAT_MAX_WIDTH = 1024        # C H Dh, a multiple of GAT_WIDTH_STEP
+GAT_WIDTH_STEP = 32         # ... and of the input width (lnz_f32_linear: K a multiple of 32)
+
+
+class GAT(nn.Module):
+    """Graph Attention Networks (Velickovic et al., ICLR 2018) as the reference builds it for QM8."""
+
+    def __init__(self, config):
+        super().__init__()
+        m = config.model
+        self.input_dim = m.input_dim
+        self.hidden_dim = list(m.hidden_dim)
+        self.output_dim = m.output_dim
+        self.num_layer = m.num_layer
+        self.num_heads = list(m.num_heads)
+        self.dropout = _opt(m, 'dropout', 0.0)
+        self.num_atom = config.dataset.num_atom
+        self.num_edgetype = config.dataset.num_bond_type
+        C, T = self.num_edgetype + 1, self.num_layer
+
+        # creation order == reference (RNG parity and named_parameters order): model/gat.py:28-75
+        self.embedding = nn.Embedding(self.num_atom, self.input_dim)
+        dims = [self.input_dim] + self.hidden_dim + [self.output_dim]
+
+        def per_head(make):
+            return nn.ModuleList([nn.ModuleList([nn.ModuleList([make(t) for _ in range(self.num_heads[t])])
+                                                 for _ in range(C)]) for t in range(T)])
+        self.filter = per_head(lambda t: nn.Linear(dims[t] * (1 if t == 0 else self.num_heads[t] * C),
+                                                   dims[t + 1], bias=False))
+        self.att_net_1 = per_head(lambda t: nn.Linear(dims[t + 1], 1))
+        self.att_net_2 = per_head(lambda t: nn.Linear(dims[t + 1], 1))
+        for t in range(T):
+            for c in range(C):
+                for h in range(self.num_heads[t]):
+                    self.register_parameter('bias_%d_%d_%d' % (h, c, t), nn.Parameter(torch.zeros(dims[t + 1])))
+        self.att_func = nn.Sequential(nn.Linear(dims[-2], 1), nn.Sigmoid())
+        self.output_func = nn.Sequential(nn.Linear(dims[-2], dims[-1]))
+
+        losses = {'CrossEntropy': nn.CrossEntropyLoss, 'MSE': nn.MSELoss, 'L1': nn.L1Loss}
+        if m.loss not in losses:
+            raise ValueError("Non-supported loss function!")
+        self.loss_func = losses[m.loss]()
+        self._init_param()
+        self._pack_cache = None
+        self._param_list = None
+        self.last_route = None
+
+    def _init_param(self):
+        # model/gat.py:88-123: Xavier-uniform weights, zero biases, in this order
+        heads = lambda nets: [l for per_t in nets for per_c in per_t for l in per_c]  # noqa: E731
+        for group in (list(self.att_func), list(self.output_func), heads(self.filter),
+                      heads(self.att_net_1), heads(self.att_net_2)):
+            for layer in group:
+                if isinstance(layer, nn.Linear):
+                    nn.init.xavier_uniform_(layer.weight.data)
+                    if layer.bias is not None:
+                        layer.bias.data.zero_()
+
+    # -- the parameters of one layer as stacked operands, block order c H + h ------------------------
+    def _used_bias(self, h, t):
+        """model/gat.py:62-70: the list of lists repeats ONE inner list, so every channel of layer t,
+        head h reads the parameter of the last channel.  Resolved by name at forward time (a replica
+        under nn.DataParallel reads its own copy)."""
+        return getattr(self, 'bias_%d_%d_%d' % (h, self.num_edgetype, t))
+
+    def _layer_operands(self, t):
+        """(W [C H, Dh, Din], a1 [C H, Dh], b1 [C H], a2, b2, bias [C H, Dh]) of the live parameters."""
+        blocks = [(c, h) for c in range(self.num_edgetype + 1) for h in range(self.num_heads[t])]
+        W = torch.stack([self.filter[t][c][h].weight for c, h in blocks])
+        a1 = torch.cat([self.att_net_1[t][c][h].weight for c, h in blocks])
+        b1 = torch.cat([self.att_net_1[t][c][h].bias for c, h in blocks])
+        a2 = torch.cat([self.att_net_2[t][c][h].weight for c, h in blocks])
+        b2 = torch.cat([self.att_net_2[t][c][h].bias for c, h in blocks])
+        bias = torch.stack([self._used_bias(h, t) for c, h in blocks])
+        return W, a1, b1, a2, b2, bias
+
+    def _param_signature(self):
+        """What the stacked operands are keyed on: the tensor version of every parameter (an optimizer step
+        or any other in-place update bumps it) and the device.  The parameter list is walked once per
+        plan, not per call: 2,357 parameters at the yaml shape."""
+        if self._param_list is None:
+            self._param_list = list(self.parameters())
+        return (str(self.embedding.weight.device),) + tuple(p._version for p in self._param_list)
+
+    def invalidate_plan(self):
+        """Drop the stacked operands.  Writes that bump no tensor version (`p.data.clamp_()`, `p.data = x`,
+        the reference's own `_init_param` idiom) and a parameter replaced by another object need this
+        call.  `load_state_dict` and `.to()/.cuda()/.float()` call it themselves."""
+        self._pack_cache = None
+        self._param_list = None
+
+    def _apply(self, fn, *a, **kw):
+        self.invalidate_plan()
+        return super()._apply(fn, *a, **kw)
+
+    def load_state_dict(self, *a, **kw):
+        self.invalidate_plan()
+        return super().load_state_dict(*a, **kw)
+
+    @torch.no_grad()
+    def _packs(self):
+        sig = self._param_signature()
+        if self._pack_cache is not None and self._pack_cache[0] == sig:
+            return self._pack_cache[1]
+        layers = []
+        for t in range(self.num_layer):
+            W, a1, b1, a2, b2, bias = self._layer_operands(t)
+            layers.append(tuple(x.detach().float().contiguous()
+                                for x in (W.reshape(-1, W.shape[2]), a1, b1, a2, b2, bias)))
+        head = tuple(x.detach().float().contiguous() for x in (
+            self.output_func[0].weight, self.output_func[0].bias, self.att_func[0].weight, self.att_func[0].bias))
+        self._pack_cache = (sig, (layers, head))
+        return self._pack_cache[1]
+
+    # -- which route serves a call ----------------------------------------------------------------
+    def _needs_grad(self):
+        return torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+
+    def _why_not_hip(self, N, L, needs_grad, drop):
+        """None when route 'gat_hip' serves the call, else the reason in words.  No GPU needed to ask."""
+        C, T = self.num_edgetype + 1, self.num_layer
+        if needs_grad:
+            return 'gradients are required (there is no HIP backward)'
+        if drop:
+            return 'dropout=%r in training' % self.dropout
+        if N > ops.GAT_MAX_NODES:
+            return '%d nodes > %d' % (N, ops.GAT_MAX_NODES)
+        Dh, H = self.hidden_dim[0], self.num_heads[0]
+        if set(self.hidden_dim[:T]) != {Dh} or set(self.num_heads[:T]) != {H}:
+            return 'hidden_dim=%r / num_heads=%r are not uniform' % (self.hidden_dim, self.num_heads)
+        if (C > ops.GAT_MAX_CHANNELS or H > ops.GAT_MAX_HEADS or Dh > ops.GAT_MAX_HEAD_WIDTH or Dh % 4
+                or (C * H * Dh) % GAT_WIDTH_STEP or C * H * Dh > GAT_MAX_WIDTH):
+            return ('%d channels x %d heads of width %d (kernel: <= %d x <= %d of a width that is a multiple of 4 '
+                    'and <= %d, %d | C H Dh <= %d)' % (C, H, Dh, ops.GAT_MAX_CHANNELS, ops.GAT_MAX_HEADS,
+                                                      ops.GAT_MAX_HEAD_WIDTH, GAT_WIDTH_STEP, GAT_MAX_WIDTH))
+        if self.input_dim % GAT_WIDTH_STEP:
+            return 'input_dim=%d is not a multiple of %d' % (self.input_dim, GAT_WIDTH_STEP)
+        if self.output_dim > ops.GAT_MAX_OUTPUTS:
+            return 'output_dim=%d > %d' % (self.output_dim, ops.GAT_MAX_OUTPUTS)
+        if L.dtype != torch.float32 or L.dim() != 4 or L.shape[3] != C:
+            return 'L is %s %s, not float32 [B, N, N, %d]' % (L.dtype, tuple(L.shape), C)
+        if self.embedding.weight.dtype != torch.float32:
+            return 'the parameters are %s, not float32' % self.embedding.weight.dtype
+        return None
+
+    def _to_module_device(self, dev, **tensors):
+        """The reference's runner hands over host tensors (runner/qm8_runner.py:301-302 leaves L on the
+        host): inputs that are not on the module's device are moved there, with one warning per module."""
+        out, moved = {}, []
+        for k, t in tensors.items():
+            if isinstance(t, torch.Tensor) and t.device != dev:
+                moved.append(k)
+                t = t.to(dev, non_blocking=True)
+            out[k] = t
+        if moved and not getattr(self, '_warned_host_inputs', False):
+            warnings.warn('lanczosnet_amd: input(s) %s were not on %s and were moved there '
+                          '(reference runner/qm8_runner.py:301-302 leaves L on the host); keep the '
+                          'batch resident on the GPU to avoid the copy' % (', '.join(moved), dev))
+            self._warned_host_inputs = True
+        return out
+
+    def forward(self, node_feat, L, label=None, mask=None):
+        """node_feat [B, N] long, L [B, N, N, E + 1] float, label [B, P], mask [B, N] (None: the mean
+        runs over all N rows, model/gat.py:192-194) -> score [B, P], or (score, loss) with a label."""
+        dev = self.embedding.weight.device
+        if dev.type != 'cuda':
+            raise RuntimeError('lanczosnet_amd models run on the AMD GPU only: move the '
+                               'module and its inputs to cuda (no CPU fallback)')
+        t = self._to_module_device(dev, node_feat=node_feat, L=L, label=label, mask=mask)
+        node_feat, L, label, mask = t['node_feat'], t['L'], t['label'], t['mask']
+        drop = self.training and self.dropout > 0
+        why = self._why_not_hip(node_feat.shape[1], L, self._needs_grad(), drop)
+        if why is None:
+            self.last_route = 'gat_hip'
+            score = self._hip_forward(node_feat, L, mask)
+        else:
+            self.last_route = 'gat_torch'
+            if not getattr(self, '_warned_torch_route', False):
+                warnings.warn('lanczosnet_amd: GAT takes the differentiable torch restatement (route '
+                              "'gat_torch', slower than the HIP kernels of route 'gat_hip'): %s" % why)
+                self._warned_torch_route = True
+            score = self._torch_forward(node_feat, L, mask, dropout=drop)
+        if label is not None:
+            return score, self.loss_func(score, label)
+        return score
+
+    @torch.no_grad()
+    def _hip_forward(self, node_feat, L, mask):
+        layers, head = self._packs()
+        H, T = self.num_heads[0], self.num_layer
+        state = self.embedding.weight.detach()[node_feat]
+        for t in range(T):
+            state = ops.gat_layer(state, L, *layers[t], H, elu=t < T - 1)
+        return ops.gat_readout(state, mask, *head, (self.num_edgetype + 1) * H)
+
+    def _torch_forward(self, node_feat, L, mask, dropout=False):
+        """Differentiable torch restatement of model/gat.py:142-196 on device tensors, all C H heads of
+        a layer batched.  dropout=True draws what the reference draws per head: the head's copy of the
+        state, its attention block and its Wh (model/gat.py:149,161-163)."""
+        p = self.dropout
+        B, N = node_feat.shape
+        C, T = self.num_edgetype + 1, self.num_layer
+        state = self.embedding(node_feat)
+        Lc = L.to(state.dtype).permute(0, 3, 1, 2)                       # [B, C, N, N]
+        for t in range(T):
+            H = self.num_heads[t]
+            W, a1, b1, a2, b2, bias = self._layer_operands(t)
+            CH, Dh, Din = W.shape
+            if dropout:
+                xh = F.dropout(state.unsqueeze(1).expand(B, CH, N, Din), p, True)
+                Wh = torch.einsum('bknd,kod->bkno', xh, W)
+            else:
+                Wh = (state.reshape(B * N, Din) @ W.reshape(CH * Dh, Din).t()).view(B, N, CH, Dh).permute(0, 2, 1, 3)
+            s1 = torch.einsum('bknd,kd->bkn', Wh, a1) + b1.view(1, CH, 1)
+            s2 = torch.einsum('bknd,kd->bkn', Wh, a2) + b2.view(1, CH, 1)
+            e = F.leaky_relu(s1.unsqueeze(3) + s2.unsqueeze(2), 0.2) + Lc.repeat_interleave(H, dim=1)
+            att = torch.softmax(e, dim=2)                                # over the ROW index, per column
+            if dropout:
+                att, Wh = F.dropout(att, p, True), F.dropout(Wh, p, True)
+            out = att @ Wh + bias.view(1, CH, 1, Dh)
+            if t == T - 1:
+                state = out.mean(dim=1)
+            else:
+                state = F.elu(out).permute(0, 2, 1, 3).reshape(B, N, CH * Dh)
+        y = self.output_func(state) * self.att_func(state)
+        if mask is None:
+            return y.mean(dim=1)
+        mk = (mask != 0).to(y.dtype).unsqueeze(2)
+        return (y * mk).sum(dim=1) / mk.sum(dim=1)

@@ -8,6 +8,8 @@ Reference interfaces replaced (paths relative to the reference repo):
   spectral_gains      model/lanczos_net.py:110-113,118-121,146-149
   lanczosnet_forward  model/lanczos_net.py:114-117,154-194
   unsorted_segment_sum operators/functions/unsorted_segment_sum.py:8-44
+  gat_attention       model/gat.py:153-175 (every channel and head of a layer; gat_layer adds :150-152)
+  gat_readout         model/gat.py:177-196
 """
 import torch
 
@@ -2352,6 +2354,92 @@ def _f32_linear_workspace(M, N, K, device):
   while len(_F32_LINEAR_WS) > _F32_LINEAR_WS_ENTRIES:
     _F32_LINEAR_WS.popitem(last=False)
   return ws
+
+
+# ----------------------------------------------------------------------------------------- GAT
+GAT_MAX_NODES, GAT_MAX_CHANNELS, GAT_MAX_HEADS, GAT_MAX_HEAD_WIDTH, GAT_MAX_OUTPUTS = 32, 8, 16, 32, 16
+
+
+def _gat_rows(x, who):
+  """The one row stride (floats) of a float32 [B, N, W] block whose B N rows are W contiguous floats."""
+  if x.dtype != torch.float32 or x.dim() != 3 or (x.shape[2] > 1 and x.stride(2) != 1):
+    raise LnzError(_lib.LNZ_EINVAL, '%s: needs a float32 [B, N, W] operand with unit column stride' % who)
+  B, N, W = x.shape
+  if N > 1:
+    ld = x.stride(1)
+    if B > 1 and x.stride(0) != N * ld:
+      raise LnzError(_lib.LNZ_EINVAL, '%s: the rows of all molecules need one stride' % who)
+    return ld
+  return x.stride(0) if B > 1 else W
+
+
+def gat_attention(Wh, L, a1, b1, a2, b2, bias, H, elu=True, out=None):
+  """lnz_gat_attention (model/gat.py:153-175 for every channel and head of a layer): Wh [B, N, C H Dh]
+  (block c H + h: what f32_linear writes for the stacked weight; a row stride beyond the width is
+  fine), L [B, N, N, C] float32 in any strides (ADDED to the logits, all N rows take part), a1 / a2 /
+  bias [C H, Dh], b1 / b2 [C H] -> out [B, N, C H Dh] = [elu](softmax_rows(leaky_relu(s1[i] + s2[j])
+  + L) @ Wh + bias) per block."""
+  _need_cuda(Wh, L, a1, b1, a2, b2, bias, out)
+  if Wh.dim() != 3 or L.dim() != 4 or L.dtype != torch.float32:
+    raise LnzError(_lib.LNZ_EINVAL, 'gat_attention: Wh [B, N, C H Dh] and a float32 L [B, N, N, C] expected')
+  B, N, width = Wh.shape
+  C = L.shape[3]
+  H = int(H)
+  if tuple(L.shape[:3]) != (B, N, N) or H < 1 or width % (C * H) != 0:
+    raise LnzError(_lib.LNZ_EINVAL, 'gat_attention: Wh %s, L %s, H = %d do not fit'
+                   % (tuple(Wh.shape), tuple(L.shape), H))
+  Dh = width // (C * H)
+  ldw = _gat_rows(Wh, 'gat_attention')
+  a1, a2, bias = _f32c(a1), _f32c(a2), _f32c(bias)
+  b1, b2 = _f32c(b1).reshape(-1), _f32c(b2).reshape(-1)
+  for t, shape in ((a1, (C * H, Dh)), (a2, (C * H, Dh)), (bias, (C * H, Dh)), (b1, (C * H,)), (b2, (C * H,))):
+    if tuple(t.shape) != shape:
+      raise LnzError(_lib.LNZ_EINVAL, 'gat_attention: operand of shape %s where %s is expected'
+                     % (tuple(t.shape), shape))
+  if out is None:
+    out = torch.empty((B, N, width), dtype=torch.float32, device=Wh.device)
+  if tuple(out.shape) != (B, N, width):
+    raise LnzError(_lib.LNZ_EINVAL, 'gat_attention: out %s, expected %s' % (tuple(out.shape), (B, N, width)))
+  ldo = _gat_rows(out, 'gat_attention')
+  with torch.cuda.device(Wh.device):
+    _abi().gat_attention(Wh, ldw, L, L.stride(0), L.stride(1), L.stride(2), L.stride(3), a1, b1, a2, b2, bias,
+                         B, N, C, H, Dh, int(bool(elu)), out, ldo)
+  return out
+
+
+def gat_readout(Hlast, mask, Wo, bo, wg, bg, CH):
+  """lnz_gat_readout (model/gat.py:177-196): Hlast [B, N, CH Dh] (the last layer's blocks) -> score
+  [B, P] = mean over the rows with mask != 0 (mask None: all N rows) of (Wo x + bo) * sigmoid(wg x +
+  bg), x = the mean of the CH blocks.  Wo [P, Dh], bo [P], wg [1, Dh] or [Dh], bg [1]."""
+  _need_cuda(Hlast, mask, Wo, bo, wg, bg)
+  CH = int(CH)
+  if Hlast.dim() != 3 or CH < 1 or Hlast.shape[2] % CH != 0:
+    raise LnzError(_lib.LNZ_EINVAL, 'gat_readout: Hlast %s is not [B, N, %d blocks]' % (tuple(Hlast.shape), CH))
+  B, N, width = Hlast.shape
+  Dh = width // CH
+  ld = _gat_rows(Hlast, 'gat_readout')
+  Wo, bo, wg, bg = _f32c(Wo), _f32c(bo).reshape(-1), _f32c(wg).reshape(-1), _f32c(bg).reshape(-1)
+  P = Wo.shape[0]
+  if tuple(Wo.shape) != (P, Dh) or bo.numel() != P or wg.numel() != Dh or bg.numel() != 1:
+    raise LnzError(_lib.LNZ_EINVAL, 'gat_readout: head operands %s, %s, %s, %s do not fit Dh = %d'
+                   % (tuple(Wo.shape), tuple(bo.shape), tuple(wg.shape), tuple(bg.shape), Dh))
+  if mask is not None:
+    if tuple(mask.shape) != (B, N):
+      raise LnzError(_lib.LNZ_EINVAL, 'gat_readout: mask %s, expected %s' % (tuple(mask.shape), (B, N)))
+    mask = (mask != 0).to(torch.uint8).contiguous()
+  score = torch.empty((B, P), dtype=torch.float32, device=Hlast.device)
+  with torch.cuda.device(Hlast.device):
+    _abi().gat_readout(Hlast, ld, mask, Wo, bo, wg, bg, B, N, CH, Dh, P, score)
+  return score
+
+
+def gat_layer(state, L, W_stacked, a1, b1, a2, b2, bias, H, elu=True):
+  """One GAT layer: Wh = state W_stacked^T for all C H heads in ONE f32_linear launch (W_stacked
+  [C H Dh, Din], block c H + h = filter[t][c][h].weight; its stream-K workspace comes from
+  `_f32_linear_workspace` like every other caller's), then gat_attention."""
+  B, N = state.shape[0], state.shape[1]
+  Wh = f32_linear(state.reshape(B * N, state.shape[2]), W_stacked)
+  return gat_attention(Wh.view(B, N, -1), L, a1, b1, a2, b2, bias, H, elu=elu)
 
 
 # ----------------------------------------------------------------------------------------- R12

@@ -40,6 +40,9 @@ extern "C" {
  *    take that backward; additive, the version stays);
  *    + the GAT baseline's attention and readout (lnz_gat_attention, lnz_gat_readout: additive, the version
  *    stays);
+ *    + lnz_forward_args.rare_strips / .no_fold / .rare_debug at the END of the block (the strip forward's folded form of
+ *    the rare bond-type channels, on by default: zeros = folded where cheaper; additive, the version
+ *    stays — a caller built against the shorter block must zero-fill lnz_forward_args_size() bytes);
  * 6: lnz_forward_args lost Wp16 / w16_off / Wp16_head / Lp16 (gemm_mode 1 is now the split precision
  *    inside the strip kernel: lnz_pack_rows_k8_split; lnz_pack_rows_f16x2 and
  *    lnz_pack_laplacian_f16x2 are gone) and gained dbias_part_cap; + lnz_midgraph_forward,
@@ -62,6 +65,7 @@ extern "C" {
 #define LNZ_STRIP_SUB 6
 #define LNZ_STRIP_INTS 80
 #define LNZ_STRIP_MAX_B 2048
+#define LNZ_RARE_DEBUG_INTS 512   /* lnz_forward_args.rare_debug: int32 words per strip */
 
 typedef void* lnz_stream_t;
 
@@ -779,6 +783,26 @@ typedef struct lnz_forward_args {
   const int32_t* strips;      /* [strip_cap][LNZ_STRIP_INTS] int32                                   */
   const int32_t* n_strips;    /* device scalar: strips in use                                        */
   int strip_cap;              /* lnz_strip_cap(B): entries in `strips` (= grid size)                 */
+  /* ---- rare bond-type channels of the strip forward (additive, ABI 7).  An edge-type channel e >= 2
+   * is the identity on every row its bond type does not touch: L_e = I + D_e.  An
+   * inference launch on strips (no act_out, 3 <= n_edge <= 7, diagonal gains, no short channels,
+   * gemm_mode 0) runs, per strip of at most 5 subtiles and where it is cheaper, ONE GEMM1 on the
+   * weights summed over channels 2 .. n_edge-1 (summed in registers from Wp) and X W_e^T on the rows
+   * channel e touches only, scattered through D_e.  The touched rows are found from the pack (a row
+   * is touched when its row or column of L_e is not the unit vector; the unit diagonal is 1 on a row the
+   * mask keeps and 0 elsewhere, so a node the mask leaves out but L_e keeps goes through the scatter), so
+   * any operator is correct and
+   * the launch needs no operand the channel loop does not have; the result differs from the channel
+   * loop's by a re-association of fp32 sums (a few 1e-7), and is the same with and without `ident`. */
+  int32_t* rare_strips;       /* optional device counter (caller zeroes it): + 1 per strip of the launch
+                                 that took the folded form                                           */
+  int32_t no_fold;            /* 1: every strip runs the channel loop (the form before this addition,
+                                 bit for bit)                                                        */
+  int32_t* rare_debug;        /* optional test output [strip_cap][LNZ_RARE_DEBUG_INTS], zeroed by the
+                                 caller; a strip of at most 5 subtiles writes [0] folded form taken,
+                                 [1] virtual subtiles, [2 + f] touched rows of channel 2 + f, [8 + v]
+                                 channel of virtual subtile v, [16 + 96 f + i] i-th touched strip row
+                                 of channel 2 + f (ascending)                                        */
 } lnz_forward_args;
 int lnz_lanczosnet_forward(const lnz_forward_args* args, lnz_stream_t stream);
 /* Backward of the conv stack w.r.t. its node-state inputs, in the forward's own structure:

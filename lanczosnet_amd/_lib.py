@@ -46,6 +46,7 @@ class ForwardArgs(C.Structure):
       ('dy_compact', C.c_void_p), ('dy_compact_rows', C.c_int64), ('dbias_part', C.c_void_p),
       ('dbias_part_cap', C.c_int32),
       ('strips', C.c_void_p), ('n_strips', C.c_void_p), ('strip_cap', C.c_int),
+      ('rare_strips', C.c_void_p), ('no_fold', C.c_int32), ('rare_debug', C.c_void_p),
   ]
 
 

@@ -136,6 +136,14 @@ constexpr int strip_lds_floats(int S, int nl, bool half = false) {
 }
 
 
+// RARE (strip_forward): LDS behind the strip's own layout — the scatter fragments of up to RARE_MAXV
+// virtual subtiles (S x 64 float4 each), their source rows and channels, the touched-row lists of up
+// to RARE_MAXF folded channels and the strip's decision
+constexpr int RARE_MAXV = 8, RARE_MAXF = 5, RARE_MAXS = 5;
+constexpr int rare_lds_floats(int S) {
+  return RARE_MAXV * S * 256 + RARE_MAXV * 16 + 2 * RARE_MAXV + 8 + RARE_MAXF * 16 * S + 8;
+}
+
 // MODE 0 = forward (a.act_out: the training forward's activation store); MODE 1 = the
 // input-gradient pass; FK 0 = diagonal gains, 2 = dense K x K filters; SHORT = short-diffusion
 // channels.  HALF: GEMM1 in split precision (x_hi w_hi + x_lo w_hi +
@@ -144,13 +152,27 @@ constexpr int strip_lds_floats(int S, int nl, bool half = false) {
 // the block products (Laplacian blocks from a pack converted by lnz_split_laplacian_pack, Ritz blocks
 // pre-split in LDS; lift and projection) run in the same split on subtile pairs (apply_split below);
 // gains, biases, ReLU, the head and all accumulation are the exact-fp32 code.
-template <int S, int MODE, int FK, bool SHORT, bool HALF>
+//
+// RARE (inference forward, diagonal gains, exact fp32, S <= 5, 3 <= n_edge <= 7, not a.no_fold): an
+// edge-type channel e >= 2 (a bond type) is the identity on every row it does not touch,
+// L_e = I + D_e with D_e supported on touched x touched rows, so
+//   sum_{e >= 2} L_e X W_e^T = X (sum_e W_e)^T + sum_e D_e (X W_e^T)
+// = ONE GEMM1 on the folded weights (summed in registers from the layer's pack: no operand the
+// channel loop does not have) + per channel a GEMM1 on the touched rows only, cut
+// into VIRTUAL subtiles of 16 slots (lane (j, kq) reads the A operand from slot j's source row) and
+// scattered with the C/D-as-B chain: out[I] += A(I, v) Zg_v, A(I, v)[node][slot] = D_e[node][source
+// row of the slot] staged in LDS once per launch.  A row is touched when its row or column of L_e in
+// the pack is not the unit vector (a masked row: when it couples to another row), so any operator is
+// computed correctly; the strip keeps the channel loop when the folded form issues no fewer MFMAs
+// (rare_cost below) or needs more than RARE_MAXV virtual subtiles.
+template <int S, int MODE, int FK, bool SHORT, bool HALF, bool RARE = false>
 __device__ __forceinline__ void strip_forward(KArgs& a, const int32_t* __restrict__ ent, float* lds,
                                               const int tid, const int wave) {
   constexpr int R = 16 * S;
   constexpr bool FWD = MODE == 0;
   constexpr bool DIAG = FK == 0;
   static_assert(!HALF || (FWD && DIAG && !SHORT), "split precision: inference forward, diagonal gains, no short channels");
+  static_assert(!RARE || (FWD && DIAG && !SHORT && !HALF && S <= RARE_MAXS), "rare form: exact inference forward, S <= 5");
 #ifdef LNZ_STRIP_PHASES  // per-wave clock64 stamps of the phases (tools/phase_probe16.py)
   long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t_all = clock64(), _t0 = t_all;
 #define LNZ_PH(i) { const long long _t1 = clock64(); ph[i] += _t1 - _t0; _t0 = _t1; }
@@ -203,6 +225,153 @@ __device__ __forceinline__ void strip_forward(KArgs& a, const int32_t* __restric
     rowok[tid] = ok;
   }
   __syncthreads();
+
+  // ---- RARE: touched rows of the folded channels, virtual subtiles, the strip's decision
+  float* rx = lds + strip_lds_floats(S, nl);
+  f32x4* Af = reinterpret_cast<f32x4*>(rx);                    // [v][I][lane]
+  int* vsrc = reinterpret_cast<int*>(rx + RARE_MAXV * S * 256);  // [v][16] source row of a slot
+  int* vchan = vsrc + RARE_MAXV * 16;                          // [v] channel, [MAXV + v] first slot in its list
+  int* tcnt = vchan + 2 * RARE_MAXV;                           // [f] touched rows of channel 2 + f
+  int* tlist = tcnt + 8;                                       // [f][R] the rows, ascending
+  int* rflag = tlist + RARE_MAXF * R;                          // [0] folded form taken, [1] virtual subtiles
+  bool rare = false;
+  int nvs = 0;
+  if constexpr (RARE) {
+    const int NF = ne - 2;
+    // the tiles (molecule of the strip, folded channel) are read once by all threads: an element off
+    // the diagonal that is not zero touches its row and its column; a diagonal touches its row when
+    // it is not the identity the folded GEMM1 supplies there — 1 on a masked-in row, 0 elsewhere (a
+    // node the mask leaves out but the operator keeps, diagonal 1, is touched: its Z_e comes through
+    // the scatter).  Bit per local row, OR-ed in LDS.  Of a tile the pack flags as an identity
+    // (diag(0/1)) only the 32 fragments that hold the diagonal are read.
+    constexpr int TCAP = RARE_MAXF * MAXMOL;
+    unsigned* tmask = reinterpret_cast<unsigned*>(rx);  // [f][MAXMOL] (this and the next two: where Af goes later)
+    int* tiles = reinterpret_cast<int*>(tmask + TCAP);  // own * 8 + f: whole tiles from the front, diagonal-only from the back
+    int* ntile = tiles + TCAP;                          // [0] whole, [1] diagonal only
+    if (tid < TCAP) tmask[tid] = 0u;
+    if (tid < 2) ntile[tid] = 0;
+    __syncthreads();
+    if (tid < nm * NF) {
+      const int own = tid / NF, f = tid - own * NF;
+      if (a.ident && ((a.ident[mid[own]] >> (2 + f)) & 1u)) tiles[TCAP - 1 - atomicAdd(ntile + 1, 1)] = own * 8 + f;
+      else tiles[atomicAdd(ntile, 1)] = own * 8 + f;
+    }
+    __syncthreads();
+    {
+      const int whole = ntile[0] * 256, total = whole + ntile[1] * 32;
+      constexpr int UN = 4;
+      for (int base = tid; base < total; base += 512 * UN) {
+        float4 v[UN];
+        int tl[UN], o[UN];
+#pragma unroll
+        for (int u = 0; u < UN; ++u) {
+          const int idx = base + 512 * u;
+          tl[u] = -1, o[u] = 0;
+          if (idx < whole) {
+            tl[u] = tiles[idx >> 8], o[u] = idx & 255;
+          } else if (idx < total) {
+            const int jd = idx - whole, r = jd & 31;
+            tl[u] = tiles[TCAP - 1 - (jd >> 5)], o[u] = (r >> 3) * 64 + ((r >> 2) & 1) * 32 + r;
+          }
+          const int64_t at = tl[u] >= 0 ? ((int64_t)mid[tl[u] >> 3] * ne + 2 + (tl[u] & 7)) * 256 + o[u] : 0;
+          v[u] = reinterpret_cast<const float4*>(a.Lp)[at];
+        }
+#pragma unroll
+        for (int u = 0; u < UN; ++u) {
+          if (tl[u] < 0) continue;
+          const int own = tl[u] >> 3;
+          const int row = o[u] & 31, col0 = 8 * (o[u] >> 6) + 4 * ((o[u] >> 5) & 1);
+          const float x[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+          const int n = mext[own], rows_own = n <= 4 ? 4 : (n + 3) & ~3;
+          unsigned bits = 0u;
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            if (col0 + c != row) bits |= x[c] != 0.0f ? (1u << row) | (1u << (col0 + c)) : 0u;
+            else if (row < rows_own && x[c] != (rowok[mstart[own] + row] != 0 ? 1.0f : 0.0f)) bits |= 1u << row;
+          }
+          if (bits) atomicOr(&tmask[(tl[u] & 7) * MAXMOL + own], bits);
+        }
+      }
+    }
+    __syncthreads();
+    if (wave < NF) {  // wave f: the rows channel 2 + f touches, ascending (a lane per row, two rounds)
+      int base = 0;
+      for (int h = 0; h < 2; ++h) {
+        const int row = lane + 64 * h;
+        bool t = false;
+        if (row < R) {
+          const int own = rowinfo[row];
+          if (own >= 0) t = (tmask[wave * MAXMOL + own] >> (row - mstart[own])) & 1;
+        }
+        const unsigned long long m = __ballot(t);
+        if (t) tlist[wave * R + base + __popcll(m & ((1ull << lane) - 1ull))] = row;
+        base += __popcll(m);
+      }
+      if (lane == 0) tcnt[wave] = base;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      int nv = 0;
+      for (int f = 0; f < NF; ++f)
+        for (int s0 = 0; s0 < tcnt[f]; s0 += 16) {
+          if (nv < RARE_MAXV) vchan[nv] = 2 + f, vchan[RARE_MAXV + nv] = s0;
+          ++nv;
+        }
+      // MFMAs per wave and 128 input columns: folded GEMM1 + per virtual subtile a GEMM1 and a scatter,
+      // against GEMM1 + GEMM2 of every folded channel (utils/flop_model.py: rare_cost)
+      const int folded = 32 * S + nv * (32 + 4 * S), plain = (32 * S + 4 * (3 * S - 2)) * NF;
+      rflag[0] = (nv <= RARE_MAXV && folded < plain) ? 1 : 0;
+      rflag[1] = nv;
+    }
+    __syncthreads();
+    rare = __builtin_amdgcn_readfirstlane(rflag[0]) != 0;
+    nvs = rare ? __builtin_amdgcn_readfirstlane(rflag[1]) : 0;
+    if (a.rare_debug) {  // test output: what this strip found and decided (LNZ_RARE_DEBUG_INTS words)
+      int32_t* dbg = a.rare_debug + (int64_t)blockIdx.x * LNZ_RARE_DEBUG_INTS;
+      if (tid == 0) dbg[0] = rflag[0], dbg[1] = rflag[1];
+      if (tid < NF) dbg[2 + tid] = tcnt[tid];
+      if (tid < RARE_MAXV && tid < rflag[1]) dbg[8 + tid] = vchan[tid];
+      for (int idx = tid; idx < NF * R; idx += 512) {
+        const int f = idx / R, i = idx - f * R;
+        if (i < tcnt[f]) dbg[16 + 96 * f + i] = tlist[idx];
+      }
+    }
+    if (rare) {
+      if (tid == 0 && a.rare_strips) atomicAdd(a.rare_strips, 1);
+      if (tid < nvs * 16) {  // a padding slot reads its subtile's first source row (its fragments are zero)
+        const int v = tid >> 4, f = vchan[v] - 2, s0 = vchan[RARE_MAXV + v], slot = s0 + (tid & 15);
+        vsrc[tid] = tlist[f * R + (slot < tcnt[f] ? slot : s0)];
+      }
+      __syncthreads();
+      // scatter fragments: lane (jj, kk) of (v, I) holds D_e[node 16 I + jj][source row of slot 4 kk + r]
+      for (int idx = tid; idx < nvs * S * 64; idx += 512) {
+        const int v = idx / (S * 64), rem = idx - v * (S * 64);
+        const int I = rem >> 6, jj = rem & 15, kk = (rem >> 4) & 3;
+        const int e = vchan[v], f = e - 2, s0 = vchan[RARE_MAXV + v];
+        const int p = 16 * I + jj, own = rowinfo[p];
+        float val[4];
+        bool ok[4];
+        int q[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int slot = 4 * kk + r;
+          q[r] = vsrc[v * 16 + slot];
+          ok[r] = s0 + slot < tcnt[f] && own >= 0 && rowinfo[q[r]] == own;
+          int64_t at = 0;
+          if (ok[r]) {
+            const int st = mstart[own], lp = p - st, lq = q[r] - st;
+            at = ((((int64_t)mid[own] * ne + e) * 256 + (lq >> 3) * 64 + ((lq >> 2) & 1) * 32 + lp) << 2) + (lq & 3);
+          }
+          val[r] = a.Lp[at];
+        }
+        f32x4 d;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          d[r] = ok[r] ? val[r] - ((q[r] == p && rowok[p] != 0) ? 1.0f : 0.0f) : 0.0f;
+        Af[idx] = d;
+      }
+    }
+  }
 
   // ---- embedding gather / float features (model/lanczos_net.py:154, lanczos_net_general.py:156)
   //      Three entries per thread at a time, every load unconditional (a row nobody owns reads
@@ -490,10 +659,38 @@ __device__ __forceinline__ void strip_forward(KArgs& a, const int32_t* __restric
     };
     // four steps; `wrap`: the A prefetch of the last one fetches k = 0 again — the first fragments
     // of the NEXT channel (channels of a block read the same rows)
+    // (RARE: the stream is not contiguous behind edge type 1 — the last three prefetches of a channel
+    // read the first steps of `wnext`, where the next GEMM1 starts)
+    const float4* __restrict__ wnext = wp;
+    const float4* __restrict__ wjump = nullptr;  // set in front of a gemm1 whose successor is elsewhere
+    // (RARE, folded form) this wave's fragments of W_F = sum_{e >= 2} W_e for the whole layer, summed
+    // in registers from the layer's own pack (e ascending: the same bits with and without the
+    // identity bits): step q is asked for in front of the q-th GEMM1 of the layer (long scales, then
+    // edge types 0 and 1) and added behind it, so the loads land under that GEMM1
+    f32x4 wf[8];
+    float4 wft[RARE_MAXF];
+    int gi = 0;
+    auto fold_load = [&](int q) {
+#pragma unroll
+      for (int f = 0; f < RARE_MAXF; ++f) {  // (beyond the last channel: re-read it, not added)
+        const int e = 2 + f < ne ? 2 + f : ne - 1;
+        wft[f] = Wl[((int64_t)rt * Gtot + (int64_t)(ns + nl + e) * Q) * 64 + wlane + q * 128];
+      }
+    };
+    auto fold_add = [&](int q) {
+      f32x4 sum = splat4(0.f);
+#pragma unroll
+      for (int f = 0; f < RARE_MAXF; ++f)
+        if (2 + f < ne) sum += f32x4{wft[f].x, wft[f].y, wft[f].z, wft[f].w};
+#pragma unroll
+      for (int qq = 0; qq < 8; ++qq)
+        if (qq == q) wf[qq] = sum;
+    };
     auto steps4 = [&](lds_cptr xb, lds_cptr x0, auto wrap) {
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        ring[(u + 3) & 3] = wp[(u + 3) * 128];
+        if (RARE && decltype(wrap)::value && u >= 1) ring[(u + 3) & 3] = wnext[(u - 1) * 128];
+        else ring[(u + 3) & 3] = wp[(u + 3) * 128];
         f32x4 anext[S];
         const lds_cptr xn = (decltype(wrap)::value && u == 3) ? x0 : xb + 16 * (u + 1);
 #pragma unroll
@@ -530,6 +727,10 @@ __device__ __forceinline__ void strip_forward(KArgs& a, const int32_t* __restric
       if (((chan_total ^ (wave >> 2)) & 1) != 0) __builtin_amdgcn_s_setprio(1);
       else __builtin_amdgcn_s_setprio(0);
       ++chan_total;
+      if constexpr (RARE) {
+        wnext = wjump ? wjump : wp + Q16 * 128;
+        wjump = nullptr;
+      }
 #pragma unroll
       for (int I = 0; I < S; ++I) Z[I] = splat4(0.f);
       if constexpr (HALF) {
@@ -574,6 +775,15 @@ __device__ __forceinline__ void strip_forward(KArgs& a, const int32_t* __restric
       }
       before_last();
       steps4(xb, x0, std::true_type{});
+      if constexpr (RARE) wp = wnext;
+    };
+    // a GEMM1 of the channel loop that carries a step of W_F along
+    auto gemm1_carry = [&](lds_cptr x0, auto&& before_last) {
+      const bool carry = RARE && rare && gi < Q16;
+      if (carry) fold_load(gi);
+      gemm1(x0, before_last);
+      if (carry) fold_add(gi);
+      ++gi;
     };
 
     // Laplacian fragments of one edge type for every block (I, J): they land under the last four
@@ -703,7 +913,8 @@ __device__ __forceinline__ void strip_forward(KArgs& a, const int32_t* __restric
       for (int I = 0; I < S; ++I) T[I] = splat4(0.f);
       for (int s = 0; s < nl; ++s) {
         if constexpr (DIAG) {
-          gemm1(y0, [] {});
+          if constexpr (RARE) gemm1_carry(y0, [] {});
+          else gemm1(y0, [] {});
 #pragma unroll
           for (int I = 0; I < S; ++I) {
             const f32x4 gv = *reinterpret_cast<const f32x4*>(gsl + s * R + 16 * I + 4 * kq);
@@ -755,14 +966,102 @@ __device__ __forceinline__ void strip_forward(KArgs& a, const int32_t* __restric
     if (active) {
       const lds_cptr x0 = xlane + cur * R * P;
       load_first(x0);
-      for (int e = 0; e < ne; ++e) {
-        gemm1(x0, [&] { fetch(e, true); });
+      // (RARE, folded form: edge types 0 and 1 here, the others below)
+      const int ne_plain = (RARE && rare) ? 2 : ne;
+      // weights of virtual subtile v's channel for this wave
+      auto wchan = [&](int v) {
+        const int e = __builtin_amdgcn_readfirstlane(vchan[v]);
+        return Wl + ((int64_t)rt * Gtot + (int64_t)(ns + nl + e) * Q) * 64 + wlane;
+      };
+      for (int e = 0; e < ne_plain; ++e) {
+        if constexpr (RARE) {
+          // (the folded GEMM1 reads no weights: the ring goes on with the first virtual subtile's)
+          if (rare && e == 1 && nvs > 0) wjump = wchan(0);
+          gemm1_carry(x0, [&] { fetch(e, true); });
+        } else {
+          gemm1(x0, [&] { fetch(e, true); });
+        }
         LNZ_PH(4)  // edge GEMM1
         apply_all(out, Z);  // (identity subtiles: zero fragments)
 #pragma unroll
         for (int I = 0; I < S; ++I)
           if ((idm[I] >> e) & 1) out[I] += Z[I];  // identity on every molecule of the subtile
         LNZ_PH(5)  // GEMM2
+      }
+      if constexpr (RARE) {
+        if (rare) {
+          // ---- folded GEMM1: the identity part of every folded channel, on the rows that hold a
+          //      node; W_F from registers (steps no GEMM1 carried — fewer than 16-k steps of them in
+          //      front — are summed here)
+          for (int q = gi; q < Q16; ++q) {
+            fold_load(q);
+            fold_add(q);
+          }
+          if (((chan_total ^ (wave >> 2)) & 1) != 0) __builtin_amdgcn_s_setprio(1);
+          else __builtin_amdgcn_s_setprio(0);
+          ++chan_total;
+#pragma unroll
+          for (int I = 0; I < S; ++I) Z[I] = splat4(0.f);
+#pragma unroll
+          for (int q = 0; q < 8; ++q) {
+            if (q < Q16) {
+              f32x4 av[S];
+#pragma unroll
+              for (int I = 0; I < S; ++I) av[I] = lds4(x0 + 16 * q + 16 * I * P);
+#pragma unroll
+              for (int c = 0; c < 4; ++c)
+#pragma unroll
+                for (int I = 0; I < S; ++I) Z[I] = mfma16(av[I][c], wf[q][c], Z[I]);
+            }
+          }
+#pragma unroll
+          for (int I = 0; I < S; ++I) {
+            const int4 okv = *reinterpret_cast<const int4*>(rowok + 16 * I + 4 * kq);
+            out[I][0] += okv.x ? Z[I][0] : 0.0f;
+            out[I][1] += okv.y ? Z[I][1] : 0.0f;
+            out[I][2] += okv.z ? Z[I][2] : 0.0f;
+            out[I][3] += okv.w ? Z[I][3] : 0.0f;
+          }
+          LNZ_PH(4)
+          // ---- per virtual subtile: GEMM1 on the touched rows (four partial accumulators, one per
+          //      k of a step's float4: a single chain would wait for its own latency), then the scatter
+          for (int v = 0; v < nvs; ++v) {
+            if (((chan_total ^ (wave >> 2)) & 1) != 0) __builtin_amdgcn_s_setprio(1);
+            else __builtin_amdgcn_s_setprio(0);
+            ++chan_total;
+            const float4* __restrict__ wn = v + 1 < nvs ? wchan(v + 1) : wp;
+            const lds_cptr xa = (lds_cptr)(Xs + cur * R * P + vsrc[v * 16 + j] * P + 4 * kq);
+            f32x4 zg[4] = {splat4(0.f), splat4(0.f), splat4(0.f), splat4(0.f)};
+            f32x4 ac = lds4(xa);
+#pragma unroll 1
+            for (int q0 = 0; q0 < Q16; q0 += 4) {
+              const bool last = q0 + 4 >= Q16;
+#pragma unroll
+              for (int u = 0; u < 4; ++u) {
+                const float4* pf = (last && u >= 1) ? wn + (u - 1) * 128 : wp + (u + 3) * 128;
+                ring[(u + 3) & 3] = *pf;
+                const f32x4 an = lds4(xa + 16 * ((q0 + u + 1) & (Q16 - 1)));
+                const float4 bv = ring[u];
+                zg[0] = mfma16(ac[0], bv.x, zg[0]);
+                zg[1] = mfma16(ac[1], bv.y, zg[1]);
+                zg[2] = mfma16(ac[2], bv.z, zg[2]);
+                zg[3] = mfma16(ac[3], bv.w, zg[3]);
+                ac = an;
+              }
+              wp += 4 * 128;
+            }
+            wp = wn;
+            const f32x4 zs = (zg[0] + zg[1]) + (zg[2] + zg[3]);
+            f32x4 fr[S];
+#pragma unroll
+            for (int I = 0; I < S; ++I) fr[I] = Af[(v * S + I) * 64 + lane];
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+              for (int I = 0; I < S; ++I) out[I] = mfma16(fr[I][r], zs[r], out[I]);
+          }
+          LNZ_PH(5)
+        }
       }
     }
 
@@ -1489,9 +1788,41 @@ __global__ __launch_bounds__(512) void lanczosnet_strip_kernel(const lnz_forward
   }
 }
 
+// The exact inference forward whose strips of up to 5 subtiles may take the folded form of the rare
+// bond-type channels (strip_forward, RARE).  Five template arguments, the third is RARE = 1: the
+// name tells the two kernels apart in a trace and in lnz_last_kernel().
+template <int MODE, int FK, int RARE, bool SHORT, bool HALF>
+__global__ __launch_bounds__(512) void lanczosnet_strip_kernel(const lnz_forward_args) {
+  static_assert(MODE == 0 && FK == 0 && RARE == 1 && !SHORT && !HALF, "one instantiation");
+  KArgs& a = *(KArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+  extern __shared__ __attribute__((aligned(16))) float lds_strip[];
+  if ((int)blockIdx.x >= *a.n_strips) return;
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int32_t* ent = a.strips + (int64_t)blockIdx.x * LNZ_STRIP_INTS;
+  const int sub = __builtin_amdgcn_readfirstlane(ent[1]);
+  switch (sub) {
+    case 1: strip_forward<1, 0, 0, false, false, true>(a, ent, lds_strip, tid, wave); break;
+    case 2: strip_forward<2, 0, 0, false, false, true>(a, ent, lds_strip, tid, wave); break;
+    case 3: strip_forward<3, 0, 0, false, false, true>(a, ent, lds_strip, tid, wave); break;
+    case 4: strip_forward<4, 0, 0, false, false, true>(a, ent, lds_strip, tid, wave); break;
+    case 5: strip_forward<5, 0, 0, false, false, true>(a, ent, lds_strip, tid, wave); break;
+    case 6: strip_forward<6, 0, 0, false, false>(a, ent, lds_strip, tid, wave); break;
+    default: break;
+  }
+}
+
 }  // namespace
 
 namespace lnz {
+
+// The folded form of the rare bond-type channels (strip_forward, RARE) is built for this launch
+static bool strip_rare_eligible(const lnz_forward_args& a, int mode) {
+  if (mode != 0 || a.act_out || a.no_fold) return false;
+  if (a.gemm_mode != 0 || a.filter_kind != 0 || a.n_short != 0) return false;
+  if (a.n_edge < 3 || a.n_edge - 2 > RARE_MAXF) return false;
+  return (size_t)(strip_lds_floats(RARE_MAXS, a.n_long) + rare_lds_floats(RARE_MAXS)) * sizeof(float) <= 160 * 1024;
+}
 
 // The forward (mode 0, with or without the activation store) and the input-gradient pass (mode 1)
 // of a width-128 model on strips: diagonal gains or dense filters in eigen space.
@@ -1564,7 +1895,19 @@ int launch_strip_gain_grad(const lnz_forward_args& a, hipStream_t s) {
 }
 
 int launch_strip_forward(const lnz_forward_args& a, int mode, hipStream_t s) {
-  const size_t bytes = (size_t)strip_lds_floats(LNZ_STRIP_SUB, a.n_long, a.gemm_mode == 1) * sizeof(float);
+  size_t bytes = (size_t)strip_lds_floats(LNZ_STRIP_SUB, a.n_long, a.gemm_mode == 1) * sizeof(float);
+  if (strip_rare_eligible(a, mode)) {
+    const size_t rb = (size_t)(strip_lds_floats(RARE_MAXS, a.n_long) + rare_lds_floats(RARE_MAXS)) * sizeof(float);
+    bytes = rb > bytes ? rb : bytes;
+    void (*kfn)(const lnz_forward_args) = lanczosnet_strip_kernel<0, 0, 1, false, false>;
+    const void* fn = (const void*)kfn;
+    note_kernel("lanczosnet_strip_kernel<0,0,1,false,false>");
+    LNZ_DYNAMIC_LDS(fn, 160 * 1024, "conv_strip.hip");
+    lnz_forward_args args = a;
+    void* params[] = {&args};
+    (void)hipLaunchKernel(fn, dim3(a.strip_cap), dim3(512), params, bytes, s);
+    return check_launch("lnz_lanczosnet_forward (strips, folded rare channels)");
+  }
   const void* fns[8] = {
       (const void*)lanczosnet_strip_kernel<0, 0, false>, (const void*)lanczosnet_strip_kernel<1, 0, false>,
       (const void*)lanczosnet_strip_kernel<0, 2, false>, (const void*)lanczosnet_strip_kernel<1, 2, false>,

@@ -74,9 +74,9 @@ const Tensor* first_defined(std::initializer_list<const Tensor*> ts) {
 // order of kIn below (None = NULL), `dims` the scalar fields in the order of kDim; the buffers a
 // launch writes are separate, alias-annotated arguments.
 enum { kNodeFeat, kNodeFeatF, kEmbedding, kMask, kLp, kV, kG, kWp, kBias, kWpHead, kBiasHead,
-       kPlan, kNwg, kAct, kX0, kIdent, kRowOff, kStrips, kNStrips, kNumIn };
+       kPlan, kNwg, kAct, kX0, kIdent, kRowOff, kStrips, kNStrips, kRareStrips, kRareDebug, kNumIn };
 enum { dB, dN, dK, dNumLayer, dDin0, dDhid, dDout, dNLong, dNEdge, dNumAtom, dFilterKind, dGemmMode,
-       dPlanCap, dBwdDin0, dMsgLayer, dDyCompactRows, dStripCap, kNumDim };
+       dPlanCap, dBwdDin0, dMsgLayer, dDyCompactRows, dStripCap, dNoFold, kNumDim };
 void fused_launch(int64_t which, const c10::List<c10::optional<Tensor>>& in, at::IntArrayRef dims,
                   at::IntArrayRef w_off, at::IntArrayRef b_off,
                   at::IntArrayRef short_dist, const c10::optional<Tensor>& score,
@@ -122,6 +122,14 @@ void fused_launch(int64_t which, const c10::List<c10::optional<Tensor>>& in, at:
   a.strips = (const int32_t*)raw_ptr(opt(kStrips), at::kInt, "strips");
   a.n_strips = (const int32_t*)raw_ptr(opt(kNStrips), at::kInt, "n_strips");
   a.strip_cap = dims[dStripCap];
+  // the folded form of the rare bond-type channels (forward): off with no_fold, and the optional
+  // counter of the strips that took it (a device word the launch adds to)
+  a.rare_strips = (int32_t*)raw_ptr(opt(kRareStrips), at::kInt, "rare_strips");
+  a.no_fold = (int32_t)dims[dNoFold];
+  a.rare_debug = (int32_t*)raw_ptr(opt(kRareDebug), at::kInt, "rare_debug");
+  if (a.rare_debug)
+    TORCH_CHECK(opt(kRareDebug)->numel() >= (int64_t)dims[dStripCap] * LNZ_RARE_DEBUG_INTS,
+                "lanczosnet::fused_launch: rare_debug shorter than strip_cap * LNZ_RARE_DEBUG_INTS");
   if (a.strips)
     TORCH_CHECK(a.n_strips && a.strip_cap > 0 &&
                     opt(kStrips)->numel() >= (int64_t)a.strip_cap * LNZ_STRIP_INTS,

@@ -1771,7 +1771,8 @@ def pairing_supported(plan):
 
 
 def lanczosnet_forward(plan, node_feat, Lp, V, G, mask, return_state=False, tiling='auto',
-                       act_out=None, use_ident=True):
+                       act_out=None, use_ident=True, rare_strips=None, fold=True,
+                       rare_debug=None):
   """Launch the fused forward.  `plan` is a dict made by LanczosNet._plan() holding the packed
   parameters and the static sizes.  tiling: 'auto' = lnz_plan_tiles with pairing where the kernel
   supports it, 'single' = planned but one molecule per tile, 'none' = no plan (batch order), or
@@ -1781,7 +1782,14 @@ def lanczosnet_forward(plan, node_feat, Lp, V, G, mask, return_state=False, tili
   a training forward needs them).
   act_out: optional zero-initialised [num_layer,B,32,dhid] that receives every layer's activations
   (training forward).  use_ident=False ignores the identity-channel bits of the pack (every
-  channel goes through its Laplacian fragments)."""
+  channel goes through its Laplacian fragments).
+  fold=False: every strip runs the channel loop over the edge types (lnz_forward_args.no_fold) — the
+  inference forward otherwise folds the rare bond-type channels where that is cheaper
+  (csrc/conv_strip.hip, RARE; the same bits with and without the identity-channel bits).
+  rare_strips: optional int32 device word; the launch adds the number of strips that took the folded
+  form (the caller zeroes it).  rare_debug: optional zeroed int32 [strip_cap, RARE_DEBUG_INTS]: what
+  every strip found and decided (lnz_forward_args.rare_debug: touched rows per folded channel, virtual
+  subtiles, form taken) — for tests."""
   _need_cuda(node_feat, Lp, V, G, mask)
   B, N, K = V.shape
   ready = getattr(Lp, 'ready', None)   # a pack on a second stream (prepare_batch(pack_stream=...))
@@ -1792,7 +1800,7 @@ def lanczosnet_forward(plan, node_feat, Lp, V, G, mask, return_state=False, tili
   elif Lp.dtype != torch.float32:
     raise RuntimeError('this Laplacian pack is the float16 form of a split-precision plan (gemm_mode 1): '
                        'the exact kernels read the fp32 pack')
-  if act_out is None and not return_state:
+  if act_out is None and not return_state and rare_strips is None and rare_debug is None and fold:
     return _forward_ext(plan, node_feat, Lp, V, G, mask, tiling, use_ident)
   ops_, dims = _fused_operands(plan, V)
   emb = None
@@ -1812,6 +1820,12 @@ def lanczosnet_forward(plan, node_feat, Lp, V, G, mask, return_state=False, tili
   ident = getattr(Lp, 'ident', None)  # identity-channel bits written by the pack kernels
   if ident is not None and use_ident:
     ops_[_IN['ident']] = ident
+  if rare_strips is not None:
+    assert rare_strips.dtype == torch.int32 and rare_strips.numel() >= 1
+    ops_[_IN['rare_strips']] = rare_strips
+  if rare_debug is not None:
+    assert rare_debug.dtype == torch.int32 and rare_debug.is_contiguous()
+    ops_[_IN['rare_debug']] = rare_debug
   fk = int(plan.get('filter_kind', 0))
   if G is not None:
     want = (plan['num_layer'], B, plan['n_long'], K) + ((K,) if fk == 1 else ())
@@ -1822,6 +1836,7 @@ def lanczosnet_forward(plan, node_feat, Lp, V, G, mask, return_state=False, tili
   ops_[_IN['Wp_head']], ops_[_IN['bias_head']] = plan['Wp_head'], plan['bias_head']
   gemm_mode = int(plan.get('gemm_mode', 0))
   dims[_DIM['gemm_mode']] = gemm_mode
+  dims[_DIM['no_fold']] = 0 if fold else 1
   # Tile plan: small molecules share a 32-row tile and the tiles are dealt, balanced by cost, over
   # one workgroup per CU (the launch is a single round: it lasts as long as its busiest CU).
   if isinstance(tiling, tuple):
@@ -1854,10 +1869,10 @@ def lanczosnet_forward(plan, node_feat, Lp, V, G, mask, return_state=False, tili
 _IN = {k: i for i, k in enumerate(
     ['node_feat', 'node_feat_f', 'embedding', 'mask', 'Lp', 'V', 'G', 'Wp', 'bias', 'Wp_head',
      'bias_head', 'plan', 'n_wg', 'act', 'x0', 'ident', 'row_off',
-     'strips', 'n_strips'])}
+     'strips', 'n_strips', 'rare_strips', 'rare_debug'])}
 _DIM = {k: i for i, k in enumerate(
     ['B', 'N', 'K', 'num_layer', 'din0', 'dhid', 'dout', 'n_long', 'n_edge', 'num_atom', 'filter_kind',
-     'gemm_mode', 'plan_cap', 'bwd_din0', 'msg_layer', 'dy_compact_rows', 'strip_cap'])}
+     'gemm_mode', 'plan_cap', 'bwd_din0', 'msg_layer', 'dy_compact_rows', 'strip_cap', 'no_fold'])}
 
 
 def _fused_operands(plan, V):
@@ -1885,6 +1900,7 @@ def _set_plan(ops_, dims, tiles, cap):
 
 
 STRIP_INTS = 80   # LNZ_STRIP_INTS
+RARE_DEBUG_INTS = 512   # LNZ_RARE_DEBUG_INTS
 
 
 def strip_plan_wanted(B, N):

@@ -42,7 +42,9 @@ strip, wave and layer
                                                              fragments and is multiplied all the same)
 
 plus the first layer's projection (din0 / 16 waves) and the head (S waves, 64 instructions), all of
-the 16x16x4 kind.  It takes the launches `strips_selected` says.
+the 16x16x4 kind.  It takes the launches `strips_selected` says.  (That is the channel loop over the edge
+types: `strip_mfma_issued`.  The inference forward folds the rare bond-type channels where that is
+cheaper, `lanczosnet_strip_kernel<0,0,1,false,false>`: `strip_rare_mfma_issued` below.)
 """
 import numpy as np
 
@@ -255,6 +257,117 @@ def strip_mfma_issued(strips, cfg):
               mfma_in_touched_blocks=int(useful),
               subtiles=int(sum(t['sub'] for t in strips)),
               max_subtiles_per_strip=int(max(t['sub'] for t in strips)))
+
+
+# ---- the folded form of the rare bond-type channels (csrc/conv_strip.hip, strip_forward RARE) ----
+RARE_MAXV, RARE_MAXF, RARE_MAXS = 8, 5, 5   # virtual subtiles, folded channels, subtiles of a strip
+
+
+def touch_masks(L, mask):
+  """The touched-row rule of the strip kernel, restated: L [B,N,N,C] float32, mask [B,N].  Returns
+  uint32 [B,C]: bit i of (b, c) is set when row i or column i of channel c holds a non-zero element
+  off the diagonal, or when its diagonal element is not the identity the folded GEMM1 supplies on
+  that row: exactly 1 on a node the mask keeps, exactly 0 elsewhere (a node that the mask leaves out
+  but the operator keeps — a hole, diagonal 1 — is touched)."""
+  L = np.asarray(L, np.float32)
+  B, N = L.shape[:2]
+  off = L != 0.0
+  eye = np.eye(N, dtype=bool)[None, :, :, None]
+  off = off & ~eye
+  t = off.any(axis=2) | off.any(axis=1)                              # [B,N,C]: row | column
+  diag = np.einsum('biic->bic', L)
+  t |= diag != (np.asarray(mask) != 0).astype(np.float32)[:, :, None]
+  bits = (np.uint64(1) << np.arange(N, dtype=np.uint64))[None, :, None]
+  return (t * bits).sum(axis=1).astype(np.uint32)
+
+
+def strip_touch_counts(strips, touch, n_edge):
+  """strips: the int32 strip plan (as for strips_from_plan); touch: uint32 [B,C] of touch_masks (C =
+  n_edge edge channels).  Returns, per strip, the touched rows of every folded channel 2 ..
+  n_edge-1 (rows of a molecule beyond its extent's 4-row block are not in the strip)."""
+  p = np.asarray(strips)
+  cap = (p.size - 1) // STRIP_INTS
+  out = []
+  for s in range(int(p[cap * STRIP_INTS])):
+    e = p[s * STRIP_INTS:(s + 1) * STRIP_INTS]
+    cnt = [0] * max(0, n_edge - 2)
+    for i in range(int(e[0])):
+      b, _, n = (int(x) for x in e[2 + 3 * i:5 + 3 * i])
+      rows = 4 if n <= 4 else (n + 3) // 4 * 4
+      for f in range(len(cnt)):
+        cnt[f] += bin(int(touch[b][2 + f]) & ((1 << rows) - 1)).count('1')
+    out.append(cnt)
+  return out
+
+
+def rare_cost(S, touch_count, n_fold):
+  """The kernel's cost rule, in MFMAs per wave and 128 input columns: (folded form, channel loop,
+  virtual subtiles).  Folded: one GEMM1 on the summed weights (32 S) and, per virtual subtile of 16
+  touched rows, a 16-row GEMM1 (32) and its scatter (4 S).  Channel loop: GEMM1 and GEMM2 of every
+  folded channel."""
+  nv = sum((c + 15) // 16 for c in touch_count)
+  return 32 * S + nv * (32 + 4 * S), (32 * S + 4 * (3 * S - 2)) * n_fold, nv
+
+
+def strip_takes_rare(S, touch_count, n_fold):
+  """Does a strip of S subtiles take the folded form?  (all of 2 .. n_edge-1 or none)"""
+  if S > RARE_MAXS or n_fold < 1 or n_fold > RARE_MAXF:
+    return False
+  folded, plain, nv = rare_cost(S, touch_count, n_fold)
+  return nv <= RARE_MAXV and folded < plain
+
+
+def strip_rare_mfma_issued(strips, touch_counts, cfg):
+  """strip_mfma_issued for the kernel with the folded form (lanczosnet_strip_kernel<0,0,1,false,false>):
+  strips from strips_from_plan, touch_counts from strip_touch_counts (None: nothing is folded).  A
+  strip that takes the folded form (strip_takes_rare) issues per wave and layer
+
+      GEMM1      (n_long + 2) * d_in / 16 * 4 * S         long scales, edge types 0 and 1
+      folded     d_in / 16 * 4 * S                        X (sum_{e >= 2} W_e)^T
+      rare       d_in / 16 * 4 + 4 * S   per virtual subtile (16 touched rows of one channel)
+      GEMM2      4 * 2 * blocks                           edge types 0 and 1
+      lift-back, projection, first projection, head       as strip_mfma_issued
+
+  and every other strip what strip_mfma_issued counts.  Adds `rare_strips`, `virtual_subtiles` and the
+  per-wave count of a 128-wide middle layer for the worst and the mean strip of S = max subtiles."""
+  n_long = len(cfg['long_diffusion_dist'])
+  n_edge = cfg['num_bond_type'] + 1
+  C = n_long + n_edge
+  n_fold = n_edge - 2
+  din0, dhid, nl = cfg['input_dim'], cfg['hidden_dim'][0], cfg['num_layer']
+  din0 = (din0 + 63) // 64 * 64
+  issued = plain = 0
+  rare_strips = nvt = 0
+  per_layer = []
+  for i, t in enumerate(strips):
+    S = t['sub']
+    blocks = 3 * S - 2
+    tc = touch_counts[i] if touch_counts is not None else None
+    rare = tc is not None and strip_takes_rare(S, tc, n_fold)
+    nv = rare_cost(S, tc, n_fold)[2] if rare else 0
+    rare_strips += int(rare)
+    nvt += nv
+    for l in range(nl):
+      d_in = din0 if l == 0 else dhid
+      proj = 1 if (n_long and l + 1 < nl) else 0
+      blk = 4 * blocks * ((1 if n_long else 0) + proj)
+      old = C * (d_in // 16) * 4 * S + blk + 4 * n_edge * blocks
+      new = old if not rare else ((n_long + 3) * (d_in // 16) * 4 * S + nv * ((d_in // 16) * 4 + 4 * S) +
+                                  blk + 4 * 2 * blocks)
+      issued += 8 * new
+      plain += 8 * old
+      if l == 1:
+        per_layer.append((S, new))
+    extra = ((din0 // 16) * 4 * blocks if n_long else 0) + S * 64
+    issued += extra
+    plain += extra
+  smax = max(t['sub'] for t in strips)
+  top = [c for s, c in per_layer if s == smax]
+  return dict(tiles=len(strips), mfma_issued=int(issued), mfma_channel_loop=int(plain),
+              flops_issued=int(issued) * FLOP_PER_MFMA16,
+              mops_counts=int(issued) * (FLOP_PER_MFMA16 // FLOP_PER_MOPS_COUNT),
+              rare_strips=rare_strips, virtual_subtiles=nvt,
+              per_wave_layer_worst=int(max(top)), per_wave_layer_mean=float(np.mean(top)))
 
 
 FLOP_PER_MFMA16X32_F16 = 2 * 16 * 16 * 32

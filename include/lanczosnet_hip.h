@@ -43,6 +43,9 @@ extern "C" {
  *    + lnz_forward_args.rare_strips / .no_fold / .rare_debug at the END of the block (the strip forward's folded form of
  *    the rare bond-type channels, on by default: zeros = folded where cheaper; additive, the version
  *    stays — a caller built against the shorter block must zero-fill lnz_forward_args_size() bytes);
+ *    + lnz_pack_fold_weights / lnz_pack_fold_weights_size and lnz_forward_args.Wf at the END of the block (the
+ *    folded weights of the rare bond-type channels, summed once per weight set instead of in every wave of every
+ *    launch; NULL = summed in registers as before, the same bits; additive, the version stays);
  * 6: lnz_forward_args lost Wp16 / w16_off / Wp16_head / Lp16 (gemm_mode 1 is now the split precision
  *    inside the strip kernel: lnz_pack_rows_k8_split; lnz_pack_rows_f16x2 and
  *    lnz_pack_laplacian_f16x2 are gone) and gained dbias_part_cap; + lnz_midgraph_forward,
@@ -585,6 +588,18 @@ int lnz_pack_rows_k8(const float* W, int rows, int cols, int64_t ld, float* Wp,
  * 64 (kq >> 1) + 32 (kq & 1) + wj) — the B operands of v_mfma_f32_16x16x32_f16. */
 int lnz_pack_rows_k8_split(const float* W, int rows, int cols, int64_t ld, float* Wp,
                            lnz_stream_t stream);
+/* Folded weights of the rare bond-type channels for the strip forward (lnz_forward_args.Wf), from the
+ * conv pack Wp / w_off (floats, per layer) of a model with hidden width dhid (a multiple of 32), layer-0
+ * input width din0 (a multiple of 16), C = n_short + n_long + n_edge channels, 3 <= n_edge:
+ *   Wf[layer l][rt][q][lane] (float4) = 0.f + Wp[l][rt][channel n_short + n_long + 2][q][lane] + ... +
+ *   Wp[l][rt][channel C - 1][q][lane], element-wise in fp32, channels ascending
+ * — one channel's fragment order (rt < dhid / 32, q < din_l / 8, 64 lanes), the layers back to back
+ * (dhid * din_l floats each), then 2048 floats of zero slack (the weight ring of the strip kernel reads
+ * up to three 16-k steps ahead).  Wf holds lnz_pack_fold_weights_size(num_layer, din0, dhid) floats;
+ * every one of them is written. */
+int64_t lnz_pack_fold_weights_size(int num_layer, int din0, int dhid);
+int lnz_pack_fold_weights(const float* Wp, const int64_t* w_off_host, int num_layer, int din0, int dhid,
+                          int n_short, int n_long, int n_edge, float* Wf, lnz_stream_t stream);
 /* bias [rows] -> bp[rt][lane][r] = bias[32*rt + (r&3) + 8*(r>>2) + 4*(lane>>5)] (the C/D
  * row of accumulator register r); holds 32*ceil(rows/32)*32 floats. */
 int lnz_pack_bias_rows(const float* bias, int rows, float* bp, lnz_stream_t stream);
@@ -802,7 +817,15 @@ typedef struct lnz_forward_args {
                                  caller; a strip of at most 5 subtiles writes [0] folded form taken,
                                  [1] virtual subtiles, [2 + f] touched rows of channel 2 + f, [8 + v]
                                  channel of virtual subtile v, [16 + 96 f + i] i-th touched strip row
-                                 of channel 2 + f (ascending)                                        */
+                                 of channel 2 + f (ascending); [7] 1 where the strip's folded GEMM1
+                                 read Wf (below)                                                     */
+  const float* Wf;            /* optional: lnz_pack_fold_weights of Wp (the folded weights W_F = sum over
+                                 channels 2 .. n_edge-1, per layer, in the fragment order of one channel).
+                                 With it a strip that takes the folded form reads W_F through its weight
+                                 ring instead of summing it in registers (kernel instantiation
+                                 lanczosnet_strip_kernel<0,0,2,..>).  NULL: the in-register
+                                 sum (<0,0,1,..>).  Both forms give the same bits.  Must be re-packed
+                                 when Wp changes.                                                     */
 } lnz_forward_args;
 int lnz_lanczosnet_forward(const lnz_forward_args* args, lnz_stream_t stream);
 /* Backward of the conv stack w.r.t. its node-state inputs, in the forward's own structure:

@@ -47,6 +47,7 @@ class ForwardArgs(C.Structure):
       ('dbias_part_cap', C.c_int32),
       ('strips', C.c_void_p), ('n_strips', C.c_void_p), ('strip_cap', C.c_int),
       ('rare_strips', C.c_void_p), ('no_fold', C.c_int32), ('rare_debug', C.c_void_p),
+      ('Wf', C.c_void_p),
   ]
 
 
@@ -122,6 +123,8 @@ SIGNATURES = {
     'lnz_packed_rows_k8_size': (C.c_int64, [_I, _I]),
     'lnz_pack_rows_k8': (C.c_int, [_P, _I, _I, _L, _P, _P]),
     'lnz_pack_rows_k8_split': (C.c_int, [_P, _I, _I, _L, _P, _P]),
+    'lnz_pack_fold_weights_size': (C.c_int64, [_I, _I, _I]),
+    'lnz_pack_fold_weights': (C.c_int, [_P, C.POINTER(C.c_int64), _I, _I, _I, _I, _I, _I, _P, _P]),
     'lnz_pack_bias_rows': (C.c_int, [_P, _I, _P, _P]),
     'lnz_pack_laplacian': (C.c_int, [_P, _L, _L, _L, _L, _I, _I, _I, _P, _P]),
     'lnz_collate_qm8': (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),

@@ -165,7 +165,19 @@ constexpr int rare_lds_floats(int S) {
 // the pack is not the unit vector (a masked row: when it couples to another row), so any operator is
 // computed correctly; the strip keeps the channel loop when the folded form issues no fewer MFMAs
 // (rare_cost below) or needs more than RARE_MAXV virtual subtiles.
-template <int S, int MODE, int FK, bool SHORT, bool HALF, bool RARE = false>
+// Two forms of the folded weights, two instantiations, the same bits:
+//   RARE = 1  (lnz_forward_args.Wf NULL) W_F is summed in registers, 0.f + W_2 + W_3 + ..., a 16-k step
+//             under each of the layer's first GEMM1s (fold_load / fold_add / gemm1_carry), and the
+//             folded GEMM1 reads it from 32 registers: 256 registers, 16 bytes of scratch.
+//   RARE = 2  (a.Wf = lnz_pack_fold_weights of the pack: the same element-wise sum in the same order,
+//             one channel's fragment order per layer) the folded GEMM1 is a plain gemm1 on that
+//             stream — behind edge type 1 the ring jumps to the layer's block of Wf, from there to the
+//             first virtual subtile's channel — so each accumulator sees the same MFMAs in the same
+//             order (step ascending, k of the float4 ascending).  The virtual subtiles are the same
+//             code.  174 registers, no scratch.  rare_debug word 7 is 1 where a strip folded in this
+//             form.  (Two virtual subtiles of one channel on one pass over its weights — 8 MFMAs per
+//             fragment — measured no faster: DESIGN.md section 7.)
+template <int S, int MODE, int FK, bool SHORT, bool HALF, int RARE = 0>
 __device__ __forceinline__ void strip_forward(KArgs& a, const int32_t* __restrict__ ent, float* lds,
                                               const int tid, const int wave) {
   constexpr int R = 16 * S;
@@ -173,6 +185,8 @@ __device__ __forceinline__ void strip_forward(KArgs& a, const int32_t* __restric
   constexpr bool DIAG = FK == 0;
   static_assert(!HALF || (FWD && DIAG && !SHORT), "split precision: inference forward, diagonal gains, no short channels");
   static_assert(!RARE || (FWD && DIAG && !SHORT && !HALF && S <= RARE_MAXS), "rare form: exact inference forward, S <= 5");
+  static_assert(RARE >= 0 && RARE <= 2, "RARE: 0 = channel loop only, 1 = W_F summed in registers, 2 = W_F from a.Wf");
+  constexpr bool PACKED = RARE == 2;
 #ifdef LNZ_STRIP_PHASES  // per-wave clock64 stamps of the phases (tools/phase_probe16.py)
   long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t_all = clock64(), _t0 = t_all;
 #define LNZ_PH(i) { const long long _t1 = clock64(); ph[i] += _t1 - _t0; _t0 = _t1; }
@@ -236,7 +250,7 @@ __device__ __forceinline__ void strip_forward(KArgs& a, const int32_t* __restric
   int* rflag = tlist + RARE_MAXF * R;                          // [0] folded form taken, [1] virtual subtiles
   bool rare = false;
   int nvs = 0;
-  if constexpr (RARE) {
+  if constexpr (RARE != 0) {
     const int NF = ne - 2;
     // the tiles (molecule of the strip, folded channel) are read once by all threads: an element off
     // the diagonal that is not zero touches its row and its column; a diagonal touches its row when
@@ -329,6 +343,7 @@ __device__ __forceinline__ void strip_forward(KArgs& a, const int32_t* __restric
     if (a.rare_debug) {  // test output: what this strip found and decided (LNZ_RARE_DEBUG_INTS words)
       int32_t* dbg = a.rare_debug + (int64_t)blockIdx.x * LNZ_RARE_DEBUG_INTS;
       if (tid == 0) dbg[0] = rflag[0], dbg[1] = rflag[1];
+      if (PACKED && tid == 0) dbg[7] = rflag[0];  // the folded GEMM1 of this strip reads a.Wf
       if (tid < NF) dbg[2 + tid] = tcnt[tid];
       if (tid < RARE_MAXV && tid < rflag[1]) dbg[8 + tid] = vchan[tid];
       for (int idx = tid; idx < NF * R; idx += 512) {
@@ -727,7 +742,7 @@ __device__ __forceinline__ void strip_forward(KArgs& a, const int32_t* __restric
       if (((chan_total ^ (wave >> 2)) & 1) != 0) __builtin_amdgcn_s_setprio(1);
       else __builtin_amdgcn_s_setprio(0);
       ++chan_total;
-      if constexpr (RARE) {
+      if constexpr (RARE != 0) {
         wnext = wjump ? wjump : wp + Q16 * 128;
         wjump = nullptr;
       }
@@ -775,11 +790,11 @@ __device__ __forceinline__ void strip_forward(KArgs& a, const int32_t* __restric
       }
       before_last();
       steps4(xb, x0, std::true_type{});
-      if constexpr (RARE) wp = wnext;
+      if constexpr (RARE != 0) wp = wnext;
     };
     // a GEMM1 of the channel loop that carries a step of W_F along
     auto gemm1_carry = [&](lds_cptr x0, auto&& before_last) {
-      const bool carry = RARE && rare && gi < Q16;
+      const bool carry = RARE == 1 && rare && gi < Q16;
       if (carry) fold_load(gi);
       gemm1(x0, before_last);
       if (carry) fold_add(gi);
@@ -913,7 +928,7 @@ __device__ __forceinline__ void strip_forward(KArgs& a, const int32_t* __restric
       for (int I = 0; I < S; ++I) T[I] = splat4(0.f);
       for (int s = 0; s < nl; ++s) {
         if constexpr (DIAG) {
-          if constexpr (RARE) gemm1_carry(y0, [] {});
+          if constexpr (RARE != 0) gemm1_carry(y0, [] {});
           else gemm1(y0, [] {});
 #pragma unroll
           for (int I = 0; I < S; ++I) {
@@ -974,9 +989,14 @@ __device__ __forceinline__ void strip_forward(KArgs& a, const int32_t* __restric
         return Wl + ((int64_t)rt * Gtot + (int64_t)(ns + nl + e) * Q) * 64 + wlane;
       };
       for (int e = 0; e < ne_plain; ++e) {
-        if constexpr (RARE) {
-          // (the folded GEMM1 reads no weights: the ring goes on with the first virtual subtile's)
-          if (rare && e == 1 && nvs > 0) wjump = wchan(0);
+        if constexpr (RARE != 0) {
+          // (RARE = 1: the folded GEMM1 reads no weights, the ring goes on with the first virtual
+          // subtile's; PACKED: it reads this layer's block of a.Wf, one channel's fragment order)
+          if constexpr (PACKED) {
+            if (rare && e == 1)
+              wjump = reinterpret_cast<const float4*>(a.Wf) + (l == 0 ? 0 : 32 * (a.din0 + (l - 1) * 128)) +
+                      rt * Q * 64 + wlane;
+          } else if (rare && e == 1 && nvs > 0) wjump = wchan(0);
           gemm1_carry(x0, [&] { fetch(e, true); });
         } else {
           gemm1(x0, [&] { fetch(e, true); });
@@ -988,30 +1008,37 @@ __device__ __forceinline__ void strip_forward(KArgs& a, const int32_t* __restric
           if ((idm[I] >> e) & 1) out[I] += Z[I];  // identity on every molecule of the subtile
         LNZ_PH(5)  // GEMM2
       }
-      if constexpr (RARE) {
+      if constexpr (RARE != 0) {
         if (rare) {
           // ---- folded GEMM1: the identity part of every folded channel, on the rows that hold a
           //      node; W_F from registers (steps no GEMM1 carried — fewer than 16-k steps of them in
-          //      front — are summed here)
-          for (int q = gi; q < Q16; ++q) {
-            fold_load(q);
-            fold_add(q);
-          }
-          if (((chan_total ^ (wave >> 2)) & 1) != 0) __builtin_amdgcn_s_setprio(1);
-          else __builtin_amdgcn_s_setprio(0);
-          ++chan_total;
+          //      front — are summed here).  PACKED: an ordinary GEMM1 on the a.Wf stream (the same
+          //      MFMA order per accumulator: step ascending, k of the float4 ascending), from where the
+          //      ring jumps to the first virtual subtile's channel
+          if constexpr (PACKED) {
+            if (nvs > 0) wjump = wchan(0);
+            gemm1(x0, [] {});
+          } else {
+            for (int q = gi; q < Q16; ++q) {
+              fold_load(q);
+              fold_add(q);
+            }
+            if (((chan_total ^ (wave >> 2)) & 1) != 0) __builtin_amdgcn_s_setprio(1);
+            else __builtin_amdgcn_s_setprio(0);
+            ++chan_total;
 #pragma unroll
-          for (int I = 0; I < S; ++I) Z[I] = splat4(0.f);
+            for (int I = 0; I < S; ++I) Z[I] = splat4(0.f);
 #pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            if (q < Q16) {
-              f32x4 av[S];
+            for (int q = 0; q < 8; ++q) {
+              if (q < Q16) {
+                f32x4 av[S];
 #pragma unroll
-              for (int I = 0; I < S; ++I) av[I] = lds4(x0 + 16 * q + 16 * I * P);
+                for (int I = 0; I < S; ++I) av[I] = lds4(x0 + 16 * q + 16 * I * P);
 #pragma unroll
-              for (int c = 0; c < 4; ++c)
+                for (int c = 0; c < 4; ++c)
 #pragma unroll
-                for (int I = 0; I < S; ++I) Z[I] = mfma16(av[I][c], wf[q][c], Z[I]);
+                  for (int I = 0; I < S; ++I) Z[I] = mfma16(av[I][c], wf[q][c], Z[I]);
+              }
             }
           }
 #pragma unroll
@@ -1789,11 +1816,15 @@ __global__ __launch_bounds__(512) void lanczosnet_strip_kernel(const lnz_forward
 }
 
 // The exact inference forward whose strips of up to 5 subtiles may take the folded form of the rare
-// bond-type channels (strip_forward, RARE).  Five template arguments, the third is RARE = 1: the
-// name tells the two kernels apart in a trace and in lnz_last_kernel().
+// bond-type channels (strip_forward, RARE).  Five template arguments, the third is RARE: the
+// name tells these kernels from the channel-loop one in a trace and in lnz_last_kernel().  Two
+// instantiations: RARE = 1 sums W_F in registers from the layer's pack (lnz_forward_args.Wf NULL),
+// RARE = 2 reads it from a.Wf through the weight ring — separate kernels, so that neither carries the
+// other's registers; the same bits.  The launcher notes `<0,0,1,false,false>` in lnz_last_kernel()
+// for both (a launch that MAY fold); in a trace the third template argument tells them apart.
 template <int MODE, int FK, int RARE, bool SHORT, bool HALF>
 __global__ __launch_bounds__(512) void lanczosnet_strip_kernel(const lnz_forward_args) {
-  static_assert(MODE == 0 && FK == 0 && RARE == 1 && !SHORT && !HALF, "one instantiation");
+  static_assert(MODE == 0 && FK == 0 && (RARE == 1 || RARE == 2) && !SHORT && !HALF, "two instantiations");
   KArgs& a = *(KArgs*)__builtin_amdgcn_kernarg_segment_ptr();
   extern __shared__ __attribute__((aligned(16))) float lds_strip[];
   if ((int)blockIdx.x >= *a.n_strips) return;
@@ -1802,11 +1833,11 @@ __global__ __launch_bounds__(512) void lanczosnet_strip_kernel(const lnz_forward
   const int32_t* ent = a.strips + (int64_t)blockIdx.x * LNZ_STRIP_INTS;
   const int sub = __builtin_amdgcn_readfirstlane(ent[1]);
   switch (sub) {
-    case 1: strip_forward<1, 0, 0, false, false, true>(a, ent, lds_strip, tid, wave); break;
-    case 2: strip_forward<2, 0, 0, false, false, true>(a, ent, lds_strip, tid, wave); break;
-    case 3: strip_forward<3, 0, 0, false, false, true>(a, ent, lds_strip, tid, wave); break;
-    case 4: strip_forward<4, 0, 0, false, false, true>(a, ent, lds_strip, tid, wave); break;
-    case 5: strip_forward<5, 0, 0, false, false, true>(a, ent, lds_strip, tid, wave); break;
+    case 1: strip_forward<1, 0, 0, false, false, RARE>(a, ent, lds_strip, tid, wave); break;
+    case 2: strip_forward<2, 0, 0, false, false, RARE>(a, ent, lds_strip, tid, wave); break;
+    case 3: strip_forward<3, 0, 0, false, false, RARE>(a, ent, lds_strip, tid, wave); break;
+    case 4: strip_forward<4, 0, 0, false, false, RARE>(a, ent, lds_strip, tid, wave); break;
+    case 5: strip_forward<5, 0, 0, false, false, RARE>(a, ent, lds_strip, tid, wave); break;
     case 6: strip_forward<6, 0, 0, false, false>(a, ent, lds_strip, tid, wave); break;
     default: break;
   }
@@ -1899,7 +1930,9 @@ int launch_strip_forward(const lnz_forward_args& a, int mode, hipStream_t s) {
   if (strip_rare_eligible(a, mode)) {
     const size_t rb = (size_t)(strip_lds_floats(RARE_MAXS, a.n_long) + rare_lds_floats(RARE_MAXS)) * sizeof(float);
     bytes = rb > bytes ? rb : bytes;
-    void (*kfn)(const lnz_forward_args) = lanczosnet_strip_kernel<0, 0, 1, false, false>;
+    // (a.Wf: the packed folded weights, lnz_pack_fold_weights — the second instantiation)
+    void (*kfn)(const lnz_forward_args) =
+        a.Wf ? lanczosnet_strip_kernel<0, 0, 2, false, false> : lanczosnet_strip_kernel<0, 0, 1, false, false>;
     const void* fn = (const void*)kfn;
     note_kernel("lanczosnet_strip_kernel<0,0,1,false,false>");
     LNZ_DYNAMIC_LDS(fn, 160 * 1024, "conv_strip.hip");

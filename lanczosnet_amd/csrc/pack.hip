@@ -112,6 +112,69 @@ extern "C" int lnz_pack_rows_k8_split(const float* W, int rows, int cols, int64_
   return lnz::check_launch("lnz_pack_rows_k8_split");
 }
 
+// Folded weights of the rare bond-type channels (conv_strip.hip, RARE = 2): per layer, in the
+// fragment order of ONE channel of that layer's pack, W_F = 0.f + W_2 + W_3 + ... (edge-type channels,
+// ascending, element-wise fp32 — the expression the strip kernel evaluates in registers without the
+// block, so both forms read the same bits), layers back to back, then zero slack.  One thread per
+// output float4.
+struct FoldPackLayers {
+  int64_t w_off4[16];  // float4 offset of a layer's conv pack
+  int64_t f_off4[17];  // float4 offset of a layer's block in Wf; [num_layer] = end of the blocks
+};
+__global__ void pack_fold_weights_kernel(const float4* __restrict__ Wp, FoldPackLayers L, int num_layer,
+                                         int din0, int dhid, int c0, int C, int ne, int64_t total4,
+                                         float4* __restrict__ Wf) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total4) return;
+  if (idx >= L.f_off4[num_layer]) {  // slack
+    Wf[idx] = make_float4(0.f, 0.f, 0.f, 0.f);
+    return;
+  }
+  int l = 0;
+  while (l + 1 < num_layer && idx >= L.f_off4[l + 1]) ++l;
+  const int Q = (l == 0 ? din0 : dhid) >> 3;
+  const int64_t local = idx - L.f_off4[l];
+  const int lane = (int)(local & 63);
+  const int q = (int)((local >> 6) % Q), rt = (int)((local >> 6) / Q);
+  float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int e = 2; e < ne; ++e) {
+    const float4 w = Wp[L.w_off4[l] + ((int64_t)rt * C * Q + (int64_t)(c0 + e) * Q + q) * 64 + lane];
+    sum.x += w.x, sum.y += w.y, sum.z += w.z, sum.w += w.w;
+  }
+  Wf[idx] = sum;
+}
+
+extern "C" int64_t lnz_pack_fold_weights_size(int num_layer, int din0, int dhid) {
+  if (num_layer < 1 || num_layer > 16 || din0 < 1 || dhid < 1) return 0;
+  return (int64_t)dhid * din0 + (int64_t)(num_layer - 1) * dhid * dhid + 2048;
+}
+
+extern "C" int lnz_pack_fold_weights(const float* Wp, const int64_t* w_off_host, int num_layer, int din0,
+                                     int dhid, int n_short, int n_long, int n_edge, float* Wf,
+                                     lnz_stream_t stream) {
+  LNZ_REQUIRE(Wp && w_off_host && Wf && num_layer >= 1 && num_layer <= 16 && din0 > 0 && din0 % 16 == 0 &&
+                  dhid > 0 && dhid % 32 == 0 && n_short >= 0 && n_long >= 0 && n_edge >= 3 &&
+                  n_short + n_long + n_edge <= LNZ_MAX_CHANNELS,
+              LNZ_EINVAL, "lnz_pack_fold_weights: bad arguments (num_layer=%d din0=%d dhid=%d channels %d+%d+%d)",
+              num_layer, din0, dhid, n_short, n_long, n_edge);
+  FoldPackLayers L = {};
+  int64_t at = 0;
+  for (int l = 0; l < num_layer; ++l) {
+    LNZ_REQUIRE(w_off_host[l] >= 0 && w_off_host[l] % 4 == 0, LNZ_EINVAL,
+                "lnz_pack_fold_weights: w_off[%d] = %lld is not a float4 offset", l, (long long)w_off_host[l]);
+    L.w_off4[l] = w_off_host[l] / 4;
+    L.f_off4[l] = at;
+    at += (int64_t)dhid * (l == 0 ? din0 : dhid) / 4;
+  }
+  L.f_off4[num_layer] = at;
+  const int64_t total4 = lnz_pack_fold_weights_size(num_layer, din0, dhid) / 4;
+  const int grid = (int)((total4 + 255) / 256);
+  hipLaunchKernelGGL(pack_fold_weights_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream,
+                     (const float4*)Wp, L, num_layer, din0, dhid, n_short + n_long,
+                     n_short + n_long + n_edge, n_edge, total4, (float4*)Wf);
+  return lnz::check_launch("lnz_pack_fold_weights");
+}
+
 __global__ __launch_bounds__(256) void split_laplacian_pack_kernel(const float4* p, float4* dst, int64_t n4) {
   lnz::split_pack_chunk<256>(p, dst, n4, blockIdx.x, threadIdx.x);
 }

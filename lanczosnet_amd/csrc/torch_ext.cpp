@@ -74,7 +74,7 @@ const Tensor* first_defined(std::initializer_list<const Tensor*> ts) {
 // order of kIn below (None = NULL), `dims` the scalar fields in the order of kDim; the buffers a
 // launch writes are separate, alias-annotated arguments.
 enum { kNodeFeat, kNodeFeatF, kEmbedding, kMask, kLp, kV, kG, kWp, kBias, kWpHead, kBiasHead,
-       kPlan, kNwg, kAct, kX0, kIdent, kRowOff, kStrips, kNStrips, kRareStrips, kRareDebug, kNumIn };
+       kPlan, kNwg, kAct, kX0, kIdent, kRowOff, kStrips, kNStrips, kRareStrips, kRareDebug, kWf, kNumIn };
 enum { dB, dN, dK, dNumLayer, dDin0, dDhid, dDout, dNLong, dNEdge, dNumAtom, dFilterKind, dGemmMode,
        dPlanCap, dBwdDin0, dMsgLayer, dDyCompactRows, dStripCap, dNoFold, kNumDim };
 void fused_launch(int64_t which, const c10::List<c10::optional<Tensor>>& in, at::IntArrayRef dims,
@@ -130,6 +130,11 @@ void fused_launch(int64_t which, const c10::List<c10::optional<Tensor>>& in, at:
   if (a.rare_debug)
     TORCH_CHECK(opt(kRareDebug)->numel() >= (int64_t)dims[dStripCap] * LNZ_RARE_DEBUG_INTS,
                 "lanczosnet::fused_launch: rare_debug shorter than strip_cap * LNZ_RARE_DEBUG_INTS");
+  // the packed folded weights (lnz_pack_fold_weights; forward): None = summed in registers
+  a.Wf = (const float*)raw_ptr(opt(kWf), at::kFloat, "Wf");
+  if (a.Wf)
+    TORCH_CHECK(opt(kWf)->numel() >= lnz_pack_fold_weights_size(a.num_layer, a.din0, a.dhid),
+                "lanczosnet::fused_launch: Wf shorter than lnz_pack_fold_weights_size(num_layer, din0, dhid)");
   if (a.strips)
     TORCH_CHECK(a.n_strips && a.strip_cap > 0 &&
                     opt(kStrips)->numel() >= (int64_t)a.strip_cap * LNZ_STRIP_INTS,
@@ -329,7 +334,8 @@ Tensor forward(const Tensor& node_feat, const c10::optional<Tensor>& embedding, 
                const Tensor& mask, const Tensor& Wp, const Tensor& bias, at::IntArrayRef w_off,
                at::IntArrayRef b_off, const Tensor& Wp_head, const Tensor& bias_head,
                const c10::optional<Tensor>& plan, int64_t plan_cap, at::IntArrayRef dims,
-               at::IntArrayRef short_dist, const c10::optional<Tensor>& strips, int64_t strip_cap) {
+               at::IntArrayRef short_dist, const c10::optional<Tensor>& strips, int64_t strip_cap,
+               const c10::optional<Tensor>& Wf) {
   TORCH_CHECK(dims.size() == 7 || dims.size() == 8,
               "lanczosnet::forward: dims = [num_layer, din0, dhid, dout, n_long, n_edge, filter_kind(, gemm_mode)]");
   TORCH_CHECK(dims.size() == 7 || dims[7] == 0 || dims[7] == 1, "lanczosnet::forward: gemm_mode 0 or 1");
@@ -408,6 +414,12 @@ Tensor forward(const Tensor& node_feat, const c10::optional<Tensor>& embedding, 
     a.n_strips = strips->data_ptr<int32_t>() + strip_cap * LNZ_STRIP_INTS;
     a.strip_cap = (int)strip_cap;
   }
+  if (Wf.has_value()) {  // lnz_pack_fold_weights of Wp: the strip forward's packed folded weights
+    need(*Wf, at::kFloat, "Wf");
+    TORCH_CHECK(Wf->numel() >= lnz_pack_fold_weights_size(a.num_layer, a.din0, a.dhid),
+                "lanczosnet::forward: Wf shorter than lnz_pack_fold_weights_size(num_layer, din0, dhid)");
+    a.Wf = Wf->data_ptr<float>();
+  }
   Tensor score = at::empty({a.B, a.dout}, V.options());
   a.score = score.data_ptr<float>();
   check(lnz_lanczosnet_forward(&a, cur_stream()), "forward");
@@ -470,7 +482,7 @@ TORCH_LIBRARY(lanczosnet, m) {
   m.def("forward(Tensor node_feat, Tensor? embedding, Tensor Lp, Tensor? ident, Tensor V, Tensor? G, "
         "Tensor mask, Tensor Wp, Tensor bias, int[] w_off, int[] b_off, Tensor Wp_head, "
         "Tensor bias_head, Tensor? plan, int plan_cap, int[] dims, int[] short_dist, Tensor? strips, "
-        "int strip_cap) -> Tensor");
+        "int strip_cap, Tensor? Wf=None) -> Tensor");
   m.def("unsorted_segment_sum_forward(Tensor data, Tensor segment_ids, int num_segments) -> Tensor");
   m.def("unsorted_segment_sum_backward(Tensor grad_out, Tensor segment_ids, int dim1) -> Tensor");
   m.def("fused_launch(int which, Tensor?[] operands, int[] dims, int[] w_off, int[] b_off, "

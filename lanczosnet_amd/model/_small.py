@@ -110,6 +110,12 @@ class _SmallMixin:
                     bias_head=bias_head,
                     embedding=emb)
         plan['gemm_mode'] = 1 if split_strips else 0
+        # the folded weights of the rare bond-type channels, packed once per weight set where the strip
+        # forward may fold (csrc/conv_strip.hip: read through the weight ring instead of summed per wave)
+        plan['Wf'] = None
+        if ops.fold_weights_eligible(plan):
+            plan['Wf'] = ops.pack_fold_weights(plan['Wp'], w_off, self.num_layer, din0p, dhid,
+                                               self.num_scale_short, self.num_scale_long, plan['n_edge'])
         if self.gemm_mode == 'f16x3' and not split_strips:
             raise NotImplementedError(
                 "gemm_mode='f16x3' runs inside the strip kernel: LanczosNet / LanczosNetGeneral with "

@@ -1350,6 +1350,26 @@ def pack_rows_k8(W):
   return out
 
 
+def fold_weights_eligible(plan):
+  """The strip forward may take the folded form of the rare bond-type channels for this plan
+  (csrc/conv_strip.hip, strip_rare_eligible): exact fp32, diagonal gains, no short scales, width 128,
+  3 <= n_edge <= 7."""
+  return (int(plan.get('gemm_mode', 0)) == 0 and int(plan.get('filter_kind', 0)) == 0 and not plan['short']
+          and plan['dhid'] == 128 and 3 <= plan['n_edge'] <= 7)
+
+
+def pack_fold_weights(Wp, w_off, num_layer, din0, dhid, n_short, n_long, n_edge):
+  """lnz_pack_fold_weights: the conv pack's bond-type channels 2 .. n_edge-1 summed per layer (0.f + W_2 +
+  W_3 + ..., fp32) in one channel's fragment order, layers back to back, 2048 floats of zero slack —
+  lnz_forward_args.Wf of the strip forward (include/lanczosnet_hip.h)."""
+  _need_cuda(Wp)
+  out = torch.empty((_abi().pack_fold_weights_size(num_layer, din0, dhid),), dtype=torch.float32, device=Wp.device)
+  with torch.cuda.device(Wp.device):
+    _abi().pack_fold_weights(Wp, [int(x) for x in w_off[:num_layer]], num_layer, din0, dhid, n_short, n_long,
+                             n_edge, out)
+  return out
+
+
 def pack_rows_k8_split(W):
   """[rows, cols] (cols a multiple of 32) -> the weight stream of the split-precision strip kernel
   (gemm_mode 1): fp16 hi / lo pieces at pack_rows_k8's size and offsets (include/lanczosnet_hip.h)."""
@@ -1772,7 +1792,7 @@ def pairing_supported(plan):
 
 def lanczosnet_forward(plan, node_feat, Lp, V, G, mask, return_state=False, tiling='auto',
                        act_out=None, use_ident=True, rare_strips=None, fold=True,
-                       rare_debug=None):
+                       rare_debug=None, packed_fold=True):
   """Launch the fused forward.  `plan` is a dict made by LanczosNet._plan() holding the packed
   parameters and the static sizes.  tiling: 'auto' = lnz_plan_tiles with pairing where the kernel
   supports it, 'single' = planned but one molecule per tile, 'none' = no plan (batch order), or
@@ -1789,7 +1809,10 @@ def lanczosnet_forward(plan, node_feat, Lp, V, G, mask, return_state=False, tili
   rare_strips: optional int32 device word; the launch adds the number of strips that took the folded
   form (the caller zeroes it).  rare_debug: optional zeroed int32 [strip_cap, RARE_DEBUG_INTS]: what
   every strip found and decided (lnz_forward_args.rare_debug: touched rows per folded channel, virtual
-  subtiles, form taken) — for tests."""
+  subtiles, form taken) — for tests.
+  packed_fold: the launch carries the plan's packed folded weights (plan['Wf'], lnz_forward_args.Wf) where the
+  plan has them; False withholds the block — the strips that fold sum the weights in registers, the
+  reference form (the same bits)."""
   _need_cuda(node_feat, Lp, V, G, mask)
   B, N, K = V.shape
   ready = getattr(Lp, 'ready', None)   # a pack on a second stream (prepare_batch(pack_stream=...))
@@ -1801,8 +1824,10 @@ def lanczosnet_forward(plan, node_feat, Lp, V, G, mask, return_state=False, tili
     raise RuntimeError('this Laplacian pack is the float16 form of a split-precision plan (gemm_mode 1): '
                        'the exact kernels read the fp32 pack')
   if act_out is None and not return_state and rare_strips is None and rare_debug is None and fold:
-    return _forward_ext(plan, node_feat, Lp, V, G, mask, tiling, use_ident)
+    return _forward_ext(plan, node_feat, Lp, V, G, mask, tiling, use_ident, packed_fold)
   ops_, dims = _fused_operands(plan, V)
+  if packed_fold:
+    ops_[_IN['Wf']] = plan.get('Wf')
   emb = None
   if node_feat.dtype in (torch.int64,):
     ops_[_IN['node_feat']] = node_feat.contiguous()
@@ -1869,7 +1894,7 @@ def lanczosnet_forward(plan, node_feat, Lp, V, G, mask, return_state=False, tili
 _IN = {k: i for i, k in enumerate(
     ['node_feat', 'node_feat_f', 'embedding', 'mask', 'Lp', 'V', 'G', 'Wp', 'bias', 'Wp_head',
      'bias_head', 'plan', 'n_wg', 'act', 'x0', 'ident', 'row_off',
-     'strips', 'n_strips', 'rare_strips', 'rare_debug'])}
+     'strips', 'n_strips', 'rare_strips', 'rare_debug', 'Wf'])}
 _DIM = {k: i for i, k in enumerate(
     ['B', 'N', 'K', 'num_layer', 'din0', 'dhid', 'dout', 'n_long', 'n_edge', 'num_atom', 'filter_kind',
      'gemm_mode', 'plan_cap', 'bwd_din0', 'msg_layer', 'dy_compact_rows', 'strip_cap', 'no_fold'])}
@@ -1926,7 +1951,7 @@ def plan_strips(mask_u8, n_cu=None):
   return buf
 
 
-def _forward_ext(plan, node_feat, Lp, V, G, mask, tiling, use_ident):
+def _forward_ext(plan, node_feat, Lp, V, G, mask, tiling, use_ident, packed_fold=True):
   """lanczosnet_forward through torch.ops.lanczosnet.forward (exact-fp32 kernel, scores only)."""
   B, N, K = V.shape
   mask_u8 = mask if mask.dtype == torch.uint8 and mask.is_contiguous() else \
@@ -1967,7 +1992,7 @@ def _forward_ext(plan, node_feat, Lp, V, G, mask, tiling, use_ident):
   scap = (strips.numel() - 1) // STRIP_INTS if strips is not None else 0
   return _ext().forward(nf, emb, Lp, ident, _f32c(V), G, mask_u8, plan['Wp'], plan['bias'], w_off,
                         b_off, plan['Wp_head'], plan['bias_head'], tiles, cap, dims, short,
-                        strips, scap)
+                        strips, scap, plan.get('Wf') if packed_fold else None)
 
 
 def _training_args(plan, Lp, V, G, mask_u8, tiling):

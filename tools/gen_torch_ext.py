@@ -7,6 +7,7 @@ Mapping of a C parameter to the op schema:
   lnz_stream_t                     dropped: the CURRENT HIP stream of the calling thread
   int / int64_t ; float / double   int ; float
   const int32_t* <name>_host       int[]?     host array (None -> NULL)
+  const int64_t* <name>_host       int[]?     host array (None -> NULL)
   const float* const*              Tensor[]   host array of device pointers
   const T*                         Tensor?    input  (None -> NULL); dtype of T checked
   T*                               Tensor(x!)? output / in-out, written in place
@@ -67,6 +68,10 @@ def generate():
         pre.append('  std::vector<int32_t> %s_v;\n  if (%s.has_value()) %s_v.assign(%s->begin(), %s->end());'
                    % (n, n, n, n, n))
         call.append('%s.has_value() ? %s_v.data() : nullptr' % (n, n))
+      elif t == 'const int64_t*' and n.endswith('_host'):
+        schema.append('int[]? %s' % n)
+        cargs.append('at::OptionalIntArrayRef %s' % n)
+        call.append('%s.has_value() ? %s->data() : nullptr' % (n, n))
       elif t == 'const float* const*':
         schema.append('Tensor[] %s' % n)
         cargs.append('at::TensorList %s' % n)

@@ -1,5 +1,5 @@
-// Backward of the large-graph layer on the nonzeros of ONE symmetric operator, exact fp32
-// (`_LargeSparseFusedFunction`, model/_large.py).  A layer of the forward is
+// Backward of the large-graph layer on the nonzeros of its symmetric operators, exact fp32
+// (`_LargeSparseFusedFunction`, model/_large.py).  With ONE operator a layer of the forward is
 //
 //     X' = relu( L Z + V T + b ),   Z = X Wn^T,   Y = V^T X,   T = sum_s diag(g_s) Y W_s^T
 //
@@ -19,10 +19,11 @@
 //                            operand rows are per graph, written at leading dimension 128 (columns
 //                            beyond the layer's input width zero) — the next layer's dX'.
 //
-// R = 2 .. 8 symmetric operators (a typed batch, `_LargeTypedSparseFusedFunction`):  X' = relu( sum_c
+// R = 2 .. 8 symmetric operators (a typed batch: the same Function):  X' = relu( sum_c
 // L_c Z_c + V T + b ),  Z_c = X Wn_c^T.  dZ_c = L_c dP is lnz_large_sparse_conv_split_f32 (csrc/conv_sparse.hip: R
 // results gathered from one source), dWn_c = dZ_c^T X one library GEMM per block, and
-//   lnz_large_grad_input_channels   dX = sum_c dZ_c Wn_c + V dY: the same GEMM over the depth R 128 + K.
+//   lnz_large_grad_input_channels   dX = sum_c dZ_c Wn_c + V dY: the same GEMM over the depth R 128 + K — the same
+//                            kernel: lnz_large_grad_input is its R = 1.
 //
 // MFMA operand maps (v_mfma_f32_16x16x4_f32): lane l holds A[i = l & 15][k = l >> 4] and
 // B[k = l >> 4][j = l & 15]; C/D register j of lane l is row 4 (l >> 4) + j, column l & 15.  The LDS
@@ -238,88 +239,19 @@ __global__ __launch_bounds__(256) void large_grad_spectral_kernel(
   }
 }
 
-// ---- dX = dZ Wn + V dY: 64 rows of one graph per workgroup ----------------------------------------
-// The row tile [64][128 + K] = [dZ | V] in LDS (the MFMA's A operand), wave w owns rows [16 w, 16 w +
-// 16) and all column tiles below the input width; the second operand is read in place: rows < 128
-// from Wn [128][128] (Wn[o][i], columns >= d zero), rows 128 + k from the graph's dY [K][128].
-constexpr int IN_ROWS = 64, ST_LD = DH + KMAX + 2;
-__global__ __launch_bounds__(256) void large_grad_input_kernel(
-    const float* __restrict__ dZ, const float* __restrict__ Wn, const float* __restrict__ V,
-    const float* __restrict__ dY, int N, int K, int d, float* __restrict__ dX) {
-  __shared__ float sT[IN_ROWS][ST_LD];
-  const int b = blockIdx.y, r0 = blockIdx.x * IN_ROWS;
-  const int t = threadIdx.x, lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int li = lane & 15, lk = lane >> 4;
-  const int Kp = (K + 3) & ~3;
-#pragma unroll
-  for (int u = 0; u < 8; ++u) {
-    const int idx = t + 256 * u, row = idx >> 5, c4 = idx & 31, r = r0 + row;
-    f32x4 z = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (r < N) z = *reinterpret_cast<const f32x4*>(dZ + ((int64_t)b * N + r) * DH + 4 * c4);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) sT[row][4 * c4 + e] = z[e];
-  }
-  for (int idx = t; idx < IN_ROWS * Kp; idx += 256) {
-    const int row = idx / Kp, k = idx - row * Kp, r = r0 + row;
-    sT[row][DH + k] = (r < N && k < K) ? V[((int64_t)b * N + r) * K + k] : 0.0f;
-  }
-  __syncthreads();
-  const int nct = (d + 15) >> 4;
-  f32x4 acc[8];
-#pragma unroll
-  for (int ct = 0; ct < 8; ++ct) acc[ct] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-  // depth index dep < 128: row dep of Wn; 128 + k: row k of the graph's dY (k >= K: padding, zero).  The
-  // second operand of the next PF steps is requested before this turn's MFMAs: its L2 latency is hidden
-  // behind them (read at use, one step at a time, the launch was latency bound: 1.03 ms per layer at
-  // config 5 against 0.16 ms of MFMA issue)
-  const int D = DH + Kp;
-  auto load = [&](float (&v)[8], const int k0) {
-    const int dep = k0 + lk;
-    const float* p = nullptr;
-    if (dep < DH) p = Wn + dep * DH + li;
-    else if (dep - DH < K) p = dY + ((int64_t)b * K + (dep - DH)) * DH + li;
-#pragma unroll
-    for (int ct = 0; ct < 8; ++ct) v[ct] = (p && ct < nct) ? p[ct * 16] : 0.0f;
-  };
-  constexpr int PF = 2;
-  float cur[PF][8], nxt[PF][8];
-#pragma unroll
-  for (int u = 0; u < PF; ++u) load(cur[u], 4 * u);
-  for (int k0 = 0; k0 < D; k0 += 4 * PF) {
-#pragma unroll
-    for (int u = 0; u < PF; ++u) load(nxt[u], k0 + 4 * PF + 4 * u);
-#pragma unroll
-    for (int u = 0; u < PF; ++u) {
-      if (k0 + 4 * u < D) {   // (uniform; D is a multiple of 4)
-        const float a = sT[16 * w + li][k0 + 4 * u + lk];
-#pragma unroll
-        for (int ct = 0; ct < 8; ++ct)
-          if (ct < nct) acc[ct] = mfma16(a, cur[u][ct], acc[ct]);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < PF; ++u)
-#pragma unroll
-      for (int ct = 0; ct < 8; ++ct) cur[u][ct] = nxt[u][ct];
-  }
-#pragma unroll
-  for (int ct = 0; ct < 8; ++ct)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int r = r0 + 16 * w + 4 * lk + j;
-      if (r < N) dX[((int64_t)b * N + r) * DH + ct * 16 + li] = ct * 16 + li < d ? acc[ct][j] : 0.0f;
-    }
-}
-
 // ---- dX = sum_c dZ_c Wn_c + V dY over R operator channels: 64 rows of one graph per workgroup -------
-// (the typed batch's layer, X' = relu( sum_c L_c Z_c + V T + b ), Z_c = X Wn_c^T: `_LargeTypedSparseFusedFunction`,
-// DESIGN.md §4.9d.)  The kernel above with the depth R 128 + K: the row tile [64][R 128 + K] does not fit LDS at
-// R = 8, so the [64][128] tile of dZ_c is restaged once per channel — requested from memory before the
-// previous channel's MFMAs, written to LDS behind them — and the V tile is staged once, in the same padded rows
-// (row stride 2 mod 32: the A operand's ds_read_b32 stays conflict free).  The second operand is read in place
-// with the same look-ahead: Wn [R][128][128] is ONE matrix of R 128 rows (row 128 c + o = Wn_c[o]), then the K
-// rows of the graph's dY.  Ascending depth into one accumulator per column tile: R = 1 gives the bits of
-// large_grad_input_kernel.
+// ONE kernel for one operator (R = 1: dX = dZ Wn + V dY) and for the R = 2 .. 8 channels of a typed batch (X' =
+// relu( sum_c L_c Z_c + V T + b ), Z_c = X Wn_c^T).  Wave w owns rows [16 w, 16 w + 16)
+// and all column tiles below the input width.  The row tile [64][R 128 + K] = [dZ_0 | .. | dZ_{R-1} | V] (the
+// MFMA's A operand) does not fit LDS at R = 8, so the [64][128] tile of dZ_c is restaged once per channel —
+// requested from memory before the previous channel's MFMAs, written to LDS behind them — and the V tile is
+// staged once, in the same padded rows (row stride 2 mod 32: the A operand's ds_read_b32 stays conflict free).
+// The second operand is read in place: Wn [R][128][128] is ONE matrix of R 128 rows (row 128 c + o = Wn_c[o],
+// columns >= d zero), then the K rows of the graph's dY [K][128].  Its next PF steps are requested before this
+// turn's MFMAs: the L2 latency is hidden behind them (read at use, one step at a time, the launch was latency
+// bound: 1.03 ms per layer at config 5 against 0.16 ms of MFMA issue).  Ascending depth into one accumulator
+// per column tile.
+constexpr int IN_ROWS = 64, ST_LD = DH + KMAX + 2;
 __global__ __launch_bounds__(256) void large_grad_input_channels_kernel(
     const float* __restrict__ dZ, const float* __restrict__ Wn, const float* __restrict__ V,
     const float* __restrict__ dY, int B, int N, int K, int R, int d, float* __restrict__ dX) {
@@ -435,36 +367,39 @@ extern "C" int lnz_large_grad_spectral(const float* A, const float* Y, int ldy, 
   return lnz::check_launch("lnz_large_grad_spectral");
 }
 
+// The two dX entries over the one kernel.  CHANNELS: the caller gives R and the [R][B][N][128] block of dZ, no
+// channel of which dX may overlap; otherwise R = 1 and the entry's own check (dX is not dZ) is all there is.
+template <bool CHANNELS>
+static int launch_grad_input(const char* who, const float* dZ, const float* Wn, const float* V, const float* dY, int B,
+                             int N, int K, int R, int d, float* dX, lnz_stream_t stream) {
+  LNZ_REQUIRE(dZ && Wn && dX && dZ != dX && B > 0 && N > 0, LNZ_EINVAL,
+              "%s: bad arguments (B=%d N=%d; dX must not alias dZ)", who, B, N);
+  if (CHANNELS)
+    LNZ_REQUIRE(R >= 1 && R <= RMAX && K >= 0 && K <= KMAX && d >= 1 && d <= DH, LNZ_ENOTSUP,
+                "%s: R=%d K=%d d=%d: 1 <= R <= %d, K <= %d, 1 <= d <= %d", who, R, K, d, RMAX, KMAX, DH);
+  else
+    LNZ_REQUIRE(K >= 0 && K <= KMAX && d >= 1 && d <= DH, LNZ_ENOTSUP, "%s: K=%d d=%d: K <= %d, 1 <= d <= %d", who, K,
+                d, KMAX, DH);
+  LNZ_REQUIRE(K == 0 || (V && dY), LNZ_EINVAL, "%s: K=%d needs V and dY", who, K);
+  LNZ_REQUIRE(B <= 65535, LNZ_ENOTSUP, "%s: B=%d > 65535 graphs", who, B);
+  if (CHANNELS) {
+    const uintptr_t block = (uintptr_t)B * N * DH * sizeof(float), z0 = (uintptr_t)dZ, x0 = (uintptr_t)dX;
+    LNZ_REQUIRE(x0 + block <= z0 || z0 + (uintptr_t)R * block <= x0, LNZ_EINVAL,
+                "%s: dX must not alias any channel of dZ", who);
+  }
+  LNZ_REQUIRE((((uintptr_t)dZ) & 15) == 0, LNZ_EINVAL, "%s: dZ must be 16-byte aligned", who);
+  hipLaunchKernelGGL(large_grad_input_channels_kernel, dim3((unsigned)((N + IN_ROWS - 1) / IN_ROWS), (unsigned)B),
+                     dim3(256), 0, (hipStream_t)stream, dZ, Wn, V, dY, B, N, K, R, d, dX);
+  lnz::note_kernel("%s_kernel", who + sizeof("lnz_") - 1);
+  return lnz::check_launch(who);
+}
+
 extern "C" int lnz_large_grad_input(const float* dZ, const float* Wn, const float* V, const float* dY, int B,
                                     int N, int K, int d, float* dX, lnz_stream_t stream) {
-  LNZ_REQUIRE(dZ && Wn && dX && dZ != dX && B > 0 && N > 0, LNZ_EINVAL,
-              "lnz_large_grad_input: bad arguments (B=%d N=%d; dX must not alias dZ)", B, N);
-  LNZ_REQUIRE(K >= 0 && K <= KMAX && d >= 1 && d <= DH, LNZ_ENOTSUP,
-              "lnz_large_grad_input: K=%d d=%d: K <= %d, 1 <= d <= %d", K, d, KMAX, DH);
-  LNZ_REQUIRE(K == 0 || (V && dY), LNZ_EINVAL, "lnz_large_grad_input: K=%d needs V and dY", K);
-  LNZ_REQUIRE(B <= 65535, LNZ_ENOTSUP, "lnz_large_grad_input: B=%d > 65535 graphs", B);
-  LNZ_REQUIRE((((uintptr_t)dZ) & 15) == 0, LNZ_EINVAL, "lnz_large_grad_input: dZ must be 16-byte aligned");
-  hipLaunchKernelGGL(large_grad_input_kernel, dim3((unsigned)((N + IN_ROWS - 1) / IN_ROWS), (unsigned)B), dim3(256),
-                     0, (hipStream_t)stream, dZ, Wn, V, dY, N, K, d, dX);
-  lnz::note_kernel("large_grad_input_kernel");
-  return lnz::check_launch("lnz_large_grad_input");
+  return launch_grad_input<false>("lnz_large_grad_input", dZ, Wn, V, dY, B, N, K, 1, d, dX, stream);   // Wn [1][128][128]
 }
 
 extern "C" int lnz_large_grad_input_channels(const float* dZ, const float* Wn, const float* V, const float* dY,
                                              int B, int N, int K, int R, int d, float* dX, lnz_stream_t stream) {
-  LNZ_REQUIRE(dZ && Wn && dX && dZ != dX && B > 0 && N > 0, LNZ_EINVAL,
-              "lnz_large_grad_input_channels: bad arguments (B=%d N=%d; dX must not alias dZ)", B, N);
-  LNZ_REQUIRE(R >= 1 && R <= RMAX && K >= 0 && K <= KMAX && d >= 1 && d <= DH, LNZ_ENOTSUP,
-              "lnz_large_grad_input_channels: R=%d K=%d d=%d: 1 <= R <= %d, K <= %d, 1 <= d <= %d", R, K, d, RMAX,
-              KMAX, DH);
-  LNZ_REQUIRE(K == 0 || (V && dY), LNZ_EINVAL, "lnz_large_grad_input_channels: K=%d needs V and dY", K);
-  LNZ_REQUIRE(B <= 65535, LNZ_ENOTSUP, "lnz_large_grad_input_channels: B=%d > 65535 graphs", B);
-  const uintptr_t block = (uintptr_t)B * N * DH * sizeof(float), z0 = (uintptr_t)dZ, x0 = (uintptr_t)dX;
-  LNZ_REQUIRE(x0 + block <= z0 || z0 + (uintptr_t)R * block <= x0, LNZ_EINVAL,
-              "lnz_large_grad_input_channels: dX must not alias any channel of dZ");
-  LNZ_REQUIRE((((uintptr_t)dZ) & 15) == 0, LNZ_EINVAL, "lnz_large_grad_input_channels: dZ must be 16-byte aligned");
-  hipLaunchKernelGGL(large_grad_input_channels_kernel, dim3((unsigned)((N + IN_ROWS - 1) / IN_ROWS), (unsigned)B),
-                     dim3(256), 0, (hipStream_t)stream, dZ, Wn, V, dY, B, N, K, R, d, dX);
-  lnz::note_kernel("large_grad_input_channels_kernel");
-  return lnz::check_launch("lnz_large_grad_input_channels");
+  return launch_grad_input<true>("lnz_large_grad_input_channels", dZ, Wn, V, dY, B, N, K, R, d, dX, stream);
 }

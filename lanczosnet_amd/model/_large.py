@@ -2,11 +2,12 @@
 the node-space term on the nonzeros of L (csrc/conv_sparse.hip) with their channel-fold and
 sparse-backoff state, and the library-GEMM restatement (hipBLASLt through torch) of everything the
 kernels are not built for.  `_plan_large` is also the cache the 33..128-node plan lives in.
-`_LargeSparseFusedFunction`: the opt-in HIP backward of the exact-fp32 sparse layers for edge-list batches
-(csrc/conv_sparse_grad.hip); `_LargeTypedSparseFusedFunction`: the same for typed batches —
-R = 3 .. 8 distinct operator channels, one sparse image each.  A DENSE collated L beyond 128
-nodes reaches the same two Functions through `_dense_operators`: its image(s), and the symmetry check that an
-edge list does not need (csrc/sparse_symmetry.hip)."""
+`_LargeSparseFusedFunction`: the opt-in HIP backward of the exact-fp32 sparse layers (csrc/conv_sparse_grad.hip)
+on a `_SparseOperators` — R symmetric operators as sparse images serving C weight channels: an edge-list batch
+(R = 1, C = 2), a typed one (R = C = 3 .. 8 distinct operator channels, one image each; §4.9d),
+or a DENSE collated L beyond 128 nodes, which reaches the Function through `_dense_operators`: its image(s), and
+the symmetry check that an edge list does not need (csrc/sparse_symmetry.hip; §4.9e).  The Function's forward
+and the inference path run the same layer loop (`_sparse_conv_layers`)."""
 import os
 import warnings
 
@@ -29,7 +30,7 @@ class _LargeMixin:
     # through `_torch_forward`.  Opt-in: its step time is recorded, not yet a reason
     large_backward_impl = os.environ.get('LANCZOSNET_LARGE_BACKWARD', 'torch')
     # typed edge-list batches (a SparseLaplacian with `images`: two or more edge types) in training: 'hip' =
-    # the backward over the channels' images (_LargeTypedSparseFusedFunction), 'torch'
+    # the same Function over the channels' images (R = channels), 'torch'
     # (default) = densify + autograd.  A switch of its own: each governs its own kind of batch
     large_typed_backward_impl = os.environ.get('LANCZOSNET_LARGE_BACKWARD_TYPED', 'torch')
     # DENSE collated batches (a float32 L [B,N,N,E+1] tensor: GraphData.collate_fn, collate_graph_adjacency)
@@ -246,7 +247,7 @@ class _LargeMixin:
             return None
         if L.dim() != 4 or L.dtype != torch.float32 or not L.is_cuda:
             return None
-        B, N, _, Cn = L.shape
+        N, Cn = L.shape[1], L.shape[3]
         if N <= MID_MAX_NODES or N > 65536 or Cn != self.num_edgetype + 1 \
                 or not self._large_dense_backward_supported(K, Cn):
             return None
@@ -260,8 +261,7 @@ class _LargeMixin:
         if img is not None and img.symmetric is not None:
             return kind if img.symmetric else None
         st = self.__dict__.setdefault('_large_dense_state', {}).setdefault(L.device.index, {})
-        if st.get('skip', 0) > 0:
-            st['skip'] -= 1
+        if self._paused(st):
             return None
         st['image_from'] = 'collate' if img is not None else 'module'
         if img is None and kind == 'each':
@@ -270,25 +270,13 @@ class _LargeMixin:
         elif img is None:
             img = ops.large_sparse_image(L, values=True)
             ops.attach_sparse_image(L, img)
-        R = Cn if kind == 'each' else 1
-        host = st.get('host')
-        if host is None or host.numel() != 1 + R * B:
-            host = st['host'] = torch.zeros((1 + R * B,), dtype=torch.int32).pin_memory()
-        status = ops.large_sparse_image_symmetry(img)
-        host[:1].copy_(img.flags, non_blocking=True)
-        host[1:].copy_(status, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        ev.synchronize()
-        words = host.tolist()
+        words = self._words_behind_event(st, img.flags, ops.large_sparse_image_symmetry(img))()
         flags, status = words[0], words[1:]
         st['last_flags'], st['last_status'] = flags, status
         img.symmetric = flags == 0 and not any(status)
+        self._pause_after(st, refused=not img.symmetric)
         if img.symmetric:
-            st['streak'] = 0
             return kind
-        st['streak'] = min(st.get('streak', 0) + 1, 6)
-        st['skip'] = self.large_sparse_backoff << (st['streak'] - 1)
         if not getattr(self, '_warned_dense_refusal', False):
             self._warned_dense_refusal = True
             warnings.warn("lanczosnet_amd: large_dense_backward_impl = 'hip': %s; the dense batch trains through "
@@ -450,25 +438,23 @@ class _LargeMixin:
         planes = 1: bf16 values x bf16 features (the streamed bf16 form's products); planes = 2, 3
         (the split-precision modes): the node-space term in EXACT fp32 — fp32 values x fp32
         features of lnz_f32_linear — and the lift from `planes` pieces as in the streamed form."""
-        B, N, _, Cn = Lf.shape
+        N, Cn = Lf.shape[1], Lf.shape[3]
         if not self.large_sparse or N > 65536 or torch.cuda.is_current_stream_capturing():
             return None
         st = self.__dict__.setdefault('_large_sparse_state', {}).setdefault(Lf.device.index, {})
-        if st.get('skip', 0) > 0:
-            st['skip'] -= 1
+        if self._paused(st):
             return None
         exact = planes != 1
         if self.large_sparse_channels not in ('one', 'each'):
             raise ValueError("large_sparse_channels is 'one' or 'each', got %r" % (self.large_sparse_channels,))
-        imgs = None                               # the images of several operators
         if isinstance(Lf, ops.SparseLaplacian) and Lf.images is not None:
-            img = imgs = Lf.images                # a typed batch: one image per channel, from the edge lists
+            img = Lf.images                       # a typed batch: one image per channel, from the edge lists
             st['image_from'] = 'edges'
         elif isinstance(Lf, ops.SparseLaplacian):
             img = Lf.image                        # built from the edge lists: no launch, no dense L
             st['image_from'] = 'edges'
         elif self.large_sparse_channels == 'each' and 1 < Cn <= LARGE_MAX_OPERATORS and Lf.stride(3) != 0:
-            img = imgs = ops.large_sparse_image_channels(Lf)
+            img = ops.large_sparse_image_channels(Lf)   # the images of several operators
             st['image_from'] = 'forward'
         else:
             img = ops.attached_sparse_image(Lf)   # left by the collate's Lanczos pass over this very tensor
@@ -477,36 +463,72 @@ class _LargeMixin:
             st['image_from'] = 'collate' if img is not None else 'forward'
             if img is None:
                 img = ops.large_sparse_image(Lf, values=exact)
-        host = st.get('host')
-        if host is None:
-            host = st['host'] = torch.zeros((1,), dtype=torch.int32).pin_memory()
-        host.copy_(img.flags, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
+        read_flags = self._words_behind_event(st, img.flags)
+        state = self._sparse_conv_layers(node_feat, img, Cn, Vf, G, planes)[1]
+        flags = st['last_flags'] = read_flags()[0]   # the image launch: long finished
+        # (a data set of dense graphs raises it every time: the pause doubles, up to 32 x)
+        self._pause_after(st, refused=flags != 0)
+        return None if flags else state
+
+    def _sparse_conv_layers(self, node_feat, img, channels, Vf, G, planes, out=None):
+        """The conv layers on the sparse image(s) `img` — a LargeSparseImage: ONE operator serving all `channels`
+        weight channels, their blocks summed; a LargeSparseImages: one operator per channel — for the inference
+        path and the training Function alike: the same launches on the same operands.  Layer t writes into
+        out[t] of a caller's [num_layer,B,N,128] buffer, or the layers ping-pong between two buffers of their own.
+        -> (the padded input state, the last layer's state [B,N,128], the work buffers)."""
+        multi = isinstance(img, ops.LargeSparseImages)
+        exact = planes != 1
         Vb = ops.large_pack_vectors(Vf, planes)
-        classes = (0,) * Cn if imgs is None else tuple(range(Cn))
+        classes = tuple(range(channels)) if multi else (0,) * channels
         plan = self._plan_large(planes, classes)
         # (lnz_f32_linear's K: the exact form takes the input columns padded to a multiple of 32)
-        state = input_state(self, node_feat, width=(self.input_dim + 31) // 32 * 32 if exact else None,
-                            as_float=True).contiguous()
+        state = X0 = input_state(self, node_feat, width=(self.input_dim + 31) // 32 * 32 if exact else None,
+                                 as_float=True).contiguous()
         bufs = [None, None]
-        work = ops.large_sparse_work_buffers(B, N, Lf.device, R=None if imgs is None else Cn, planes=planes)
-        weight = 'Wb' if not exact else 'Wn32' if imgs is None else 'Wn32s'
+        work = ops.large_sparse_work_buffers(img.B, img.N, Vf.device, R=img.R if multi else None, planes=planes)
+        weight = 'Wb' if not exact else 'Wn32s' if multi else 'Wn32'
         for t, lay in enumerate(plan['conv'][(planes, classes)]):
             state = ops.large_sparse_conv_layer(state, lay['din'], img, Vb, Vf, lay[weight], lay['Wt'],
                                                 G[t] if G is not None else None, lay['bias'], work,
-                                                planes, relu=True, out=bufs[t & 1])
+                                                planes, relu=True, out=bufs[t & 1] if out is None else out[t])
             bufs[t & 1] = state
-        ev.synchronize()   # the image launch: long finished
-        flags = int(host.item())
-        st['last_flags'] = flags
-        if flags:
-            # (a data set of dense graphs raises it every time: the pause doubles, up to 32 x)
-            st['streak'] = min(st.get('streak', 0) + 1, 6)
+        return X0, state, work
+
+    # -- the pause after a refused image, and the words that decide it (`_large_sparse_state`, `_large_dense_state`) --
+    @staticmethod
+    def _paused(st):
+        """True while the pause after a refusal lasts: one call fewer to go."""
+        if st.get('skip', 0) > 0:
+            st['skip'] -= 1
+            return True
+        return False
+
+    def _pause_after(self, st, refused):
+        """A refusal pauses the question for `large_sparse_backoff` calls on this device, twice as many after every
+        further refusal in a row (up to 32 x); an accepted image ends the row."""
+        st['streak'] = min(st.get('streak', 0) + 1, 6) if refused else 0
+        if refused:
             st['skip'] = self.large_sparse_backoff << (st['streak'] - 1)
-            return None
-        st['streak'] = 0
-        return state
+
+    @staticmethod
+    def _words_behind_event(st, *words):
+        """Start the copy of the device int32 `words` into the state's pinned buffer behind an event -> read(),
+        which waits for that event alone (not for launches issued since) and returns the words as one list."""
+        n = sum(w.numel() for w in words)
+        host = st.get('host')
+        if host is None or host.numel() != n:
+            host = st['host'] = torch.zeros((n,), dtype=torch.int32).pin_memory()
+        at = 0
+        for w in words:
+            host[at:at + w.numel()].copy_(w.reshape(-1), non_blocking=True)
+            at += w.numel()
+        ev = torch.cuda.Event()
+        ev.record()
+
+        def read():
+            ev.synchronize()
+            return host.tolist()
+        return read
 
     @torch.no_grad()
     def _large_graph_forward_hip(self, node_feat, L, D, V, mask, planes=3):
@@ -547,74 +569,77 @@ class _LargeMixin:
         return masked_readout(self, state, mask)
 
 
-class _DenseBatch:
-    """What the two Functions below read of a batch — B, N, channels, image / images, n_nodes — for a dense
-    collated L whose image(s) `_dense_operators` left riding on it.  n_nodes is None: the mask need not be a
-    prefix, and rows outside it get an exactly zero gradient from the masked readout (from then on they receive
-    gradient only through L and V, as autograd computes it)."""
-    __slots__ = ('B', 'N', 'channels', 'image', 'images', 'n_nodes')
+class _SparseOperators:
+    """What `_LargeSparseFusedFunction` reads of a batch: R symmetric operators as sparse images with their fp32
+    values, serving `channels` weight channels — R = 1 (`img` a LargeSparseImage: every channel is that operator)
+    or R = channels (`img` a LargeSparseImages: one operator per channel).
+      an untyped SparseLaplacian           R = 1, channels = 2
+      a typed one                          R = channels = 3 .. 8
+      a dense L, `_dense_operators` 'one'  R = 1: the image riding on the tensor
+      ... 'each' (`each=True`)             R = channels: the images riding on it
+    n_nodes is the edge lists'; None for a dense L: the mask need not be a prefix, and rows outside it get an
+    exactly zero gradient from the masked readout (from then on they receive gradient only through L and V, as
+    autograd computes it)."""
+    __slots__ = ('B', 'N', 'channels', 'R', 'img', 'n_nodes')
 
-    def __init__(self, L, each):
+    def __init__(self, L, each=False):
         self.B, self.N, self.channels = L.shape[0], L.shape[1], L.shape[3]
-        self.images = ops.attached_sparse_images(L) if each else None
-        self.image = self.images.channel(0) if each else ops.attached_sparse_image(L)
-        self.n_nodes = None
-        assert self.image is not None and self.image.values is not None
+        if isinstance(L, ops.SparseLaplacian):
+            self.img, self.n_nodes = (L.image if L.images is None else L.images), L.n_nodes
+        else:
+            self.img, self.n_nodes = (ops.attached_sparse_images(L) if each else ops.attached_sparse_image(L)), None
+        assert self.img is not None and self.img.values is not None
+        self.R = self.channels if isinstance(self.img, ops.LargeSparseImages) else 1
 
 
 class _LargeSparseFusedFunction(torch.autograd.Function):
-    """Training an edge-list batch (an untyped SparseLaplacian: ONE symmetric operator as its sparse
-    image) through the HIP kernels, with no dense L.
+    """Training a batch of graphs beyond the dense kernels' sizes whose operators are symmetric and given as
+    sparse images (`_SparseOperators`: an edge-list batch, a typed one, or a dense collated L with its image(s))
+    through the HIP kernels, with no dense L (DESIGN.md §4.9c - e).
 
-    forward: spectral gains + the exact ops.large_sparse_conv_layer per layer — the launches of
-    `_large_sparse_layers` on the same operands, so the score is the inference route's bit for bit —
-    each layer into its own slice of ONE [num_layer, B, N, 128] buffer, then the readout.
-    backward, last layer first: lnz_large_grad_project (dP, db, A = V^T dP), the forward's gather on dP
-    (dZ = L dP = L^T dP), lnz_large_grad_spectral (dG, Q, dY; Y = V^T X recomputed by one library
-    GEMM), library GEMMs for dWn = dZ^T X and dW_s = A^T Q_s, lnz_large_grad_input (dX = dZ Wn + V dY);
-    the head by autograd on the stored last state; lnz_spectral_mlp_grad; lnz_embedding_grad.
-    Inputs L, D, V, mask, node features are data: no gradient."""
+    forward: spectral gains + `_sparse_conv_layers` — the launches of the inference route, so the score is that
+    route's bit for bit — each layer into its own slice of ONE [num_layer, B, N, 128] buffer, then the readout.
+    backward, last layer first: lnz_large_grad_project (dP, db, A = V^T dP); dZ_c = L_c dP = L_c^T dP into the
+    forward's feature buffer — R = 1: the forward's gather on dP onto zeros, R > 1:
+    lnz_large_sparse_conv_split_f32, R results from one source —; lnz_large_grad_spectral (dG, Q, dY; Y = V^T X
+    recomputed by one library GEMM); library GEMMs for dWn_c = dZ_c^T X (R = 1: the one block serves every
+    channel) and dW_s = A^T Q_s; dX = sum_c dZ_c Wn_c + V dY by lnz_large_grad_input (R = 1: Wn the channels'
+    blocks summed) or lnz_large_grad_input_channels; the head by autograd on the stored last state;
+    lnz_spectral_mlp_grad; lnz_embedding_grad.  Inputs L, D, V, mask, node features are data: no gradient."""
 
     @staticmethod
     def forward(ctx, module, node_feat, L, D, V, mask, *params):
-        m = module
-        S, planes = m.num_scale_long, m.large_split_planes
-        B, N = L.B, L.N
-        dev = V.device
+        m, op = module, L
+        S = m.num_scale_long
         Vf = V.float().contiguous()
         cache = m._plan_large()
         G = None
         if S > 0:
             G = ops.spectral_gains(D, m.long_diffusion_dist, m.num_layer, cache['mlp_pack'])
-        img = L.image
-        Vb = ops.large_pack_vectors(Vf, planes)
-        classes = (0,) * L.channels
-        plan = m._plan_large(planes, classes)
-        X0 = input_state(m, node_feat, width=(m.input_dim + 31) // 32 * 32, as_float=True).contiguous()
-        work = ops.large_sparse_work_buffers(B, N, dev, planes=planes)
-        Xs = torch.empty((m.num_layer, B, N, 128), dtype=torch.float32, device=dev)
-        state = X0
-        for t, lay in enumerate(plan['conv'][(planes, classes)]):
-            state = ops.large_sparse_conv_layer(state, lay['din'], img, Vb, Vf, lay['Wn32'], lay['Wt'],
-                                                G[t] if G is not None else None, lay['bias'], work,
-                                                planes, relu=True, out=Xs[t])
+        Xs = torch.empty((m.num_layer, op.B, op.N, 128), dtype=torch.float32, device=V.device)
+        X0, state, work = m._sparse_conv_layers(node_feat, op.img, op.channels, Vf, G, m.large_split_planes, out=Xs)
         mask_u8 = mask.to(torch.uint8).contiguous()
         if m.large_head_kernel and m.output_dim <= 16:
             score = ops.large_head(state, mask_u8, *m._plan_head(cache))
         else:
             score = masked_readout(m, state, mask)
-        ctx.module, ctx.image, ctx.has_gains, ctx.channels = m, img, G is not None, L.channels
-        ctx.save_for_backward(node_feat, X0, D, Vf, mask_u8, L.n_nodes, Xs, *([G] if G is not None else []))
+        # (the [R, B, N, 128] feature buffer of the forward is the backward's dZ: no allocation of its own)
+        ctx.module, ctx.op, ctx.has_gains, ctx.dZ = m, op, G is not None, work[0].view(op.R, op.B, op.N, 128)
+        ctx.save_for_backward(node_feat, X0, D, Vf, mask_u8, op.n_nodes, Xs, *([G] if G is not None else []))
         return score
 
     @staticmethod
     def backward(ctx, grad_score):
-        m, img = ctx.module, ctx.image
+        m, op = ctx.module, ctx.op
         node_feat, X0, D, V, mask_u8, n_nodes, Xs = ctx.saved_tensors[:7]
         G = ctx.saved_tensors[7] if ctx.has_gains else None
         Lnum, B, N, _ = Xs.shape
-        K, S, C = V.shape[2], m.num_scale_long, ctx.channels   # (C channels that are ONE operator: 2 from edge lists)
-        dev = Xs.device
+        K, S, C, R = V.shape[2], m.num_scale_long, op.channels, op.R
+        # (the buffer goes with this backward, not with the graph, which a caller's `loss` keeps alive into the
+        # next step; a second backward over a retained graph takes a buffer of its own)
+        dZ, ctx.dZ = ctx.dZ, None
+        if dZ is None:
+            dZ = torch.empty((R, B, N, 128), dtype=torch.float32, device=Xs.device)
         grads = {}
         # ---- head (model/lanczos_net.py:185-194): autograd on the stored last state
         Whead, bhead = m._plan_head(m._plan_large())
@@ -626,19 +651,23 @@ class _LargeSparseFusedFunction(torch.autograd.Function):
                                                 [XL, Wh, bh], grad_score.contiguous())
         scatter_head_grads(m, grads, dWh, dbh)
         g = dXL.contiguous()            # dX' of the layer at hand; lnz_large_grad_project masks it in place
-        dZ = torch.empty_like(g)
         Vt = V.transpose(1, 2)
         dGs = []
         for t in range(Lnum - 1, -1, -1):
             X = X0 if t == 0 else Xs[t - 1]
             d = m.input_dim if t == 0 else 128
-            W = m.filter[t].weight.detach().float().contiguous()      # [128, (S + 2) d]
+            W = m.filter[t].weight.detach().float().contiguous()      # [128, (S + C) d]
             A, dbg = ops.large_grad_project(g, Xs[t], V, n_nodes)     # g is dP from here on
-            dZ.zero_()
-            with torch.cuda.device(dev):
-                ops._abi().large_sparse_conv_f32(img.entries, img.values, img.counts, img.cap, g, B, N, 0, dZ)
-            dWn = _tn_split_k(dZ.view(B * N, 128), X.view(B * N, X.shape[2]))[:, :d]
-            blocks = [dWn] * C
+            if R == 1:
+                dZ.zero_()
+                with torch.cuda.device(dZ.device):
+                    ops._abi().large_sparse_conv_f32(op.img.entries, op.img.values, op.img.counts, op.img.cap, g,
+                                                     B, N, 0, dZ[0])
+            else:
+                ops.large_sparse_conv_split(op.img, g, out=dZ)        # dZ[c] = L_c dP
+            Xr = X.view(B * N, X.shape[2])
+            # (R = 1: the C channels are ONE operator, its block is every channel's)
+            blocks = [_tn_split_k(dZ[c].view(B * N, 128), Xr)[:, :d] for c in range(R)] * (C // R)
             dY = None
             if S > 0:
                 Y = torch.bmm(Vt, X)                                  # V^T X  [B, K, ldx]
@@ -651,11 +680,15 @@ class _LargeSparseFusedFunction(torch.autograd.Function):
             grads[id(m.filter[t].bias)] = dbg.sum(dim=0)
             if t > 0 or not m.general:
                 Wv = W.view(128, S + C, d)
-                Wsum = Wv[:, S]
-                for c in range(1, C):
-                    Wsum = Wsum + Wv[:, S + c]
-                Wn = torch.nn.functional.pad(Wsum, (0, 128 - d)).contiguous()
-                ops.large_grad_input(dZ, Wn, V if S > 0 else None, dY, d, out=g)
+                if R == 1:
+                    Wn = Wv[:, S]
+                    for c in range(1, C):
+                        Wn = Wn + Wv[:, S + c]
+                    Wn = torch.nn.functional.pad(Wn, (0, 128 - d)).contiguous()
+                    ops.large_grad_input(dZ[0], Wn, V if S > 0 else None, dY, d, out=g)
+                else:
+                    Wn = torch.nn.functional.pad(Wv[:, S:].permute(1, 0, 2), (0, 128 - d)).contiguous()
+                    ops.large_grad_input_channels(dZ, Wn, V if S > 0 else None, dY, d, out=g)
         # ---- spectral filter MLPs from dG [L, B K, S]
         if dGs:
             _spectral_mlp_param_grads(m, grads, D, torch.stack(dGs[::-1]).view(Lnum, B * K, S))
@@ -665,97 +698,3 @@ class _LargeSparseFusedFunction(torch.autograd.Function):
         return param_grad_tuple(m, grads, 6)
 
 
-class _LargeTypedSparseFusedFunction(torch.autograd.Function):
-    """Training a TYPED edge-list batch (a SparseLaplacian with `images`: R = E + 1 = 3 .. 8 symmetric operators,
-    one sparse image each) through the HIP kernels, with no dense L.
-
-    forward: the launches of `_large_sparse_layers` for a typed batch (one lnz_f32_linear per channel on the
-    stacked weight blocks, lnz_large_sparse_conv_channels_f32), each layer into its slice of ONE [num_layer, B,
-    N, 128] buffer, then the readout: the score is the inference route's.
-    backward, last layer first: lnz_large_grad_project; lnz_large_sparse_conv_split_f32 (dZ_c = L_c dP, R results
-    from one source); library GEMMs dWn_c = dZ_c^T X, one per channel block; lnz_large_grad_spectral and dW_s as for
-    one operator; lnz_large_grad_input_channels (dX = sum_c dZ_c Wn_c + V dY).  Head, filter MLPs and embedding
-    rows as `_LargeSparseFusedFunction`."""
-
-    @staticmethod
-    def forward(ctx, module, node_feat, L, D, V, mask, *params):
-        m = module
-        S, planes = m.num_scale_long, m.large_split_planes
-        B, N, R = L.B, L.N, L.channels
-        dev = V.device
-        Vf = V.float().contiguous()
-        cache = m._plan_large()
-        G = None
-        if S > 0:
-            G = ops.spectral_gains(D, m.long_diffusion_dist, m.num_layer, cache['mlp_pack'])
-        imgs = L.images
-        Vb = ops.large_pack_vectors(Vf, planes)
-        classes = tuple(range(R))
-        plan = m._plan_large(planes, classes)
-        X0 = input_state(m, node_feat, width=(m.input_dim + 31) // 32 * 32, as_float=True).contiguous()
-        work = ops.large_sparse_work_buffers(B, N, dev, R=R, planes=planes)
-        Xs = torch.empty((m.num_layer, B, N, 128), dtype=torch.float32, device=dev)
-        state = X0
-        for t, lay in enumerate(plan['conv'][(planes, classes)]):
-            state = ops.large_sparse_conv_layer(state, lay['din'], imgs, Vb, Vf, lay['Wn32s'], lay['Wt'],
-                                                G[t] if G is not None else None, lay['bias'], work,
-                                                planes, relu=True, out=Xs[t])
-        mask_u8 = mask.to(torch.uint8).contiguous()
-        if m.large_head_kernel and m.output_dim <= 16:
-            score = ops.large_head(state, mask_u8, *m._plan_head(cache))
-        else:
-            score = masked_readout(m, state, mask)
-        # (the [R, B, N, 128] feature buffer of the forward is the backward's dZ: no allocation of its own)
-        ctx.module, ctx.images, ctx.has_gains, ctx.dZ = m, imgs, G is not None, work[0]
-        ctx.save_for_backward(node_feat, X0, D, Vf, mask_u8, L.n_nodes, Xs, *([G] if G is not None else []))
-        return score
-
-    @staticmethod
-    def backward(ctx, grad_score):
-        m, imgs = ctx.module, ctx.images
-        node_feat, X0, D, V, mask_u8, n_nodes, Xs = ctx.saved_tensors[:7]
-        G = ctx.saved_tensors[7] if ctx.has_gains else None
-        Lnum, B, N, _ = Xs.shape
-        K, S, R = V.shape[2], m.num_scale_long, imgs.R
-        grads = {}
-        # ---- head (model/lanczos_net.py:185-194): autograd on the stored last state
-        Whead, bhead = m._plan_head(m._plan_large())
-        with torch.enable_grad():
-            XL = Xs[-1].detach().requires_grad_(True)
-            Wh = Whead.detach().requires_grad_(True)
-            bh = bhead.detach().requires_grad_(True)
-            dXL, dWh, dbh = torch.autograd.grad(masked_readout(m, XL, mask_u8, stacked=(Wh, bh)),
-                                                [XL, Wh, bh], grad_score.contiguous())
-        scatter_head_grads(m, grads, dWh, dbh)
-        g = dXL.contiguous()            # dX' of the layer at hand; lnz_large_grad_project masks it in place
-        dZ = ctx.dZ
-        Vt = V.transpose(1, 2)
-        dGs = []
-        for t in range(Lnum - 1, -1, -1):
-            X = X0 if t == 0 else Xs[t - 1]
-            d = m.input_dim if t == 0 else 128
-            W = m.filter[t].weight.detach().float().contiguous()      # [128, (S + R) d]
-            A, dbg = ops.large_grad_project(g, Xs[t], V, n_nodes)     # g is dP from here on
-            ops.large_sparse_conv_split(imgs, g, out=dZ)              # dZ[c] = L_c dP
-            Xr = X.view(B * N, X.shape[2])
-            blocks = [_tn_split_k(dZ[c].view(B * N, 128), Xr)[:, :d] for c in range(R)]
-            dY = None
-            if S > 0:
-                Y = torch.bmm(Vt, X)                                  # V^T X  [B, K, ldx]
-                dG, Q, dY = ops.large_grad_spectral(A, Y, G[t], W, d, want_dgains=m._has_mlp())
-                dWl = A.view(B * K, 128).t() @ Q.view(B * K, S * d)
-                blocks = list(dWl.view(128, S, d).unbind(1)) + blocks
-                if dG is not None:
-                    dGs.append(dG)
-            grads[id(m.filter[t].weight)] = torch.stack(blocks, dim=1).reshape(128, -1)
-            grads[id(m.filter[t].bias)] = dbg.sum(dim=0)
-            if t > 0 or not m.general:
-                Wn = torch.nn.functional.pad(W.view(128, S + R, d)[:, S:].permute(1, 0, 2), (0, 128 - d)).contiguous()
-                ops.large_grad_input_channels(dZ, Wn, V if S > 0 else None, dY, d, out=g)
-        # ---- spectral filter MLPs from dG [L, B K, S]
-        if dGs:
-            _spectral_mlp_param_grads(m, grads, D, torch.stack(dGs[::-1]).view(Lnum, B * K, S))
-        # ---- embedding rows
-        if not m.general:
-            grads[id(m.embedding.weight)] = embedding_grad(m, node_feat, g, N, m.input_dim)
-        return param_grad_tuple(m, grads, 6)

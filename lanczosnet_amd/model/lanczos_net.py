@@ -16,12 +16,12 @@ for dW).  Architectures outside the fused kernels (other widths
 > 0 in training, AdaLanczosNet's backward) differentiate a device-side torch restatement of the
 same math (`_torch_forward`) — still GPU only; there is no CPU path.  Graphs of 33..128 nodes have
 a HIP backward of their own (`_MidGraphFusedFunction`, csrc/conv_mid_grad.hip),
-opt-in through `mid_backward_impl`; edge-list batches beyond that (an untyped `ops.SparseLaplacian`) have
-one on their sparse image (`_LargeSparseFusedFunction`, csrc/conv_sparse_grad.hip), opt-in
-through `large_backward_impl`; typed ones (two or more edge types) through `large_typed_backward_impl`
-(`_LargeTypedSparseFusedFunction`); a DENSE collated `L` beyond 128 nodes whose operators are
-symmetric takes the same two Functions on the image(s) of the tensor, opt-in through `large_dense_backward_impl`
-(DESIGN.md §4.9e).
+opt-in through `mid_backward_impl`; beyond that ONE Function (`_LargeSparseFusedFunction`,
+csrc/conv_sparse_grad.hip) trains on the sparse image(s) of symmetric operators (`_SparseOperators`): edge-list
+batches (an untyped `ops.SparseLaplacian`), opt-in through `large_backward_impl`; typed ones (two
+or more edge types: one image per operator channel; §4.9d) through `large_typed_backward_impl`; a DENSE collated
+`L` beyond 128 nodes whose operators are symmetric, on the image(s) of the tensor, through
+`large_dense_backward_impl` (§4.9e).
 
 One regime per module: `_small` (<= 32 nodes, the fused kernels), `_mid` (33..128 nodes, one launch),
 `_large` (beyond: streamed and sparse kernels, library GEMMs), `_ada` (AdaLanczosNet); `_common`
@@ -38,7 +38,7 @@ from .. import ops
 from ..utils.data_helper import check_dist
 from ._common import (FUSED_MAX_NODES, FUSED_WIDTHS, LARGE_MAX_OPERATORS, MAX_CHANNELS, MAX_INPUT_DIM,
                       MAX_SHORT_SCALES, MID_MAX_NODES, STRIP_MAX_LONG_SCALES, STRIP_WIDTH, _opt, input_state, masked_readout)
-from ._large import _DenseBatch, _LargeMixin, _LargeSparseFusedFunction, _LargeTypedSparseFusedFunction
+from ._large import _LargeMixin, _LargeSparseFusedFunction, _SparseOperators
 from ._mid import _MidGraphFusedFunction, _MidMixin
 from ._small import _LanczosNetFunction, _LanczosNetFusedFunction, _SmallMixin
 
@@ -47,10 +47,9 @@ __all__ = ['LanczosNet', 'LanczosNetGeneral', 'AdaLanczosNet']
 # the routes of `_LanczosNetBase._route` that train through an autograd.Function of their own
 _TRAIN_FUNCTIONS = {'fused_train_hip': _LanczosNetFusedFunction, 'fused_train_torch': _LanczosNetFunction,
                     'mid_train_hip': _MidGraphFusedFunction, 'large_train_hip': _LargeSparseFusedFunction,
-                    'large_typed_train_hip': _LargeTypedSparseFusedFunction,
+                    'large_typed_train_hip': _LargeSparseFusedFunction,
                     'large_dense_train_hip': _LargeSparseFusedFunction,
-                    'large_dense_channels_train_hip': _LargeTypedSparseFusedFunction}
-_DENSE_TRAIN_ROUTES = ('large_dense_train_hip', 'large_dense_channels_train_hip')
+                    'large_dense_channels_train_hip': _LargeSparseFusedFunction}
 
 
 class _LanczosNetBase(_SmallMixin, _MidMixin, _LargeMixin, nn.Module):
@@ -245,13 +244,14 @@ class _LanczosNetBase(_SmallMixin, _MidMixin, _LargeMixin, nn.Module):
           'mid'                33..128 nodes in one launch (`_mid_graph_forward_hip`)
           'mid_train_hip'      ... training, opted in (`_MidGraphFusedFunction`)
           'large_hip'          > 32 nodes: the streamed / sparse kernels (`_large_graph_forward_hip`)
-          'large_train_hip'    ... an edge-list batch in training, opted in (`_LargeSparseFusedFunction`)
-          'large_typed_train_hip'  ... a typed edge-list batch in training, opted in
-                               (`_LargeTypedSparseFusedFunction`)
+          'large_train_hip'    ... an edge-list batch in training, opted in (`_LargeSparseFusedFunction` on
+                               the batch's image: one operator)
+          'large_typed_train_hip'  ... a typed edge-list batch in training, opted in (the same Function on
+                               the batch's images: one operator per channel)
           'large_dense_train_hip'  > 128 nodes: a dense L of one symmetric operator class in training, opted in
-                               (`_LargeSparseFusedFunction` on the tensor's image)
+                               (the same Function on the tensor's image)
           'large_dense_channels_train_hip'  ... of 3 .. 8 distinct symmetric channels, opted in
-                               (`_LargeTypedSparseFusedFunction` on the tensor's images)
+                               (the same Function on the tensor's images)
           'library'            > 32 nodes or an architecture outside the fused kernels, inference:
                                hipBLASLt conv + HIP spectral gains (`_large_graph_forward`)
           'torch'              gradients or dropout outside the kernels: `_torch_forward`"""
@@ -379,9 +379,9 @@ class _LanczosNetBase(_SmallMixin, _MidMixin, _LargeMixin, nn.Module):
                 L = self._densify(L, "route '%s'" % route)
         if N <= FUSED_MAX_NODES and not route.startswith('fused'):
             self._warn_library_path(drop)
-        if route in _DENSE_TRAIN_ROUTES:
-            # (the two Functions read the image(s) `_dense_operators` left riding on the tensor)
-            L = _DenseBatch(L, each=route == 'large_dense_channels_train_hip')
+        if _TRAIN_FUNCTIONS.get(route) is _LargeSparseFusedFunction:
+            # (the batch's own image(s), or those `_dense_operators` left riding on the tensor)
+            L = _SparseOperators(L, each=route == 'large_dense_channels_train_hip')
         if route in _TRAIN_FUNCTIONS:
             # forward = HIP kernels keeping their states (runner/qm8_runner.py:216-248); backward =
             # HIP kernels + library GEMMs where built, else autograd through a torch recomputation

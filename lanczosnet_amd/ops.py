@@ -1276,22 +1276,29 @@ def large_grad_spectral(A, Y, G, W, d, want_dgains=True):
   return dG, Q, dY
 
 
+def _grad_input_operands(dZ, Wn, V, dY, out):
+  """The operand checks of the two dX entries (dZ [R,B,N,128], Wn [R,128,128]) -> (R, B, N, K)."""
+  _need_cuda(dZ, Wn, V, dY, out)
+  R, B, N, _ = dZ.shape
+  K = 0 if dY is None else dY.shape[1]
+  assert dZ.dtype == Wn.dtype == out.dtype == torch.float32
+  assert dZ.is_contiguous() and Wn.is_contiguous() and out.is_contiguous()
+  assert tuple(dZ.shape) == (R, B, N, 128) and tuple(out.shape) == (B, N, 128) and tuple(Wn.shape) == (R, 128, 128)
+  assert not dZ.data_ptr() <= out.data_ptr() < dZ.data_ptr() + dZ.numel() * 4
+  if K:
+    assert V.dtype == dY.dtype == torch.float32 and V.is_contiguous() and dY.is_contiguous()
+    assert tuple(V.shape) == (B, N, K) and tuple(dY.shape) == (B, K, 128)
+  return R, B, N, K
+
+
 def large_grad_input(dZ, Wn, V, dY, d, out):
   """lnz_large_grad_input: out [B,N,128] = dZ Wn + V dY in one exact-fp32 MFMA launch (dZ [B,N,128],
   Wn [128,128] with columns >= d zero, V [B,N,K], dY [B,K,128]; V = dY = None: no long scales);
   columns >= d of `out` are written zero.  `out` must not be dZ.  Names itself to last_kernel()."""
-  _need_cuda(dZ, Wn, V, dY, out)
-  B, N, _ = dZ.shape
-  K = 0 if dY is None else dY.shape[1]
-  assert dZ.dtype == Wn.dtype == out.dtype == torch.float32
-  assert dZ.is_contiguous() and Wn.is_contiguous() and out.is_contiguous()
-  assert tuple(out.shape) == tuple(dZ.shape) == (B, N, 128) and tuple(Wn.shape) == (128, 128)
-  assert out.data_ptr() != dZ.data_ptr()
-  if K:
-    assert V.dtype == dY.dtype == torch.float32 and V.is_contiguous() and dY.is_contiguous()
-    assert tuple(V.shape) == (B, N, K) and tuple(dY.shape) == (B, K, 128)
+  assert dZ.dim() == 3 and Wn.dim() == 2
+  _, B, N, K = _grad_input_operands(dZ[None], Wn[None], V, dY, out)
   with torch.cuda.device(dZ.device):
-    _abi().large_grad_input(dZ, Wn, V if K else None, dY, B, N, K, d, out)
+    _abi().large_grad_input(dZ, Wn, V if K else None, dY if K else None, B, N, K, d, out)
   note_autograd_kernel()
   return out
 
@@ -1321,16 +1328,7 @@ def large_grad_input_channels(dZ, Wn, V, dY, d, out):
   (dZ [R,B,N,128], Wn [R,128,128] with columns >= d zero, V [B,N,K], dY [B,K,128]; V = dY = None: no long
   scales); columns >= d of `out` are written zero.  `out` must not be (part of) dZ.  Names itself to
   last_kernel()."""
-  _need_cuda(dZ, Wn, V, dY, out)
-  R, B, N, _ = dZ.shape
-  K = 0 if dY is None else dY.shape[1]
-  assert dZ.dtype == Wn.dtype == out.dtype == torch.float32
-  assert dZ.is_contiguous() and Wn.is_contiguous() and out.is_contiguous()
-  assert tuple(dZ.shape) == (R, B, N, 128) and tuple(out.shape) == (B, N, 128) and tuple(Wn.shape) == (R, 128, 128)
-  assert not dZ.data_ptr() <= out.data_ptr() < dZ.data_ptr() + dZ.numel() * 4
-  if K:
-    assert V.dtype == dY.dtype == torch.float32 and V.is_contiguous() and dY.is_contiguous()
-    assert tuple(V.shape) == (B, N, K) and tuple(dY.shape) == (B, K, 128)
+  R, B, N, K = _grad_input_operands(dZ, Wn, V, dY, out)
   with torch.cuda.device(dZ.device):
     _abi().large_grad_input_channels(dZ, Wn, V if K else None, dY if K else None, B, N, K, R, d, out)
   note_autograd_kernel()

@@ -1,5 +1,5 @@
 """Training TYPED edge-list batches (two or more edge types: R = E + 1 = 3 .. 8 distinct operators, one sparse
-image each) through the opt-in HIP backward (`_LargeTypedSparseFusedFunction`; lnz_large_sparse_conv_split_f32 in
+image each) through the opt-in HIP backward (`_LargeSparseFusedFunction` on R operators; lnz_large_sparse_conv_split_f32 in
 csrc/conv_sparse.hip, lnz_large_grad_input_channels in csrc/conv_sparse_grad.hip).  Every module
 test opts in (`large_typed_backward_impl = 'hip'`), turns the 'densified' warning into an error, patches
 `SparseLaplacian.to_dense` to raise during the step and reads from `ops.last_kernel()` that the new
@@ -296,18 +296,45 @@ def test_grad_input_channels_equals_float64(shape):
   assert (res[..., d:] == 0).all()
 
 
-def test_grad_input_channels_with_one_channel_is_grad_input_bit_for_bit(launches):
-  """Real-valued operands at B 5, N 300, K 20, d 128; and two calls at R = 3 give the same bits."""
-  from lanczosnet_amd import ops
+def _real_input_operands(B, N, K, d):
+  """Real-valued (dZ [3,B,N,128], Wn [3,128,128] with columns >= d zero, V, dY) from RandomState(6), on the device."""
   rs = np.random.RandomState(6)
-  B, N, K, d = 5, 300, 20, 128
   dZ = _t(rs.randn(3, B, N, 128).astype(np.float32))
-  Wn = _t((rs.randn(3, 128, 128) * 0.05).astype(np.float32))
+  Wn = (rs.randn(3, 128, 128) * 0.05).astype(np.float32)
+  Wn[:, :, d:] = 0.0
   V = _t((rs.randn(B, N, K) / np.sqrt(N)).astype(np.float32))
   dY = _t(rs.randn(B, K, 128).astype(np.float32))
+  return dZ, _t(Wn), V, dY
+
+
+# the one-operator kernel that lnz_large_grad_input launched before it became the R = 1 of the channels kernel:
+# its output on the MI355X for `_real_input_operands`' channel 0 — key: (B, N, K, d)
+PARENT_GOLDEN = {'k20_d128': (2, 65, 20, 128),    # one full 64-row tile and one row of a second; K a multiple of 4
+                 'k17_d127': (2, 65, 17, 127)}    # K padded to 20, a partial last column tile
+
+
+def test_grad_input_channels_with_one_channel_is_grad_input_bit_for_bit(launches):
+  """Both dX entries at R = 1 reproduce, bit for bit, what the retired one-operator kernel gave for the same
+  real-valued operands (tests/golden/large_grad_input_parent.npz); and two calls at R = 3 (B 5, N 300, K 20,
+  d 128) give the same bits."""
+  import os
+  from lanczosnet_amd import ops
+  golden = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'large_grad_input_parent.npz'))
+  assert sorted(golden.files) == sorted(PARENT_GOLDEN)
+  for key, (B, N, K, d) in PARENT_GOLDEN.items():
+    dZ, Wn, V, dY = _real_input_operands(B, N, K, d)
+    want = _t(golden[key])
+    assert want.dtype == torch.float32 and tuple(want.shape) == (B, N, 128) and float(want.abs().max()) > 0
+    one = ops.large_grad_input_channels(dZ[:1], Wn[:1], V, dY, d,
+                                        out=torch.full((B, N, 128), float('nan'), device=DEV))
+    assert ops.last_kernel() == 'large_grad_input_channels_kernel'
+    ref = ops.large_grad_input(dZ[0], Wn[0], V, dY, d, out=torch.full((B, N, 128), float('nan'), device=DEV))
+    assert ops.last_kernel() == 'large_grad_input_kernel'
+    assert torch.equal(one, want) and torch.equal(ref, want), key
+    assert torch.isfinite(one).all() and (one[..., d:] == 0).all()
+  B, N, K, d = 5, 300, 20, 128
+  dZ, Wn, V, dY = _real_input_operands(B, N, K, d)
   one = ops.large_grad_input_channels(dZ[:1], Wn[:1], V, dY, d, out=torch.full((B, N, 128), float('nan'), device=DEV))
-  ref = ops.large_grad_input(dZ[0], Wn[0], V, dY, d, out=torch.empty((B, N, 128), device=DEV))
-  assert torch.equal(one, ref) and torch.isfinite(one).all()
   runs = [ops.large_grad_input_channels(dZ, Wn, V, dY, d, out=torch.full((B, N, 128), float('nan'), device=DEV))
           for _ in range(2)]
   assert torch.equal(runs[0], runs[1]) and not torch.equal(runs[0], one)

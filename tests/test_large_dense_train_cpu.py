@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import symmetry_mirror as SM
-from test_large_train_cpu import _todays_route
+from test_large_train_cpu import _todays_route, host_image, one_function_serves_the_large_routes
 from test_route_cpu import CASES, G, Q, _module
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -74,7 +74,6 @@ def test_the_keywords_are_keyword_only():
 
 def test_routes_are_taken_inside_the_envelope():
   from lanczosnet_amd.model import lanczos_net
-  from lanczosnet_amd.model._large import _LargeSparseFusedFunction, _LargeTypedSparseFusedFunction
   for name, C in itertools.product((G, Q), (1, 2, 3, 8)):
     net = _net(name, C)
     for N, K in itertools.product((129, 193, 2048, 16384), (1, 20, 64)):
@@ -83,10 +82,41 @@ def test_routes_are_taken_inside_the_envelope():
     net = _net(name, C, switches=dict(large_sparse_channels='each'))
     for N, K in itertools.product((129, 2048), (1, 64)):
       assert net._route(N, K, C, *TRAIN, dense_channel_operators=True) == EACH, (name, C, N, K)
-  assert lanczos_net._TRAIN_FUNCTIONS[ONE] is _LargeSparseFusedFunction
-  assert lanczos_net._TRAIN_FUNCTIONS[EACH] is _LargeTypedSparseFusedFunction
+  one_function_serves_the_large_routes()
+  operand_description_of_a_dense_tensor()
   doc = lanczos_net._LanczosNetBase._route.__doc__
   assert "'%s'" % ONE in doc and "'%s'" % EACH in doc
+
+
+def operand_description_of_a_dense_tensor():
+  """'one': R = 1 whatever the channel count, the image riding on the tensor; 'each': R = channels, the images
+  riding on it; n_nodes is None in both.  An image that does not ride on THIS state of the tensor is refused."""
+  import torch
+  from lanczosnet_amd import ops
+  from lanczosnet_amd.model._large import _SparseOperators
+  for C in (1, 2, 3):
+    L = torch.zeros(2, 130, 130, C)
+    img = host_image(2, 130)
+    ops.attach_sparse_image(L, img)
+    op = _SparseOperators(L)
+    assert (op.B, op.N, op.channels, op.R) == (2, 130, C, 1)
+    assert op.img is img and op.n_nodes is None
+  for C in (3, 8):
+    L = torch.zeros(2, 130, 130, C)
+    imgs = host_image(2, 130, R=C)
+    ops.attach_sparse_images(L, imgs)
+    op = _SparseOperators(L, each=True)
+    assert (op.B, op.N, op.channels, op.R) == (2, 130, C, C)
+    assert op.img is imgs and op.n_nodes is None
+    with pytest.raises(AssertionError):
+      _SparseOperators(L)                       # no single image rides on it
+  L.add_(1.0)                                   # (the tensor changed: its images are stale)
+  with pytest.raises(AssertionError):
+    _SparseOperators(L, each=True)
+  L = torch.zeros(2, 130, 130, 2)
+  ops.attach_sparse_image(L, host_image(2, 130, values=False))
+  with pytest.raises(AssertionError):
+    _SparseOperators(L)
 
 
 @pytest.mark.parametrize('case,over,switches,call', [

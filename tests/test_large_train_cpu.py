@@ -32,9 +32,46 @@ def test_route_is_taken_inside_the_envelope():
       assert net._route(N, K, 2, *TRAIN, sparse_one_operator=True) == ROUTE, (name, N, K)
   # the route is one of the functions `forward` trains through
   from lanczosnet_amd.model import lanczos_net
-  from lanczosnet_amd.model._large import _LargeSparseFusedFunction
-  assert lanczos_net._TRAIN_FUNCTIONS[ROUTE] is _LargeSparseFusedFunction
+  one_function_serves_the_large_routes()
+  operand_description_of_an_untyped_edge_list_batch()
   assert ROUTE in lanczos_net._LanczosNetBase._route.__doc__
+
+
+LARGE_TRAIN_ROUTES = ('large_train_hip', 'large_typed_train_hip', 'large_dense_train_hip',
+                      'large_dense_channels_train_hip')
+
+
+def one_function_serves_the_large_routes():
+  """Each of the four large training routes maps to the ONE Function; the names it replaced are gone."""
+  from lanczosnet_amd.model import _large, lanczos_net
+  for route in LARGE_TRAIN_ROUTES:
+    assert lanczos_net._TRAIN_FUNCTIONS[route] is _large._LargeSparseFusedFunction, route
+  for gone in ('_LargeTypedSparseFusedFunction', '_DenseBatch'):
+    assert not hasattr(_large, gone) and not hasattr(lanczos_net, gone), gone
+
+
+def host_image(B, N, R=None, cap=32, values=True):
+  """A LargeSparseImage (R None) or the LargeSparseImages of R channels, of host tensors: no GPU to describe it."""
+  import torch
+  from lanczosnet_amd import ops
+  lead = (B, N) if R is None else (R, B, N)
+  cls = ops.LargeSparseImage if R is None else ops.LargeSparseImages
+  return cls(torch.zeros(lead + (cap,), dtype=torch.int32), torch.zeros(lead, dtype=torch.int32),
+             torch.zeros((1,), dtype=torch.int32), cap, torch.zeros(lead + (cap,)) if values else None)
+
+
+def operand_description_of_an_untyped_edge_list_batch():
+  """One operator serving the two channels: R = 1, channels = 2, the batch's image and node counts."""
+  import torch
+  from lanczosnet_amd import ops
+  from lanczosnet_amd.model._large import _SparseOperators
+  n = torch.tensor([300, 7], dtype=torch.int32)
+  sl = ops.SparseLaplacian(2, 300, n, host_image(2, 300), None, None)
+  op = _SparseOperators(sl)
+  assert (op.B, op.N, op.channels, op.R) == (2, 300, 2, 1)
+  assert op.img is sl.image and op.n_nodes is n
+  with pytest.raises(AssertionError):
+    _SparseOperators(ops.SparseLaplacian(2, 300, n, host_image(2, 300, values=False), None, None))
 
 
 @pytest.mark.parametrize('case,over,switches,call', [

@@ -1,5 +1,5 @@
-"""Host side of the opt-in HIP backward for TYPED edge-list batches (`_LargeTypedSparseFusedFunction`,
-lnz_large_sparse_conv_split_f32, lnz_large_grad_input_channels): the route
+"""Host side of the opt-in HIP backward for TYPED edge-list batches (`_LargeSparseFusedFunction` on R = channels
+operators, lnz_large_sparse_conv_split_f32, lnz_large_grad_input_channels): the route
 `'large_typed_train_hip'` and its envelope, asked of `_LanczosNetBase._route` with no GPU; the new entries in the
 header, the bindings and the library; the preconditions of the exact kernel cases
 (tests/large_typed_train_fixture.py)."""
@@ -40,9 +40,29 @@ def test_route_is_taken_inside_the_envelope():
     for N, K in itertools.product((193, 2048, 2740, 16384), (1, 20, 64)):
       assert net._route(N, K, channels, *TRAIN, sparse_typed_operators=True) == ROUTE, (name, channels, N, K)
   from lanczosnet_amd.model import lanczos_net
-  from lanczosnet_amd.model._large import _LargeTypedSparseFusedFunction
-  assert lanczos_net._TRAIN_FUNCTIONS[ROUTE] is _LargeTypedSparseFusedFunction
+  from test_large_train_cpu import one_function_serves_the_large_routes
+  one_function_serves_the_large_routes()
+  operand_description_of_a_typed_edge_list_batch()
   assert ROUTE in lanczos_net._LanczosNetBase._route.__doc__
+
+
+def operand_description_of_a_typed_edge_list_batch():
+  """One operator per channel: R = channels = 3 .. 8, the batch's images and node counts."""
+  import torch
+  from lanczosnet_amd import ops
+  from lanczosnet_amd.model._large import _SparseOperators
+  from test_large_train_cpu import host_image
+  n = torch.tensor([300, 7], dtype=torch.int32)
+  for channels in (3, 8):
+    imgs = host_image(2, 300, R=channels)
+    sl = ops.SparseLaplacian(2, 300, n, imgs.channel(0), None, None, channels=channels,
+                             edge_type=torch.zeros(0, dtype=torch.int32), images=imgs)
+    op = _SparseOperators(sl)
+    assert (op.B, op.N, op.channels, op.R) == (2, 300, channels, channels)
+    assert op.img is imgs and op.n_nodes is n
+  novals = host_image(2, 300, R=3, values=False)
+  with pytest.raises(AssertionError):
+    _SparseOperators(ops.SparseLaplacian(2, 300, n, novals.channel(0), None, None, channels=3, images=novals))
 
 
 @pytest.mark.parametrize('case,over,switches,call', [

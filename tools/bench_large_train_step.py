@@ -14,7 +14,7 @@ parameters and optimizer state.
 
 TYPED shapes (`typed`: config 5's graphs, `typed_wide`: the wide corner — (E + 1) N beyond `to_dense`'s limit, the
 switch on only —, each with two edge types drawn per edge): the same two routes under the typed switch
-(`large_typed_backward_impl`: `_LargeTypedSparseFusedFunction`), and one layer's split gather
+(`large_typed_backward_impl`: the same Function on R = 3 operators), and one layer's split gather
 (lnz_large_sparse_conv_split_f32) beside R launches of lnz_large_sparse_conv_f32 onto zeroed buffers on the same
 operands.  They are written to profiles/large_typed_train_step.json.
 

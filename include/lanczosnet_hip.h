@@ -40,6 +40,8 @@ extern "C" {
  *    take that backward; additive, the version stays);
  *    + the GAT baseline's attention and readout (lnz_gat_attention, lnz_gat_readout: additive, the version
  *    stays);
+ *    + their backward (lnz_gat_attention_backward, lnz_gat_readout_backward and the two
+ *    _workspace_floats queries: additive, the version stays);
  *    + lnz_forward_args.rare_strips / .no_fold / .rare_debug at the END of the block (the strip forward's folded form of
  *    the rare bond-type channels, on by default: zeros = folded where cheaper; additive, the version
  *    stays — a caller built against the shorter block must zero-fill lnz_forward_args_size() bytes);
@@ -1162,6 +1164,44 @@ int lnz_gat_attention(const float* Wh, int ldw, const float* L, int64_t stride_b
 int lnz_gat_readout(const float* Hlast, int ld, const uint8_t* mask, const float* Wo, const float* bo,
                     const float* wg, const float* bg, int B, int N, int CH, int Dh, int P, float* score,
                     lnz_stream_t stream);
+/* The backward of lnz_gat_attention (model/gat.py:153-175 under loss.backward()) for every channel and
+ * head of one layer.  The attention block P is recomputed from Wh by the forward's own instructions; with
+ *   dO = dOut * elu'(.) (elu: 1 where out > 0, else out + 1; out is read for nothing else and may be NULL
+ *   when elu = 0), dP[i][j] = dO[i] . Wh[j], t[j] = sum_i P dP, dE = P (dP - t), dZ = dE * (s1[i] + s2[j] > 0
+ *   ? 1 : 0.2), ds1[i] = sum_j dZ, ds2[j] = sum_i dZ:
+ *   dWh[j] = sum_i P[i][j] dO[i] + ds1[j] a1 + ds2[j] a2                  [B N, ldg], block c H + h
+ *   da1 = sum ds1[i] Wh[i], da2 = sum ds2[i] Wh[i], dbias = sum dO[i]    [C H][Dh], summed over the molecules
+ *   db1 = sum ds1[i], db2 = sum ds2[i]                                   [C H]
+ * L gets no gradient; all N padded rows and columns take part.  dbias is the gradient of the bias AS
+ * PASSED (one row per block; the caller adds the rows of an aliased parameter).  The sums over the
+ * molecules use no atomics: every workgroup writes its partials to workspace
+ * [lnz_gat_attention_backward_workspace_floats(B, C, H, Dh)] (no initialisation needed) and a second
+ * launch adds them in a fixed order; every sum inside a block runs in a fixed order: bit-reproducible.
+ * The envelope of lnz_gat_attention; ldw / ldo / ldd / ldg multiples of 4 (LNZ_ENOTSUP otherwise); Wh, out,
+ * dOut, dWh 16-byte aligned; dWh must alias none of Wh, out, dOut.  One workgroup per (molecule, channel),
+ * 60 KB of LDS. */
+int64_t lnz_gat_attention_backward_workspace_floats(int B, int C, int H, int Dh);
+int lnz_gat_attention_backward(const float* Wh, int ldw, const float* L, int64_t stride_b, int64_t stride_r,
+                               int64_t stride_c, int64_t stride_ch, const float* a1, const float* b1,
+                               const float* a2, const float* b2, const float* out, int ldo, const float* dOut,
+                               int ldd, int B, int N, int C, int H, int Dh, int elu, float* workspace,
+                               float* dWh, int ldg, float* da1, float* db1, float* da2, float* db2,
+                               float* dbias, lnz_stream_t stream);
+/* The backward of lnz_gat_readout (model/gat.py:177-196 under loss.backward()): x, o = Wo x + bo and
+ * g = sigmoid(wg x + bg) recomputed as the forward computes them; per row i of the mask (cnt of them; all N
+ * without a mask), with dscore [B, P]:
+ *   dy = dscore / cnt, do = dy g, dzg = (sum_p dy[p] o[p]) g (1 - g), dx = Wo^T do + wg dzg
+ *   dHlast[i, every one of the CH blocks] = dx / CH        [B N, ldg]; exactly 0 on rows outside the mask
+ *   dWo [P][Dh] = sum do x^T, dbo [P] = sum do, dwg [Dh] = sum dzg x, dbg [1] = sum dzg   (rows, molecules)
+ * The same reduction scheme: per-molecule partials in workspace
+ * [lnz_gat_readout_backward_workspace_floats(B, Dh, P)], added in a fixed order by a second launch.
+ * A molecule without a masked row (NaN in the forward) is unspecified.  The envelope of lnz_gat_readout;
+ * dHlast must not alias Hlast. */
+int64_t lnz_gat_readout_backward_workspace_floats(int B, int Dh, int P);
+int lnz_gat_readout_backward(const float* Hlast, int ld, const uint8_t* mask, const float* Wo, const float* bo,
+                             const float* wg, const float* bg, const float* dscore, int B, int N, int CH,
+                             int Dh, int P, float* workspace, float* dHlast, int ldg, float* dWo, float* dbo,
+                             float* dwg, float* dbg, lnz_stream_t stream);
 
 
 /* ---- next row (SURVEY.md 8f rank 1 + 3): device-side collate from a packed molecule shard ----

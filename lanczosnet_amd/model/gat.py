@@ -14,8 +14,18 @@ Route 'gat_hip' (inference, and training calls that need no gradient): per layer
 launch on the weight stack [C H Dh, Din], then `gat_attention`; `gat_readout` after the last layer.
 Everything else — gradients, dropout in training, shapes outside the kernels — takes 'gat_torch', a
 device-side differentiable torch restatement, with one UserWarning per module that names the reason.
-There is no CPU path and no HIP backward.
+There is no CPU path.
+
+Route 'gat_hip_train' (opt-in: `LANCZOSNET_GAT_BACKWARD=hip`, or `net.gat_backward_impl = 'hip'`;
+default 'torch': nothing changes): a call that needs gradients runs the same three kernels forward
+(the score's bits are route 'gat_hip's) inside one autograd Function on the stacked operands of every
+layer, and backward `gat_readout_backward`, per layer `gat_attention_backward` + `f32_linear` (dstate) +
+a library GEMM (dW), and `embedding_grad` (csrc/gat_grad.hip).  Autograd's own backward
+of `torch.stack` / `torch.cat` hands the pieces to the parameters: the C copies of the aliased
+`bias_{h}_{E}_{t}` are summed, the never-read biases keep `grad is None`.  Dropout in training and
+every shape reason still take 'gat_torch'.
 """
+import os
 import warnings
 
 import torch
@@ -33,8 +43,59 @@ GAT_MAX_WIDTH = 1024        # C H Dh, a multiple of GAT_WIDTH_STEP
 GAT_WIDTH_STEP = 32         # ... and of the input width (lnz_f32_linear: K a multiple of 32)
 
 
+class _GatTrainFunction(torch.autograd.Function):
+    """Route 'gat_hip_train': forward = `GAT._hip_forward`'s three kernels on the stacked operands,
+    saving per layer the input state and Wh (the output of layer t is the state of layer t + 1);
+    backward = readout backward, layers T-1 .. 0, the embedding table's gradient (all N rows take
+    part, the padding id included, as in the reference).  Inputs after the five plain ones: the
+    embedding table, Wo, bo, wg, bg, then per layer W [C H, Dh, Din], a1, b1, a2, b2, bias."""
+
+    @staticmethod
+    def forward(ctx, H, CH, node_feat, L, mask, emb, Wo, bo, wg, bg, *layer_ops):
+        T = len(layer_ops) // 6
+        f = lambda x: x.detach().float().contiguous()  # noqa: E731
+        layers = []
+        for t in range(T):
+            W, a1, b1, a2, b2, bias = layer_ops[6 * t:6 * t + 6]
+            layers.append((f(W.reshape(-1, W.shape[2])), f(a1), f(b1), f(a2), f(b2), f(bias)))
+        head = (f(Wo), f(bo), f(wg), f(bg))
+        B, N = node_feat.shape
+        states, whs = [emb.detach()[node_feat]], []
+        for t in range(T):
+            W, a1, b1, a2, b2, bias = layers[t]
+            Wh = ops.f32_linear(states[t].reshape(B * N, states[t].shape[2]), W).view(B, N, -1)
+            whs.append(Wh)
+            states.append(ops.gat_attention(Wh, L, a1, b1, a2, b2, bias, H, elu=t < T - 1))
+        score = ops.gat_readout(states[T], mask, *head, CH)
+        ctx.H, ctx.CH, ctx.T, ctx.num_atom = H, CH, T, emb.shape[0]
+        ctx.layers, ctx.head = layers, head
+        ctx.save_for_backward(node_feat, L, mask)
+        ctx.states, ctx.whs = states, whs
+        return score
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dscore):
+        T, H = ctx.T, ctx.H
+        node_feat, L, mask = ctx.saved_tensors
+        states, whs = ctx.states, ctx.whs
+        dstate, dWo, dbo, dwg, dbg = ops.gat_readout_backward(states[T], mask, *ctx.head, ctx.CH,
+                                                              dscore.contiguous())
+        grads = [None] * (6 * T)
+        for t in range(T - 1, -1, -1):
+            W, a1, b1, a2, b2, _ = ctx.layers[t]
+            elu = t < T - 1
+            dstate, dW, da1, db1, da2, db2, dbias = ops.gat_layer_backward(
+                states[t], dstate, whs[t], states[t + 1] if elu else None, L, W, a1, b1, a2, b2, H, elu=elu)
+            grads[6 * t:6 * t + 6] = [dW.view(a1.shape[0], a1.shape[1], -1), da1, db1, da2, db2, dbias]
+        demb = ops.embedding_grad(node_feat.contiguous(), dstate, dstate.shape[2], ctx.num_atom)
+        return (None, None, None, None, None, demb, dWo, dbo, dwg.view(1, -1), dbg) + tuple(grads)
+
+
 class GAT(nn.Module):
     """Graph Attention Networks (Velickovic et al., ICLR 2018) as the reference builds it for QM8."""
+    # 'torch': a call that needs gradients takes route 'gat_torch'; 'hip': route 'gat_hip_train'
+    gat_backward_impl = os.environ.get('LANCZOSNET_GAT_BACKWARD', 'torch')
 
     def __init__(self, config):
         super().__init__()
@@ -150,8 +211,8 @@ class GAT(nn.Module):
     def _why_not_hip(self, N, L, needs_grad, drop):
         """None when route 'gat_hip' serves the call, else the reason in words.  No GPU needed to ask."""
         C, T = self.num_edgetype + 1, self.num_layer
-        if needs_grad:
-            return 'gradients are required (there is no HIP backward)'
+        if needs_grad and self.gat_backward_impl != 'hip':
+            return 'gradients are required (the HIP backward is opt-in: LANCZOSNET_GAT_BACKWARD=hip)'
         if drop:
             return 'dropout=%r in training' % self.dropout
         if N > ops.GAT_MAX_NODES:
@@ -200,8 +261,12 @@ class GAT(nn.Module):
         t = self._to_module_device(dev, node_feat=node_feat, L=L, label=label, mask=mask)
         node_feat, L, label, mask = t['node_feat'], t['L'], t['label'], t['mask']
         drop = self.training and self.dropout > 0
-        why = self._why_not_hip(node_feat.shape[1], L, self._needs_grad(), drop)
-        if why is None:
+        needs_grad = self._needs_grad()
+        why = self._why_not_hip(node_feat.shape[1], L, needs_grad, drop)
+        if why is None and needs_grad:
+            self.last_route = 'gat_hip_train'
+            score = self._hip_train_forward(node_feat, L, mask)
+        elif why is None:
             self.last_route = 'gat_hip'
             score = self._hip_forward(node_feat, L, mask)
         else:
@@ -223,6 +288,16 @@ class GAT(nn.Module):
         for t in range(T):
             state = ops.gat_layer(state, L, *layers[t], H, elu=t < T - 1)
         return ops.gat_readout(state, mask, *head, (self.num_edgetype + 1) * H)
+
+    def _hip_train_forward(self, node_feat, L, mask):
+        """The kernels of `_hip_forward` under autograd: the stacked operands come from the live
+        parameters (`_layer_operands`, not the detached `_packs` cache), so that the backward of
+        torch.stack / torch.cat distributes the gradients."""
+        layer_ops = [x for t in range(self.num_layer) for x in self._layer_operands(t)]
+        return _GatTrainFunction.apply(
+            self.num_heads[0], (self.num_edgetype + 1) * self.num_heads[0], node_feat, L, mask,
+            self.embedding.weight, self.output_func[0].weight, self.output_func[0].bias,
+            self.att_func[0].weight, self.att_func[0].bias, *layer_ops)
 
     def _torch_forward(self, node_feat, L, mask, dropout=False):
         """Differentiable torch restatement of model/gat.py:142-196 on device tensors, all C H heads of

@@ -10,6 +10,7 @@ Reference interfaces replaced (paths relative to the reference repo):
   unsorted_segment_sum operators/functions/unsorted_segment_sum.py:8-44
   gat_attention       model/gat.py:153-175 (every channel and head of a layer; gat_layer adds :150-152)
   gat_readout         model/gat.py:177-196
+  gat_attention_backward / gat_readout_backward / gat_layer_backward   the same lines under loss.backward()
 """
 import torch
 
@@ -2479,6 +2480,108 @@ def gat_layer(state, L, W_stacked, a1, b1, a2, b2, bias, H, elu=True):
   B, N = state.shape[0], state.shape[1]
   Wh = f32_linear(state.reshape(B * N, state.shape[2]), W_stacked)
   return gat_attention(Wh.view(B, N, -1), L, a1, b1, a2, b2, bias, H, elu=elu)
+
+
+def gat_attention_backward(Wh, L, a1, b1, a2, b2, out, dOut, H, elu=True, dWh=None):
+  """lnz_gat_attention_backward (model/gat.py:153-175 under loss.backward()): the operands of
+  gat_attention, the layer's output `out` (read for the ELU derivative only; None is fine with
+  elu=False) and dOut [B, N, C H Dh] -> (dWh [B, N, C H Dh], da1 [C H, Dh], db1 [C H], da2, db2, dbias
+  [C H, Dh]: the gradient of the bias as passed, one row per block).  No gradient for L.  No atomics:
+  per-molecule partials in a workspace, added in a fixed order — the same bits from call to call."""
+  _need_cuda(Wh, L, a1, b1, a2, b2, out, dOut, dWh)
+  if Wh.dim() != 3 or L.dim() != 4 or L.dtype != torch.float32:
+    raise LnzError(_lib.LNZ_EINVAL, 'gat_attention_backward: Wh [B, N, C H Dh] and a float32 L [B, N, N, C] expected')
+  B, N, width = Wh.shape
+  C = L.shape[3]
+  H = int(H)
+  if tuple(L.shape[:3]) != (B, N, N) or H < 1 or width % (C * H) != 0:
+    raise LnzError(_lib.LNZ_EINVAL, 'gat_attention_backward: Wh %s, L %s, H = %d do not fit'
+                   % (tuple(Wh.shape), tuple(L.shape), H))
+  Dh = width // (C * H)
+  elu = bool(elu)
+  if elu and out is None:
+    raise LnzError(_lib.LNZ_EINVAL, 'gat_attention_backward: elu=True needs the layer\'s output')
+  if not elu:
+    out = None
+  for t, name in ((dOut, 'dOut'), (out, 'out'), (dWh, 'dWh')):
+    if t is not None and tuple(t.shape) != (B, N, width):
+      raise LnzError(_lib.LNZ_EINVAL, 'gat_attention_backward: %s %s, expected %s' % (name, tuple(t.shape), (B, N, width)))
+  ldw = _gat_rows(Wh, 'gat_attention_backward')
+  ldd = _gat_rows(dOut, 'gat_attention_backward')
+  ldo = _gat_rows(out, 'gat_attention_backward') if out is not None else ldw
+  a1, a2 = _f32c(a1), _f32c(a2)
+  b1, b2 = _f32c(b1).reshape(-1), _f32c(b2).reshape(-1)
+  for t, shape in ((a1, (C * H, Dh)), (a2, (C * H, Dh)), (b1, (C * H,)), (b2, (C * H,))):
+    if tuple(t.shape) != shape:
+      raise LnzError(_lib.LNZ_EINVAL, 'gat_attention_backward: operand of shape %s where %s is expected'
+                     % (tuple(t.shape), shape))
+  if dWh is None:
+    dWh = torch.empty((B, N, width), dtype=torch.float32, device=Wh.device)
+  ldg = _gat_rows(dWh, 'gat_attention_backward')
+  new = lambda *s: torch.empty(s, dtype=torch.float32, device=Wh.device)  # noqa: E731
+  da1, da2, dbias, db1, db2 = new(C * H, Dh), new(C * H, Dh), new(C * H, Dh), new(C * H), new(C * H)
+  with torch.cuda.device(Wh.device):
+    ws = new(max(int(_abi().gat_attention_backward_workspace_floats(B, C, H, Dh)), 1))
+    _abi().gat_attention_backward(Wh, ldw, L, L.stride(0), L.stride(1), L.stride(2), L.stride(3), a1, b1, a2, b2,
+                                  out, ldo, dOut, ldd, B, N, C, H, Dh, int(elu), ws, dWh, ldg, da1, db1, da2, db2,
+                                  dbias)
+  return dWh, da1, db1, da2, db2, dbias
+
+
+def gat_readout_backward(Hlast, mask, Wo, bo, wg, bg, CH, dscore, dHlast=None):
+  """lnz_gat_readout_backward (model/gat.py:177-196 under loss.backward()): the operands of gat_readout
+  and dscore [B, P] -> (dHlast [B, N, CH Dh] — exactly 0 on rows outside the mask —, dWo [P, Dh], dbo [P],
+  dwg [Dh], dbg [1]).  Per-molecule partials added in a fixed order."""
+  _need_cuda(Hlast, mask, Wo, bo, wg, bg, dscore, dHlast)
+  CH = int(CH)
+  if Hlast.dim() != 3 or CH < 1 or Hlast.shape[2] % CH != 0:
+    raise LnzError(_lib.LNZ_EINVAL, 'gat_readout_backward: Hlast %s is not [B, N, %d blocks]'
+                   % (tuple(Hlast.shape), CH))
+  B, N, width = Hlast.shape
+  Dh = width // CH
+  ld = _gat_rows(Hlast, 'gat_readout_backward')
+  Wo, bo, wg, bg = _f32c(Wo), _f32c(bo).reshape(-1), _f32c(wg).reshape(-1), _f32c(bg).reshape(-1)
+  P = Wo.shape[0]
+  if tuple(Wo.shape) != (P, Dh) or bo.numel() != P or wg.numel() != Dh or bg.numel() != 1:
+    raise LnzError(_lib.LNZ_EINVAL, 'gat_readout_backward: head operands %s, %s, %s, %s do not fit Dh = %d'
+                   % (tuple(Wo.shape), tuple(bo.shape), tuple(wg.shape), tuple(bg.shape), Dh))
+  if tuple(dscore.shape) != (B, P):
+    raise LnzError(_lib.LNZ_EINVAL, 'gat_readout_backward: dscore %s, expected %s' % (tuple(dscore.shape), (B, P)))
+  dscore = _f32c(dscore)
+  if mask is not None:
+    if tuple(mask.shape) != (B, N):
+      raise LnzError(_lib.LNZ_EINVAL, 'gat_readout_backward: mask %s, expected %s' % (tuple(mask.shape), (B, N)))
+    mask = (mask != 0).to(torch.uint8).contiguous()
+  if dHlast is None:
+    dHlast = torch.empty((B, N, width), dtype=torch.float32, device=Hlast.device)
+  if tuple(dHlast.shape) != (B, N, width):
+    raise LnzError(_lib.LNZ_EINVAL, 'gat_readout_backward: dHlast %s, expected %s'
+                   % (tuple(dHlast.shape), (B, N, width)))
+  ldg = _gat_rows(dHlast, 'gat_readout_backward')
+  new = lambda *s: torch.empty(s, dtype=torch.float32, device=Hlast.device)  # noqa: E731
+  dWo, dbo, dwg, dbg = new(P, Dh), new(P), new(Dh), new(1)
+  with torch.cuda.device(Hlast.device):
+    ws = new(max(int(_abi().gat_readout_backward_workspace_floats(B, Dh, P)), 1))
+    _abi().gat_readout_backward(Hlast, ld, mask, Wo, bo, wg, bg, dscore, B, N, CH, Dh, P, ws, dHlast, ldg, dWo,
+                                dbo, dwg, dbg)
+  return dHlast, dWo, dbo, dwg, dbg
+
+
+def gat_layer_backward(state, dOutLayer, Wh, out, L, W_stacked, a1, b1, a2, b2, H, elu=True, need_dstate=True):
+  """The backward of gat_layer from what its forward saved (the input state [B, N, Din], Wh [B, N, C H
+  Dh] and — for the ELU derivative — the layer's output): gat_attention_backward, then
+  dstate = dWh W_stacked through f32_linear on the transposed stack (K = C H Dh) and dW_stacked = dWh^T
+  state through the library GEMM of every other training route here (`_tn_split_k`).
+  -> (dstate [B, N, Din] or None, dW_stacked [C H Dh, Din], da1, db1, da2, db2, dbias)."""
+  from .model._common import _tn_split_k
+  B, N, Din = state.shape
+  dWh, da1, db1, da2, db2, dbias = gat_attention_backward(Wh, L, a1, b1, a2, b2, out, dOutLayer, H, elu=elu)
+  d2 = dWh.view(B * N, -1)
+  dstate = None
+  if need_dstate:
+    dstate = f32_linear(d2, W_stacked.t().contiguous()).view(B, N, Din)
+  dW = _tn_split_k(d2, state.reshape(B * N, Din))
+  return dstate, dW, da1, db1, da2, db2, dbias
 
 
 # ----------------------------------------------------------------------------------------- R12

@@ -23,8 +23,10 @@ using lnz::kEpsF64;
 using lnz::rcp_nr;
 using lnz::readlane_f64;
 
-// |A| <= 1 for L4.  Dropping a coupling beta < tol perturbs T by tol; keeping it leaves q_{j+1}
-// orthogonal only to eps/beta after CGS2 — both errors balance at sqrt(eps) ~ 1e-8.
+// Relative to the matrix' scale (lnz::matrix_scale_pow2: 1 for L4, |A| <= 1).  Dropping a coupling
+// beta < tol perturbs T by tol; keeping it leaves q_{j+1} orthogonal only to eps/beta after CGS2 —
+// both errors balance at sqrt(eps) ~ 1e-8.  (As an absolute number it cut couplings of 1e-2 |A| out
+// of a matrix scaled by 2^-20 and kept round-off of one scaled by 2^20.)
 constexpr double kBreakdownTol = 1e-8;
 
 // =========================================================================================
@@ -117,12 +119,20 @@ __device__ inline double dot16(const double (&a)[16], const double (&b)[16]) {
 
 // x <- (I - Q Q^T)^2 x over all stored basis rows (rows not yet written are zero); returns the
 // accumulated coefficient on basis vector j.  r = lane & 31, h = lane >> 5.
-// The second pass runs only where the first one removed more than 99 % of the vector's squared
-// length (sum of the squared coefficients against its squared norm, both from the 16-element
-// blocks the pass has in registers anyway; every lane computes the same two numbers, so the
-// decision is wave uniform): what is left then has lost two digits to cancellation and is
-// re-orthogonalised ("twice is enough").  LNZ_RITZ32_CGS2_ALWAYS restores the unconditional form.
-__device__ inline double cgs2_32(const Ritz32Smem& sm, double& x, int j, int r, int h) {
+// The second pass runs where the first one removed more than 99 % of the vector's squared length
+// (sum of the squared coefficients against its squared norm, both from the 16-element blocks the
+// pass has in registers anyway: what is left then has lost two digits to cancellation), and where
+// the carried bound on the loss of orthogonality says so (lnz::CgsBound, wave.hpp).  The 99 % rule
+// alone, the kernel's rule until then, lets that loss grow by |c| / |x'| per step: harmless on
+// graph Laplacians, 4e-6 at n = 32 on a matrix with an evenly spread spectrum (the bar is 2e-6).
+// The unconditional form (LNZ_RITZ32_CGS2_ALWAYS) and the classical threshold 0.5 are right as
+// well, but repeat the pass at every / every other step of a molecule; with the bound a molecule
+// batch stays on the single pass.  `restart`: x is a restart vector.
+__device__ inline double cgs2_32(const Ritz32Smem& sm, double& x, int j, int r, int h, lnz::CgsBound& ob,
+                                 const bool restart) {
+#ifndef LNZ_RITZ32_CGS2_ALWAYS
+  const float thr = ob.threshold(0.99, restart);  // (ahead of the pass: off its critical path)
+#endif
   constexpr int LD = Ritz32Smem::LD;
   double qrow[16], qcol[16], v[16];
   double coef = 0.0;
@@ -150,7 +160,7 @@ __device__ inline double cgs2_32(const Ritz32Smem& sm, double& x, int j, int r, 
 #ifndef LNZ_RITZ32_CGS2_ALWAYS
     if (pass == 0) {
       const double cc2 = xhalf_sum(dot16(v, v));  // sum of the squared coefficients
-      if (cc2 <= 0.99 * xx) break;
+      if (!ob.second_pass(xx, cc2, thr, restart)) break;
     }
 #endif
   }
@@ -736,6 +746,14 @@ __device__ __forceinline__ void lanczos_ritz32_body(
   if (n > 0) {
     double w = 0.0;
     if (r < n) w = lnz::lanczos_start_entry(r);
+    // breakdown tolerance: relative to the largest entry of the matrix
+    double amax = 0.0;
+#pragma unroll
+    for (int t = 0; t < 16; ++t) amax = fmax(amax, fabs(arow[t]));
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) amax = fmax(amax, __shfl_xor(amax, off, 64));
+    const double tol = lnz::wave_uniform(kBreakdownTol * lnz::matrix_scale_pow2(amax));
+    lnz::CgsBound ob;
     bool fresh = true;  // w is a start/restart vector: its norm is not a coupling beta
     for (int j = 0; j < n; ++j) {
       double beta, u, binv;
@@ -755,7 +773,7 @@ __device__ __forceinline__ void lanczos_ritz32_body(
           beta = nn > 0.0 ? nn * y : 0.0;
         }
         __syncthreads();
-        if (fresh || beta > kBreakdownTol) break;
+        if (fresh || beta > tol) break;
         // breakdown: span(q_0..q_{j-1}) is A-invariant -> restart from the unit vector with the
         // largest residual against the basis; T[j-1][j] stays 0
         ++nrestart;
@@ -775,16 +793,17 @@ __device__ __forceinline__ void lanczos_ritz32_body(
           cand = take ? oc : cand;
         }
         w = (r == cand) ? 1.0 : 0.0;
-        (void)cgs2_32(sm, w, 0, r, h);
+        (void)cgs2_32(sm, w, 0, r, h, ob, true);
         fresh = true;
       }
       if (!fresh && r == j - 1) ereg = beta;
+      if (j > 0) ob.accept();  // (w is basis vector j now)
       fresh = false;
       const double q = w * binv;
       double x = u * binv;  // A q
       if (h == 0) sm.Qt[j * LD + r] = q;
       // (the __syncthreads inside cgs2_32 orders this store before the basis reads)
-      const double alpha = cgs2_32(sm, x, j, r, h);
+      const double alpha = cgs2_32(sm, x, j, r, h, ob, false);
       if (r == j) dreg = alpha;
       w = x;
     }
@@ -952,7 +971,11 @@ __device__ __forceinline__ void lanczos_ritz32_body(
 #ifdef LNZ_RITZ_VGPR160   // (probe: a wave that fits next to two 176-register forward waves on a SIMD)
 #define LNZ_RITZ32_ATTR __attribute__((amdgpu_num_vgpr(80)))
 #else
-#define LNZ_RITZ32_ATTR
+// three waves per SIMD (168 registers), what the kernel had by itself until the Gram-Schmidt bound:
+// left alone the compiler now takes 188 registers; held to 168 it spills four (four scratch stores
+// and seven reloads in the whole body) — with more than one molecule per SIMD (B > 1024) the third
+// wave is worth more
+#define LNZ_RITZ32_ATTR __attribute__((amdgpu_waves_per_eu(3)))
 #endif
 __global__ __launch_bounds__(64) LNZ_RITZ32_ATTR void lanczos_ritz32_kernel(
     const float* __restrict__ A, int64_t sb, int64_t sr, int64_t sc,

@@ -38,6 +38,12 @@ using lnz::wave_sum;
 #ifndef LNZ_WG_CGS_AGAIN_WAVES
 #define LNZ_WG_CGS_AGAIN_WAVES 0.99   // the same for the wave-level form (n <= 128)
 #endif
+// Either fraction is one half of the rule: the second pass also runs where the carried bound on the
+// loss of orthogonality asks for it (lnz::CgsBound, wave.hpp).  At 0.99 alone an evenly spread
+// spectrum (Q diag(1..n)/n Q^T) lost orthogonality by a factor ~2.2 per step: 5e-4 at n = 40, Ritz
+// values off by |A| from n = 64 on, info = 0.  With the bound the graphs the
+// fractions were chosen on stay on the single pass (the bound's own arithmetic costs the graph
+// configuration's launch 4 %, against the 22 % quoted below for a tighter fraction).
 #ifndef LNZ_WG_CGS_AGAIN
 // Second Gram-Schmidt pass when the first removed more than this part of |x|^2.  The eight-wave form
 // (n > 128) used 0.99 until r05: forests of equal stars with 134..192 nodes — massively degenerate
@@ -414,6 +420,7 @@ template <int G, int H>
 __device__ __forceinline__ int lanczos_waves(WgFixed& sm, LwExtra& lw, double* __restrict__ Qt,
                                              const float* __restrict__ As, const int n,
                                              const int LD, const int LA, const int lane, const int wave,
+                                             const double tol,   // breakdown: beta <= tol
                                              long long* tl = nullptr) {  // tl: LNZ_PROFILE_PHASES (A w, dots, sums, update)
 #ifdef LNZ_PROFILE_PHASES
   long long _lt = clock64();
@@ -447,9 +454,12 @@ __device__ __forceinline__ int lanczos_waves(WgFixed& sm, LwExtra& lw, double* _
 
   // x <- (I - Q Q^T) x once or twice over basis vectors 0..cnt-1 (x: this lane's row); returns the
   // accumulated coefficient on vector jidx.  The second pass runs where the first removed more
-  // than 99 % of the squared length (the rule of the eight-wave form).
-  auto cgs2 = [&](double& x, const int cnt, const int jidx) -> double {
+  // than 99 % of the squared length or the bound on the loss of orthogonality asks for it (the
+  // rule of the eight-wave form; every wave holds the same numbers).
+  lnz::CgsBound ob;
+  auto cgs2 = [&](double& x, const int cnt, const int jidx, const bool restart) -> double {
     double coef = 0.0;
+    const float thr = ob.threshold(LNZ_WG_CGS_AGAIN_WAVES, restart);
     const bool vk0 = lane < cnt, vk1 = lane + 64 < cnt;
     int uk0, uk1;
     part_range(cnt, H, h, uk0, uk1);   // this wave's vectors of the update
@@ -487,7 +497,7 @@ __device__ __forceinline__ int lanczos_waves(WgFixed& sm, LwExtra& lw, double* _
       bool again = true;
       if (pass == 0) {
         const double cc2 = wave_sum(fma(c0, c0, c1 * c1));
-        again = !(cc2 <= LNZ_WG_CGS_AGAIN_WAVES * xx);
+        again = ob.second_pass(xx, cc2, thr, restart);
       }
       wave_sync();
       coef += cbw[jidx];
@@ -540,7 +550,7 @@ __device__ __forceinline__ int lanczos_waves(WgFixed& sm, LwExtra& lw, double* _
       }
       beta = sqrt(nn);
       LNZ_WT(0)
-      if (fresh || beta > kBreakdownTol) break;
+      if (fresh || beta > tol) break;
       // breakdown: span(q_0..q_{j-1}) is A-invariant.  Restart from the unit vector with the
       // largest residual against the basis (residual^2 >= (n-j)/n > 0; ties: the lowest row);
       // T[j-1][j] stays 0.
@@ -568,16 +578,17 @@ __device__ __forceinline__ int lanczos_waves(WgFixed& sm, LwExtra& lw, double* _
         if (G == 2 && lw.best[1] > best) cand = lw.cand[1];   // (equal: group 0's row is the lower one)
       }
       w = (row == cand) ? 1.0 : 0.0;
-      (void)cgs2(w, j, 0);
+      (void)cgs2(w, j, 0, true);
       fresh = true;
     }
     if (!fresh && wave == 0 && lane == 0) sm.ee[j - 1] = beta;
+    if (j > 0) ob.accept();   // (w is basis vector j now)
     fresh = false;
     const double binv = 1.0 / beta;
     double x = u * binv;  // A q_j
     if (vr && h == 0) Qt[(size_t)j * LD + row] = w * binv;
     // (the barrier inside cgs2 orders this store before the basis reads)
-    const double alpha = cgs2(x, j + 1, j);
+    const double alpha = cgs2(x, j + 1, j, false);
     if (wave == 0 && lane == 0) sm.dd[j] = alpha;
     w = x;
   }
@@ -622,14 +633,29 @@ __global__ __launch_bounds__(kNT) void lanczos_ritz_wg_kernel(
   {
     const float* Ab = A + (int64_t)b * sb;
     const int nc = one_wave ? (n + 3) & ~3 : n;   // (one-wave phase: rows are read four columns at a time)
+    float amax = 0.0f;   // largest |entry|: the scale of the breakdown tolerance
     for (int r = wave; r < n; r += kWaves)
-      for (int c = lane; c < nc; c += 64) As[r * LA + c] = c < n ? Ab[r * sr + c * sc] : 0.0f;
+      for (int c = lane; c < nc; c += 64) {
+        const float a = c < n ? Ab[r * sr + c * sc] : 0.0f;
+        As[r * LA + c] = a;
+        amax = fmaxf(amax, fabsf(a));
+      }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off, 64));
+    if (lane == 0) sm.pc[wave] = (double)amax;
   }
   if (tid < kNMax) {
     sm.dd[tid] = 0.0;
     sm.ee[tid] = 0.0;
   }
   __syncthreads();
+  double tol;   // breakdown: beta <= tol (workgroup uniform)
+  {
+    double amax = sm.pc[0];
+#pragma unroll
+    for (int wv = 1; wv < kWaves; ++wv) amax = fmax(amax, sm.pc[wv]);
+    tol = lnz::wave_uniform(kBreakdownTol * lnz::matrix_scale_pow2(amax));
+  }
 
   int nrestart = 0;
   bool solved_out = false;  // the parallel eigensolver ran: V = Q S is formed at the output
@@ -661,12 +687,12 @@ __global__ __launch_bounds__(kNT) void lanczos_ritz_wg_kernel(
     if (wave >= nw) {
       if (nw > 1) lanczos_idle_waves(sm);   // (one wave alone has no barrier to keep company at)
     } else if (n <= 64) {
-      if (parts == 1) nrestart = lanczos_waves<1, 1>(sm, lwx, Qt, As, n, LD, LA, lane, wave, tlw);
-      else if (parts == 2) nrestart = lanczos_waves<1, 2>(sm, lwx, Qt, As, n, LD, LA, lane, wave, tlw);
-      else nrestart = lanczos_waves<1, 4>(sm, lwx, Qt, As, n, LD, LA, lane, wave, tlw);
+      if (parts == 1) nrestart = lanczos_waves<1, 1>(sm, lwx, Qt, As, n, LD, LA, lane, wave, tol, tlw);
+      else if (parts == 2) nrestart = lanczos_waves<1, 2>(sm, lwx, Qt, As, n, LD, LA, lane, wave, tol, tlw);
+      else nrestart = lanczos_waves<1, 4>(sm, lwx, Qt, As, n, LD, LA, lane, wave, tol, tlw);
     } else {
-      if (parts == 1) nrestart = lanczos_waves<2, 1>(sm, lwx, Qt, As, n, LD, LA, lane, wave, tlw);
-      else nrestart = lanczos_waves<2, 2>(sm, lwx, Qt, As, n, LD, LA, lane, wave, tlw);
+      if (parts == 1) nrestart = lanczos_waves<2, 1>(sm, lwx, Qt, As, n, LD, LA, lane, wave, tol, tlw);
+      else nrestart = lanczos_waves<2, 2>(sm, lwx, Qt, As, n, LD, LA, lane, wave, tol, tlw);
     }
     __syncthreads();
 #ifdef LNZ_PROFILE_PHASES
@@ -686,8 +712,10 @@ __global__ __launch_bounds__(kNT) void lanczos_ritz_wg_kernel(
 
     // x <- (I - Q Q^T)^2 x over basis vectors 0..cnt-1 (thread tid < n owns x[tid]); returns the
     // accumulated coefficient on vector jidx
-    auto cgs2 = [&](double& x, const int cnt, const int jidx) -> double {
+    lnz::CgsBound ob;
+    auto cgs2 = [&](double& x, const int cnt, const int jidx, const bool restart) -> double {
       double coef = 0.0;
+      const float thr = ob.threshold(n > 128 ? LNZ_WG_CGS_AGAIN : LNZ_WG_CGS_AGAIN_WAVES, restart);
       // dot products: cnt outputs, reduction over the n node rows
       int nsd = kNT / cnt;
       {
@@ -773,7 +801,9 @@ __global__ __launch_bounds__(kNT) void lanczos_ritz_wg_kernel(
           double xx = sm.pn[0], cc2 = sm.pc[0];
           for (int s = 1; s < nsd; ++s) xx += sm.pn[s];
           for (int wv = 1; wv < kWaves; ++wv) cc2 += sm.pc[wv];
-          again = !(cc2 <= (n > 128 ? LNZ_WG_CGS_AGAIN : LNZ_WG_CGS_AGAIN_WAVES) * xx);
+          // ... and where single passes have compounded (lnz::CgsBound): |x'| >= 0.1 |x| lets the
+          // loss of orthogonality grow up to tenfold per step
+          again = ob.second_pass(xx, cc2, thr, restart);
         }
         if (seg_n < nsu) {
           double p0 = 0.0, p1 = 0.0, p2 = 0.0, p3 = 0.0;
@@ -881,7 +911,7 @@ __global__ __launch_bounds__(kNT) void lanczos_ritz_wg_kernel(
         for (int s = 1; s < nss; ++s) nn += sm.pn[s];
         beta = sqrt(nn);
         LNZ_LACC(tl_mv)
-        if (fresh || beta > kBreakdownTol) break;
+        if (fresh || beta > tol) break;
         // breakdown: span(q_0..q_{j-1}) is A-invariant.  Restart from the unit vector with the
         // largest residual against the basis (residual^2 >= (n-j)/n > 0); T[j-1][j] stays 0.
         ++nrestart;
@@ -906,16 +936,17 @@ __global__ __launch_bounds__(kNT) void lanczos_ritz_wg_kernel(
         }
         __syncthreads();
         w = (tid == cand) ? 1.0 : 0.0;
-        (void)cgs2(w, j, 0);
+        (void)cgs2(w, j, 0, true);
         fresh = true;
       }
       if (!fresh && tid == 0) sm.ee[j - 1] = beta;
+      if (j > 0) ob.accept();   // (w is basis vector j now)
       fresh = false;
       const double binv = 1.0 / beta;
       double x = u * binv;  // A q_j
       if (tid < n) Qt[(size_t)j * LD + tid] = w * binv;
       // (the first barrier inside cgs2 orders this store before the basis reads)
-      const double alpha = cgs2(x, j + 1, j);
+      const double alpha = cgs2(x, j + 1, j, false);
       if (tid == 0) sm.dd[j] = alpha;
       w = x;
     }

@@ -86,6 +86,70 @@ __device__ __forceinline__ double rsq_nr(double x) {
   return y;
 }
 
+// When the second classical Gram-Schmidt pass of a full-length Lanczos step runs (lanczos_ritz.hip,
+// lanczos_ritz_wg.hip; tests/algo_mirror.py _cgs2 is the same rule in Python).  One pass against a
+// basis whose Gram matrix is I + E leaves Q^T x' = -E c behind, |E c| / |x'| relative to the new
+// vector, and c lives on the last two vectors (alpha_j, beta_{j-1}).  The loss of orthogonality e
+// therefore obeys  e_new <= g max(e_cur, e_prev) + eps |x| / |x'|,  g = |c| / |x'|,
+// |x'|^2 = |x|^2 - |c|^2.  "Second pass where the first removed more than 99 % of |x|^2" alone
+// bounds g by 10, not by 1: a spectrum spread evenly over its range has alpha ~ 2 beta, g ~ 2.2 at
+// every step, and e grows geometrically — 4e-6 after 32 steps, garbage after 64.
+// Graph Laplacians have g < 1 at most steps, which is why the 99 % rule held on them.  The rule
+// here keeps the single pass wherever it is safe and cannot compound: the bound is carried along
+// (in squares, (a + b)^2 <= 9/8 a^2 + 9 b^2: one reciprocal, no square root; every lane holds the
+// same numbers, so the decision is wave uniform) and the second pass also runs once it passes
+// kBound2 = (1e-9)^2, a sixtieth of an fp32 ulp of the outputs.  After two passes the new vector
+// is orthogonal to g e^2 + eps.  A restart vector's c is spread over ALL basis vectors, each within
+// the bound: it always takes both passes.  Molecules stay on the single pass (5 extra second passes
+// in 4,000 steps), a spread spectrum takes the second one every sixth step.
+// a wave-uniform value, told to the compiler: it lives in a scalar register
+__device__ __forceinline__ float wave_uniform(float x) {
+  return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x)));
+}
+__device__ __forceinline__ double wave_uniform(double x) {
+  return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(x)),
+                          __builtin_amdgcn_readfirstlane(__double2loint(x)));
+}
+
+struct CgsBound {
+  static constexpr float kBound2 = 1e-18f;
+  static constexpr float kFloor = (float)(9.0 * kEpsF64 * kEpsF64);
+  // (floats in scalar registers: a bound needs no more, and the vector registers of the Lanczos
+  // step are all taken — three more cost the N <= 32 kernel its third wave per SIMD)
+  float cur = 0.0f, prev = 0.0f;  // e^2 of the last two accepted basis vectors
+  float cand = 0.0f;              // ... of the vector the last call produced
+  // The part of |x|^2 the first pass may remove without a second one: `frac` (the pass is repeated
+  // beyond it whatever the bound says), or less where the bound would pass kBound2 —
+  // g2 (kFloor + 9/8 emax) + kFloor <= kBound2 with g2 = cc2 / (xx - cc2), solved for cc2 / xx.
+  // Known BEFORE the pass: the decision behind it stays one product and one comparison.
+  __device__ __forceinline__ float threshold(double frac, bool restart) const {
+    const float c1 = fmaf(1.125f, fmaxf(cur, prev), kFloor), room = kBound2 - kFloor;
+    return restart ? 0.0f : wave_uniform(fminf((float)frac, room * __builtin_amdgcn_rcpf(c1 + room)));
+  }
+  // Behind the first pass.  xx = |x|^2, cc2 = sum of the squared coefficients.  -> run the second pass
+  __device__ __forceinline__ bool second_pass(double xx, double cc2, float thr, bool restart) {
+    const bool again = !(cc2 <= (double)thr * xx);
+    // (the bound of the new vector: needed by the next step only)
+    const float g2 = xx > 0.0 ? (float)(cc2 * rcp_nr(fmax(xx - cc2, 1e-30 * xx))) : 0.0f;
+    const float emax = restart ? kBound2 : fmaxf(cur, prev);
+    const float ge = 1.125f * g2 * emax;
+    cand = wave_uniform(again ? fmaf(ge, emax, kFloor) : fmaf(kFloor, g2, ge + kFloor));
+    return again;
+  }
+  // the vector is taken into the basis (a candidate that broke down is replaced, not accepted)
+  __device__ __forceinline__ void accept() { prev = cur, cur = cand; }
+};
+
+// The breakdown tolerance of the full-length Lanczos kernels is relative to the matrix: this power
+// of two, 2^ceil(log2 max |a_ij|) (0 for the zero matrix), times 1e-8.  A power of two so that a
+// matrix times a power of two takes the same decisions step by step; 1 for every matrix whose
+// largest entry lies in (1/2, 1] — the L4 Laplacian of a graph with a leaf or an isolated node.
+__device__ __forceinline__ double matrix_scale_pow2(double amax) {
+  if (!(amax > 0.0)) return 0.0;
+  const double s = __builtin_ldexp(1.0, __builtin_amdgcn_frexp_exp(amax));  // amax = m s, 1/2 <= m < 1
+  return 0.5 * s == amax ? amax : s;
+}
+
 // entry r of the Lanczos start vector: deterministic, strictly positive, non-symmetric — every
 // Lanczos kernel starts from the same vector (lnz_tri::start_entry is another hash: probe vectors)
 __device__ __forceinline__ double lanczos_start_entry(unsigned r) {

@@ -7,21 +7,69 @@ reference's eigh-based (D, V) on the CPU; the GPU tests then check the kernel it
 """
 import numpy as np
 
-TOL = 1e-8
+TOL = 1e-8          # breakdown: beta <= TOL * (the matrix' scale, matrix_scale below)
 EPS = 2.220446049250313e-16
+CGS_AGAIN = 0.99    # second pass where the first removed more than this part of |x|^2 ...
+ORTH_BOUND2 = 1e-18  # ... or where the bound on the new vector's squared loss of orthogonality passes this
 
 
-def _cgs2(Qt, w, j):
-  """Classical Gram-Schmidt against the stored basis; the second pass only where the first one
-  removed more than 99 % of the vector's squared length (csrc/lanczos_ritz.hip cgs2_32)."""
-  coef = 0.0
-  for p in range(2):
-    xx = float(w @ w)
+def matrix_scale(A):
+  """2^ceil(log2 max |a_ij|) (0 for the zero matrix): the power of two the breakdown tolerance is
+  taken relative to — a matrix times a power of two takes the same decisions."""
+  amax = float(np.abs(A).max()) if A.size else 0.0
+  if amax == 0.0:
+    return 0.0
+  m, e = np.frexp(amax)
+  return float(np.ldexp(1.0, e - 1 if m == 0.5 else e))
+
+
+class OrthBound:
+  """lnz::CgsBound (csrc/wave.hpp): bounds on the squared loss of orthogonality of the last two
+  accepted basis vectors (cur, prev) and of the candidate the last Gram-Schmidt call produced."""
+
+  def __init__(self):
+    self.cur = self.prev = self.cand = 0.0
+    self.second_passes = 0
+    self.worst = 0.0   # (the largest accepted bound: statistics)
+
+  def accept(self):
+    self.prev, self.cur = self.cur, self.cand
+    self.worst = max(self.worst, self.cand)
+
+
+def _cgs2(Qt, w, j, rule='bound', ob=None, restart=False):
+  """Classical Gram-Schmidt against the stored basis, once or twice (csrc/lanczos_ritz.hip cgs2_32).
+  One pass against a basis whose Gram matrix is I + E leaves Q^T x' = -E c: relative to the new
+  vector |E c| / |x'|, and c lives on the last two vectors (alpha, beta) — the loss of orthogonality
+  follows e_new <= g max(e_cur, e_prev) + eps |x| / |x'| with g = |c| / |x'|, |x'|^2 = |x|^2 - |c|^2.
+  Where g > 1 step after step (a spectrum spread evenly: alpha ~ 2 beta) this compounds.
+  rule 'bound' (the kernels'): the second pass runs where the first removed more than 99 % of
+  |x|^2, where the bound (carried in squares, (a + b)^2 <= 9/8 a^2 + 9 b^2) passes ORTH_BOUND2, and
+  for a restart vector (its c is spread over all basis vectors, each within the bound);
+  'fraction': the 99 % rule alone — the kernels' rule until the spread spectra, kept to show what
+  it does; 'always'."""
+  ob = ob if ob is not None else OrthBound()
+  floor = 9.0 * EPS * EPS
+  emax = ORTH_BOUND2 if restart else max(ob.cur, ob.prev)
+  # the part of |x|^2 the first pass may remove: g2 (floor + 9/8 emax) + floor <= ORTH_BOUND2 with
+  # g2 = cc2 / (xx - cc2), solved for cc2 / xx — known before the pass (lnz::CgsBound::threshold)
+  room = ORTH_BOUND2 - floor
+  thr = {'fraction': CGS_AGAIN, 'always': 0.0,
+         'bound': 0.0 if restart else min(CGS_AGAIN, room / (floor + 1.125 * max(ob.cur, ob.prev) + room))}[rule]
+  xx = float(w @ w)
+  c = Qt[:j + 1] @ w
+  w = w - Qt[:j + 1].T @ c
+  coef = c[j]
+  cc2 = float(c @ c)
+  again = rule == 'always' or not (cc2 <= thr * xx)
+  if again:
+    ob.second_passes += 1
     c = Qt[:j + 1] @ w
     w = w - Qt[:j + 1].T @ c
     coef += c[j]
-    if p == 0 and float(c @ c) <= 0.99 * xx:
-      break
+  g2 = cc2 / max(xx - cc2, 1e-30 * xx) if xx > 0.0 else 0.0
+  ge = 1.125 * g2 * emax
+  ob.cand = ge * emax + floor if again else floor * g2 + (ge + floor)
   return w, coef
 
 
@@ -290,12 +338,16 @@ def _tridiag_eig_parallel(dd, ee, Qt, n):
   return True
 
 
-def lanczos_ritz_mirror(A, K, solver='parallel'):
+def lanczos_ritz_mirror(A, K, solver='parallel', cgs_rule='bound', stats=None):
   """A: [n, n] float32/64 symmetric.  Returns D [K], V [n, K] (float32), restarts.
   solver: 'parallel' = the N <= 32 kernel's lane-parallel tridiagonal eigensolver (QL sweep as its
-  last resort), 'ql' = the implicit-QL sweep of the generic kernel."""
+  last resort), 'ql' = the implicit-QL sweep of the generic kernel.
+  cgs_rule: when the second Gram-Schmidt pass runs (_cgs2); stats: a dict that receives the number
+  of second passes and the largest bound."""
   A = np.asarray(A, dtype=np.float32).astype(np.float64)
   n = A.shape[0]
+  tol = TOL * matrix_scale(A)
+  ob = OrthBound()
   kk = min(K, n)
   Qt = np.zeros((n, n))
   dd = np.zeros(n)
@@ -308,12 +360,13 @@ def lanczos_ritz_mirror(A, K, solver='parallel'):
   for j in range(n):
     Qt[j] = q
     w = A @ q
-    w, alpha = _cgs2(Qt, w, j)
+    w, alpha = _cgs2(Qt, w, j, cgs_rule, ob)
     dd[j] = alpha
     if j == n - 1:
       break
     beta = np.sqrt((w * w).sum())
-    if beta > TOL:
+    if beta > tol:
+      ob.accept()
       ee[j] = beta
       q = w / beta
     else:
@@ -323,8 +376,11 @@ def lanczos_ritz_mirror(A, K, solver='parallel'):
       cand = int(np.argmax(res))
       w = np.zeros(n)
       w[cand] = 1.0
-      w, _ = _cgs2(Qt, w, j)
+      w, _ = _cgs2(Qt, w, j, cgs_rule, ob, restart=True)
+      ob.accept()
       q = w / np.sqrt((w * w).sum())
+  if stats is not None:
+    stats.update(second_passes=ob.second_passes, bound=float(np.sqrt(ob.worst)))
   solved = solver == 'parallel' and n <= 32 and _tridiag_eig_parallel(dd, ee, Qt, n)
   if not solved:
     if solver == 'parallel' and n <= 32:

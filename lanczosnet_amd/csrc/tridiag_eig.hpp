@@ -314,7 +314,9 @@ __device__ inline void invit_body(const int n, const int ldz, const double* dg, 
       Z[(int64_t)slot * N + r] = x[r];
     }
     res = block_max<EIG_T>(res, red);
-    if (!(res <= 1e-9 * fmax(tnorm, 1e-300))) fail = 1;
+    // relative to ||T||, and never below what bisection resolves: it places an eigenvalue of the
+    // zero matrix within its pad of 2 pivmin (at -1.5 pivmin), a residual of that size on T = 0
+    if (!(res <= fmax(1e-9 * tnorm, 4.0 * pivmin))) fail = 1;
     if (t == 0) clus[ncl] = slot;
     __syncthreads();
   }

@@ -42,6 +42,8 @@ extern "C" {
  *    stays);
  *    + their backward (lnz_gat_attention_backward, lnz_gat_readout_backward and the two
  *    _workspace_floats queries: additive, the version stays);
+ *    + the GGNN baseline's fused gated propagation and readout (lnz_ggnn_forward: additive, the version
+ *    stays);
  *    + lnz_forward_args.rare_strips / .no_fold / .rare_debug at the END of the block (the strip forward's folded form of
  *    the rare bond-type channels, on by default: zeros = folded where cheaper; additive, the version
  *    stays — a caller built against the shorter block must zero-fill lnz_forward_args_size() bytes);
@@ -1202,6 +1204,33 @@ int lnz_gat_readout_backward(const float* Hlast, int ld, const uint8_t* mask, co
                              const float* wg, const float* bg, const float* dscore, int B, int N, int CH,
                              int Dh, int P, float* workspace, float* dHlast, int ldg, float* dWo, float* dbo,
                              float* dwg, float* dbg, lnz_stream_t stream);
+
+/* ---- the GGNN baseline (model/ggnn.py:137-197, config/qm8_ggnn.yaml), csrc/ggnn.hip ----
+ * All num_prop gated propagation steps and the readout in ONE launch.  state0 [B N, ld0] is
+ * input_func(embedding(node_feat)); with C = num_bond_type + 1 channels, state width D, message hidden
+ * width 128, per step on the state S
+ *   H_c = relu(S W1_c^T + b1_c), M_c = H_c W2_c^T + b2_c                (msg_func[c]; W1 [C][128][D], W2 [C][D][128])
+ *   A_c = Â_c M_c per molecule; Â_c = (L[.., c] != 0), for avg != 0 divided by (row degree + FLT_EPSILON)
+ *   S'  = GRUCell(cat_c A_c, S)                                        (Wih [3 D][C D], Whh [3 D][D], gates r, z, n)
+ * then y = (Wo s + bo) * sigmoid(wg s + bg) and score [B, P] = mean of y over the rows with mask != 0
+ * (mask [B, N] u8; NULL: all N rows; no masked row: NaN).  All N rows of a molecule take part in the
+ * propagation.  L (element (b, i, j, c) at b stride_b + i stride_r + j stride_c + c stride_ch floats,
+ * strides >= 0) is only compared with zero — a NaN or a negative entry is an edge — and never written.
+ * state_out [B N, ldso] (may be NULL) receives the final state.  num_prop = 0: the readout of state0.
+ * 1 <= N <= 32, 1 <= C <= 8, D a multiple of 32 and <= 128, 1 <= P <= 16, num_prop >= 0, ld0 / ldso
+ * multiples of 4, state0 / state_out / the weights 16-byte aligned (LNZ_ENOTSUP otherwise); null
+ * pointers, B or N <= 0, ld0 / ldso below D, negative strides, score or state_out overlapping state0
+ * or each other, tile_rows other than 0, 32, 64: LNZ_EINVAL.  A workgroup holds the state of
+ * floor(tile_rows / N) molecules in LDS for all steps (139,520 B of dynamic LDS at D = 128 and 64 rows);
+ * tile_rows = 0: 32 while the 32-row tiles all fit in one round of the compute units, 64 beyond — a
+ * row's arithmetic and bits do not depend on it.  Exact-fp32 MFMA, no atomics, every sum in a fixed
+ * order: bit-reproducible. */
+int lnz_ggnn_forward(const float* state0, int ld0, const float* L, int64_t stride_b, int64_t stride_r,
+                     int64_t stride_c, int64_t stride_ch, const uint8_t* mask, const float* W1,
+                     const float* b1, const float* W2, const float* b2, const float* Wih, const float* bih,
+                     const float* Whh, const float* bhh, const float* Wo, const float* bo, const float* wg,
+                     const float* bg, int B, int N, int C, int D, int P, int num_prop, int avg, float* score,
+                     float* state_out, int ldso, int tile_rows, lnz_stream_t stream);
 
 
 /* ---- next row (SURVEY.md 8f rank 1 + 3): device-side collate from a packed molecule shard ----

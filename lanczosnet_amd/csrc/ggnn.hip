@@ -1,0 +1,385 @@
+// The GGNN baseline (reference model/ggnn.py:137-197, config/qm8_ggnn.yaml): all num_prop gated
+// propagation steps and the gated masked-mean readout in ONE launch.
+//
+// lnz_ggnn_forward — with the state S [rows, D], channels c = 0 .. C-1 (C = num_bond_type + 1) and the
+// message hidden width 128 (hard-coded in the reference), per step
+//     H_c  = relu(S W1_c^T + b1_c)                         [rows, 128]
+//     M_c  = H_c W2_c^T + b2_c                             [rows, D]
+//     A_c  = Â_c M_c per molecule, Â_c = (L[.., c] != 0)            ('sum')
+//                                  Â_c = (L[.., c] != 0) / (row degree + FLT_EPSILON)   ('avg')
+//     gi   = sum_c A_c W_ih[:, cD:(c+1)D]^T + b_ih ;  gh = S W_hh^T + b_hh             [rows, 3D]
+//     r, z = sigmoid(gi_r + gh_r), sigmoid(gi_z + gh_z) ;  n = tanh(gi_n + r * gh_n)
+//     S'   = (1 - z) * n + z * S
+// and after the last step y = (Wo s + bo) * sigmoid(wg s + bg), score = mean of y over the rows with
+// mask != 0 (all N rows without a mask; no masked row: 0 / 0 = NaN like the reference's empty mean).
+// Every one of the N rows of a molecule takes part in the propagation: a padded row evolves under
+// GRU(0, h).  L is only ever compared with zero (a NaN or a negative entry is an edge), never written.
+//
+// Shape as built.  A workgroup of eight waves (512 threads) owns a tile of floor(R / N) whole
+// molecules = at most R rows, packed densely, R = 64 or 32 (below); their state stays in LDS from the
+// first step to the readout, nothing of it goes to HBM between steps.  L is read once, through its
+// four strides, into per-row bit masks (bit j of row i of channel c) and the 'avg' reciprocal
+// denominators.  The GEMMs run on v_mfma_f32_16x16x4_f32 (exact fp32, a k-ordered fma chain) in the
+// transposed form of f32_linear.hip: the A operand is a 16-byte fragment of a weight row read from
+// global memory (L2 resident: 2.5 MB at the yaml shape), the B operand a 16-byte fragment of a state
+// row read from LDS, so a lane ends up with four consecutive features of one row.  The weight
+// fragments of a product run two (gates) or four 16-column blocks ahead of its MFMAs.  Wave w owns the
+// 16 hidden columns 16 w .. of H_c and, where 16 w < D, the 16 features 16 w .. of M_c and of the three
+// gates: its gi accumulators (r; z; n: 3 x R / 16 row tiles x 4 registers = 48 per lane at R = 64)
+// live in registers across the channel loop, channel c's product (a k-ordered chain of D terms of its
+// own, 48 more registers) is added into them, and the [rows, C 128] message hidden never exists as a
+// whole.  gh = S W_hh^T follows the channel loop, in front of the GRU cell.  The aggregate Â_c M_c
+// runs on the VALU over the set bits only, j ascending.  Three barriers per channel, two per step.
+// LDS at D = 128, R = 64: S, M_c, A_c 64 x 132 floats each + H_c 64 x 132 + masks = 139,520 B (the
+// per-device dynamic-LDS grant of common.hpp), one workgroup per CU; R = 32: 69,760 B.  254 VGPRs at
+// R = 64, no scratch.  No atomics, no cross-workgroup traffic, every sum in a fixed order:
+// bit-reproducible.  sigmoid = 1 / (1 + expf(-x)) and tanhf stay finite and correct at |x| >= 100.
+//
+// Tile height: a tile's 15 steps take the same time whatever the batch, so R = 64 (half the weight
+// reads per row) serves batches that fill the chip and R = 32 batches whose 32-row tiles all fit in one
+// round of the compute units (tile_rows = 0 chooses; a row's arithmetic and bits are the same in
+// both).  R = 128 (192 accumulator registers per lane at 256 threads) and the folded form F_c =
+// W_ih[:, c] W2_c were not built.  Measurements: DESIGN.md §4.12.
+#include <float.h>
+
+#include "common.hpp"
+
+namespace {
+
+constexpr int GHID = 128;      // message hidden width (model/ggnn.py:59-61)
+constexpr int GNW = 8;         // waves per workgroup
+constexpr int GNT = 64 * GNW;  // threads
+constexpr int GMAXN = 32, GMAXC = 8, GMAXP = 16, GMAXD = 128;
+constexpr int HS = GHID + 4;   // row stride of H_c (floats): 16-byte rows, fragment reads spread over the banks
+
+// floats of dynamic LDS: S, M, A [GR][D + 4], H [GR][132], bits + inv [8][GR], rowbase [GR]
+__host__ __device__ constexpr int ggnn_lds_floats(int D, int GR) {
+  return 3 * GR * (D + 4) + GR * HS + 2 * GMAXC * GR + GR;
+}
+
+__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
+
+// acc[t][rt] += (16 RT rows of the LDS operand, K = 16 KB columns) x (16 weight rows of tile t)^T.
+// `as` = the operand's row (lane & 15) + 4 (lane >> 4) floats; wp[t] = the weight row of this lane
+// + 4 (lane >> 4) floats.  Lane (m, g) multiplies k = 16 kb + 4 g + u in MFMA step u on both operands;
+// register e of acc[t][rt] is row 16 rt + m, feature (tile base) + 4 g + e.  The weight fragments are
+// loaded PF blocks ahead of the MFMAs that use them.
+template <int NT, int KB, int RT>
+__device__ __forceinline__ void tile_gemm(const float* as, const int lda, const float* const (&wp)[NT],
+                                          f32x4 (*acc)[RT]) {
+  constexpr int PF0 = NT >= 3 ? 2 : 4, PF = KB < PF0 ? KB : PF0;
+  f32x4 w[KB][NT];
+#pragma unroll
+  for (int kb = 0; kb < PF; ++kb)
+#pragma unroll
+    for (int t = 0; t < NT; ++t) w[kb][t] = *reinterpret_cast<const f32x4*>(wp[t] + 16 * kb);
+#pragma unroll
+  for (int kb = 0; kb < KB; ++kb) {
+    f32x4 a[RT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) a[rt] = *reinterpret_cast<const f32x4*>(as + 16 * rt * lda + 16 * kb);
+    if (kb + PF < KB) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t) w[kb + PF][t] = *reinterpret_cast<const f32x4*>(wp[t] + 16 * (kb + PF));
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) acc[t][rt] = mfma16(w[kb][t][u], a[rt][u], acc[t][rt]);
+  }
+}
+
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+template <int D, int RT>
+__global__ __launch_bounds__(GNT) void ggnn_forward_kernel(
+    const float* __restrict__ state0, const int ld0, const float* __restrict__ L, const int64_t stride_b,
+    const int64_t stride_r, const int64_t stride_c, const int64_t stride_ch,
+    const unsigned char* __restrict__ mask, const float* __restrict__ W1, const float* __restrict__ b1,
+    const float* __restrict__ W2, const float* __restrict__ b2, const float* __restrict__ Wih,
+    const float* __restrict__ bih, const float* __restrict__ Whh, const float* __restrict__ bhh,
+    const float* __restrict__ Wo, const float* __restrict__ bo, const float* __restrict__ wg,
+    const float* __restrict__ bg, const int B, const int N, const int C, const int P, const int num_prop,
+    const int avg, float* __restrict__ score, float* __restrict__ state_out, const int ldso) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  constexpr int GR = 16 * RT;    // rows per tile
+  constexpr int SS = D + 4;      // row stride of S, M_c, A_c
+  constexpr int DQ = D / 4;      // float4 per state row
+  constexpr int DB = D / 16;     // 16-feature blocks of a state row: waves 0 .. DB-1 own one each
+  float* const Sb = smem;
+  float* const Mb = Sb + GR * SS;
+  float* const Ab = Mb + GR * SS;
+  float* const Hb = Ab + GR * SS;
+  unsigned* const bits = reinterpret_cast<unsigned*>(Hb + GR * HS);   // [c][row]
+  float* const inv = reinterpret_cast<float*>(bits + GMAXC * GR);      // [c][row]
+  int* const rowbase = reinterpret_cast<int*>(inv + GMAXC * GR);       // first row of the row's molecule
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int m = lane & 15, g = lane >> 4;
+  const int mpt = GR / N;                                  // molecules per tile
+  const int64_t mol0 = (int64_t)blockIdx.x * mpt;
+  const int nm = (int)(B - mol0 < mpt ? B - mol0 : mpt);   // molecules of this tile
+  const int rows = nm * N;                                 // live rows; the others stay zero and unread
+
+  // ---- the state, the bit masks and denominators of L, the molecule of every row
+  for (int idx = tid; idx < GR * DQ; idx += GNT) {
+    const int r = idx / DQ, q = idx - r * DQ;
+    f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (r < rows) v = *reinterpret_cast<const f32x4*>(state0 + (mol0 * N + r) * (int64_t)ld0 + 4 * q);
+    *reinterpret_cast<f32x4*>(Sb + r * SS + 4 * q) = v;
+  }
+  for (int idx = tid; idx < GR * C; idx += GNT) {
+    const int r = idx / C, c = idx - r * C;
+    unsigned bm = 0;
+    if (r < rows) {
+      const int ml = r / N, i = r - ml * N;
+      const float* Lr = L + (mol0 + ml) * stride_b + i * stride_r + c * stride_ch;
+      for (int j = 0; j < N; ++j) bm |= (Lr[j * stride_c] != 0.0f ? 1u : 0u) << j;   // NaN != 0: an edge
+    }
+    bits[c * GR + r] = bm;
+    // model/ggnn.py:156-157: every entry of the row is 1 / (degree + EPS), in float32
+    inv[c * GR + r] = avg ? 1.0f / ((float)__popc(bm) + FLT_EPSILON) : 1.0f;
+  }
+  if (tid < GR) rowbase[tid] = tid < rows ? (tid / N) * N : 0;
+  __syncthreads();
+
+  const bool owner = wave < DB;          // wave-uniform: this wave owns features 16 wave .. 16 wave + 15
+  const int f0 = 16 * wave + 4 * g;      // this lane's four features (owner waves) / hidden columns
+  const float* const s_frag = Sb + m * SS + 4 * g;
+  const float* const h_frag = Hb + m * HS + 4 * g;
+  const float* const a_frag = Ab + m * SS + 4 * g;
+
+  for (int step = 0; step < num_prop; ++step) {
+    // gate accumulators of this wave's feature block: [0] r, [1] z, [2] gi_n
+    f32x4 acc[3][RT];
+#pragma unroll
+    for (int t = 0; t < 3; ++t)
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt) acc[t][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int c = 0; c < C; ++c) {
+      {   // H_c = relu(S W1_c^T + b1_c): hidden columns 16 wave ..
+        f32x4 h[1][RT];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) h[0][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        const float* const wp[1] = {W1 + ((int64_t)c * GHID + 16 * wave + m) * D + 4 * g};
+        tile_gemm<1, DB, RT>(s_frag, SS, wp, h);
+        const f32x4 bv = *reinterpret_cast<const f32x4*>(b1 + c * GHID + f0);
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) {
+          f32x4 v;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = fmaxf(h[0][rt][e] + bv[e], 0.0f);
+          *reinterpret_cast<f32x4*>(Hb + (16 * rt + m) * HS + f0) = v;
+        }
+      }
+      __syncthreads();
+      if (owner) {   // M_c = H_c W2_c^T + b2_c: features 16 wave ..
+        f32x4 mm[1][RT];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) mm[0][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        const float* const wp[1] = {W2 + ((int64_t)c * D + 16 * wave + m) * GHID + 4 * g};
+        tile_gemm<1, GHID / 16, RT>(h_frag, HS, wp, mm);
+        const f32x4 bv = *reinterpret_cast<const f32x4*>(b2 + c * D + f0);
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+          *reinterpret_cast<f32x4*>(Mb + (16 * rt + m) * SS + f0) = mm[0][rt] + bv;
+      }
+      __syncthreads();
+      // A_c = Â_c M_c: four features of one row per task, the set bits of the row in ascending j
+      for (int idx = tid; idx < GR * DQ; idx += GNT) {
+        const int r = idx / DQ, q = idx - r * DQ;
+        unsigned bm = bits[c * GR + r];
+        const float wgt = inv[c * GR + r];
+        const float* const src = Mb + rowbase[r] * SS + 4 * q;
+        f32x4 s = {0.0f, 0.0f, 0.0f, 0.0f};
+        while (bm) {
+          const int j = __ffs(bm) - 1;
+          bm &= bm - 1;
+          const f32x4 v = *reinterpret_cast<const f32x4*>(src + j * SS);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) s[e] = fmaf(wgt, v[e], s[e]);
+        }
+        *reinterpret_cast<f32x4*>(Ab + r * SS + 4 * q) = s;
+      }
+      __syncthreads();
+      if (owner) {   // gi += A_c W_ih[:, c D ..]^T: tiles r, z, gi_n
+        const float* const row = Wih + (int64_t)(16 * wave + m) * ((int64_t)C * D) + c * D + 4 * g;
+        const int64_t gate = (int64_t)D * C * D;
+        const float* const wp[3] = {row, row + gate, row + 2 * gate};
+        f32x4 part[3][RT];   // a chain of D terms per channel, then one add: the error of a short sum
+#pragma unroll
+        for (int t = 0; t < 3; ++t)
+#pragma unroll
+          for (int rt = 0; rt < RT; ++rt) part[t][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        tile_gemm<3, DB, RT>(a_frag, SS, wp, part);
+#pragma unroll
+        for (int t = 0; t < 3; ++t)
+#pragma unroll
+          for (int rt = 0; rt < RT; ++rt) acc[t][rt] += part[t][rt];
+      }
+    }
+    // gh = S W_hh^T (the state is still the step's input): r and z join gi, gh_n stays apart.  Every wave
+    // reads ALL columns of S here, so the barrier below stands between these reads and the cell's writes
+    f32x4 gh[3][RT];
+    if (owner) {
+#pragma unroll
+      for (int t = 0; t < 3; ++t)
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) gh[t][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      const float* const row = Whh + (int64_t)(16 * wave + m) * D + 4 * g;
+      const float* const wp[3] = {row, row + D * D, row + 2 * D * D};
+      tile_gemm<3, DB, RT>(s_frag, SS, wp, gh);
+    }
+    __syncthreads();
+    if (owner) {   // the GRU cell on this wave's features
+      const f32x4 b_r = *reinterpret_cast<const f32x4*>(bih + f0) + *reinterpret_cast<const f32x4*>(bhh + f0);
+      const f32x4 b_z = *reinterpret_cast<const f32x4*>(bih + D + f0) + *reinterpret_cast<const f32x4*>(bhh + D + f0);
+      const f32x4 b_in = *reinterpret_cast<const f32x4*>(bih + 2 * D + f0);
+      const f32x4 b_hn = *reinterpret_cast<const f32x4*>(bhh + 2 * D + f0);
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt) {
+        float* const sp = Sb + (16 * rt + m) * SS + f0;
+        const f32x4 so = *reinterpret_cast<const f32x4*>(sp);
+        f32x4 sn;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float r = sigmoidf_((acc[0][rt][e] + gh[0][rt][e]) + b_r[e]);
+          const float z = sigmoidf_((acc[1][rt][e] + gh[1][rt][e]) + b_z[e]);
+          const float n = tanhf((acc[2][rt][e] + b_in[e]) + r * (gh[2][rt][e] + b_hn[e]));
+          sn[e] = (1.0f - z) * n + z * so[e];
+        }
+        *reinterpret_cast<f32x4*>(sp) = sn;
+      }
+    }
+    __syncthreads();
+  }
+
+  // ---- the final state, on request
+  if (state_out != nullptr) {
+    for (int idx = tid; idx < rows * DQ; idx += GNT) {
+      const int r = idx / DQ, q = idx - r * DQ;
+      *reinterpret_cast<f32x4*>(state_out + (mol0 * N + r) * (int64_t)ldso + 4 * q) =
+          *reinterpret_cast<const f32x4*>(Sb + r * SS + 4 * q);
+    }
+  }
+  // ---- readout: slot p < P: Wo[p] s + bo[p]; slot P: sigmoid(wg s + bg); d ascending
+  float* const ys = Hb;   // [row][GMAXP + 1]: H_c is dead
+  for (int idx = tid; idx < rows * (P + 1); idx += GNT) {
+    const int r = idx / (P + 1), p = idx - r * (P + 1);
+    const float* const w = p < P ? Wo + (int64_t)p * D : wg;
+    float a = 0.0f;
+    for (int d = 0; d < D; ++d) a = fmaf(Sb[r * SS + d], w[d], a);
+    a += p < P ? bo[p] : bg[0];
+    ys[r * (GMAXP + 1) + p] = p < P ? a : sigmoidf_(a);
+  }
+  __syncthreads();
+  for (int idx = tid; idx < nm * P; idx += GNT) {
+    const int ml = idx / P, p = idx - ml * P;
+    float s = 0.0f, cnt = 0.0f;
+    for (int i = 0; i < N; ++i) {
+      if (mask == nullptr || mask[(mol0 + ml) * N + i] != 0) {
+        const int r = ml * N + i;
+        s += ys[r * (GMAXP + 1) + p] * ys[r * (GMAXP + 1) + P];
+        cnt += 1.0f;
+      }
+    }
+    score[(mol0 + ml) * P + p] = s / cnt;   // (no masked row: 0 / 0, the reference's mean of nothing)
+  }
+}
+
+inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+inline bool overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + nb && b0 < a0 + na;
+}
+
+template <int D, int RT>
+int launch(const float* state0, int ld0, const float* L, int64_t sb, int64_t sr, int64_t sc, int64_t sch,
+           const uint8_t* mask, const float* W1, const float* b1, const float* W2, const float* b2,
+           const float* Wih, const float* bih, const float* Whh, const float* bhh, const float* Wo,
+           const float* bo, const float* wg, const float* bg, int B, int N, int C, int P, int num_prop, int avg,
+           float* score, float* state_out, int ldso, int grid, hipStream_t s) {
+  const size_t lds = sizeof(float) * (size_t)ggnn_lds_floats(D, 16 * RT);
+  auto kfn = ggnn_forward_kernel<D, RT>;
+  LNZ_DYNAMIC_LDS(kfn, lds, "ggnn.hip");
+  hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(GNT), lds, s, state0, ld0, L, sb, sr, sc, sch, mask, W1, b1,
+                     W2, b2, Wih, bih, Whh, bhh, Wo, bo, wg, bg, B, N, C, P, num_prop, avg, score, state_out, ldso);
+  return lnz::check_launch("lnz_ggnn_forward");
+}
+
+}  // namespace
+
+extern "C" int lnz_ggnn_forward(const float* state0, int ld0, const float* L, int64_t stride_b, int64_t stride_r,
+                                int64_t stride_c, int64_t stride_ch, const uint8_t* mask, const float* W1,
+                                const float* b1, const float* W2, const float* b2, const float* Wih,
+                                const float* bih, const float* Whh, const float* bhh, const float* Wo,
+                                const float* bo, const float* wg, const float* bg, int B, int N, int C, int D,
+                                int P, int num_prop, int avg, float* score, float* state_out, int ldso,
+                                int tile_rows, lnz_stream_t stream) {
+  LNZ_REQUIRE(state0 && L && W1 && b1 && W2 && b2 && Wih && bih && Whh && bhh && Wo && bo && wg && bg && score,
+              LNZ_EINVAL, "lnz_ggnn_forward: null pointer");
+  LNZ_REQUIRE(B > 0 && N > 0, LNZ_EINVAL, "lnz_ggnn_forward: B = %d, N = %d must be positive", B, N);
+  LNZ_REQUIRE(N <= GMAXN && C >= 1 && C <= GMAXC && D >= 32 && D <= GMAXD && D % 32 == 0 && P >= 1 && P <= GMAXP &&
+                  num_prop >= 0,
+              LNZ_ENOTSUP,
+              "lnz_ggnn_forward: N = %d, C = %d, D = %d, P = %d, num_prop = %d outside 1 <= N <= 32, 1 <= C <= 8, "
+              "D a multiple of 32 and <= 128, 1 <= P <= 16, num_prop >= 0", N, C, D, P, num_prop);
+  LNZ_REQUIRE(ld0 >= D && (state_out == nullptr || ldso >= D), LNZ_EINVAL,
+              "lnz_ggnn_forward: ld0 = %d, ldso = %d below the width %d", ld0, ldso, D);
+  LNZ_REQUIRE(stride_b >= 0 && stride_r >= 0 && stride_c >= 0 && stride_ch >= 0, LNZ_EINVAL,
+              "lnz_ggnn_forward: negative stride of L");
+  LNZ_REQUIRE(ld0 % 4 == 0 && (state_out == nullptr || ldso % 4 == 0) && aligned16(state0) && aligned16(state_out) &&
+                  aligned16(W1) && aligned16(b1) && aligned16(W2) && aligned16(b2) && aligned16(Wih) &&
+                  aligned16(bih) && aligned16(Whh) && aligned16(bhh),
+              LNZ_ENOTSUP, "lnz_ggnn_forward: the rows of state0, state_out and of the weights must be 16-byte "
+              "aligned (ld0 = %d, ldso = %d)", ld0, ldso);
+  {
+    const uint64_t rows = (uint64_t)B * N;
+    const uint64_t n0 = ((rows - 1) * (uint64_t)ld0 + D) * sizeof(float);
+    const uint64_t nsc = (uint64_t)B * P * sizeof(float);
+    LNZ_REQUIRE(!overlap(score, nsc, state0, n0), LNZ_EINVAL, "lnz_ggnn_forward: score must not alias state0");
+    if (state_out != nullptr) {
+      const uint64_t no = ((rows - 1) * (uint64_t)ldso + D) * sizeof(float);
+      LNZ_REQUIRE(!overlap(state_out, no, state0, n0) && !overlap(state_out, no, score, nsc), LNZ_EINVAL,
+                  "lnz_ggnn_forward: state_out must not alias state0 or score");
+    }
+  }
+  LNZ_REQUIRE(tile_rows == 0 || tile_rows == 32 || tile_rows == 64, LNZ_EINVAL,
+              "lnz_ggnn_forward: tile_rows = %d is not 0 (chosen by the batch), 32 or 64", tile_rows);
+  int rows_per_tile = tile_rows;
+  if (rows_per_tile == 0) {
+    // 32-row tiles while they all fit in one round of the compute units, 64-row tiles beyond
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
+      (void)hipGetLastError();
+      cus = 256;
+    }
+    const int mpt32 = 32 / N;
+    rows_per_tile = ((int64_t)B + mpt32 - 1) / mpt32 <= cus ? 32 : 64;
+  }
+  const int mpt = rows_per_tile / N;
+  const int64_t grid = ((int64_t)B + mpt - 1) / mpt;
+  hipStream_t s = (hipStream_t)stream;
+  lnz::note_kernel("ggnn_forward_kernel<%d, %d>", D, rows_per_tile / 16);
+#define LNZ_GGNN_LAUNCH(DD)                                                                                          \
+  return rows_per_tile == 32                                                                                         \
+             ? launch<DD, 2>(state0, ld0, L, stride_b, stride_r, stride_c, stride_ch, mask, W1, b1, W2, b2, Wih, bih, \
+                             Whh, bhh, Wo, bo, wg, bg, B, N, C, P, num_prop, avg ? 1 : 0, score, state_out, ldso,    \
+                             (int)grid, s)                                                                           \
+             : launch<DD, 4>(state0, ld0, L, stride_b, stride_r, stride_c, stride_ch, mask, W1, b1, W2, b2, Wih, bih, \
+                             Whh, bhh, Wo, bo, wg, bg, B, N, C, P, num_prop, avg ? 1 : 0, score, state_out, ldso,    \
+                             (int)grid, s)
+  switch (D) {
+    case 32: LNZ_GGNN_LAUNCH(32);
+    case 64: LNZ_GGNN_LAUNCH(64);
+    case 96: LNZ_GGNN_LAUNCH(96);
+    default: LNZ_GGNN_LAUNCH(128);
+  }
+#undef LNZ_GGNN_LAUNCH
+}

@@ -11,6 +11,7 @@ Reference interfaces replaced (paths relative to the reference repo):
   gat_attention       model/gat.py:153-175 (every channel and head of a layer; gat_layer adds :150-152)
   gat_readout         model/gat.py:177-196
   gat_attention_backward / gat_readout_backward / gat_layer_backward   the same lines under loss.backward()
+  ggnn_forward        model/ggnn.py:143-197 (all num_prop steps and the readout)
 """
 import torch
 
@@ -2599,3 +2600,55 @@ def unsorted_segment_sum_backward(grad_out, segment_ids, dim1):
   ids = segment_ids.to(torch.int64).contiguous()
   B, S, D2 = g.shape
   return _ext().unsorted_segment_sum_backward(g, ids, dim1)
+
+
+# ---------------------------------------------------------------------------------------- GGNN
+GGNN_MAX_NODES, GGNN_MAX_CHANNELS, GGNN_MAX_WIDTH, GGNN_WIDTH_STEP, GGNN_MAX_OUTPUTS = 32, 8, 128, 32, 16
+GGNN_MSG_HIDDEN = 128   # model/ggnn.py:59-61
+
+
+def ggnn_forward(state0, L, mask, W1, b1, W2, b2, Wih, bih, Whh, bhh, Wo, bo, wg, bg, num_prop, avg=True,
+                 state_out=None, return_state=False, tile_rows=0):
+  """lnz_ggnn_forward (model/ggnn.py:137-197): every propagation step and the readout in one launch.
+  state0 [B, N, D] = input_func(embedding(node_feat)) (a row stride beyond D is fine), L [B, N, N, C]
+  float32 in any strides (read as L != 0, never written), mask [B, N] or None (all N rows), W1 [C, 128, D],
+  b1 [C, 128], W2 [C, D, 128], b2 [C, D] (msg_func), Wih [3 D, C D], bih [3 D], Whh [3 D, D], bhh [3 D]
+  (the GRU cell), Wo [P, D], bo [P], wg [1, D] or [D], bg [1] -> score [B, P]; with return_state (or a
+  `state_out` buffer [B, N, D]) also the final state.  tile_rows: 0 = chosen by the batch, 32 or 64 rows of
+  state per workgroup (a row's bits do not depend on it)."""
+  _need_cuda(state0, L, mask, W1, b1, W2, b2, Wih, bih, Whh, bhh, Wo, bo, wg, bg, state_out)
+  if state0.dim() != 3 or L.dim() != 4 or L.dtype != torch.float32:
+    raise LnzError(_lib.LNZ_EINVAL, 'ggnn_forward: state0 [B, N, D] and a float32 L [B, N, N, C] expected')
+  B, N, D = state0.shape
+  C = L.shape[3]
+  if tuple(L.shape[:3]) != (B, N, N):
+    raise LnzError(_lib.LNZ_EINVAL, 'ggnn_forward: state0 %s and L %s do not fit' % (tuple(state0.shape), tuple(L.shape)))
+  ld0 = _gat_rows(state0, 'ggnn_forward')
+  W1, b1, W2, b2 = _f32c(W1), _f32c(b1), _f32c(W2), _f32c(b2)
+  Wih, bih, Whh, bhh = _f32c(Wih), _f32c(bih).reshape(-1), _f32c(Whh), _f32c(bhh).reshape(-1)
+  Wo, bo, wg, bg = _f32c(Wo), _f32c(bo).reshape(-1), _f32c(wg).reshape(-1), _f32c(bg).reshape(-1)
+  P = Wo.shape[0]
+  Hd = GGNN_MSG_HIDDEN
+  for t, shape in ((W1, (C, Hd, D)), (b1, (C, Hd)), (W2, (C, D, Hd)), (b2, (C, D)), (Wih, (3 * D, C * D)),
+                   (bih, (3 * D,)), (Whh, (3 * D, D)), (bhh, (3 * D,)), (Wo, (P, D)), (bo, (P,)), (wg, (D,)),
+                   (bg, (1,))):
+    if tuple(t.shape) != shape:
+      raise LnzError(_lib.LNZ_EINVAL, 'ggnn_forward: operand of shape %s where %s is expected'
+                     % (tuple(t.shape), shape))
+  if mask is not None:
+    if tuple(mask.shape) != (B, N):
+      raise LnzError(_lib.LNZ_EINVAL, 'ggnn_forward: mask %s, expected %s' % (tuple(mask.shape), (B, N)))
+    mask = (mask != 0).to(torch.uint8).contiguous()
+  if state_out is None and return_state:
+    state_out = torch.empty((B, N, D), dtype=torch.float32, device=state0.device)
+  ldso = D
+  if state_out is not None:
+    if tuple(state_out.shape) != (B, N, D):
+      raise LnzError(_lib.LNZ_EINVAL, 'ggnn_forward: state_out %s, expected %s' % (tuple(state_out.shape), (B, N, D)))
+    ldso = _gat_rows(state_out, 'ggnn_forward')
+  score = torch.empty((B, P), dtype=torch.float32, device=state0.device)
+  with torch.cuda.device(state0.device):
+    _abi().ggnn_forward(state0, ld0, L, L.stride(0), L.stride(1), L.stride(2), L.stride(3), mask, W1, b1, W2, b2,
+                        Wih, bih, Whh, bhh, Wo, bo, wg, bg, B, N, C, D, P, int(num_prop), int(bool(avg)), score,
+                        state_out, ldso, int(tile_rows))
+  return (score, state_out) if state_out is not None else score

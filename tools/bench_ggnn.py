@@ -1,0 +1,164 @@
+#!/usr/bin/env python
+"""Secondary measurement: the GGNN baseline at the shape of the reference's config/qm8_ggnn.yaml (D 128,
+7 channels, 15 propagation steps, 'avg', input 64, 16 outputs) on the package's synthetic QM8 batch,
+inference, 1 x MI355X — route 'ggnn_hip' (a gather from the [num_atom, D] table + ONE ggnn_forward
+launch) against route 'ggnn_torch' (the module's own torch restatement) on the same device in the same
+run, the two alternating; HIP events, medians over the repeats.  Per route: the time, the number of
+device kernels of one call (torch.profiler, a pass of its own), the rate on the model of
+C (2 D 128 + 2 128 D + 2 D 3D) + 2 D 3D FLOP per row and step (1.245 MFLOP at the yaml shape) over the
+CALL time as TFLOP/s and as a fraction of the 155 TFLOP/s fp32 MFMA peak, and the parity of the timed
+batch against the restatement evaluated in float64.  For 'ggnn_hip' also the ggnn_forward launch on
+its own, and with each of its two tile heights forced.  Writes profiles/ggnn_bench.json.  Not the
+headline bench (bench.py).
+
+    python tools/bench_ggnn.py [--batches 64 1024] [--steps 30] [--warmup 5] [--out profiles/ggnn_bench.json]
+"""
+import argparse
+import copy
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from lanczosnet_amd import ops  # noqa: E402
+from lanczosnet_amd.model import GGNN  # noqa: E402
+from lanczosnet_amd.synthetic import draw_batch  # noqa: E402
+from lanczosnet_amd.utils.arg_helper import AttrDict  # noqa: E402
+
+WIDTH, PROP, INPUT, OUTPUT, BONDS, ATOMS, HIDDEN = 128, 15, 64, 16, 6, 70, 128
+PEAK_TFLOPS = 155.0
+
+
+def config():
+  model = dict(name='GGNN', input_dim=INPUT, hidden_dim=WIDTH, output_dim=OUTPUT, num_layer=1, num_prop=PROP,
+               update_func='GRU', msg_func='MLP', aggregate_type='avg', dropout=0.0, loss='MSE')
+  return AttrDict(dict(seed=1234, dataset=dict(num_atom=ATOMS, num_bond_type=BONDS), model=model))
+
+
+def model_flop(B, N):
+  C, D = BONDS + 1, WIDTH
+  per_row_step = C * (2 * D * HIDDEN + 2 * HIDDEN * D + 2 * D * 3 * D) + 2 * D * 3 * D
+  return float(B) * N * PROP * per_row_step
+
+
+def median_ms(fn, steps, warmup):
+  for _ in range(warmup):
+    fn()
+  times = []
+  for _ in range(steps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    times.append(e0.elapsed_time(e1))
+  return float(np.median(times)), float(np.min(times)), float(np.max(times))
+
+
+def device_kernels(fn):
+  """the number of device kernels one call launches (None where the profiler reports no device events)"""
+  from torch.profiler import ProfilerActivity, profile
+  fn()
+  torch.cuda.synchronize()
+  with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+    fn()
+    torch.cuda.synchronize()
+  n = sum(1 for e in prof.events() if str(getattr(e, 'device_type', '')).endswith('CUDA'))
+  return n or None
+
+
+def main():
+  ap = argparse.ArgumentParser()
+  ap.add_argument('--batches', type=int, nargs='+', default=[64, 1024])
+  ap.add_argument('--steps', type=int, default=30)
+  ap.add_argument('--warmup', type=int, default=5)
+  ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'ggnn_bench.json'))
+  args = ap.parse_args()
+  assert torch.cuda.is_available(), 'bench_ggnn.py needs the MI355X'
+  torch.manual_seed(1234)
+  net = GGNN(config()).eval().cuda()
+  net64 = copy.deepcopy(net).double()
+  rows = []
+  t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()  # noqa: E731
+  with torch.no_grad():
+    for B in args.batches:
+      b = draw_batch(B, seed=0)
+      L = ops.laplacian_l4(t(b['adjs']), t(b['n_nodes']))
+      nf, mask = t(b['node_feat']), t(b['node_mask'])
+      N = int(nf.shape[1])
+      hip = lambda: net(nf, L, mask=mask)  # noqa: E731
+      tor = lambda: net._torch_forward(nf, L, mask)  # noqa: E731
+      table, operands = net._packs()
+      state0 = table[nf]
+      kern = lambda: ops.ggnn_forward(state0, L, mask, *operands, PROP, avg=True)  # noqa: E731
+      score = hip()
+      assert net.last_route == 'ggnn_hip'
+      ref = net64._torch_forward(nf, L.double(), mask)
+      scale = float(ref.abs().max())
+      par_hip = float((score.double() - ref).abs().max()) / scale
+      par_tor = float((tor().double() - ref).abs().max()) / scale
+      # alternate the two routes, twice each; keep the better median of each
+      res = {'ggnn_hip': [], 'ggnn_torch': []}
+      for _ in range(2):
+        res['ggnn_hip'].append(median_ms(hip, args.steps, args.warmup))
+        res['ggnn_torch'].append(median_ms(tor, args.steps, args.warmup))
+      kernel_ms = median_ms(kern, args.steps, args.warmup)[0]
+      chosen = ops.last_kernel()
+      # the two tile heights, forced, alternating (tile_rows = 0 above chooses between them by the batch)
+      tiles = {32: [], 64: []}
+      for _ in range(2):
+        for rows_per_tile in (32, 64):
+          tiles[rows_per_tile].append(median_ms(
+              lambda: ops.ggnn_forward(state0, L, mask, *operands, PROP, avg=True, tile_rows=rows_per_tile),
+              args.steps, args.warmup)[0])
+      try:
+        launches = {'ggnn_hip': device_kernels(hip), 'ggnn_torch': device_kernels(tor)}
+      except Exception as e:   # the count is a side figure: say why it is missing
+        launches = {'ggnn_hip': None, 'ggnn_torch': None, 'error': repr(e)[:200]}
+      flop = model_flop(B, N)
+      row = {'batch': B, 'nodes_padded': N, 'model_gflop': round(flop / 1e9, 2),
+             'ggnn_hip_ms': round(min(r[0] for r in res['ggnn_hip']), 4),
+             'ggnn_torch_ms': round(min(r[0] for r in res['ggnn_torch']), 4),
+             'ggnn_hip_medians_ms': [round(r[0], 4) for r in res['ggnn_hip']],
+             'ggnn_torch_medians_ms': [round(r[0], 4) for r in res['ggnn_torch']],
+             'ggnn_forward_launch_ms': round(kernel_ms, 4), 'ggnn_forward_kernel': chosen,
+             'ggnn_forward_launch_ms_by_tile_rows': {str(k): round(min(v), 4) for k, v in tiles.items()},
+             'device_kernels_per_call': launches,
+             'rel_err_vs_float64': {'ggnn_hip': par_hip, 'ggnn_torch': par_tor},
+             'finite': bool(torch.isfinite(score).all())}
+      for route in ('ggnn_hip', 'ggnn_torch'):
+        tf = flop / (row[route + '_ms'] * 1e-3) / 1e12
+        row[route + '_tflops'] = round(tf, 2)
+        row[route + '_fraction_of_fp32_mfma_peak'] = round(tf / PEAK_TFLOPS, 4)
+      tfk = flop / (kernel_ms * 1e-3) / 1e12
+      row['ggnn_forward_launch_tflops'] = round(tfk, 2)
+      row['ggnn_forward_launch_fraction_of_fp32_mfma_peak'] = round(tfk / PEAK_TFLOPS, 4)
+      row['speedup'] = round(row['ggnn_torch_ms'] / row['ggnn_hip_ms'], 3)
+      row['hip_not_slower'] = bool(row['ggnn_hip_ms'] <= row['ggnn_torch_ms'])
+      row['molecules_per_s'] = round(B / row['ggnn_hip_ms'] * 1e3, 1)
+      rows.append(row)
+      print(json.dumps(row))
+  out = {'workload': 'GGNN forward (inference), config/qm8_ggnn.yaml shape: D %d, %d channels, %d steps, avg, '
+                     'synthetic QM8 batch, fp32' % (WIDTH, BONDS + 1, PROP),
+         'device': torch.cuda.get_device_name(0), 'steps': args.steps, 'warmup': args.warmup,
+         'timing': 'HIP events around one forward call, median over the steps; the two routes alternate, two '
+                   'rounds each, the lower median is reported; ggnn_forward_launch_ms: the one kernel launch on a '
+                   'state gathered beforehand, timed the same way',
+         'rate': 'the FLOP model of the recurrence (C (2 D 128 + 2 128 D + 2 D 3D) + 2 D 3D per row and step, every '
+                 'padded row counted) over the time named; fraction of the %.0f TFLOP/s fp32 MFMA peak' % PEAK_TFLOPS,
+         'parity': 'max |score - s64| / max |s64|, s64 = the torch restatement in float64 on the timed batch',
+         'condition': "'ggnn_hip' is not slower than 'ggnn_torch' at either batch: %s"
+                      % all(r['hip_not_slower'] for r in rows),
+         'results': rows}
+  os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+  with open(args.out, 'w') as f:
+    json.dump(out, f, indent=1)
+    f.write('\n')
+
+
+if __name__ == '__main__':
+  main()

@@ -370,8 +370,11 @@ int lnz_tridiag_eigh(const double* diag, const double* offdiag, int B, int M, do
 
 /* ---- R2 + R6, large graphs (BASELINE config 5: N = 2048, K = 64) -------------------------------
  * M-step Lanczos (full re-orthogonalisation: classical Gram-Schmidt against every previous vector,
- * a second pass when the first cancelled |w| below 1e-3; stops early if the Krylov space becomes
- * invariant) -> QL on the M x M tridiagonal -> Ritz vectors V = Q S, top-K by |theta|, zero
+ * a second pass where the first removed more than 1 - 1e-6 of |w|^2 or where the carried bound on
+ * the loss of orthogonality asks for it (lnz::CgsBound, csrc/wave.hpp: L1, L2, raw adjacencies and
+ * evenly spread spectra need it every few steps, L4 Laplacians almost never); stops once |w| falls
+ * to 1e-8 times 2^ceil(log2 max |a_ij|): the Krylov space has become invariant, whatever power of
+ * two the matrix is scaled by) -> QL on the M x M tridiagonal -> Ritz vectors V = Q S, top-K by |theta|, zero
  * padded.  The dense A (rows contiguous, 16-byte aligned, row stride stride_r, N %% 4 == 0,
  * N <= 2048) is re-streamed from HBM every step: this is the HBM-bound regime of the path.
  * The reference's counterpart is scipy.sparse.linalg.eigsh(L, k, which='LM')

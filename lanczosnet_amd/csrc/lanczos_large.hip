@@ -30,8 +30,17 @@ constexpr int NWAVE = TPB / 64;
 constexpr int NCH = 8;          // 256-column chunks -> N <= 2048
 constexpr int MMAX = 64;        // Lanczos steps
 constexpr int ZLD = MMAX;      // QL accumulator rows (aliases the q/w vectors, dead by then)
+// Early stop: |w| <= kTol times the matrix' scale, the power of two lnz::matrix_scale_pow2(max |a_ij|)
+// (1 for an L4 Laplacian with an entry in (1/2, 1]; as an absolute number the stop took a matrix
+// times 2^-30 for an invariant subspace after one step).  Every SpMV mode sees every entry (the
+// symmetric stream: the upper triangle) in step 0 and takes the maximum there: exact, so the dense
+// streams, the image and the edge-list image agree on it bit for bit.
 constexpr double kTol = 1e-8;
-constexpr double kReorth = 1e-6;  // second Gram-Schmidt pass when |w1|^2 < kReorth |w0|^2
+// Second Gram-Schmidt pass where the first removed more than this part of |w|^2, or where the
+// carried bound on the loss of orthogonality asks for it (lnz::CgsBound, wave.hpp).
+// The fraction alone bounds the growth factor g of 4.3d by 1000: on L1, L2 and evenly spread spectra
+// the basis lost its orthogonality altogether within 64 steps.
+constexpr double kCgsFrac = 1.0 - 1e-6;
 
 struct LargeSmem {
   union {
@@ -65,6 +74,23 @@ __device__ inline double block_sum(LargeSmem& sm, double part, int tid) {
   for (int k = 0; k < NWAVE; ++k) t += sm.red[k];
   __syncthreads();
   return t;
+}
+
+// max over the workgroup (every thread gets it)
+__device__ inline float block_max(LargeSmem& sm, float part, int tid) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) part = fmaxf(part, __shfl_xor(part, o, 64));
+  if ((tid & 63) == 0) sm.red[tid >> 6] = (double)part;
+  __syncthreads();
+  double t = 0.0;
+#pragma unroll
+  for (int k = 0; k < NWAVE; ++k) t = fmax(t, sm.red[k]);
+  __syncthreads();
+  return (float)t;
+}
+
+__device__ __forceinline__ float abs_max4(float m, const float4& a) {
+  return fmaxf(fmaxf(m, fmaxf(fabsf(a.x), fabsf(a.y))), fmaxf(fabsf(a.z), fabsf(a.w)));
 }
 
 // ---- symmetric SpMV (SYM): only the 256 x 256 chunk blocks (I, J >= I) of A are streamed -------
@@ -335,10 +361,14 @@ __global__ __launch_bounds__(TPB) void lanczos_ritz_large_kernel(
   double nrm2 = block_sum(sm, part, tid);
 
   int steps = 0;
+  float amax = 0.0f;   // max |a_ij| of this thread's share of A (step 0)
+  double tol = 0.0;    // the stop, known behind step 0's product (before it: an empty graph's |w| = 0)
+  lnz::CgsBound ob;
   for (int j = 0; j < M; ++j) {
     const double nrm = sqrt(nrm2);
+    const bool first = j == 0;
     // invariant subspace reached: stop (slots stay zero); an empty graph takes no step at all
-    if ((j > 0 || n_b == 0) && nrm <= kTol) break;
+    if ((j > 0 || n_b == 0) && nrm <= tol) break;
     if (j > 0 && tid == 0) sm.ee[j - 1] = nrm;
     const double ninv = 1.0 / nrm;
     for (int r = tid; r < NCH * 256; r += TPB) {
@@ -448,6 +478,7 @@ __global__ __launch_bounds__(TPB) void lanczos_ritz_large_kernel(
           for (int i = 0; i < SYM_RG; ++i) {
             const double ax = (double)buf[i].x, ay = (double)buf[i].y, az = (double)buf[i].z,
                          aw = (double)buf[i].w;
+            if (first) amax = abs_max4(amax, buf[i]);
             fetch(i);
             p[i] = fma(ax, qJ[0], ay * qJ[1]) + fma(az, qJ[2], aw * qJ[3]);
             colacc[0] = fma(ax, qr[i], colacc[0]);
@@ -531,6 +562,10 @@ __global__ __launch_bounds__(TPB) void lanczos_ritz_large_kernel(
             acc0 = fma((double)vb[i], sm.qs[cb[i]], acc0);
             acc1 = fma((double)vb[i + 1], sm.qs[cb[i + 1]], acc1);
           }
+          if (first) {
+#pragma unroll
+            for (int i = 0; i < ELL_UNROLL; ++i) amax = fmaxf(amax, fabsf(vb[i]));
+          }
           if (more_k) {
 #pragma unroll
             for (int i = 0; i < ELL_UNROLL; ++i) {
@@ -564,6 +599,10 @@ __global__ __launch_bounds__(TPB) void lanczos_ritz_large_kernel(
         }
       };
       auto dot_row = [&](const float4 (&a)[NCH]) {
+        if (first) {
+#pragma unroll
+          for (int s = 0; s < NCH; ++s) amax = abs_max4(amax, a[s]);
+        }
         double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
 #pragma unroll
         for (int s = 0; s < NCH; ++s) {
@@ -594,25 +633,23 @@ __global__ __launch_bounds__(TPB) void lanczos_ritz_large_kernel(
     __syncthreads();
     LNZ_PROBE(3);
 
-    // ---- Gram-Schmidt against q_0..q_j: one classical pass; a second one only when the first
-    //      cancelled more than kReorth of w's norm (the projection's rounding error relative to
-    //      what is left is eps * |w0| / |w1|: below 1e-3 that is still < 3e-13, far inside the
-    //      fp32 outputs; near an invariant subspace |w1| collapses and the second pass runs).
-    //      oracle/lanczos_kstep.py states the same rule.
+    if (first) tol = kTol * lnz::matrix_scale_pow2((double)block_max(sm, amax, tid));
+
+    // ---- Gram-Schmidt against q_0..q_j: one classical pass; a second one where the first removed
+    //      more than kCgsFrac of |w|^2 (near an invariant subspace |w| collapses) or where single
+    //      passes have compounded (lnz::CgsBound: the bound carried from step to step decides,
+    //      from |w|^2 before the pass and the sum of the squared coefficients behind it — every
+    //      thread forms the same numbers in the same order).  oracle/lanczos_kstep.py states the
+    //      same rule.
     double coef = 0.0;
     if constexpr (MODE == 0) {
       part = 0.0;
       for (int r = tid; r < N; r += TPB) part = fma(sm.ws[r], sm.ws[r], part);
     }
-    const double nrm2_before = block_sum(sm, part, tid);
+    const double xx = block_sum(sm, part, tid);
+    const float thr = ob.threshold(kCgsFrac, false);
     LNZ_PROBE(4);
     for (int pass = 0; pass < 2; ++pass) {
-      if (pass == 1) {
-        part = 0.0;
-        for (int r = tid; r < N; r += TPB) part = fma(sm.ws[r], sm.ws[r], part);
-        nrm2 = block_sum(sm, part, tid);
-        if (nrm2 >= kReorth * nrm2_before) break;
-      }
       if constexpr (MODE != 0) {
         cgs_pass(sm, Qg, N, j, wave, lane);
       } else {
@@ -652,11 +689,21 @@ __global__ __launch_bounds__(TPB) void lanczos_ritz_large_kernel(
       }
       coef += sm.cs[j];
       LNZ_PROBE(5 + pass);
+      if (pass == 0) {
+        // (every thread, in index order: a wave sum or an unrolled loop here costs the image kernel
+        //  six more spilled registers, and the wave sum 1.5 % of the compacted leg)
+        double cc2 = 0.0;
+        for (int i = 0; i <= j; ++i) cc2 = fma(sm.cs[i], sm.cs[i], cc2);
+        const bool again = ob.second_pass(xx, cc2, thr, false);
+        ob.accept();   // (a K-step run has no restarts: every vector it makes is taken)
+        if (!again) break;
+        __syncthreads();  // the second pass overwrites cs
+      }
     }
     if (tid == 0) sm.dd[j] = coef;
     part = 0.0;
     for (int r = tid; r < N; r += TPB) part = fma(sm.ws[r], sm.ws[r], part);
-    nrm2 = block_sum(sm, part, tid);  // (after a skipped second pass: the same sum again)
+    nrm2 = block_sum(sm, part, tid);
     steps = j + 1;
     LNZ_PROBE(7);
   }

@@ -1,10 +1,11 @@
 // The K-step Lanczos Ritz pairs (csrc/lanczos_large.hip: the reference's `eigsh` branch,
 // utils/data_helper.py:205-208) for what one workgroup cannot hold: graphs of up to 16384 nodes and
 // up to 256 Lanczos steps.  Same function as lnz_lanczos_ritz_kstep — same start vector, classical
-// Gram-Schmidt against every previous vector with a second pass under the kReorth rule, early stop on
-// an invariant subspace, top-K |theta| Ritz pairs — on another schedule: a graph is spread over many
-// workgroups, and the stages are ordered by launch boundaries only (no grid-wide barrier, no
-// spinning; the only atomics are the slab widths of the shared compaction pass, a max).  All
+// Gram-Schmidt against every previous vector with a second pass under the lnz::CgsBound rule, early
+// stop on an invariant subspace (relative to the matrix' scale), top-K |theta| Ritz pairs — on
+// another schedule: a graph is spread over many workgroups, and the stages are ordered by launch
+// boundaries only (no grid-wide barrier, no spinning; the only atomics are the slab widths of the
+// shared compaction pass, a max).  All
 // arithmetic fp64, fp32 in and out.
 //
 // Per call:  compaction (csrc/ell_image.hpp: A read from HBM once into a sliced-ELL image) ->
@@ -14,10 +15,13 @@
 //
 // What depends on the data — "this graph has stopped", "the second pass runs" — is decided on the
 // device by every workgroup for itself from the same words in the workspace: the per-slab / per-chunk
-// partial sums of |w|^2 that the previous launches left in fixed slots, and alive[b][j] (step j of
-// graph b was taken).  A launch only reads words that an EARLIER launch wrote (the slots it writes
-// itself belong to the current step: the SpMV's partials alternate between two sets by the parity of
-// j).  The host never looks.  Every sum has a fixed order that depends on N and the graph only:
+// partial sums of |w|^2 that the previous launches left in fixed slots, alive[b][j] (step j of
+// graph b was taken), again[b][j] and bound[b][j] (the second pass of step j runs; the bound on the
+// loss of orthogonality of the vector it made: written by chunk 0's workgroup of the first update
+// launch of step j) and tol[b] (the stop, from max |a_ij| as step 0's product met it).  A launch
+// only reads words that an EARLIER launch wrote (the slots it writes itself belong to the current
+// step: the SpMV's partials alternate between two sets by the parity of j).  The host never looks.
+// Every sum has a fixed order that depends on N and the graph only:
 // results are bitwise repeatable and independent of the rest of the batch.
 //
 // Bytes per graph and step j: the image (6 B per stored entry, slab padding included) + the gather
@@ -38,9 +42,12 @@ constexpr int CH = 512;          // rows per Gram-Schmidt chunk (one workgroup)
 constexpr int MAX_N = 16384;
 constexpr int MAX_M = 256;       // Lanczos steps (= lnz_tri::MAX_K: the tridiagonal stage's limit)
 constexpr int DOT_U = 4;         // basis vectors a wave has in flight in the dots kernel
+// early stop: |w| <= kTol lnz::matrix_scale_pow2(max |a_ij|); second Gram-Schmidt pass beyond kCgsFrac
+// of |w|^2 or by the carried bound (lnz::CgsBound) — the rules of lanczos_large.hip, DESIGN.md 4.5h
 constexpr double kTol = 1e-8;
-constexpr double kReorth = 1e-6;  // second Gram-Schmidt pass when |w1|^2 < kReorth |w0|^2
+constexpr double kCgsFrac = 1.0 - 1e-6;
 
+using lnz_tri::block_max;
 using lnz_tri::block_sum;
 using lnz_tri::wave_sum_butterfly;
 
@@ -48,6 +55,7 @@ inline int64_t al256(int64_t x) { return (x + 255) / 256 * 256; }
 
 struct Layout {
   int64_t Q, w, d, e, p0, p1, p2, cpart, Z, lam, sel, alive, steps, over, widths, vals, cols, rowcnt, total;
+  int64_t again, bound, amax, tol;
   int64_t sel_stride;
   int nslab, nchunk;
 };
@@ -81,6 +89,10 @@ Layout layout(int B, int N, int M, int row_cap) {
   L.vals = take((int64_t)B * L.nslab * row_cap * 64 * 4);
   L.cols = take((int64_t)B * L.nslab * row_cap * 64 * 2);
   L.rowcnt = take((int64_t)B * N * 4);
+  L.again = take((int64_t)B * M * 4);
+  L.bound = take((int64_t)B * M * 4);
+  L.amax = take((int64_t)B * L.nslab * 4);
+  L.tol = take((int64_t)B * 8);
   L.total = at;
   return L;
 }
@@ -100,6 +112,10 @@ struct Wide {
   int64_t sel_stride;
   int32_t* alive;  // [B][M]
   int32_t* steps;  // [B]
+  int32_t* again;  // [B][M] the second Gram-Schmidt pass of step j runs
+  float* bound;    // [B][M] lnz::CgsBound's e^2 of the vector step j made
+  float* amax;     // [B][nslab] max |a_ij| by slab (step 0)
+  double* tol;     // [B] the stop: kTol times the matrix' scale
   const int32_t* over;   // [B] the image could not hold a row of this graph
   const float* vals;
   const uint16_t* cols;
@@ -121,14 +137,6 @@ __device__ inline bool skipped(const Wide& p, int b) { return p.skip_over && p.o
 __device__ inline double sum_slots(const double* s, int cnt, double* red) {
   const int t = threadIdx.x;
   return block_sum<WT>(t < cnt ? s[t] : 0.0, red);
-}
-
-// does the second Gram-Schmidt pass of step j run?  (|w1|^2 < kReorth |w0|^2, as oracle/lanczos_kstep.py)
-__device__ inline bool second_pass(const Wide& p, int b, int j, double* red, double* n1_out) {
-  const double n0 = sum_slots(p.p0 + ((int64_t)(j & 1) * p.B + b) * p.nslab, p.nslab, red);
-  const double n1 = sum_slots(p.p1 + (int64_t)b * p.nchunk, p.nchunk, red);
-  if (n1_out) *n1_out = n1;
-  return n1 < kReorth * n0;
 }
 
 // ---- start vector (same hash as every Ritz kernel of the project) ---------------------------------
@@ -171,18 +179,13 @@ __global__ __launch_bounds__(WT) void wide_spmv_kernel(Wide p, const float* __re
     return;
   }
   const int n_b = graph_n(p, b);
-  double nrm2;
-  if (j == 0) {
-    nrm2 = sum_slots(p.p1 + (int64_t)b * p.nchunk, p.nchunk, red);
-  } else {
-    double n1;
-    const bool ran2 = second_pass(p, b, j - 1, red, &n1);
-    const double n2 = sum_slots(p.p2 + (int64_t)b * p.nchunk, p.nchunk, red);
-    nrm2 = ran2 ? n2 : n1;
-  }
+  // |w|^2 as the last Gram-Schmidt pass that ran left it (the start vector's before step 0)
+  const bool ran2 = j > 0 && p.again[(int64_t)b * p.M + j - 1] != 0;
+  const double nrm2 = sum_slots((ran2 ? p.p2 : p.p1) + (int64_t)b * p.nchunk, p.nchunk, red);
   const double nrm = sqrt(nrm2);
+  const double tol = j > 0 ? p.tol[b] : 0.0;
   // invariant subspace reached: stop (slots stay zero); an empty graph takes no step at all
-  if ((j > 0 || n_b == 0) && nrm <= kTol) {
+  if ((j > 0 || n_b == 0) && nrm <= tol) {
     if (first) alive[j] = 0;
     return;
   }
@@ -202,6 +205,7 @@ __global__ __launch_bounds__(WT) void wide_spmv_kernel(Wide p, const float* __re
   const int g = blockIdx.x * (WT / 64) + wave;
   if (g >= p.nslab) return;
   double acc;
+  float amax = 0.0f;
   if (p.over[b] == 0) {
     const int wdt = __builtin_amdgcn_readfirstlane(p.widths[(int64_t)b * p.nslab + g]);
     const int64_t base = (((int64_t)b * p.nslab + g) * p.cap) * 64 + lane;
@@ -215,6 +219,7 @@ __global__ __launch_bounds__(WT) void wide_spmv_kernel(Wide p, const float* __re
       for (int i = 0; i < ELL_UNROLL; ++i) {
         vb[i] = vp[(int64_t)(k0 + i) * 64];
         qb[i] = win[cp[(int64_t)(k0 + i) * 64]];
+        amax = fmaxf(amax, fabsf(vb[i]));   // (kept at j == 0 only: cheaper than a branch here)
       }
 #pragma unroll
       for (int i = 0; i < ELL_UNROLL; i += 2) {
@@ -233,6 +238,7 @@ __global__ __launch_bounds__(WT) void wide_spmv_kernel(Wide p, const float* __re
       double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
       for (int q = lane; q < nq; q += 64) {
         const float4 a = src[q];
+        amax = fmaxf(fmaxf(amax, fmaxf(fabsf(a.x), fabsf(a.y))), fmaxf(fabsf(a.z), fabsf(a.w)));
         const double2* wp = reinterpret_cast<const double2*>(win + 4 * q);
         const double2 x = wp[0], y = wp[1];
         s0 = fma((double)a.x, x.x * ninv, s0);
@@ -248,6 +254,11 @@ __global__ __launch_bounds__(WT) void wide_spmv_kernel(Wide p, const float* __re
   if (row < p.N) wout[row] = acc;   // (rows in [N, 64 nslab) have no entries: acc = 0)
   const double s = wave_sum_butterfly(acc * acc);
   if (lane == 0) p.p0[((int64_t)(j & 1) * p.B + b) * p.nslab + g] = s;
+  if (j == 0) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    if (lane == 0) p.amax[(int64_t)b * p.nslab + g] = amax;
+  }
 }
 
 // ---- Gram-Schmidt, first half: the chunk's share of c_i = <q_i, w>, i <= j ---------------------------
@@ -256,7 +267,7 @@ __global__ __launch_bounds__(WT) void wide_dots_kernel(Wide p, int j, int pass) 
   __shared__ double red[WT];
   const int ch = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
   if (skipped(p, b) || p.alive[(int64_t)b * p.M + j] == 0) return;
-  if (pass == 1 && !second_pass(p, b, j, red, nullptr)) return;
+  if (pass == 1 && p.again[(int64_t)b * p.M + j] == 0) return;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63;
   const double* w = p.w + ((int64_t)((j + 1) & 1) * p.B + b) * p.N;
   const double* Qb = p.Q + (int64_t)b * p.M * p.N;
@@ -300,7 +311,7 @@ __global__ __launch_bounds__(WT) void wide_update_kernel(Wide p, int j, int pass
   __shared__ double cs[MAX_M];
   const int ch = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
   if (skipped(p, b) || p.alive[(int64_t)b * p.M + j] == 0) return;
-  if (pass == 1 && !second_pass(p, b, j, red, nullptr)) return;
+  if (pass == 1 && p.again[(int64_t)b * p.M + j] == 0) return;
   if (t <= j) {
     const double* cp = p.cpart + (int64_t)b * p.nchunk * p.M + t;
     double c = 0.0;
@@ -308,6 +319,23 @@ __global__ __launch_bounds__(WT) void wide_update_kernel(Wide p, int j, int pass
     cs[t] = c;
   }
   __syncthreads();
+  if (pass == 0 && ch == 0) {
+    // Does the second pass run (lnz::CgsBound, wave.hpp)?  One workgroup decides for the graph, from
+    // |A q|^2 and the squared coefficients, and leaves the word for the launches behind it.
+    const double xx = sum_slots(p.p0 + ((int64_t)(j & 1) * p.B + b) * p.nslab, p.nslab, red);
+    const double cc2 = block_sum<WT>(t <= j ? cs[t] * cs[t] : 0.0, red);
+    lnz::CgsBound ob;
+    ob.cur = j > 0 ? p.bound[(int64_t)b * p.M + j - 1] : 0.0f;
+    ob.prev = j > 1 ? p.bound[(int64_t)b * p.M + j - 2] : 0.0f;
+    const bool again = ob.second_pass(xx, cc2, ob.threshold(kCgsFrac, false), false);
+    double am = 0.0;
+    if (j == 0) am = block_max<WT>(t < p.nslab ? (double)p.amax[(int64_t)b * p.nslab + t] : 0.0, red);
+    if (t == 0) {
+      p.again[(int64_t)b * p.M + j] = again ? 1 : 0;
+      p.bound[(int64_t)b * p.M + j] = ob.cand;
+      if (j == 0) p.tol[b] = kTol * lnz::matrix_scale_pow2(am);
+    }
+  }
   double* w = p.w + ((int64_t)((j + 1) & 1) * p.B + b) * p.N;
   const double* Qb = p.Q + (int64_t)b * p.M * p.N;
   double part = 0.0;
@@ -523,6 +551,10 @@ static int wide_steps(const char* who, const Layout& L, char* ws, const int32_t*
   p.sel_stride = L.sel_stride;
   p.alive = (int32_t*)(ws + L.alive);
   p.steps = (int32_t*)(ws + L.steps);
+  p.again = (int32_t*)(ws + L.again);
+  p.bound = (float*)(ws + L.bound);
+  p.amax = (float*)(ws + L.amax);
+  p.tol = (double*)(ws + L.tol);
   p.over = over;
   p.vals = (const float*)(ws + L.vals);
   p.cols = (const uint16_t*)(ws + L.cols);

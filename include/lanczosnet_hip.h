@@ -44,6 +44,8 @@ extern "C" {
  *    _workspace_floats queries: additive, the version stays);
  *    + the GGNN baseline's fused gated propagation and readout (lnz_ggnn_forward: additive, the version
  *    stays);
+ *    + its backward (lnz_ggnn_forward_states, lnz_ggnn_backward_step, lnz_ggnn_readout_backward and the
+ *    _workspace_floats query: additive, the version stays);
  *    + lnz_forward_args.rare_strips / .no_fold / .rare_debug at the END of the block (the strip forward's folded form of
  *    the rare bond-type channels, on by default: zeros = folded where cheaper; additive, the version
  *    stays — a caller built against the shorter block must zero-fill lnz_forward_args_size() bytes);
@@ -1234,6 +1236,59 @@ int lnz_ggnn_forward(const float* state0, int ld0, const float* L, int64_t strid
                      const float* Whh, const float* bhh, const float* Wo, const float* bo, const float* wg,
                      const float* bg, int B, int N, int C, int D, int P, int num_prop, int avg, float* score,
                      float* state_out, int ldso, int tile_rows, lnz_stream_t stream);
+
+/* ---- the GGNN baseline's backward, csrc/ggnn.hip and csrc/ggnn_grad.hip ----
+ * lnz_ggnn_forward_states: lnz_ggnn_forward (the same kernel template, arguments, envelope and errors; score
+ * and state_out have its bits) that also leaves the state trajectory states [num_prop + 1][B N][D] (row
+ * stride D, 16-byte aligned, no overlap with state0, score or state_out): S_t at the start of step t, S_T
+ * after the last.  Nothing else is saved: the backward recomputes a step from S_t. */
+int lnz_ggnn_forward_states(const float* state0, int ld0, const float* L, int64_t stride_b, int64_t stride_r,
+                            int64_t stride_c, int64_t stride_ch, const uint8_t* mask, const float* W1,
+                            const float* b1, const float* W2, const float* b2, const float* Wih, const float* bih,
+                            const float* Whh, const float* bhh, const float* Wo, const float* bo, const float* wg,
+                            const float* bg, int B, int N, int C, int D, int P, int num_prop, int avg,
+                            float* score, float* state_out, int ldso, float* states, int tile_rows,
+                            lnz_stream_t stream);
+
+/* lnz_ggnn_backward_step: one propagation step of backpropagation through time for the whole batch, launched
+ * for t = T-1 .. 0.  S [B N, lds] = S_t, dSnext [B N, ldd] = dL/dS_{t+1}; the step is recomputed on chip with
+ * the forward's arithmetic (H_c, M_c, A_c, gi, gh, r, z, n), then
+ *   dn = dS' (1 - z), dz = dS' (S - n), dS = dS' z, dn_pre = dn (1 - n^2), dz_pre = dz z (1 - z),
+ *   dr_pre = dn_pre gh_n r (1 - r), dgi = [dr_pre, dz_pre, dn_pre], dgh = [dr_pre, dz_pre, dn_pre r]
+ *   dS += dgh Whh ; per channel c: dA_c = dgi Wih[:, cD:(c+1)D], dM_c = Â_c^T dA_c per molecule,
+ *   dHpre_c = (dM_c W2_c) [H_c > 0], dS += dHpre_c W1_c
+ * W1, b1, .. bhh: the forward's operands; W1T [C][D][128], W2T [C][128][D], WihT [C][D][3 D] (block c =
+ * Wih[:, cD:(c+1)D]^T), WhhT [D][3 D]: their transposes, packed by the caller.  Out: dS [B N, ldo] = dL/dS_t and
+ * the row-space operands of this step's weight gradients, contiguous: dgi [B N][3 D], dghn [B N][D] (the n
+ * part of dgh; its r and z parts are dgi's), A [B N][C D] = cat_c A_c, dM [B N][C D], H [B N][C 128],
+ * dHpre [B N][C 128].  The caller contracts them over the rows (dWih = dgi^T A, dWhh = dgh^T S, dW2_c =
+ * dM_c^T H_c, dW1_c = dHpre_c^T S, the biases their column sums) and may reuse the buffers for the next step.
+ * The envelope of lnz_ggnn_forward (N <= 32, C <= 8, D a multiple of 32 and <= 128: LNZ_ENOTSUP, as are rows
+ * that are not 16-byte aligned); null pointers, B or N <= 0, a row stride below D, negative strides of L,
+ * an output overlapping an input or another output: LNZ_EINVAL.  L is read through its four strides and
+ * never written.  32-row tiles, 138,368 B of dynamic LDS at D = 128; no atomics, every sum in a fixed order:
+ * bit-reproducible. */
+int lnz_ggnn_backward_step(const float* S, int lds, const float* dSnext, int ldd, const float* L, int64_t stride_b,
+                           int64_t stride_r, int64_t stride_c, int64_t stride_ch, const float* W1, const float* b1,
+                           const float* W2, const float* b2, const float* Wih, const float* bih, const float* Whh,
+                           const float* bhh, const float* W1T, const float* W2T, const float* WihT,
+                           const float* WhhT, int B, int N, int C, int D, int avg, float* dS, int ldo, float* dgi,
+                           float* dghn, float* A, float* dM, float* H, float* dHpre, lnz_stream_t stream);
+
+/* lnz_ggnn_readout_backward: the readout of lnz_ggnn_forward under loss.backward().  Slast [B N, ld] = S_T;
+ * o = Wo s + bo and g = sigmoid(wg s + bg) recomputed as the forward computes them; per row i of the mask
+ * (cnt of them; all N without a mask), with dscore [B, P]:
+ *   dy = dscore / cnt, do = dy g, dzg = (sum_p dy[p] o[p]) g (1 - g), dSlast[i] = Wo^T do + wg dzg
+ * dSlast [B N, ldg] is exactly 0 on rows outside the mask; dWo [P][D] = sum do s^T, dbo [P] = sum do,
+ * dwg [D] = sum dzg s, dbg [1] = sum dzg over rows and molecules: per-molecule partials in workspace
+ * [lnz_ggnn_readout_backward_workspace_floats(B, D, P)], added in a fixed order by a second launch.  A
+ * molecule without a masked row (NaN in the forward) is unspecified.  N <= 32, D a multiple of 32 and <= 128,
+ * P <= 16 (LNZ_ENOTSUP); dSlast must not alias Slast. */
+int64_t lnz_ggnn_readout_backward_workspace_floats(int B, int D, int P);
+int lnz_ggnn_readout_backward(const float* Slast, int ld, const uint8_t* mask, const float* Wo, const float* bo,
+                              const float* wg, const float* bg, const float* dscore, int B, int N, int D, int P,
+                              float* workspace, float* dSlast, int ldg, float* dWo, float* dbo, float* dwg,
+                              float* dbg, lnz_stream_t stream);
 
 
 /* ---- next row (SURVEY.md 8f rank 1 + 3): device-side collate from a packed molecule shard ----

@@ -12,6 +12,8 @@
 //     S'   = (1 - z) * n + z * S
 // and after the last step y = (Wo s + bo) * sigmoid(wg s + bg), score = mean of y over the rows with
 // mask != 0 (all N rows without a mask; no masked row: 0 / 0 = NaN like the reference's empty mean).
+// lnz_ggnn_forward_states is the same kernel template with one more pointer: it also leaves the state
+// trajectory [num_prop + 1][B N][D], all the backward (ggnn_grad.hip) keeps of the forward.
 // Every one of the N rows of a molecule takes part in the propagation: a padded row evolves under
 // GRU(0, h).  L is only ever compared with zero (a NaN or a negative entry is an edge), never written.
 //
@@ -43,59 +45,16 @@
 #include <float.h>
 
 #include "common.hpp"
+#include "ggnn_tile.hpp"
 
 namespace {
-
-constexpr int GHID = 128;      // message hidden width (model/ggnn.py:59-61)
-constexpr int GNW = 8;         // waves per workgroup
-constexpr int GNT = 64 * GNW;  // threads
-constexpr int GMAXN = 32, GMAXC = 8, GMAXP = 16, GMAXD = 128;
-constexpr int HS = GHID + 4;   // row stride of H_c (floats): 16-byte rows, fragment reads spread over the banks
 
 // floats of dynamic LDS: S, M, A [GR][D + 4], H [GR][132], bits + inv [8][GR], rowbase [GR]
 __host__ __device__ constexpr int ggnn_lds_floats(int D, int GR) {
   return 3 * GR * (D + 4) + GR * HS + 2 * GMAXC * GR + GR;
 }
 
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-// acc[t][rt] += (16 RT rows of the LDS operand, K = 16 KB columns) x (16 weight rows of tile t)^T.
-// `as` = the operand's row (lane & 15) + 4 (lane >> 4) floats; wp[t] = the weight row of this lane
-// + 4 (lane >> 4) floats.  Lane (m, g) multiplies k = 16 kb + 4 g + u in MFMA step u on both operands;
-// register e of acc[t][rt] is row 16 rt + m, feature (tile base) + 4 g + e.  The weight fragments are
-// loaded PF blocks ahead of the MFMAs that use them.
-template <int NT, int KB, int RT>
-__device__ __forceinline__ void tile_gemm(const float* as, const int lda, const float* const (&wp)[NT],
-                                          f32x4 (*acc)[RT]) {
-  constexpr int PF0 = NT >= 3 ? 2 : 4, PF = KB < PF0 ? KB : PF0;
-  f32x4 w[KB][NT];
-#pragma unroll
-  for (int kb = 0; kb < PF; ++kb)
-#pragma unroll
-    for (int t = 0; t < NT; ++t) w[kb][t] = *reinterpret_cast<const f32x4*>(wp[t] + 16 * kb);
-#pragma unroll
-  for (int kb = 0; kb < KB; ++kb) {
-    f32x4 a[RT];
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) a[rt] = *reinterpret_cast<const f32x4*>(as + 16 * rt * lda + 16 * kb);
-    if (kb + PF < KB) {
-#pragma unroll
-      for (int t = 0; t < NT; ++t) w[kb + PF][t] = *reinterpret_cast<const f32x4*>(wp[t] + 16 * (kb + PF));
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) acc[t][rt] = mfma16(w[kb][t][u], a[rt][u], acc[t][rt]);
-  }
-}
-
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-template <int D, int RT>
+template <int D, int RT, bool TRAJ>
 __global__ __launch_bounds__(GNT) void ggnn_forward_kernel(
     const float* __restrict__ state0, const int ld0, const float* __restrict__ L, const int64_t stride_b,
     const int64_t stride_r, const int64_t stride_c, const int64_t stride_ch,
@@ -104,7 +63,8 @@ __global__ __launch_bounds__(GNT) void ggnn_forward_kernel(
     const float* __restrict__ bih, const float* __restrict__ Whh, const float* __restrict__ bhh,
     const float* __restrict__ Wo, const float* __restrict__ bo, const float* __restrict__ wg,
     const float* __restrict__ bg, const int B, const int N, const int C, const int P, const int num_prop,
-    const int avg, float* __restrict__ score, float* __restrict__ state_out, const int ldso) {
+    const int avg, float* __restrict__ score, float* __restrict__ state_out, const int ldso,
+    float* __restrict__ states) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int GR = 16 * RT;    // rows per tile
   constexpr int SS = D + 4;      // row stride of S, M_c, A_c
@@ -154,7 +114,19 @@ __global__ __launch_bounds__(GNT) void ggnn_forward_kernel(
   const float* const h_frag = Hb + m * HS + 4 * g;
   const float* const a_frag = Ab + m * SS + 4 * g;
 
+  // the state trajectory [num_prop + 1][B N][D] (TRAJ: lnz_ggnn_forward_states; `states` is null and unread
+  // otherwise): S_t at the start of step t, S_T after the last.  A copy of the LDS rows: the arithmetic does
+  // not see it, and the instantiation without it is the kernel lnz_ggnn_forward always launched
+  const auto put_state = [&](const int t) {
+    float* const dst = states + ((int64_t)t * B + mol0) * N * D;
+    for (int idx = tid; idx < rows * DQ; idx += GNT) {
+      const int r = idx / DQ, q = idx - r * DQ;
+      *reinterpret_cast<f32x4*>(dst + (int64_t)r * D + 4 * q) = *reinterpret_cast<const f32x4*>(Sb + r * SS + 4 * q);
+    }
+  };
+
   for (int step = 0; step < num_prop; ++step) {
+    if constexpr (TRAJ) put_state(step);
     // gate accumulators of this wave's feature block: [0] r, [1] z, [2] gi_n
     f32x4 acc[3][RT];
 #pragma unroll
@@ -260,6 +232,7 @@ __global__ __launch_bounds__(GNT) void ggnn_forward_kernel(
   }
 
   // ---- the final state, on request
+  if constexpr (TRAJ) put_state(num_prop);
   if (state_out != nullptr) {
     for (int idx = tid; idx < rows * DQ; idx += GNT) {
       const int r = idx / DQ, q = idx - r * DQ;
@@ -292,65 +265,68 @@ __global__ __launch_bounds__(GNT) void ggnn_forward_kernel(
   }
 }
 
-inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-inline bool overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + nb && b0 < a0 + na;
-}
-
-template <int D, int RT>
+template <int D, int RT, bool TRAJ>
 int launch(const float* state0, int ld0, const float* L, int64_t sb, int64_t sr, int64_t sc, int64_t sch,
            const uint8_t* mask, const float* W1, const float* b1, const float* W2, const float* b2,
            const float* Wih, const float* bih, const float* Whh, const float* bhh, const float* Wo,
            const float* bo, const float* wg, const float* bg, int B, int N, int C, int P, int num_prop, int avg,
-           float* score, float* state_out, int ldso, int grid, hipStream_t s) {
+           float* score, float* state_out, int ldso, float* states, int grid, hipStream_t s, const char* who) {
   const size_t lds = sizeof(float) * (size_t)ggnn_lds_floats(D, 16 * RT);
-  auto kfn = ggnn_forward_kernel<D, RT>;
+  auto kfn = ggnn_forward_kernel<D, RT, TRAJ>;
   LNZ_DYNAMIC_LDS(kfn, lds, "ggnn.hip");
   hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(GNT), lds, s, state0, ld0, L, sb, sr, sc, sch, mask, W1, b1,
-                     W2, b2, Wih, bih, Whh, bhh, Wo, bo, wg, bg, B, N, C, P, num_prop, avg, score, state_out, ldso);
-  return lnz::check_launch("lnz_ggnn_forward");
+                     W2, b2, Wih, bih, Whh, bhh, Wo, bo, wg, bg, B, N, C, P, num_prop, avg, score, state_out, ldso,
+                     states);
+  return lnz::check_launch(who);
 }
 
-}  // namespace
-
-extern "C" int lnz_ggnn_forward(const float* state0, int ld0, const float* L, int64_t stride_b, int64_t stride_r,
-                                int64_t stride_c, int64_t stride_ch, const uint8_t* mask, const float* W1,
-                                const float* b1, const float* W2, const float* b2, const float* Wih,
-                                const float* bih, const float* Whh, const float* bhh, const float* Wo,
-                                const float* bo, const float* wg, const float* bg, int B, int N, int C, int D,
-                                int P, int num_prop, int avg, float* score, float* state_out, int ldso,
-                                int tile_rows, lnz_stream_t stream) {
+int forward_impl(const char* who, const float* state0, int ld0, const float* L, int64_t stride_b, int64_t stride_r,
+                 int64_t stride_c, int64_t stride_ch, const uint8_t* mask, const float* W1, const float* b1,
+                 const float* W2, const float* b2, const float* Wih, const float* bih, const float* Whh,
+                 const float* bhh, const float* Wo, const float* bo, const float* wg, const float* bg, int B, int N,
+                 int C, int D, int P, int num_prop, int avg, float* score, float* state_out, int ldso,
+                 float* states, int tile_rows, lnz_stream_t stream) {
   LNZ_REQUIRE(state0 && L && W1 && b1 && W2 && b2 && Wih && bih && Whh && bhh && Wo && bo && wg && bg && score,
-              LNZ_EINVAL, "lnz_ggnn_forward: null pointer");
-  LNZ_REQUIRE(B > 0 && N > 0, LNZ_EINVAL, "lnz_ggnn_forward: B = %d, N = %d must be positive", B, N);
+              LNZ_EINVAL, "%s: null pointer", who);
+  LNZ_REQUIRE(B > 0 && N > 0, LNZ_EINVAL, "%s: B = %d, N = %d must be positive", who, B, N);
   LNZ_REQUIRE(N <= GMAXN && C >= 1 && C <= GMAXC && D >= 32 && D <= GMAXD && D % 32 == 0 && P >= 1 && P <= GMAXP &&
                   num_prop >= 0,
               LNZ_ENOTSUP,
-              "lnz_ggnn_forward: N = %d, C = %d, D = %d, P = %d, num_prop = %d outside 1 <= N <= 32, 1 <= C <= 8, "
-              "D a multiple of 32 and <= 128, 1 <= P <= 16, num_prop >= 0", N, C, D, P, num_prop);
+              "%s: N = %d, C = %d, D = %d, P = %d, num_prop = %d outside 1 <= N <= 32, 1 <= C <= 8, "
+              "D a multiple of 32 and <= 128, 1 <= P <= 16, num_prop >= 0", who, N, C, D, P, num_prop);
   LNZ_REQUIRE(ld0 >= D && (state_out == nullptr || ldso >= D), LNZ_EINVAL,
-              "lnz_ggnn_forward: ld0 = %d, ldso = %d below the width %d", ld0, ldso, D);
+              "%s: ld0 = %d, ldso = %d below the width %d", who, ld0, ldso, D);
   LNZ_REQUIRE(stride_b >= 0 && stride_r >= 0 && stride_c >= 0 && stride_ch >= 0, LNZ_EINVAL,
-              "lnz_ggnn_forward: negative stride of L");
+              "%s: negative stride of L", who);
   LNZ_REQUIRE(ld0 % 4 == 0 && (state_out == nullptr || ldso % 4 == 0) && aligned16(state0) && aligned16(state_out) &&
                   aligned16(W1) && aligned16(b1) && aligned16(W2) && aligned16(b2) && aligned16(Wih) &&
                   aligned16(bih) && aligned16(Whh) && aligned16(bhh),
-              LNZ_ENOTSUP, "lnz_ggnn_forward: the rows of state0, state_out and of the weights must be 16-byte "
-              "aligned (ld0 = %d, ldso = %d)", ld0, ldso);
+              LNZ_ENOTSUP, "%s: the rows of state0, state_out and of the weights must be 16-byte "
+              "aligned (ld0 = %d, ldso = %d)", who, ld0, ldso);
   {
     const uint64_t rows = (uint64_t)B * N;
     const uint64_t n0 = ((rows - 1) * (uint64_t)ld0 + D) * sizeof(float);
     const uint64_t nsc = (uint64_t)B * P * sizeof(float);
-    LNZ_REQUIRE(!overlap(score, nsc, state0, n0), LNZ_EINVAL, "lnz_ggnn_forward: score must not alias state0");
+    LNZ_REQUIRE(!overlap(score, nsc, state0, n0), LNZ_EINVAL, "%s: score must not alias state0", who);
     if (state_out != nullptr) {
       const uint64_t no = ((rows - 1) * (uint64_t)ldso + D) * sizeof(float);
       LNZ_REQUIRE(!overlap(state_out, no, state0, n0) && !overlap(state_out, no, score, nsc), LNZ_EINVAL,
-                  "lnz_ggnn_forward: state_out must not alias state0 or score");
+                  "%s: state_out must not alias state0 or score", who);
     }
   }
+  if (states != nullptr) {
+    const uint64_t rows = (uint64_t)B * N;
+    const uint64_t n0 = ((rows - 1) * (uint64_t)ld0 + D) * sizeof(float);
+    const uint64_t nsc = (uint64_t)B * P * sizeof(float);
+    const uint64_t nst = ((uint64_t)num_prop + 1) * rows * D * sizeof(float);
+    LNZ_REQUIRE(aligned16(states), LNZ_ENOTSUP, "%s: states must be 16-byte aligned", who);
+    LNZ_REQUIRE(!overlap(states, nst, state0, n0) && !overlap(states, nst, score, nsc) &&
+                    (state_out == nullptr ||
+                     !overlap(states, nst, state_out, ((rows - 1) * (uint64_t)ldso + D) * sizeof(float))),
+                LNZ_EINVAL, "%s: states must not alias state0, score or state_out", who);
+  }
   LNZ_REQUIRE(tile_rows == 0 || tile_rows == 32 || tile_rows == 64, LNZ_EINVAL,
-              "lnz_ggnn_forward: tile_rows = %d is not 0 (chosen by the batch), 32 or 64", tile_rows);
+              "%s: tile_rows = %d is not 0 (chosen by the batch), 32 or 64", who, tile_rows);
   int rows_per_tile = tile_rows;
   if (rows_per_tile == 0) {
     // 32-row tiles while they all fit in one round of the compute units, 64-row tiles beyond
@@ -367,14 +343,13 @@ extern "C" int lnz_ggnn_forward(const float* state0, int ld0, const float* L, in
   const int64_t grid = ((int64_t)B + mpt - 1) / mpt;
   hipStream_t s = (hipStream_t)stream;
   lnz::note_kernel("ggnn_forward_kernel<%d, %d>", D, rows_per_tile / 16);
-#define LNZ_GGNN_LAUNCH(DD)                                                                                          \
-  return rows_per_tile == 32                                                                                         \
-             ? launch<DD, 2>(state0, ld0, L, stride_b, stride_r, stride_c, stride_ch, mask, W1, b1, W2, b2, Wih, bih, \
-                             Whh, bhh, Wo, bo, wg, bg, B, N, C, P, num_prop, avg ? 1 : 0, score, state_out, ldso,    \
-                             (int)grid, s)                                                                           \
-             : launch<DD, 4>(state0, ld0, L, stride_b, stride_r, stride_c, stride_ch, mask, W1, b1, W2, b2, Wih, bih, \
-                             Whh, bhh, Wo, bo, wg, bg, B, N, C, P, num_prop, avg ? 1 : 0, score, state_out, ldso,    \
-                             (int)grid, s)
+#define LNZ_GGNN_LAUNCH_(DD, RTT, TR)                                                                              \
+  launch<DD, RTT, TR>(state0, ld0, L, stride_b, stride_r, stride_c, stride_ch, mask, W1, b1, W2, b2, Wih, bih, Whh,  \
+                      bhh, Wo, bo, wg, bg, B, N, C, P, num_prop, avg ? 1 : 0, score, state_out, ldso, states,        \
+                      (int)grid, s, who)
+#define LNZ_GGNN_LAUNCH(DD)                                                                     \
+  return rows_per_tile == 32 ? (states ? LNZ_GGNN_LAUNCH_(DD, 2, true) : LNZ_GGNN_LAUNCH_(DD, 2, false)) \
+                             : (states ? LNZ_GGNN_LAUNCH_(DD, 4, true) : LNZ_GGNN_LAUNCH_(DD, 4, false))
   switch (D) {
     case 32: LNZ_GGNN_LAUNCH(32);
     case 64: LNZ_GGNN_LAUNCH(64);
@@ -382,4 +357,33 @@ extern "C" int lnz_ggnn_forward(const float* state0, int ld0, const float* L, in
     default: LNZ_GGNN_LAUNCH(128);
   }
 #undef LNZ_GGNN_LAUNCH
+#undef LNZ_GGNN_LAUNCH_
+}
+
+}  // namespace
+
+extern "C" int lnz_ggnn_forward(const float* state0, int ld0, const float* L, int64_t stride_b, int64_t stride_r,
+                                int64_t stride_c, int64_t stride_ch, const uint8_t* mask, const float* W1,
+                                const float* b1, const float* W2, const float* b2, const float* Wih,
+                                const float* bih, const float* Whh, const float* bhh, const float* Wo,
+                                const float* bo, const float* wg, const float* bg, int B, int N, int C, int D,
+                                int P, int num_prop, int avg, float* score, float* state_out, int ldso,
+                                int tile_rows, lnz_stream_t stream) {
+  return forward_impl("lnz_ggnn_forward", state0, ld0, L, stride_b, stride_r, stride_c, stride_ch, mask, W1, b1, W2, b2,
+                      Wih, bih, Whh, bhh, Wo, bo, wg, bg, B, N, C, D, P, num_prop, avg, score, state_out, ldso, nullptr,
+                      tile_rows, stream);
+}
+
+extern "C" int lnz_ggnn_forward_states(const float* state0, int ld0, const float* L, int64_t stride_b,
+                                       int64_t stride_r, int64_t stride_c, int64_t stride_ch, const uint8_t* mask,
+                                       const float* W1, const float* b1, const float* W2, const float* b2,
+                                       const float* Wih, const float* bih, const float* Whh, const float* bhh,
+                                       const float* Wo, const float* bo, const float* wg, const float* bg, int B,
+                                       int N, int C, int D, int P, int num_prop, int avg, float* score,
+                                       float* state_out, int ldso, float* states, int tile_rows,
+                                       lnz_stream_t stream) {
+  LNZ_REQUIRE(states, LNZ_EINVAL, "lnz_ggnn_forward_states: null pointer");
+  return forward_impl("lnz_ggnn_forward_states", state0, ld0, L, stride_b, stride_r, stride_c, stride_ch, mask, W1, b1,
+                      W2, b2, Wih, bih, Whh, bhh, Wo, bo, wg, bg, B, N, C, D, P, num_prop, avg, score, state_out, ldso,
+                      states, tile_rows, stream);
 }

@@ -21,7 +21,16 @@ table is ONE `f32_linear` launch per weight version, gathered per call — then 
 launch for all `num_prop` steps and the readout.  Everything else — gradients, dropout in training,
 `update_func: 'RNN'`, shapes outside the envelope — takes 'ggnn_torch', a device-side differentiable
 torch restatement, with one UserWarning per module that names the reason.  There is no CPU path.
+
+Route 'ggnn_hip_train' (opt-in: `LANCZOSNET_GGNN_BACKWARD=hip`, or `net.ggnn_backward_impl = 'hip'`; a
+call that needs gradients inside the same envelope): the same table and gather, ONE `ggnn_forward_states`
+launch (route 'ggnn_hip''s kernel and bits, plus the state trajectory [num_prop + 1, B, N, D] — nothing else
+is saved), and under `loss.backward()` the readout backward, one `ggnn_backward_step` launch per step
+t = T-1 .. 0 (the step is recomputed on chip from S_t) with the step's weight gradients by the library
+GEMM, `embedding_grad` into the table and the tiny input gradients in torch (csrc/ggnn_grad.hip).  Dropout
+in training, the RNN update and every shape reason still take 'ggnn_torch'.
 """
+import os
 import warnings
 
 import numpy as np
@@ -38,8 +47,53 @@ EPS = float(np.finfo(np.float32).eps)
 GGNN_INPUT_STEP = 32   # lnz_f32_linear: K (= input_dim) a multiple of 32
 
 
+class _GgnnTrainFunction(torch.autograd.Function):
+    """Route 'ggnn_hip_train': forward = `GGNN._hip_forward`'s table, gather and kernel, leaving the state
+    trajectory; backward = readout backward, the steps T-1 .. 0 (each recomputed from its S_t, its weight
+    gradients accumulated by the library GEMM), the table's gradient by atom id (all N rows take part, the
+    padding id included, as in the reference), the input layer and the embedding in torch.  Inputs after
+    the six plain ones: embedding.weight, input_func W, b, the stacked W1, b1, W2, b2, the cell's W_ih,
+    b_ih, W_hh, b_hh, Wo, bo, wg, bg."""
+
+    @staticmethod
+    def forward(ctx, avg, num_prop, transposes, node_feat, L, mask, emb, Win, bin_, *operands):
+        f = lambda x: x.detach().float().contiguous()  # noqa: E731
+        emb, Win, bin_ = f(emb), f(Win), f(bin_)
+        operands = tuple(f(x) for x in operands)
+        table = ops.f32_linear(emb, Win, bias=bin_)
+        score, states = ops.ggnn_forward_states(table[node_feat], L, mask, *operands, num_prop, avg=avg)
+        ctx.avg, ctx.transposes, ctx.operands, ctx.input = avg, transposes, operands, (emb, Win)
+        ctx.save_for_backward(node_feat, L, mask)
+        ctx.states = states
+        return score
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dscore):
+        node_feat, L, mask = ctx.saved_tensors
+        states, prop, head = ctx.states, ctx.operands[:8], ctx.operands[8:]
+        emb, Win = ctx.input
+        T, B, N, D = states.shape[0] - 1, states.shape[1], states.shape[2], states.shape[3]
+        C = L.shape[3]
+        dS, dWo, dbo, dwg, dbg = ops.ggnn_readout_backward(states[T], mask, *head, dscore.contiguous())
+        grads = None
+        if T > 0:
+            spare, bufs = torch.empty_like(dS), ops.ggnn_step_buffers(B, N, C, D, dS.device)
+            for t in range(T - 1, -1, -1):
+                spare, _ = ops.ggnn_backward_step(states[t], dS, L, *prop, transposes=ctx.transposes, avg=ctx.avg,
+                                                  dS=spare, buffers=bufs)
+                dS, spare = spare, dS
+                grads = ops.ggnn_step_weight_grads(states[t], bufs, C, grads)
+        dtable = ops.embedding_grad(node_feat.contiguous(), dS, D, emb.shape[0])
+        dWin, dbin, demb = dtable.t() @ emb, dtable.sum(dim=0), dtable @ Win
+        return ((None,) * 6 + (demb, dWin, dbin) + (tuple(grads) if grads is not None else (None,) * 8)
+                + (dWo, dbo, dwg.view(1, -1), dbg))
+
+
 class GGNN(nn.Module):
     """Gated Graph Sequence Neural Networks (Li et al., ICLR 2016) as the reference builds it for QM8."""
+    # 'torch': a call that needs gradients takes route 'ggnn_torch'; 'hip': route 'ggnn_hip_train'
+    ggnn_backward_impl = os.environ.get('LANCZOSNET_GGNN_BACKWARD', 'torch')
 
     def __init__(self, config):
         super().__init__()
@@ -83,6 +137,7 @@ class GGNN(nn.Module):
         self.loss_func = losses[m.loss]()
         self._init_param()
         self._pack_cache = None
+        self._transpose_cache = None
         self._param_list = None
         self.last_route = None
 
@@ -131,6 +186,7 @@ class GGNN(nn.Module):
         (`p.data.clamp_()`, `p.data = x`) and a parameter replaced by another object need this call.
         `load_state_dict` and `.to()/.cuda()/.float()` call it themselves."""
         self._pack_cache = None
+        self._transpose_cache = None
         self._param_list = None
 
     def _apply(self, fn, *a, **kw):
@@ -156,15 +212,27 @@ class GGNN(nn.Module):
         self._pack_cache = (sig, (table, operands))
         return self._pack_cache[1]
 
+    @torch.no_grad()
+    def _transposes(self):
+        """(W1T, W2T, WihT, WhhT) of ops.ggnn_backward_step, once per weight version like `_packs`."""
+        sig = self._param_signature()
+        if self._transpose_cache is not None and self._transpose_cache[0] == sig:
+            return self._transpose_cache[1]
+        W1, _, W2, _ = self._msg_operands()
+        packs = ops.ggnn_pack_transposes(W1, W2, self.update_func.weight_ih, self.update_func.weight_hh)
+        self._transpose_cache = (sig, packs)
+        return packs
+
     # -- which route serves a call ----------------------------------------------------------------
     def _needs_grad(self):
         return torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
 
     def _why_not_hip(self, N, L, needs_grad, drop):
-        """None when route 'ggnn_hip' serves the call, else the reason in words.  No GPU needed to ask."""
+        """None when route 'ggnn_hip' (or, for a call that needs gradients with the switch on, route
+        'ggnn_hip_train') serves the call, else the reason in words.  No GPU needed to ask."""
         C, D = self.num_edgetype + 1, self.hidden_dim
-        if needs_grad:
-            return 'gradients are required (the kernel has no backward)'
+        if needs_grad and self.ggnn_backward_impl != 'hip':
+            return 'gradients are required (the HIP backward is opt-in: LANCZOSNET_GGNN_BACKWARD=hip)'
         if drop:
             return 'dropout=%r in training' % self.dropout
         if self.update_kind != 'GRU':
@@ -222,7 +290,10 @@ class GGNN(nn.Module):
         node_feat, L, label, mask = t['node_feat'], t['L'], t['label'], t['mask']
         drop = self.training and self.dropout > 0
         why = self._why_not_hip(node_feat.shape[1], L, self._needs_grad(), drop)
-        if why is None:
+        if why is None and self._needs_grad():
+            self.last_route = 'ggnn_hip_train'
+            score = self._hip_train_forward(node_feat, L, mask)
+        elif why is None:
             self.last_route = 'ggnn_hip'
             score = self._hip_forward(node_feat, L, mask)
         else:
@@ -241,6 +312,14 @@ class GGNN(nn.Module):
         table, operands = self._packs()
         return ops.ggnn_forward(table[node_feat], L, mask, *operands, self.num_prop,
                                 avg=self.aggregate_type == 'avg')
+
+    def _hip_train_forward(self, node_feat, L, mask):
+        cell = self.update_func
+        return _GgnnTrainFunction.apply(
+            self.aggregate_type == 'avg', self.num_prop, self._transposes(), node_feat, L, mask,
+            self.embedding.weight, self.input_func[0].weight, self.input_func[0].bias, *self._msg_operands(),
+            cell.weight_ih, cell.bias_ih, cell.weight_hh, cell.bias_hh, self.output_func[0].weight,
+            self.output_func[0].bias, self.att_func[0].weight, self.att_func[0].bias)
 
     def _torch_forward(self, node_feat, L, mask, dropout=False):
         """Differentiable torch restatement of model/ggnn.py:138-192 on device tensors, the C message

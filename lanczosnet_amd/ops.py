@@ -2652,3 +2652,204 @@ def ggnn_forward(state0, L, mask, W1, b1, W2, b2, Wih, bih, Whh, bhh, Wo, bo, wg
                         Wih, bih, Whh, bhh, Wo, bo, wg, bg, B, N, C, D, P, int(num_prop), int(bool(avg)), score,
                         state_out, ldso, int(tile_rows))
   return (score, state_out) if state_out is not None else score
+
+
+def _ggnn_operands(who, C, D, W1, b1, W2, b2, Wih, bih, Whh, bhh):
+  """The eight propagation operands as float32 contiguous tensors of the shapes the kernels read."""
+  W1, b1, W2, b2 = _f32c(W1), _f32c(b1), _f32c(W2), _f32c(b2)
+  Wih, bih, Whh, bhh = _f32c(Wih), _f32c(bih).reshape(-1), _f32c(Whh), _f32c(bhh).reshape(-1)
+  Hd = GGNN_MSG_HIDDEN
+  for t, shape in ((W1, (C, Hd, D)), (b1, (C, Hd)), (W2, (C, D, Hd)), (b2, (C, D)), (Wih, (3 * D, C * D)),
+                   (bih, (3 * D,)), (Whh, (3 * D, D)), (bhh, (3 * D,))):
+    if tuple(t.shape) != shape:
+      raise LnzError(_lib.LNZ_EINVAL, '%s: operand of shape %s where %s is expected' % (who, tuple(t.shape), shape))
+  return W1, b1, W2, b2, Wih, bih, Whh, bhh
+
+
+def ggnn_forward_states(state0, L, mask, W1, b1, W2, b2, Wih, bih, Whh, bhh, Wo, bo, wg, bg, num_prop, avg=True,
+                        states=None, tile_rows=0):
+  """lnz_ggnn_forward_states: ggnn_forward (same operands, envelope, errors and bits) that also leaves the
+  state trajectory -> (score [B, P], states [num_prop + 1, B, N, D]): states[t] = S_t at the start of step
+  t, states[num_prop] the final state.  Nothing else is saved for the backward."""
+  who = 'ggnn_forward_states'
+  _need_cuda(state0, L, mask, W1, b1, W2, b2, Wih, bih, Whh, bhh, Wo, bo, wg, bg, states)
+  if state0.dim() != 3 or L.dim() != 4 or L.dtype != torch.float32:
+    raise LnzError(_lib.LNZ_EINVAL, '%s: state0 [B, N, D] and a float32 L [B, N, N, C] expected' % who)
+  B, N, D = state0.shape
+  C = L.shape[3]
+  if tuple(L.shape[:3]) != (B, N, N):
+    raise LnzError(_lib.LNZ_EINVAL, '%s: state0 %s and L %s do not fit' % (who, tuple(state0.shape), tuple(L.shape)))
+  ld0 = _gat_rows(state0, who)
+  W1, b1, W2, b2, Wih, bih, Whh, bhh = _ggnn_operands(who, C, D, W1, b1, W2, b2, Wih, bih, Whh, bhh)
+  Wo, bo, wg, bg = _f32c(Wo), _f32c(bo).reshape(-1), _f32c(wg).reshape(-1), _f32c(bg).reshape(-1)
+  P = Wo.shape[0]
+  for t, shape in ((Wo, (P, D)), (bo, (P,)), (wg, (D,)), (bg, (1,))):
+    if tuple(t.shape) != shape:
+      raise LnzError(_lib.LNZ_EINVAL, '%s: operand of shape %s where %s is expected' % (who, tuple(t.shape), shape))
+  if mask is not None:
+    if tuple(mask.shape) != (B, N):
+      raise LnzError(_lib.LNZ_EINVAL, '%s: mask %s, expected %s' % (who, tuple(mask.shape), (B, N)))
+    mask = (mask != 0).to(torch.uint8).contiguous()
+  T = int(num_prop)
+  if T < 0:
+    raise NotSupported(_lib.LNZ_ENOTSUP, '%s: num_prop = %d' % (who, T))
+  if states is None:
+    states = torch.empty((T + 1, B, N, D), dtype=torch.float32, device=state0.device)
+  if tuple(states.shape) != (T + 1, B, N, D) or states.dtype != torch.float32 or not states.is_contiguous():
+    raise LnzError(_lib.LNZ_EINVAL, '%s: states %s, expected a contiguous float32 %s'
+                   % (who, tuple(states.shape), (T + 1, B, N, D)))
+  score = torch.empty((B, P), dtype=torch.float32, device=state0.device)
+  with torch.cuda.device(state0.device):
+    _abi().ggnn_forward_states(state0, ld0, L, L.stride(0), L.stride(1), L.stride(2), L.stride(3), mask, W1, b1,
+                               W2, b2, Wih, bih, Whh, bhh, Wo, bo, wg, bg, B, N, C, D, P, T, int(bool(avg)), score,
+                               None, D, states, int(tile_rows))
+  return score, states
+
+
+def ggnn_pack_transposes(W1, W2, Wih, Whh):
+  """The transposed weights lnz_ggnn_backward_step reads (its data-gradient products contract over the output
+  index of a forward weight): W1 [C, 128, D], W2 [C, D, 128], Wih [3 D, C D], Whh [3 D, D] -> W1T [C, D, 128],
+  W2T [C, 128, D], WihT [C, D, 3 D] (block c = Wih[:, cD:(c+1)D]^T), WhhT [D, 3 D].  Once per weight version."""
+  C, _, D = W1.shape
+  f = lambda x: x.detach().float().contiguous()  # noqa: E731
+  return (f(W1.transpose(1, 2)), f(W2.transpose(1, 2)), f(Wih.reshape(3 * D, C, D).permute(1, 2, 0)), f(Whh.t()))
+
+
+def ggnn_step_buffers(B, N, C, D, device):
+  """The row-space outputs of one ggnn_backward_step besides dS: (dgi [B N, 3 D], dghn [B N, D], A [B N, C D],
+  dM [B N, C D], H [B N, C 128], dHpre [B N, C 128]); a step loop allocates them once."""
+  new = lambda w: torch.empty((B * N, w), dtype=torch.float32, device=device)  # noqa: E731
+  return (new(3 * D), new(D), new(C * D), new(C * D), new(C * GGNN_MSG_HIDDEN), new(C * GGNN_MSG_HIDDEN))
+
+
+def ggnn_backward_step(S, dSnext, L, W1, b1, W2, b2, Wih, bih, Whh, bhh, transposes=None, avg=True, dS=None,
+                       buffers=None):
+  """lnz_ggnn_backward_step: one propagation step of backpropagation through time.  S [B, N, D] = S_t (a
+  slice of ggnn_forward_states' trajectory), dSnext [B, N, D] = dL/dS_{t+1} (row strides beyond D are fine
+  for both and for dS), L and the eight propagation operands as in ggnn_forward, transposes =
+  ggnn_pack_transposes(W1, W2, Wih, Whh) (None: packed here), buffers = ggnn_step_buffers(..) (None:
+  allocated here; overwritten) -> (dS [B, N, D] = dL/dS_t, buffers).  The weight gradients of the step are
+  contractions of the buffers over the rows (ggnn_step_weight_grads)."""
+  who = 'ggnn_backward_step'
+  tr = tuple(transposes) if transposes is not None else ()
+  bufs = tuple(buffers) if buffers is not None else ()
+  _need_cuda(S, dSnext, L, W1, b1, W2, b2, Wih, bih, Whh, bhh, dS, *(tr + bufs))
+  if S.dim() != 3 or L.dim() != 4 or L.dtype != torch.float32:
+    raise LnzError(_lib.LNZ_EINVAL, '%s: S [B, N, D] and a float32 L [B, N, N, C] expected' % who)
+  B, N, D = S.shape
+  C = L.shape[3]
+  if tuple(L.shape[:3]) != (B, N, N) or tuple(dSnext.shape) != (B, N, D):
+    raise LnzError(_lib.LNZ_EINVAL, '%s: S %s, dSnext %s and L %s do not fit'
+                   % (who, tuple(S.shape), tuple(dSnext.shape), tuple(L.shape)))
+  lds, ldd = _gat_rows(S, who), _gat_rows(dSnext, who)
+  W1, b1, W2, b2, Wih, bih, Whh, bhh = _ggnn_operands(who, C, D, W1, b1, W2, b2, Wih, bih, Whh, bhh)
+  if transposes is None:
+    tr = ggnn_pack_transposes(W1, W2, Wih, Whh)
+  Hd = GGNN_MSG_HIDDEN
+  if len(tr) != 4:
+    raise LnzError(_lib.LNZ_EINVAL, '%s: four transposed weights expected' % who)
+  for t, shape in zip(tr, ((C, D, Hd), (C, Hd, D), (C, D, 3 * D), (D, 3 * D))):
+    if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous():
+      raise LnzError(_lib.LNZ_EINVAL, '%s: transposed weight %s where a contiguous float32 %s is expected'
+                     % (who, tuple(t.shape), shape))
+  if dS is None:
+    dS = torch.empty((B, N, D), dtype=torch.float32, device=S.device)
+  if tuple(dS.shape) != (B, N, D):
+    raise LnzError(_lib.LNZ_EINVAL, '%s: dS %s, expected %s' % (who, tuple(dS.shape), (B, N, D)))
+  ldo = _gat_rows(dS, who)
+  if buffers is None:
+    bufs = ggnn_step_buffers(B, N, C, D, S.device)
+  if len(bufs) != 6:
+    raise LnzError(_lib.LNZ_EINVAL, '%s: six row-space buffers expected' % who)
+  for t, w in zip(bufs, (3 * D, D, C * D, C * D, C * Hd, C * Hd)):
+    if tuple(t.shape) != (B * N, w) or t.dtype != torch.float32 or not t.is_contiguous():
+      raise LnzError(_lib.LNZ_EINVAL, '%s: row-space buffer %s where a contiguous float32 %s is expected'
+                     % (who, tuple(t.shape), (B * N, w)))
+  with torch.cuda.device(S.device):
+    _abi().ggnn_backward_step(S, lds, dSnext, ldd, L, L.stride(0), L.stride(1), L.stride(2), L.stride(3), W1, b1,
+                              W2, b2, Wih, bih, Whh, bhh, tr[0], tr[1], tr[2], tr[3], B, N, C, D, int(bool(avg)),
+                              dS, ldo, *bufs)
+  return dS, bufs
+
+
+GGNN_GRAD_SPLITS, GGNN_GRAD_SPLIT_ROWS = 4, 1024
+
+
+def _tn_row_splits(a, b):
+  """a^T b for tall operands a [R, m], b [R, n]: from GGNN_GRAD_SPLIT_ROWS rows on, GGNN_GRAD_SPLITS batched
+  partial products over row slices, added in a fixed order (model._common._tn_split_k's form from a lower row
+  count: a contraction over all 2,015 rows of a batch in ONE k-ordered float32 chain measured 3.9 x the
+  float32 autograd's own error; more and shorter chunks measured slower — 512-row chunks: 12.8 against 7.3 ms
+  per training step at B = 64)."""
+  R = a.shape[0]
+  if R < GGNN_GRAD_SPLIT_ROWS:
+    return a.t() @ b
+  k = GGNN_GRAD_SPLITS
+  Rs = R // k
+  out = torch.bmm(a[:k * Rs].view(k, Rs, a.shape[1]).transpose(1, 2), b[:k * Rs].view(k, Rs, b.shape[1])).sum(dim=0)
+  if k * Rs < R:
+    out = out + a[k * Rs:].t() @ b[k * Rs:]
+  return out
+
+
+def ggnn_step_weight_grads(S, buffers, C, grads=None):
+  """The weight gradients of one step from what ggnn_backward_step left, by the library GEMM of every other
+  training route here (_tn_row_splits; the C blocks of dW2 in one batched GEMM): dW1 [C, 128, D] = dHpre_c^T S,
+  db1, dW2 [C, D, 128] = dM_c^T H_c, db2, dWih [3 D, C D] = dgi^T A, dbih, dWhh [3 D, D] = dgh^T S, dbhh (the
+  biases: column sums).  grads: the eight accumulators of the earlier steps (added into, in place) or None
+  -> the eight tensors."""
+  dgi, dghn, A, dM, H, dHpre = buffers
+  R, D = dghn.shape
+  Hd = GGNN_MSG_HIDDEN
+  S2 = S.reshape(R, D)
+  dgh = torch.cat((dgi[:, :2 * D], dghn), dim=1)
+  k = GGNN_GRAD_SPLITS if R >= GGNN_GRAD_SPLIT_ROWS else 1
+  Rs = R // k
+  # [k, Rs, C, D]^T [k, Rs, C, 128] per (slice, channel), the k slices added in order, then the last R % k rows
+  dW2 = torch.bmm(dM[:k * Rs].view(k, Rs, C, D).permute(0, 2, 3, 1).reshape(k * C, D, Rs),
+                  H[:k * Rs].view(k, Rs, C, Hd).permute(0, 2, 1, 3).reshape(k * C, Rs, Hd)).view(k, C, D, Hd).sum(dim=0)
+  if k * Rs < R:
+    dW2 = dW2 + torch.bmm(dM[k * Rs:].view(-1, C, D).permute(1, 2, 0), H[k * Rs:].view(-1, C, Hd).transpose(0, 1))
+  new = (_tn_row_splits(dHpre, S2).view(C, Hd, D), dHpre.sum(dim=0).view(C, Hd), dW2, dM.sum(dim=0).view(C, D),
+         _tn_row_splits(dgi, A), dgi.sum(dim=0), _tn_row_splits(dgh, S2), dgh.sum(dim=0))
+  if grads is None:
+    return list(new)
+  for acc, x in zip(grads, new):
+    acc.add_(x)
+  return grads
+
+
+def ggnn_readout_backward(Slast, mask, Wo, bo, wg, bg, dscore, dSlast=None):
+  """lnz_ggnn_readout_backward: the readout of ggnn_forward under loss.backward().  Slast [B, N, D] = the
+  final state, dscore [B, P] -> (dSlast [B, N, D] — exactly 0 on rows outside the mask —, dWo [P, D], dbo [P],
+  dwg [D], dbg [1]).  Per-molecule partials added in a fixed order."""
+  who = 'ggnn_readout_backward'
+  _need_cuda(Slast, mask, Wo, bo, wg, bg, dscore, dSlast)
+  if Slast.dim() != 3:
+    raise LnzError(_lib.LNZ_EINVAL, '%s: Slast [B, N, D] expected' % who)
+  B, N, D = Slast.shape
+  ld = _gat_rows(Slast, who)
+  Wo, bo, wg, bg = _f32c(Wo), _f32c(bo).reshape(-1), _f32c(wg).reshape(-1), _f32c(bg).reshape(-1)
+  P = Wo.shape[0]
+  if tuple(Wo.shape) != (P, D) or bo.numel() != P or wg.numel() != D or bg.numel() != 1:
+    raise LnzError(_lib.LNZ_EINVAL, '%s: head operands %s, %s, %s, %s do not fit D = %d'
+                   % (who, tuple(Wo.shape), tuple(bo.shape), tuple(wg.shape), tuple(bg.shape), D))
+  if tuple(dscore.shape) != (B, P):
+    raise LnzError(_lib.LNZ_EINVAL, '%s: dscore %s, expected %s' % (who, tuple(dscore.shape), (B, P)))
+  dscore = _f32c(dscore)
+  if mask is not None:
+    if tuple(mask.shape) != (B, N):
+      raise LnzError(_lib.LNZ_EINVAL, '%s: mask %s, expected %s' % (who, tuple(mask.shape), (B, N)))
+    mask = (mask != 0).to(torch.uint8).contiguous()
+  if dSlast is None:
+    dSlast = torch.empty((B, N, D), dtype=torch.float32, device=Slast.device)
+  if tuple(dSlast.shape) != (B, N, D):
+    raise LnzError(_lib.LNZ_EINVAL, '%s: dSlast %s, expected %s' % (who, tuple(dSlast.shape), (B, N, D)))
+  ldg = _gat_rows(dSlast, who)
+  new = lambda *s: torch.empty(s, dtype=torch.float32, device=Slast.device)  # noqa: E731
+  dWo, dbo, dwg, dbg = new(P, D), new(P), new(D), new(1)
+  with torch.cuda.device(Slast.device):
+    ws = new(max(int(_abi().ggnn_readout_backward_workspace_floats(B, D, P)), 1))
+    _abi().ggnn_readout_backward(Slast, ld, mask, Wo, bo, wg, bg, dscore, B, N, D, P, ws, dSlast, ldg, dWo, dbo,
+                                 dwg, dbg)
+  return dSlast, dWo, dbo, dwg, dbg

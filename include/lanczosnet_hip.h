@@ -46,6 +46,8 @@ extern "C" {
  *    stays);
  *    + its backward (lnz_ggnn_forward_states, lnz_ggnn_backward_step, lnz_ggnn_readout_backward and the
  *    _workspace_floats query: additive, the version stays);
+ *    + the MPNN baseline's fused edge-network propagation and Set2Vec readout (lnz_mpnn_forward,
+ *    lnz_set2vec_readout: additive, the version stays);
  *    + lnz_forward_args.rare_strips / .no_fold / .rare_debug at the END of the block (the strip forward's folded form of
  *    the rare bond-type channels, on by default: zeros = folded where cheaper; additive, the version
  *    stays — a caller built against the shorter block must zero-fill lnz_forward_args_size() bytes);
@@ -1289,6 +1291,46 @@ int lnz_ggnn_readout_backward(const float* Slast, int ld, const uint8_t* mask, c
                               const float* wg, const float* bg, const float* dscore, int B, int N, int D, int P,
                               float* workspace, float* dSlast, int ldg, float* dWo, float* dbo, float* dwg,
                               float* dbg, lnz_stream_t stream);
+
+/* ---- the MPNN baseline (model/mpnn.py:125-212, model/set2set.py:60-100, config/qm8_mpnn.yaml), csrc/mpnn.hip ----
+ * lnz_mpnn_forward: all num_prop edge-network propagation steps (msg_func 'MLP') in ONE launch.  state0
+ * [B N, ld0] is input_func(node_embedding(node_feat)); with C = num_bond_type + 1 channels, state width D,
+ * message hidden width 64 and W1_c = [W1n_c | W1s_c] (columns 0 .. D-1 act on the neighbour h_b, columns
+ * D .. 2D-1 on the row's own h_a), per step on the state S
+ *   P_c = S W1n_c^T ; Q_c = S W1s_c^T + b1_c ; R_c[a] = sum over b with L[a, b, c] != 0 of relu(Q_c[a] + P_c[b])
+ *   M_c[a] = R_c[a] W2_c^T + deg_c[a] b2_c, for avg != 0 divided by (deg_c[a] + FLT_EPSILON) AFTER the sum
+ *   S' = GRUCell(cat_c M_c, S)     (the cell of lnz_ggnn_forward: Wih [3 D, C D], bih, Whh [3 D, D], bhh)
+ * which is the reference's 2D -> 64 -> D MLP on all N^2 ordered pairs, factored.  W1 [C][64][2 D], b1 [C][64],
+ * W2 [C][D][64], b2 [C][D].  Every one of the N rows of a molecule propagates (a padded row has degree 0, a
+ * message of exactly 0 and evolves under GRU(0, h)).  L [B, N, N, C] is read through its four strides
+ * (elements, >= 0), only compared with zero (a NaN or a negative entry is an edge) and never written.
+ * state_out [B N, ldso] receives the final state (num_prop = 0: a copy of state0).
+ * Envelope: N <= 32, C <= 8, D a multiple of 32 and <= 128, num_prop >= 0, 16-byte aligned rows (LNZ_ENOTSUP);
+ * null pointers, B or N <= 0, a row stride below D, negative strides, state_out overlapping state0,
+ * tile_rows other than 0, 32, 64: LNZ_EINVAL.  tile_rows as in lnz_ggnn_forward: a row's arithmetic and
+ * bits do not depend on it.  Exact-fp32 MFMA, no atomics, every sum in a fixed order: bit-reproducible. */
+int lnz_mpnn_forward(const float* state0, int ld0, const float* L, int64_t stride_b, int64_t stride_r,
+                     int64_t stride_c, int64_t stride_ch, const float* W1, const float* b1, const float* W2,
+                     const float* b2, const float* Wih, const float* bih, const float* Whh, const float* bhh, int B,
+                     int N, int C, int D, int num_prop, int avg, float* state_out, int ldso, int tile_rows,
+                     lnz_stream_t stream);
+
+/* lnz_set2vec_readout: Set2Vec (model/set2set.py:79-100) and output_func in ONE launch.  Per molecule, with
+ * X = the rows of X [B N, ld] where mask [B, N] != 0 (NULL: all N rows), q* [2 D] = 0, mem [D] = 0, num_step times
+ *   f, i, o = sigmoid(W_f q* + b_f), sigmoid(W_i q* + b_i), sigmoid(W_o q* + b_o) ; g = tanh(W_m q* + b_m)
+ *   mem = f mem + i g ; q = o tanh(mem) ; e_j = sum_f tanh((q W_1)_f + X_jf) W_2[f]
+ *   w = softmax_j(e) over the set (max-subtracted) ; q* = [q, sum_j w_j X_j]
+ * then score [B, P] = Wout q* + bout.  Wg [4][D][2 D] and bg [4][D] stack the forget, input, output and memory
+ * gates; W1T [D][D] is W_1 TRANSPOSED (W1T[f][k] = W_1[k][f]), w2 [D], Wout [P][2 D], bout [P].  Rows outside
+ * the set are never loaded (they may hold NaN); a molecule with an empty set reads exactly 0 (finite score);
+ * num_step = 0: score = bout.  N <= 32, D a multiple of 32 and <= 128, 1 <= P <= 16, num_step >= 0, 16-byte
+ * aligned rows (LNZ_ENOTSUP); null pointers, B or N <= 0, ld < D, score overlapping X, mols_per_group outside
+ * 0 .. 16: LNZ_EINVAL.  mols_per_group = 0: as few molecules per workgroup as spread the batch over the compute
+ * units, at most the 16 rows of an MFMA tile; 1 .. 16 force it — a molecule's arithmetic and bits do not depend
+ * on it.  No atomics, every sum in a fixed order: bit-reproducible. */
+int lnz_set2vec_readout(const float* X, int ld, const uint8_t* mask, const float* Wg, const float* bg,
+                        const float* W1T, const float* w2, const float* Wout, const float* bout, int B, int N, int D,
+                        int P, int num_step, float* score, int mols_per_group, lnz_stream_t stream);
 
 
 /* ---- next row (SURVEY.md 8f rank 1 + 3): device-side collate from a packed molecule shard ----

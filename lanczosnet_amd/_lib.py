@@ -191,6 +191,9 @@ SIGNATURES = {
     'lnz_ggnn_readout_backward_workspace_floats': (C.c_int64, [_I, _I, _I]),
     'lnz_ggnn_readout_backward': (C.c_int, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P,
                                             _P]),
+    'lnz_mpnn_forward': (C.c_int, [_P, _I, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I,
+                                   _P, _I, _I, _P]),
+    'lnz_set2vec_readout': (C.c_int, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P]),
     'lnz_unsorted_segment_sum_forward': (C.c_int, [_P, _P, _I, _I, _I, _I, _P, _P]),
     'lnz_unsorted_segment_sum_backward': (C.c_int, [_P, _P, _I, _I, _I, _I, _P, _P]),
 }

@@ -1,0 +1,500 @@
+// The MPNN baseline (reference model/mpnn.py:125-212, model/set2set.py:60-100, config/qm8_mpnn.yaml): all
+// num_prop edge-network propagation steps in ONE launch, the Set2Vec readout and output_func in another.
+//
+// lnz_mpnn_forward — the reference's default msg_func 'MLP' runs a 2D -> 64 -> D MLP on all N^2 ordered
+// node pairs per channel and step.  Its first Linear splits over the concatenation [h_b, h_a] (h_b the
+// neighbour, h_a the row the message is aggregated into), W1_c = [W1n_c | W1s_c], so per step on the
+// state S [rows, D], channels c = 0 .. C-1 (C = num_bond_type + 1), hidden width 64:
+//     P_c  = S W1n_c^T ;  Q_c = S W1s_c^T + b1_c                    [rows, 64] each
+//     R_c[a] = sum over b with L[a, b, c] != 0 of relu(Q_c[a] + P_c[b])          (b ascending)
+//     M_c[a] = R_c[a] W2_c^T + deg_c[a] b2_c                                      ('sum')
+//     M_c[a] = (R_c[a] W2_c^T + deg_c[a] b2_c) / (deg_c[a] + FLT_EPSILON)         ('avg': divided AFTER the sum)
+//     gi   = sum_c M_c W_ih[:, cD:(c+1)D]^T + b_ih ;  gh = S W_hh^T + b_hh        [rows, 3D]
+//     r, z = sigmoid(gi_r + gh_r), sigmoid(gi_z + gh_z) ;  n = tanh(gi_n + r * gh_n)
+//     S'   = (1 - z) * n + z * S
+// Every one of the N rows of a molecule propagates: a padded row has degree 0, message exactly 0 and
+// evolves under GRU(0, h).  L is only ever compared with zero (a NaN or a negative entry is an edge),
+// never written.  The kernel leaves the final state; the readout is the second kernel.
+//
+// Shape as built: ggnn.hip's.  A workgroup of eight waves owns a tile of floor(R / N) whole molecules,
+// R = 64 or 32 rows, whose state stays in LDS for every step.  L is read once, through its four strides,
+// into per-row bit masks and degrees.  The GEMMs run on v_mfma_f32_16x16x4_f32 through tile_gemm
+// (ggnn_tile.hpp), weights streamed from L2.  [P_c | Q_c] is ONE 128-column product (wave w < 4: the 16
+// columns 16 w .. of P_c, wave w >= 4: of Q_c — the two halves of the rows of W1_c, read where they
+// lie), R_c runs on the VALU over the set bits only, M_c = R_c W2_c^T is a K = 64 product of the waves
+// that own features, whose gate accumulators live across the channel loop as in ggnn.hip; gh and the
+// GRU cell are ggnn.hip's.  Three barriers per channel, two per step.  LDS at D = 128, R = 64: S, M_c
+// 64 x 132 floats each + [P|Q] 64 x 132 + R_c 64 x 68 + masks = 123,136 B.  No atomics, no
+// cross-workgroup traffic, every sum in a fixed order: bit-reproducible, and a row's bits do not depend
+// on the tile height.  The folded form W_ih[:, c] W2_c ([3D, 64] per channel) was not built.
+//
+// lnz_set2vec_readout — per molecule, X = the rows with mask != 0 (all N without a mask), q* [2D] = 0,
+// mem [D] = 0; num_step times
+//     f, i, o = sigmoid(W_f q* + b_f), sigmoid(W_i q* + b_i), sigmoid(W_o q* + b_o) ;  g = tanh(W_m q* + b_m)
+//     mem = f mem + i g ;  q = o tanh(mem)
+//     e_j = sum_f tanh((q W_1)_f + X_jf) W_2[f] ;  w = softmax_j(e) over the masked rows (max-subtracted)
+//     q* = [q, sum_j w_j X_j]
+// then score = W_out q* + b_out.  A workgroup batches up to 16 molecules as the 16 rows of an MFMA tile:
+// wave w owns the features 16 w .. of all four gates (one tile_gemm with four weight tiles over K = 2D)
+// and of q W_1 (W_1^T packed by the caller); a lane keeps `mem` of its (molecule, four features) in
+// registers over the steps.  The energies take sixteen lanes per row (coalesced 16-byte reads of X, a
+// fixed xor tree), the softmax one thread per molecule, the weighted sum one thread per (molecule, four
+// features), j ascending.  X is re-read from L2 in every step: a full tile of sixteen 32-row molecules is
+// 256 KB at D = 128, more than a workgroup's LDS, and a tile with fewer molecules would leave MFMA rows
+// empty.  Rows outside the mask are never loaded; a molecule without a masked row reads exactly 0.
+#include <float.h>
+
+#include "common.hpp"
+#include "ggnn_tile.hpp"
+
+namespace {
+
+constexpr int MHID = 64;        // message hidden width (model/mpnn.py:60-62)
+constexpr int RS = MHID + 4;    // row stride of R_c (floats)
+constexpr int SMOL = 16;        // molecules per Set2Vec workgroup: the rows of one MFMA tile
+
+// floats of dynamic LDS: S, M [GR][D + 4], [P|Q] [GR][132], R [GR][68], bits + deg [8][GR], rowbase [GR]
+__host__ __device__ constexpr int mpnn_lds_floats(int D, int GR) {
+  return 2 * GR * (D + 4) + GR * HS + GR * RS + 2 * GMAXC * GR + GR;
+}
+
+template <int D, int RT>
+__global__ __launch_bounds__(GNT) void mpnn_forward_kernel(
+    const float* __restrict__ state0, const int ld0, const float* __restrict__ L, const int64_t stride_b,
+    const int64_t stride_r, const int64_t stride_c, const int64_t stride_ch, const float* __restrict__ W1,
+    const float* __restrict__ b1, const float* __restrict__ W2, const float* __restrict__ b2,
+    const float* __restrict__ Wih, const float* __restrict__ bih, const float* __restrict__ Whh,
+    const float* __restrict__ bhh, const int B, const int N, const int C, const int num_prop, const int avg,
+    float* __restrict__ state_out, const int ldso) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  constexpr int GR = 16 * RT;    // rows per tile
+  constexpr int SS = D + 4;      // row stride of S and M_c
+  constexpr int DQ = D / 4;      // float4 per state row
+  constexpr int DB = D / 16;     // 16-feature blocks of a state row: waves 0 .. DB-1 own one each
+  constexpr int HQ = MHID / 4;   // float4 per row of R_c
+  float* const Sb = smem;
+  float* const Mb = Sb + GR * SS;
+  float* const Hb = Mb + GR * SS;                                       // [row][P_c 0..63 | Q_c 64..127]
+  float* const Rb = Hb + GR * HS;
+  unsigned* const bits = reinterpret_cast<unsigned*>(Rb + GR * RS);     // [c][row]
+  float* const deg = reinterpret_cast<float*>(bits + GMAXC * GR);       // [c][row]
+  int* const rowbase = reinterpret_cast<int*>(deg + GMAXC * GR);        // first row of the row's molecule
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int m = lane & 15, g = lane >> 4;
+  const int mpt = GR / N;                                  // molecules per tile
+  const int64_t mol0 = (int64_t)blockIdx.x * mpt;
+  const int nm = (int)(B - mol0 < mpt ? B - mol0 : mpt);   // molecules of this tile
+  const int rows = nm * N;                                 // live rows; the others stay zero and unread
+
+  // ---- the state, the bit masks and degrees of L, the molecule of every row
+  for (int idx = tid; idx < GR * DQ; idx += GNT) {
+    const int r = idx / DQ, q = idx - r * DQ;
+    f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (r < rows) v = *reinterpret_cast<const f32x4*>(state0 + (mol0 * N + r) * (int64_t)ld0 + 4 * q);
+    *reinterpret_cast<f32x4*>(Sb + r * SS + 4 * q) = v;
+  }
+  for (int idx = tid; idx < GR * C; idx += GNT) {
+    const int r = idx / C, c = idx - r * C;
+    unsigned bm = 0;
+    if (r < rows) {
+      const int ml = r / N, i = r - ml * N;
+      const float* Lr = L + (mol0 + ml) * stride_b + i * stride_r + c * stride_ch;
+      for (int j = 0; j < N; ++j) bm |= (Lr[j * stride_c] != 0.0f ? 1u : 0u) << j;   // NaN != 0: an edge
+    }
+    bits[c * GR + r] = bm;
+    deg[c * GR + r] = (float)__popc(bm);
+  }
+  if (tid < GR) rowbase[tid] = tid < rows ? (tid / N) * N : 0;
+  __syncthreads();
+
+  const bool owner = wave < DB;          // wave-uniform: this wave owns features 16 wave .. 16 wave + 15
+  const int f0 = 16 * wave + 4 * g;      // this lane's four features (owner waves) / columns of [P|Q]
+  const float* const s_frag = Sb + m * SS + 4 * g;
+  const float* const r_frag = Rb + m * RS + 4 * g;
+  const float* const m_frag = Mb + m * SS + 4 * g;
+  // the row of W1_c [64, 2 D] behind this wave's 16 columns of [P|Q]: waves 0 .. 3 the neighbour half
+  // (columns 0 .. D-1 of the rows 16 wave ..), waves 4 .. 7 the own half (columns D .. of the rows 16 (wave - 4) ..)
+  const int hrow = 16 * (wave & 3) + m;
+  const int hoff = wave < 4 ? 0 : D;
+
+  for (int step = 0; step < num_prop; ++step) {
+    // gate accumulators of this wave's feature block: [0] r, [1] z, [2] gi_n
+    f32x4 acc[3][RT];
+#pragma unroll
+    for (int t = 0; t < 3; ++t)
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt) acc[t][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int c = 0; c < C; ++c) {
+      {   // [P_c | Q_c + b1_c]: columns 16 wave ..
+        f32x4 h[1][RT];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) h[0][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        const float* const wp[1] = {W1 + ((int64_t)c * MHID + hrow) * (2 * D) + hoff + 4 * g};
+        tile_gemm<1, DB, RT>(s_frag, SS, wp, h);
+        f32x4 bv = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (wave >= 4) bv = *reinterpret_cast<const f32x4*>(b1 + c * MHID + 16 * (wave - 4) + 4 * g);
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+          *reinterpret_cast<f32x4*>(Hb + (16 * rt + m) * HS + f0) = h[0][rt] + bv;
+      }
+      __syncthreads();
+      // R_c[a] = sum over the set bits b of relu(Q_c[a] + P_c[b]): four hidden columns of one row per task
+      for (int idx = tid; idx < GR * HQ; idx += GNT) {
+        const int r = idx / HQ, q = idx - r * HQ;
+        unsigned bm = bits[c * GR + r];
+        const f32x4 qv = *reinterpret_cast<const f32x4*>(Hb + r * HS + MHID + 4 * q);
+        const float* const src = Hb + rowbase[r] * HS + 4 * q;
+        f32x4 s = {0.0f, 0.0f, 0.0f, 0.0f};
+        while (bm) {
+          const int j = __ffs(bm) - 1;
+          bm &= bm - 1;
+          const f32x4 v = *reinterpret_cast<const f32x4*>(src + j * HS);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) s[e] += fmaxf(qv[e] + v[e], 0.0f);
+        }
+        *reinterpret_cast<f32x4*>(Rb + r * RS + 4 * q) = s;
+      }
+      __syncthreads();
+      if (owner) {   // M_c = R_c W2_c^T + deg_c b2_c [/ (deg_c + EPS)]: features 16 wave ..
+        f32x4 mm[1][RT];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) mm[0][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        const float* const wp[1] = {W2 + ((int64_t)c * D + 16 * wave + m) * MHID + 4 * g};
+        tile_gemm<1, MHID / 16, RT>(r_frag, RS, wp, mm);
+        const f32x4 bv = *reinterpret_cast<const f32x4*>(b2 + c * D + f0);
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) {
+          const float dg = deg[c * GR + 16 * rt + m];
+          f32x4 v = mm[0][rt] + dg * bv;
+          if (avg) v = v / (dg + FLT_EPSILON);   // model/mpnn.py:172-177: the sum, then the division
+          *reinterpret_cast<f32x4*>(Mb + (16 * rt + m) * SS + f0) = v;
+        }
+      }
+      __syncthreads();
+      if (owner) {   // gi += M_c W_ih[:, c D ..]^T: tiles r, z, gi_n
+        const float* const row = Wih + (int64_t)(16 * wave + m) * ((int64_t)C * D) + c * D + 4 * g;
+        const int64_t gate = (int64_t)D * C * D;
+        const float* const wp[3] = {row, row + gate, row + 2 * gate};
+        f32x4 part[3][RT];   // a chain of D terms per channel, then one add: the error of a short sum
+#pragma unroll
+        for (int t = 0; t < 3; ++t)
+#pragma unroll
+          for (int rt = 0; rt < RT; ++rt) part[t][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        tile_gemm<3, DB, RT>(m_frag, SS, wp, part);
+#pragma unroll
+        for (int t = 0; t < 3; ++t)
+#pragma unroll
+          for (int rt = 0; rt < RT; ++rt) acc[t][rt] += part[t][rt];
+      }
+    }
+    // gh = S W_hh^T (the state is still the step's input): r and z join gi, gh_n stays apart.  Every wave
+    // reads ALL columns of S here, so the barrier below stands between these reads and the cell's writes
+    f32x4 gh[3][RT];
+    if (owner) {
+#pragma unroll
+      for (int t = 0; t < 3; ++t)
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) gh[t][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      const float* const row = Whh + (int64_t)(16 * wave + m) * D + 4 * g;
+      const float* const wp[3] = {row, row + D * D, row + 2 * D * D};
+      tile_gemm<3, DB, RT>(s_frag, SS, wp, gh);
+    }
+    __syncthreads();
+    if (owner) {   // the GRU cell on this wave's features
+      const f32x4 b_r = *reinterpret_cast<const f32x4*>(bih + f0) + *reinterpret_cast<const f32x4*>(bhh + f0);
+      const f32x4 b_z = *reinterpret_cast<const f32x4*>(bih + D + f0) + *reinterpret_cast<const f32x4*>(bhh + D + f0);
+      const f32x4 b_in = *reinterpret_cast<const f32x4*>(bih + 2 * D + f0);
+      const f32x4 b_hn = *reinterpret_cast<const f32x4*>(bhh + 2 * D + f0);
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt) {
+        float* const sp = Sb + (16 * rt + m) * SS + f0;
+        const f32x4 so = *reinterpret_cast<const f32x4*>(sp);
+        f32x4 sn;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float r = sigmoidf_((acc[0][rt][e] + gh[0][rt][e]) + b_r[e]);
+          const float z = sigmoidf_((acc[1][rt][e] + gh[1][rt][e]) + b_z[e]);
+          const float n = tanhf((acc[2][rt][e] + b_in[e]) + r * (gh[2][rt][e] + b_hn[e]));
+          sn[e] = (1.0f - z) * n + z * so[e];
+        }
+        *reinterpret_cast<f32x4*>(sp) = sn;
+      }
+    }
+    __syncthreads();
+  }
+
+  // ---- the final state
+  for (int idx = tid; idx < rows * DQ; idx += GNT) {
+    const int r = idx / DQ, q = idx - r * DQ;
+    *reinterpret_cast<f32x4*>(state_out + (mol0 * N + r) * (int64_t)ldso + 4 * q) =
+        *reinterpret_cast<const f32x4*>(Sb + r * SS + 4 * q);
+  }
+}
+
+template <int D, int RT>
+int launch_mpnn(const float* state0, int ld0, const float* L, int64_t sb, int64_t sr, int64_t sc, int64_t sch,
+                const float* W1, const float* b1, const float* W2, const float* b2, const float* Wih,
+                const float* bih, const float* Whh, const float* bhh, int B, int N, int C, int num_prop, int avg,
+                float* state_out, int ldso, int grid, hipStream_t s) {
+  const size_t lds = sizeof(float) * (size_t)mpnn_lds_floats(D, 16 * RT);
+  auto kfn = mpnn_forward_kernel<D, RT>;
+  LNZ_DYNAMIC_LDS(kfn, lds, "mpnn.hip");
+  hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(GNT), lds, s, state0, ld0, L, sb, sr, sc, sch, W1, b1, W2, b2,
+                     Wih, bih, Whh, bhh, B, N, C, num_prop, avg, state_out, ldso);
+  return lnz::check_launch("lnz_mpnn_forward");
+}
+
+// ------------------------------------------------------------------------------------------ Set2Vec
+template <int D>
+__global__ __launch_bounds__(GNT) void set2vec_readout_kernel(
+    const float* __restrict__ X, const int ld, const unsigned char* __restrict__ mask,
+    const float* __restrict__ Wg, const float* __restrict__ bg, const float* __restrict__ W1T,
+    const float* __restrict__ w2, const float* __restrict__ Wout, const float* __restrict__ bout, const int B,
+    const int N, const int P, const int num_step, const int mpw, float* __restrict__ score) {
+  constexpr int QS = 2 * D + 4;   // row stride of q* = [q | read]
+  constexpr int US = D + 4;       // row stride of q W_1
+  constexpr int DQ = D / 4;
+  constexpr int DB = D / 16;
+  __shared__ __attribute__((aligned(16))) float qs[SMOL * QS];
+  __shared__ __attribute__((aligned(16))) float ub[SMOL * US];
+  __shared__ float en[SMOL * GMAXN];    // energies, then softmax weights, [molecule][row]
+  __shared__ unsigned mbits[SMOL];      // bit j: row j of the molecule is in the set
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int m = lane & 15, g = lane >> 4;
+  const int64_t mol0 = (int64_t)blockIdx.x * mpw;
+  const int nm = (int)(B - mol0 < mpw ? B - mol0 : mpw);   // molecules of this workgroup: rows 0 .. nm-1 of the tile
+
+  for (int idx = tid; idx < SMOL * QS; idx += GNT) qs[idx] = 0.0f;
+  if (tid < SMOL) {
+    unsigned bm = 0;
+    if (tid < nm) {
+      if (mask == nullptr) {
+        bm = N >= 32 ? 0xffffffffu : (1u << N) - 1u;
+      } else {
+        for (int j = 0; j < N; ++j) bm |= (mask[(mol0 + tid) * N + j] != 0 ? 1u : 0u) << j;
+      }
+    }
+    mbits[tid] = bm;
+  }
+  __syncthreads();
+
+  const bool owner = wave < DB;
+  const int f0 = 16 * wave + 4 * g;      // this lane's four features of molecule m (owner waves)
+  const float* const q_frag = qs + m * QS + 4 * g;
+  f32x4 mem = {0.0f, 0.0f, 0.0f, 0.0f};
+  const int grp = tid >> 4, gl = tid & 15;   // the sixteen-lane group of the energies and the lane in it
+
+  for (int step = 0; step < num_step; ++step) {
+    // the four gates of this wave's features: f, i, o, memory (model/set2set.py:49-55)
+    f32x4 ga[4][1];
+    if (owner) {
+#pragma unroll
+      for (int t = 0; t < 4; ++t) ga[t][0] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      const float* const row = Wg + (int64_t)(16 * wave + m) * (2 * D) + 4 * g;
+      const float* const wp[4] = {row, row + 2 * D * D, row + 4 * D * D, row + 6 * D * D};
+      tile_gemm<4, 2 * DB, 1>(q_frag, QS, wp, ga);
+    }
+    __syncthreads();   // every wave has read all of q*
+    if (owner) {
+      const f32x4 b_f = *reinterpret_cast<const f32x4*>(bg + f0);
+      const f32x4 b_i = *reinterpret_cast<const f32x4*>(bg + D + f0);
+      const f32x4 b_o = *reinterpret_cast<const f32x4*>(bg + 2 * D + f0);
+      const f32x4 b_m = *reinterpret_cast<const f32x4*>(bg + 3 * D + f0);
+      f32x4 qn;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float ft = sigmoidf_(ga[0][0][e] + b_f[e]);
+        const float it = sigmoidf_(ga[1][0][e] + b_i[e]);
+        const float ot = sigmoidf_(ga[2][0][e] + b_o[e]);
+        const float ct = tanhf(ga[3][0][e] + b_m[e]);
+        mem[e] = ft * mem[e] + it * ct;
+        qn[e] = ot * tanhf(mem[e]);
+      }
+      *reinterpret_cast<f32x4*>(qs + m * QS + f0) = qn;
+    }
+    __syncthreads();
+    if (owner) {   // u = q W_1: features 16 wave ..
+      f32x4 u[1][1] = {{f32x4{0.0f, 0.0f, 0.0f, 0.0f}}};
+      const float* const wp[1] = {W1T + (int64_t)(16 * wave + m) * D + 4 * g};
+      tile_gemm<1, DB, 1>(q_frag, QS, wp, u);
+      *reinterpret_cast<f32x4*>(ub + m * US + f0) = u[0][0];
+    }
+    __syncthreads();
+    // e_j = sum_f tanh(u_f + X_jf) W_2[f]: sixteen lanes per row of the set, the others are not loaded
+    for (int task = grp; task < nm * N; task += GNT / 16) {
+      const int ml = task / N, j = task - ml * N;
+      if ((mbits[ml] >> j) & 1u) {
+        const float* const xr = X + ((mol0 + ml) * N + j) * (int64_t)ld;
+        float s = 0.0f;
+        for (int q = gl; q < DQ; q += 16) {
+          const f32x4 xv = *reinterpret_cast<const f32x4*>(xr + 4 * q);
+          const f32x4 uv = *reinterpret_cast<const f32x4*>(ub + ml * US + 4 * q);
+          const f32x4 wv = *reinterpret_cast<const f32x4*>(w2 + 4 * q);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) s = fmaf(tanhf(uv[e] + xv[e]), wv[e], s);
+        }
+        s += __shfl_xor(s, 8, 16);
+        s += __shfl_xor(s, 4, 16);
+        s += __shfl_xor(s, 2, 16);
+        s += __shfl_xor(s, 1, 16);
+        if (gl == 0) en[ml * GMAXN + j] = s;
+      }
+    }
+    __syncthreads();
+    if (tid < nm) {   // softmax over the set, max-subtracted; an empty set has no weights
+      const unsigned bm0 = mbits[tid];
+      float* const e = en + tid * GMAXN;
+      float mx = -FLT_MAX, sum = 0.0f;
+      for (unsigned bm = bm0; bm; bm &= bm - 1) mx = fmaxf(mx, e[__ffs(bm) - 1]);
+      for (unsigned bm = bm0; bm; bm &= bm - 1) {
+        const int j = __ffs(bm) - 1;
+        const float p = expf(e[j] - mx);
+        e[j] = p;
+        sum += p;
+      }
+      for (unsigned bm = bm0; bm; bm &= bm - 1) e[__ffs(bm) - 1] /= sum;
+    }
+    __syncthreads();
+    // read = sum_j w_j X_j over the set, j ascending: four features of one molecule per task
+    for (int idx = tid; idx < nm * DQ; idx += GNT) {
+      const int ml = idx / DQ, q = idx - ml * DQ;
+      const float* const xm = X + (mol0 + ml) * N * (int64_t)ld + 4 * q;
+      f32x4 s = {0.0f, 0.0f, 0.0f, 0.0f};
+      for (unsigned bm = mbits[ml]; bm; bm &= bm - 1) {
+        const int j = __ffs(bm) - 1;
+        const float wj = en[ml * GMAXN + j];
+        const f32x4 xv = *reinterpret_cast<const f32x4*>(xm + j * (int64_t)ld);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s[e] = fmaf(wj, xv[e], s[e]);
+      }
+      *reinterpret_cast<f32x4*>(qs + ml * QS + D + 4 * q) = s;
+    }
+    __syncthreads();
+  }
+
+  // ---- output_func: score = W_out q* + b_out, k ascending
+  for (int idx = tid; idx < nm * P; idx += GNT) {
+    const int ml = idx / P, p = idx - ml * P;
+    const float* const w = Wout + (int64_t)p * (2 * D);
+    float a = 0.0f;
+    for (int k = 0; k < 2 * D; ++k) a = fmaf(qs[ml * QS + k], w[k], a);
+    score[(mol0 + ml) * P + p] = a + bout[p];
+  }
+}
+
+template <int D>
+int launch_set2vec(const float* X, int ld, const uint8_t* mask, const float* Wg, const float* bg, const float* W1T,
+                   const float* w2, const float* Wout, const float* bout, int B, int N, int P, int num_step, int mpw,
+                   float* score, hipStream_t s) {
+  const int64_t grid = ((int64_t)B + mpw - 1) / mpw;
+  hipLaunchKernelGGL(set2vec_readout_kernel<D>, dim3((unsigned)grid), dim3(GNT), 0, s, X, ld, mask, Wg, bg, W1T, w2,
+                     Wout, bout, B, N, P, num_step, mpw, score);
+  return lnz::check_launch("lnz_set2vec_readout");
+}
+
+int device_cus() {
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
+    (void)hipGetLastError();
+    cus = 256;
+  }
+  return cus;
+}
+
+}  // namespace
+
+extern "C" int lnz_mpnn_forward(const float* state0, int ld0, const float* L, int64_t stride_b, int64_t stride_r,
+                                int64_t stride_c, int64_t stride_ch, const float* W1, const float* b1,
+                                const float* W2, const float* b2, const float* Wih, const float* bih,
+                                const float* Whh, const float* bhh, int B, int N, int C, int D, int num_prop, int avg,
+                                float* state_out, int ldso, int tile_rows, lnz_stream_t stream) {
+  const char* const who = "lnz_mpnn_forward";
+  LNZ_REQUIRE(state0 && L && W1 && b1 && W2 && b2 && Wih && bih && Whh && bhh && state_out, LNZ_EINVAL,
+              "%s: null pointer", who);
+  LNZ_REQUIRE(B > 0 && N > 0, LNZ_EINVAL, "%s: B = %d, N = %d must be positive", who, B, N);
+  LNZ_REQUIRE(N <= GMAXN && C >= 1 && C <= GMAXC && D >= 32 && D <= GMAXD && D % 32 == 0 && num_prop >= 0,
+              LNZ_ENOTSUP,
+              "%s: N = %d, C = %d, D = %d, num_prop = %d outside 1 <= N <= 32, 1 <= C <= 8, "
+              "D a multiple of 32 and <= 128, num_prop >= 0", who, N, C, D, num_prop);
+  LNZ_REQUIRE(ld0 >= D && ldso >= D, LNZ_EINVAL, "%s: ld0 = %d, ldso = %d below the width %d", who, ld0, ldso, D);
+  LNZ_REQUIRE(stride_b >= 0 && stride_r >= 0 && stride_c >= 0 && stride_ch >= 0, LNZ_EINVAL,
+              "%s: negative stride of L", who);
+  LNZ_REQUIRE(ld0 % 4 == 0 && ldso % 4 == 0 && aligned16(state0) && aligned16(state_out) && aligned16(W1) &&
+                  aligned16(b1) && aligned16(W2) && aligned16(b2) && aligned16(Wih) && aligned16(bih) &&
+                  aligned16(Whh) && aligned16(bhh),
+              LNZ_ENOTSUP, "%s: the rows of state0, state_out and of the weights must be 16-byte "
+              "aligned (ld0 = %d, ldso = %d)", who, ld0, ldso);
+  {
+    const uint64_t rows = (uint64_t)B * N;
+    const uint64_t n0 = ((rows - 1) * (uint64_t)ld0 + D) * sizeof(float);
+    const uint64_t no = ((rows - 1) * (uint64_t)ldso + D) * sizeof(float);
+    LNZ_REQUIRE(!overlap(state_out, no, state0, n0), LNZ_EINVAL, "%s: state_out must not alias state0", who);
+  }
+  LNZ_REQUIRE(tile_rows == 0 || tile_rows == 32 || tile_rows == 64, LNZ_EINVAL,
+              "%s: tile_rows = %d is not 0 (chosen by the batch), 32 or 64", who, tile_rows);
+  int rows_per_tile = tile_rows;
+  if (rows_per_tile == 0) {
+    // 32-row tiles while they all fit in one round of the compute units, 64-row tiles beyond
+    const int mpt32 = 32 / N;
+    rows_per_tile = ((int64_t)B + mpt32 - 1) / mpt32 <= device_cus() ? 32 : 64;
+  }
+  const int mpt = rows_per_tile / N;
+  const int64_t grid = ((int64_t)B + mpt - 1) / mpt;
+  hipStream_t s = (hipStream_t)stream;
+  lnz::note_kernel("mpnn_forward_kernel<%d, %d>", D, rows_per_tile / 16);
+#define LNZ_MPNN_LAUNCH_(DD, RTT)                                                                                  \
+  launch_mpnn<DD, RTT>(state0, ld0, L, stride_b, stride_r, stride_c, stride_ch, W1, b1, W2, b2, Wih, bih, Whh, bhh, \
+                       B, N, C, num_prop, avg ? 1 : 0, state_out, ldso, (int)grid, s)
+#define LNZ_MPNN_LAUNCH(DD) return rows_per_tile == 32 ? LNZ_MPNN_LAUNCH_(DD, 2) : LNZ_MPNN_LAUNCH_(DD, 4)
+  switch (D) {
+    case 32: LNZ_MPNN_LAUNCH(32);
+    case 64: LNZ_MPNN_LAUNCH(64);
+    case 96: LNZ_MPNN_LAUNCH(96);
+    default: LNZ_MPNN_LAUNCH(128);
+  }
+#undef LNZ_MPNN_LAUNCH
+#undef LNZ_MPNN_LAUNCH_
+}
+
+extern "C" int lnz_set2vec_readout(const float* X, int ld, const uint8_t* mask, const float* Wg, const float* bg,
+                                   const float* W1T, const float* w2, const float* Wout, const float* bout, int B,
+                                   int N, int D, int P, int num_step, float* score, int mols_per_group,
+                                   lnz_stream_t stream) {
+  const char* const who = "lnz_set2vec_readout";
+  LNZ_REQUIRE(X && Wg && bg && W1T && w2 && Wout && bout && score, LNZ_EINVAL, "%s: null pointer", who);
+  LNZ_REQUIRE(B > 0 && N > 0, LNZ_EINVAL, "%s: B = %d, N = %d must be positive", who, B, N);
+  LNZ_REQUIRE(N <= GMAXN && D >= 32 && D <= GMAXD && D % 32 == 0 && P >= 1 && P <= GMAXP && num_step >= 0,
+              LNZ_ENOTSUP,
+              "%s: N = %d, D = %d, P = %d, num_step = %d outside 1 <= N <= 32, D a multiple of 32 and <= 128, "
+              "1 <= P <= 16, num_step >= 0", who, N, D, P, num_step);
+  LNZ_REQUIRE(ld >= D, LNZ_EINVAL, "%s: ld = %d below the width %d", who, ld, D);
+  LNZ_REQUIRE(ld % 4 == 0 && aligned16(X) && aligned16(Wg) && aligned16(bg) && aligned16(W1T) && aligned16(w2),
+              LNZ_ENOTSUP, "%s: the rows of X and of the weights must be 16-byte aligned (ld = %d)", who, ld);
+  {
+    const uint64_t rows = (uint64_t)B * N;
+    const uint64_t nx = ((rows - 1) * (uint64_t)ld + D) * sizeof(float);
+    LNZ_REQUIRE(!overlap(score, (uint64_t)B * P * sizeof(float), X, nx), LNZ_EINVAL, "%s: score must not alias X", who);
+  }
+  LNZ_REQUIRE(mols_per_group >= 0 && mols_per_group <= SMOL, LNZ_EINVAL,
+              "%s: mols_per_group = %d is not 0 (chosen by the batch) or 1 .. 16", who, mols_per_group);
+  // molecules per workgroup: as few as spread the batch over the compute units, at most the 16 rows of a tile
+  int mpw = mols_per_group;
+  if (mpw == 0) {
+    const int cus = device_cus();
+    mpw = (int)(((int64_t)B + cus - 1) / cus);
+    mpw = mpw < 1 ? 1 : mpw > SMOL ? SMOL : mpw;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  lnz::note_kernel("set2vec_readout_kernel<%d> x %d", D, mpw);
+  switch (D) {
+    case 32: return launch_set2vec<32>(X, ld, mask, Wg, bg, W1T, w2, Wout, bout, B, N, P, num_step, mpw, score, s);
+    case 64: return launch_set2vec<64>(X, ld, mask, Wg, bg, W1T, w2, Wout, bout, B, N, P, num_step, mpw, score, s);
+    case 96: return launch_set2vec<96>(X, ld, mask, Wg, bg, W1T, w2, Wout, bout, B, N, P, num_step, mpw, score, s);
+    default: return launch_set2vec<128>(X, ld, mask, Wg, bg, W1T, w2, Wout, bout, B, N, P, num_step, mpw, score, s);
+  }
+}

@@ -12,6 +12,8 @@ Reference interfaces replaced (paths relative to the reference repo):
   gat_readout         model/gat.py:177-196
   gat_attention_backward / gat_readout_backward / gat_layer_backward   the same lines under loss.backward()
   ggnn_forward        model/ggnn.py:143-197 (all num_prop steps and the readout)
+  mpnn_forward        model/mpnn.py:136-196 (all num_prop steps, msg_func 'MLP')
+  set2vec_readout     model/set2set.py:79-100 and output_func (model/mpnn.py:199-207)
 """
 import torch
 
@@ -2853,3 +2855,78 @@ def ggnn_readout_backward(Slast, mask, Wo, bo, wg, bg, dscore, dSlast=None):
     _abi().ggnn_readout_backward(Slast, ld, mask, Wo, bo, wg, bg, dscore, B, N, D, P, ws, dSlast, ldg, dWo, dbo,
                                  dwg, dbg)
   return dSlast, dWo, dbo, dwg, dbg
+
+
+# ---------------------------------------------------------------------------------------- MPNN
+MPNN_MAX_NODES, MPNN_MAX_CHANNELS, MPNN_MAX_WIDTH, MPNN_WIDTH_STEP, MPNN_MAX_OUTPUTS = 32, 8, 128, 32, 16
+MPNN_MSG_HIDDEN = 64   # model/mpnn.py:60-62
+
+
+def mpnn_forward(state0, L, W1, b1, W2, b2, Wih, bih, Whh, bhh, num_prop, avg=True, state_out=None, tile_rows=0):
+  """lnz_mpnn_forward (model/mpnn.py:136-196, msg_func 'MLP'): every propagation step in one launch.
+  state0 [B, N, D] = input_func(node_embedding(node_feat)) (a row stride beyond D is fine), L [B, N, N, C]
+  float32 in any strides (read as L != 0, never written), W1 [C, 64, 2 D] (columns 0 .. D-1 act on the
+  neighbour, D .. 2 D-1 on the row itself), b1 [C, 64], W2 [C, D, 64], b2 [C, D] (edge_func), Wih [3 D, C D],
+  bih [3 D], Whh [3 D, D], bhh [3 D] (the GRU cell) -> the final state [B, N, D] (in `state_out` when given).
+  tile_rows: 0 = chosen by the batch, 32 or 64 rows of state per workgroup (a row's bits do not depend on it)."""
+  who = 'mpnn_forward'
+  _need_cuda(state0, L, W1, b1, W2, b2, Wih, bih, Whh, bhh, state_out)
+  if state0.dim() != 3 or L.dim() != 4 or L.dtype != torch.float32:
+    raise LnzError(_lib.LNZ_EINVAL, '%s: state0 [B, N, D] and a float32 L [B, N, N, C] expected' % who)
+  B, N, D = state0.shape
+  C = L.shape[3]
+  if tuple(L.shape[:3]) != (B, N, N):
+    raise LnzError(_lib.LNZ_EINVAL, '%s: state0 %s and L %s do not fit' % (who, tuple(state0.shape), tuple(L.shape)))
+  ld0 = _gat_rows(state0, who)
+  W1, b1, W2, b2 = _f32c(W1), _f32c(b1), _f32c(W2), _f32c(b2)
+  Wih, bih, Whh, bhh = _f32c(Wih), _f32c(bih).reshape(-1), _f32c(Whh), _f32c(bhh).reshape(-1)
+  Hd = MPNN_MSG_HIDDEN
+  for t, shape in ((W1, (C, Hd, 2 * D)), (b1, (C, Hd)), (W2, (C, D, Hd)), (b2, (C, D)), (Wih, (3 * D, C * D)),
+                   (bih, (3 * D,)), (Whh, (3 * D, D)), (bhh, (3 * D,))):
+    if tuple(t.shape) != shape:
+      raise LnzError(_lib.LNZ_EINVAL, '%s: operand of shape %s where %s is expected' % (who, tuple(t.shape), shape))
+  if state_out is None:
+    state_out = torch.empty((B, N, D), dtype=torch.float32, device=state0.device)
+  if tuple(state_out.shape) != (B, N, D):
+    raise LnzError(_lib.LNZ_EINVAL, '%s: state_out %s, expected %s' % (who, tuple(state_out.shape), (B, N, D)))
+  ldso = _gat_rows(state_out, who)
+  with torch.cuda.device(state0.device):
+    _abi().mpnn_forward(state0, ld0, L, L.stride(0), L.stride(1), L.stride(2), L.stride(3), W1, b1, W2, b2, Wih, bih,
+                        Whh, bhh, B, N, C, D, int(num_prop), int(bool(avg)), state_out, ldso, int(tile_rows))
+  return state_out
+
+
+def set2vec_pack(gates, W_1):
+  """The packed operands of set2vec_readout, once per weight version: gates = ((W_f, b_f), (W_i, b_i), (W_o,
+  b_o), (W_m, b_m)), each [D, 2 D] / [D] -> (Wg [4, D, 2 D], bg [4, D], W1T [D, D] = W_1 transposed)."""
+  Wg = torch.stack([_f32c(w) for w, _ in gates]).contiguous()
+  bg = torch.stack([_f32c(b) for _, b in gates]).contiguous()
+  return Wg, bg, _f32c(W_1).t().contiguous()
+
+
+def set2vec_readout(X, mask, Wg, bg, W1T, W_2, Wout, bout, num_step, mols_per_group=0):
+  """lnz_set2vec_readout (model/set2set.py:79-100 per molecule, then output_func): X [B, N, D] (a row stride
+  beyond D is fine), mask [B, N] or None (all N rows; rows outside the mask are never loaded), (Wg [4, D, 2 D],
+  bg [4, D], W1T [D, D]) of set2vec_pack, W_2 [D, 1] or [D], Wout [P, 2 D], bout [P] -> score [B, P].
+  mols_per_group: 0 = chosen by the batch, 1 .. 16 molecules per workgroup (a molecule's bits do not depend on it)."""
+  who = 'set2vec_readout'
+  _need_cuda(X, mask, Wg, bg, W1T, W_2, Wout, bout)
+  if X.dim() != 3:
+    raise LnzError(_lib.LNZ_EINVAL, '%s: X [B, N, D] expected' % who)
+  B, N, D = X.shape
+  ld = _gat_rows(X, who)
+  Wg, bg, W1T, w2 = _f32c(Wg), _f32c(bg), _f32c(W1T), _f32c(W_2).reshape(-1)
+  Wout, bout = _f32c(Wout), _f32c(bout).reshape(-1)
+  P = Wout.shape[0]
+  for t, shape in ((Wg, (4, D, 2 * D)), (bg, (4, D)), (W1T, (D, D)), (w2, (D,)), (Wout, (P, 2 * D)), (bout, (P,))):
+    if tuple(t.shape) != shape:
+      raise LnzError(_lib.LNZ_EINVAL, '%s: operand of shape %s where %s is expected' % (who, tuple(t.shape), shape))
+  if mask is not None:
+    if tuple(mask.shape) != (B, N):
+      raise LnzError(_lib.LNZ_EINVAL, '%s: mask %s, expected %s' % (who, tuple(mask.shape), (B, N)))
+    mask = (mask != 0).to(torch.uint8).contiguous()
+  score = torch.empty((B, P), dtype=torch.float32, device=X.device)
+  with torch.cuda.device(X.device):
+    _abi().set2vec_readout(X, ld, mask, Wg, bg, W1T, w2, Wout, bout, B, N, D, P, int(num_step), score,
+                           int(mols_per_group))
+  return score

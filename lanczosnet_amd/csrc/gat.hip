@@ -23,14 +23,9 @@
 // (ascending) of the last layer's output, y = (Wo x + bo) * sigmoid(wg x + bg), score = mean of y over
 // the masked rows (all N without a mask; no masked row: 0 / 0 = NaN like the reference's empty mean).
 #include "common.hpp"
+#include "gat_tile.hpp"
 
 namespace {
-
-constexpr int GN = 32;        // nodes per molecule at most
-constexpr int GD = 32;        // head width at most
-constexpr int GW = 4;         // waves per workgroup
-constexpr int LS = GN + 1;    // row stride of the L and attention blocks (floats): column reads conflict-free
-constexpr int WS = GD + 4;    // row stride of a staged Wh block: 16-byte rows for ds_read_b128
 
 __global__ __launch_bounds__(64 * GW) void gat_attention_kernel(
     const float* __restrict__ Wh, int ldw, const float* __restrict__ L, int64_t stride_b, int64_t stride_r,
@@ -145,8 +140,6 @@ __global__ __launch_bounds__(64 * GW) void gat_attention_kernel(
   }
 }
 
-constexpr int RP = 16;   // outputs at most
-
 __global__ __launch_bounds__(256) void gat_readout_kernel(
     const float* __restrict__ Hlast, int ld, const unsigned char* __restrict__ mask,
     const float* __restrict__ Wo, const float* __restrict__ bo, const float* __restrict__ wg,
@@ -185,8 +178,6 @@ __global__ __launch_bounds__(256) void gat_readout_kernel(
     score[b * P + threadIdx.x] = s / cnt;   // (no masked row: 0 / 0, the reference's mean of nothing)
   }
 }
-
-inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 }  // namespace
 

@@ -32,15 +32,10 @@
 //     dHlast[i, every block] = dx / CH                                            exactly 0 outside the mask
 // and the molecule's partials [dWo | dbo | dwg | dbg] for the same fixed-order reduction.
 #include "common.hpp"
+#include "gat_tile.hpp"
+#include "partial_sum.hpp"
 
 namespace {
-
-constexpr int GN = 32;        // nodes per molecule at most           (the constants of csrc/gat.hip)
-constexpr int GD = 32;        // head width at most
-constexpr int GW = 4;         // waves per workgroup
-constexpr int LS = GN + 1;    // row stride of the L and attention blocks (floats)
-constexpr int WS = GD + 4;    // row stride of a staged Wh / dO block: 16-byte rows
-constexpr int RP = 16;        // outputs at most
 
 __global__ __launch_bounds__(64 * GW) void gat_attention_backward_kernel(
     const float* __restrict__ Wh, int ldw, const float* __restrict__ L, int64_t stride_b, int64_t stride_r,
@@ -258,37 +253,6 @@ __global__ __launch_bounds__(64 * GW) void gat_attention_backward_kernel(
   }
 }
 
-// out[col] = the sum over the B rows of ws [B][M], col < M, cut into up to five consecutive segments with
-// an output pointer each.  Fixed order: four contiguous quarters of the rows, each ascending, then
-// ((q0 + q1) + q2) + q3.
-struct Segments {
-  float* p[5];
-  int n[5];
-};
-
-__global__ __launch_bounds__(256) void gat_partial_sum_kernel(const float* __restrict__ ws, int B, int64_t M,
-                                                              Segments seg) {
-  __shared__ float part[4][64];
-  const int x = threadIdx.x & 63, s = threadIdx.x >> 6;
-  const int64_t col = (int64_t)blockIdx.x * 64 + x;
-  const int q = (B + 3) / 4;
-  const int b0 = s * q, b1 = min(B, b0 + q);
-  float acc = 0.0f;
-  if (col < M)
-    for (int b = b0; b < b1; ++b) acc += ws[(int64_t)b * M + col];
-  part[s][x] = acc;
-  __syncthreads();
-  if (s == 0 && col < M) {
-    const float v = ((part[0][x] + part[1][x]) + part[2][x]) + part[3][x];
-    int64_t off = col;
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      if (off >= 0 && off < seg.n[k]) seg.p[k][off] = v;
-      off -= seg.n[k];
-    }
-  }
-}
-
 __global__ __launch_bounds__(256) void gat_readout_backward_kernel(
     const float* __restrict__ Hlast, int ld, const unsigned char* __restrict__ mask,
     const float* __restrict__ Wo, const float* __restrict__ bo, const float* __restrict__ wg,
@@ -378,15 +342,6 @@ __global__ __launch_bounds__(256) void gat_readout_backward_kernel(
   }
 }
 
-inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
-// [p, p + ((rows - 1) ld + width) floats)
-inline bool overlap(const void* p, const void* q, uint64_t rows, int ldp, int ldq, int width) {
-  const uintptr_t p0 = (uintptr_t)p, p1 = p0 + ((rows - 1) * (uint64_t)ldp + width) * sizeof(float);
-  const uintptr_t q0 = (uintptr_t)q, q1 = q0 + ((rows - 1) * (uint64_t)ldq + width) * sizeof(float);
-  return !(p1 <= q0 || q1 <= p0);
-}
-
 }  // namespace
 
 extern "C" int64_t lnz_gat_attention_backward_workspace_floats(int B, int C, int H, int Dh) {
@@ -437,9 +392,7 @@ extern "C" int lnz_gat_attention_backward(const float* Wh, int ldw, const float*
   const int CH = C * H;
   const int64_t M = (int64_t)CH * (3 * Dh + 2);
   Segments seg = {{da1, da2, dbias, db1, db2}, {CH * Dh, CH * Dh, CH * Dh, CH, CH}};
-  hipLaunchKernelGGL(gat_partial_sum_kernel, dim3((unsigned)((M + 63) / 64)), dim3(256), 0, (hipStream_t)stream,
-                     workspace, B, M, seg);
-  return lnz::check_launch("lnz_gat_attention_backward (sum of the partials)");
+  return sum_partials(workspace, B, M, seg, (hipStream_t)stream, "lnz_gat_attention_backward (sum of the partials)");
 }
 
 extern "C" int64_t lnz_gat_readout_backward_workspace_floats(int B, int Dh, int P) {
@@ -470,7 +423,5 @@ extern "C" int lnz_gat_readout_backward(const float* Hlast, int ld, const uint8_
   if (rc != LNZ_OK) return rc;
   const int M = P * Dh + P + Dh + 1;
   Segments seg = {{dWo, dbo, dwg, dbg, nullptr}, {P * Dh, P, Dh, 1, 0}};
-  hipLaunchKernelGGL(gat_partial_sum_kernel, dim3((unsigned)((M + 63) / 64)), dim3(256), 0, (hipStream_t)stream,
-                     workspace, B, (int64_t)M, seg);
-  return lnz::check_launch("lnz_gat_readout_backward (sum of the partials)");
+  return sum_partials(workspace, B, M, seg, (hipStream_t)stream, "lnz_gat_readout_backward (sum of the partials)");
 }

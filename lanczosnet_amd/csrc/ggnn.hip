@@ -33,17 +33,17 @@
 // whole.  gh = S W_hh^T follows the channel loop, in front of the GRU cell.  The aggregate Â_c M_c
 // runs on the VALU over the set bits only, j ascending.  Three barriers per channel, two per step.
 // LDS at D = 128, R = 64: S, M_c, A_c 64 x 132 floats each + H_c 64 x 132 + masks = 139,520 B (the
-// per-device dynamic-LDS grant of common.hpp), one workgroup per CU; R = 32: 69,760 B.  254 VGPRs at
-// R = 64, no scratch.  No atomics, no cross-workgroup traffic, every sum in a fixed order:
-// bit-reproducible.  sigmoid = 1 / (1 + expf(-x)) and tanhf stay finite and correct at |x| >= 100.
+// per-device dynamic-LDS grant of common.hpp), one workgroup per CU; R = 32: 69,760 B.  At most 254
+// VGPRs at R = 64, no scratch (the table: DESIGN.md §4.12).  No atomics, no cross-workgroup traffic, every
+// sum in a fixed order: bit-reproducible.  sigmoid = 1 / (1 + expf(-x)) and tanhf stay finite and correct at |x| >= 100.
 //
 // Tile height: a tile's 15 steps take the same time whatever the batch, so R = 64 (half the weight
 // reads per row) serves batches that fill the chip and R = 32 batches whose 32-row tiles all fit in one
 // round of the compute units (tile_rows = 0 chooses; a row's arithmetic and bits are the same in
-// both).  R = 128 (192 accumulator registers per lane at 256 threads) and the folded form F_c =
+// both).  The prologue, the message block, the gates, the cell and the state store are ggnn_tile.hpp's,
+// shared to the letter with ggnn_grad.hip and mpnn.hip; this file keeps the step loop and the readout.
+// R = 128 (192 accumulator registers per lane at 256 threads) and the folded form F_c =
 // W_ih[:, c] W2_c were not built.  Measurements: DESIGN.md §4.12.
-#include <float.h>
-
 #include "common.hpp"
 #include "ggnn_tile.hpp"
 
@@ -68,7 +68,6 @@ __global__ __launch_bounds__(GNT) void ggnn_forward_kernel(
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int GR = 16 * RT;    // rows per tile
   constexpr int SS = D + 4;      // row stride of S, M_c, A_c
-  constexpr int DQ = D / 4;      // float4 per state row
   constexpr int DB = D / 16;     // 16-feature blocks of a state row: waves 0 .. DB-1 own one each
   float* const Sb = smem;
   float* const Mb = Sb + GR * SS;
@@ -81,165 +80,49 @@ __global__ __launch_bounds__(GNT) void ggnn_forward_kernel(
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int m = lane & 15, g = lane >> 4;
-  const int mpt = GR / N;                                  // molecules per tile
-  const int64_t mol0 = (int64_t)blockIdx.x * mpt;
-  const int nm = (int)(B - mol0 < mpt ? B - mol0 : mpt);   // molecules of this tile
-  const int rows = nm * N;                                 // live rows; the others stay zero and unread
+  const TileSpan ts = tile_span<RT>(B, N);
+  const int64_t mol0 = ts.mol0, row0 = ts.mol0 * N;   // first molecule and first global row of the tile
+  const int nm = ts.nm, rows = ts.rows;
 
   // ---- the state, the bit masks and denominators of L, the molecule of every row
-  for (int idx = tid; idx < GR * DQ; idx += GNT) {
-    const int r = idx / DQ, q = idx - r * DQ;
-    f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (r < rows) v = *reinterpret_cast<const f32x4*>(state0 + (mol0 * N + r) * (int64_t)ld0 + 4 * q);
-    *reinterpret_cast<f32x4*>(Sb + r * SS + 4 * q) = v;
-  }
-  for (int idx = tid; idx < GR * C; idx += GNT) {
-    const int r = idx / C, c = idx - r * C;
-    unsigned bm = 0;
-    if (r < rows) {
-      const int ml = r / N, i = r - ml * N;
-      const float* Lr = L + (mol0 + ml) * stride_b + i * stride_r + c * stride_ch;
-      for (int j = 0; j < N; ++j) bm |= (Lr[j * stride_c] != 0.0f ? 1u : 0u) << j;   // NaN != 0: an edge
-    }
-    bits[c * GR + r] = bm;
-    // model/ggnn.py:156-157: every entry of the row is 1 / (degree + EPS), in float32
-    inv[c * GR + r] = avg ? 1.0f / ((float)__popc(bm) + FLT_EPSILON) : 1.0f;
-  }
-  if (tid < GR) rowbase[tid] = tid < rows ? (tid / N) * N : 0;
+  load_state_tile<D, RT>(Sb, state0, row0, ld0, rows);
+  load_edge_bits<RT>(bits, L, stride_b, stride_r, stride_c, stride_ch, ts, N, C,
+                     [&](const int at, const int degree) { inv[at] = ggnn_edge_weight(avg, degree); });
+  set_rowbase<RT>(rowbase, N, rows);
   __syncthreads();
 
   const bool owner = wave < DB;          // wave-uniform: this wave owns features 16 wave .. 16 wave + 15
-  const int f0 = 16 * wave + 4 * g;      // this lane's four features (owner waves) / hidden columns
   const float* const s_frag = Sb + m * SS + 4 * g;
-  const float* const h_frag = Hb + m * HS + 4 * g;
   const float* const a_frag = Ab + m * SS + 4 * g;
+  const MessageTile mt = {Sb, Mb, Ab, Hb, bits, inv, rowbase};
 
   // the state trajectory [num_prop + 1][B N][D] (TRAJ: lnz_ggnn_forward_states; `states` is null and unread
   // otherwise): S_t at the start of step t, S_T after the last.  A copy of the LDS rows: the arithmetic does
   // not see it, and the instantiation without it is the kernel lnz_ggnn_forward always launched
   const auto put_state = [&](const int t) {
-    float* const dst = states + ((int64_t)t * B + mol0) * N * D;
-    for (int idx = tid; idx < rows * DQ; idx += GNT) {
-      const int r = idx / DQ, q = idx - r * DQ;
-      *reinterpret_cast<f32x4*>(dst + (int64_t)r * D + 4 * q) = *reinterpret_cast<const f32x4*>(Sb + r * SS + 4 * q);
-    }
+    store_state_tile<D>(states + ((int64_t)t * B + mol0) * N * D, D, Sb, rows);
   };
 
   for (int step = 0; step < num_prop; ++step) {
     if constexpr (TRAJ) put_state(step);
     // gate accumulators of this wave's feature block: [0] r, [1] z, [2] gi_n
     f32x4 acc[3][RT];
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt) acc[t][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    for (int c = 0; c < C; ++c) {
-      {   // H_c = relu(S W1_c^T + b1_c): hidden columns 16 wave ..
-        f32x4 h[1][RT];
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) h[0][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        const float* const wp[1] = {W1 + ((int64_t)c * GHID + 16 * wave + m) * D + 4 * g};
-        tile_gemm<1, DB, RT>(s_frag, SS, wp, h);
-        const f32x4 bv = *reinterpret_cast<const f32x4*>(b1 + c * GHID + f0);
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) {
-          f32x4 v;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = fmaxf(h[0][rt][e] + bv[e], 0.0f);
-          *reinterpret_cast<f32x4*>(Hb + (16 * rt + m) * HS + f0) = v;
-        }
-      }
-      __syncthreads();
-      if (owner) {   // M_c = H_c W2_c^T + b2_c: features 16 wave ..
-        f32x4 mm[1][RT];
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) mm[0][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        const float* const wp[1] = {W2 + ((int64_t)c * D + 16 * wave + m) * GHID + 4 * g};
-        tile_gemm<1, GHID / 16, RT>(h_frag, HS, wp, mm);
-        const f32x4 bv = *reinterpret_cast<const f32x4*>(b2 + c * D + f0);
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
-          *reinterpret_cast<f32x4*>(Mb + (16 * rt + m) * SS + f0) = mm[0][rt] + bv;
-      }
-      __syncthreads();
-      // A_c = Â_c M_c: four features of one row per task, the set bits of the row in ascending j
-      for (int idx = tid; idx < GR * DQ; idx += GNT) {
-        const int r = idx / DQ, q = idx - r * DQ;
-        unsigned bm = bits[c * GR + r];
-        const float wgt = inv[c * GR + r];
-        const float* const src = Mb + rowbase[r] * SS + 4 * q;
-        f32x4 s = {0.0f, 0.0f, 0.0f, 0.0f};
-        while (bm) {
-          const int j = __ffs(bm) - 1;
-          bm &= bm - 1;
-          const f32x4 v = *reinterpret_cast<const f32x4*>(src + j * SS);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) s[e] = fmaf(wgt, v[e], s[e]);
-        }
-        *reinterpret_cast<f32x4*>(Ab + r * SS + 4 * q) = s;
-      }
-      __syncthreads();
-      if (owner) {   // gi += A_c W_ih[:, c D ..]^T: tiles r, z, gi_n
-        const float* const row = Wih + (int64_t)(16 * wave + m) * ((int64_t)C * D) + c * D + 4 * g;
-        const int64_t gate = (int64_t)D * C * D;
-        const float* const wp[3] = {row, row + gate, row + 2 * gate};
-        f32x4 part[3][RT];   // a chain of D terms per channel, then one add: the error of a short sum
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-#pragma unroll
-          for (int rt = 0; rt < RT; ++rt) part[t][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        tile_gemm<3, DB, RT>(a_frag, SS, wp, part);
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-#pragma unroll
-          for (int rt = 0; rt < RT; ++rt) acc[t][rt] += part[t][rt];
-      }
+    zero_tiles(acc);
+    for (int c = 0; c < C; ++c) {   // three barriers per channel
+      ggnn_message<D, RT>(mt, c, W1, b1, W2, b2, wave, m, g, [](int, const f32x4&) {},
+                          [](int, int, const f32x4&) {});
+      if (owner) gate_accumulate<D, RT>(a_frag, Wih, c, C, wave, m, g, acc);
     }
-    // gh = S W_hh^T (the state is still the step's input): r and z join gi, gh_n stays apart.  Every wave
-    // reads ALL columns of S here, so the barrier below stands between these reads and the cell's writes
     f32x4 gh[3][RT];
-    if (owner) {
-#pragma unroll
-      for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) gh[t][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-      const float* const row = Whh + (int64_t)(16 * wave + m) * D + 4 * g;
-      const float* const wp[3] = {row, row + D * D, row + 2 * D * D};
-      tile_gemm<3, DB, RT>(s_frag, SS, wp, gh);
-    }
+    if (owner) hidden_gates<D, RT>(s_frag, Whh, wave, m, g, gh);
     __syncthreads();
-    if (owner) {   // the GRU cell on this wave's features
-      const f32x4 b_r = *reinterpret_cast<const f32x4*>(bih + f0) + *reinterpret_cast<const f32x4*>(bhh + f0);
-      const f32x4 b_z = *reinterpret_cast<const f32x4*>(bih + D + f0) + *reinterpret_cast<const f32x4*>(bhh + D + f0);
-      const f32x4 b_in = *reinterpret_cast<const f32x4*>(bih + 2 * D + f0);
-      const f32x4 b_hn = *reinterpret_cast<const f32x4*>(bhh + 2 * D + f0);
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt) {
-        float* const sp = Sb + (16 * rt + m) * SS + f0;
-        const f32x4 so = *reinterpret_cast<const f32x4*>(sp);
-        f32x4 sn;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float r = sigmoidf_((acc[0][rt][e] + gh[0][rt][e]) + b_r[e]);
-          const float z = sigmoidf_((acc[1][rt][e] + gh[1][rt][e]) + b_z[e]);
-          const float n = tanhf((acc[2][rt][e] + b_in[e]) + r * (gh[2][rt][e] + b_hn[e]));
-          sn[e] = (1.0f - z) * n + z * so[e];
-        }
-        *reinterpret_cast<f32x4*>(sp) = sn;
-      }
-    }
+    if (owner) LNZ_GRU_CELL(D, RT);
     __syncthreads();
   }
 
   // ---- the final state, on request
   if constexpr (TRAJ) put_state(num_prop);
-  if (state_out != nullptr) {
-    for (int idx = tid; idx < rows * DQ; idx += GNT) {
-      const int r = idx / DQ, q = idx - r * DQ;
-      *reinterpret_cast<f32x4*>(state_out + (mol0 * N + r) * (int64_t)ldso + 4 * q) =
-          *reinterpret_cast<const f32x4*>(Sb + r * SS + 4 * q);
-    }
-  }
+  if (state_out != nullptr) store_state_tile<D>(state_out + row0 * (int64_t)ldso, ldso, Sb, rows);
   // ---- readout: slot p < P: Wo[p] s + bo[p]; slot P: sigmoid(wg s + bg); d ascending
   float* const ys = Hb;   // [row][GMAXP + 1]: H_c is dead
   for (int idx = tid; idx < rows * (P + 1); idx += GNT) {
@@ -288,57 +171,27 @@ int forward_impl(const char* who, const float* state0, int ld0, const float* L, 
                  float* states, int tile_rows, lnz_stream_t stream) {
   LNZ_REQUIRE(state0 && L && W1 && b1 && W2 && b2 && Wih && bih && Whh && bhh && Wo && bo && wg && bg && score,
               LNZ_EINVAL, "%s: null pointer", who);
-  LNZ_REQUIRE(B > 0 && N > 0, LNZ_EINVAL, "%s: B = %d, N = %d must be positive", who, B, N);
-  LNZ_REQUIRE(N <= GMAXN && C >= 1 && C <= GMAXC && D >= 32 && D <= GMAXD && D % 32 == 0 && P >= 1 && P <= GMAXP &&
-                  num_prop >= 0,
-              LNZ_ENOTSUP,
-              "%s: N = %d, C = %d, D = %d, P = %d, num_prop = %d outside 1 <= N <= 32, 1 <= C <= 8, "
-              "D a multiple of 32 and <= 128, 1 <= P <= 16, num_prop >= 0", who, N, C, D, P, num_prop);
-  LNZ_REQUIRE(ld0 >= D && (state_out == nullptr || ldso >= D), LNZ_EINVAL,
-              "%s: ld0 = %d, ldso = %d below the width %d", who, ld0, ldso, D);
-  LNZ_REQUIRE(stride_b >= 0 && stride_r >= 0 && stride_c >= 0 && stride_ch >= 0, LNZ_EINVAL,
-              "%s: negative stride of L", who);
-  LNZ_REQUIRE(ld0 % 4 == 0 && (state_out == nullptr || ldso % 4 == 0) && aligned16(state0) && aligned16(state_out) &&
-                  aligned16(W1) && aligned16(b1) && aligned16(W2) && aligned16(b2) && aligned16(Wih) &&
-                  aligned16(bih) && aligned16(Whh) && aligned16(bhh),
-              LNZ_ENOTSUP, "%s: the rows of state0, state_out and of the weights must be 16-byte "
-              "aligned (ld0 = %d, ldso = %d)", who, ld0, ldso);
   {
-    const uint64_t rows = (uint64_t)B * N;
-    const uint64_t n0 = ((rows - 1) * (uint64_t)ld0 + D) * sizeof(float);
-    const uint64_t nsc = (uint64_t)B * P * sizeof(float);
-    LNZ_REQUIRE(!overlap(score, nsc, state0, n0), LNZ_EINVAL, "%s: score must not alias state0", who);
-    if (state_out != nullptr) {
-      const uint64_t no = ((rows - 1) * (uint64_t)ldso + D) * sizeof(float);
-      LNZ_REQUIRE(!overlap(state_out, no, state0, n0) && !overlap(state_out, no, score, nsc), LNZ_EINVAL,
-                  "%s: state_out must not alias state0 or score", who);
-    }
+    const float* const w[8] = {W1, b1, W2, b2, Wih, bih, Whh, bhh};
+    const int rc = check_propagation(who, state0, ld0, state_out, ldso, stride_b, stride_r, stride_c, stride_ch, w, B,
+                                     N, C, D, &P, num_prop);
+    if (rc != LNZ_OK) return rc;
   }
+  const uint64_t rows = (uint64_t)B * N;
+  const uint64_t n0 = span(rows, ld0, D), no = span(rows, ldso, D), nsc = (uint64_t)B * P * sizeof(float);
+  LNZ_REQUIRE(!overlap(score, nsc, state0, n0), LNZ_EINVAL, "%s: score must not alias state0", who);
+  LNZ_REQUIRE(state_out == nullptr || (!overlap(state_out, no, state0, n0) && !overlap(state_out, no, score, nsc)),
+              LNZ_EINVAL, "%s: state_out must not alias state0 or score", who);
   if (states != nullptr) {
-    const uint64_t rows = (uint64_t)B * N;
-    const uint64_t n0 = ((rows - 1) * (uint64_t)ld0 + D) * sizeof(float);
-    const uint64_t nsc = (uint64_t)B * P * sizeof(float);
     const uint64_t nst = ((uint64_t)num_prop + 1) * rows * D * sizeof(float);
     LNZ_REQUIRE(aligned16(states), LNZ_ENOTSUP, "%s: states must be 16-byte aligned", who);
     LNZ_REQUIRE(!overlap(states, nst, state0, n0) && !overlap(states, nst, score, nsc) &&
-                    (state_out == nullptr ||
-                     !overlap(states, nst, state_out, ((rows - 1) * (uint64_t)ldso + D) * sizeof(float))),
+                    (state_out == nullptr || !overlap(states, nst, state_out, no)),
                 LNZ_EINVAL, "%s: states must not alias state0, score or state_out", who);
   }
   LNZ_REQUIRE(tile_rows == 0 || tile_rows == 32 || tile_rows == 64, LNZ_EINVAL,
               "%s: tile_rows = %d is not 0 (chosen by the batch), 32 or 64", who, tile_rows);
-  int rows_per_tile = tile_rows;
-  if (rows_per_tile == 0) {
-    // 32-row tiles while they all fit in one round of the compute units, 64-row tiles beyond
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
-      (void)hipGetLastError();
-      cus = 256;
-    }
-    const int mpt32 = 32 / N;
-    rows_per_tile = ((int64_t)B + mpt32 - 1) / mpt32 <= cus ? 32 : 64;
-  }
+  const int rows_per_tile = choose_tile_rows(B, N, tile_rows);
   const int mpt = rows_per_tile / N;
   const int64_t grid = ((int64_t)B + mpt - 1) / mpt;
   hipStream_t s = (hipStream_t)stream;
@@ -347,15 +200,10 @@ int forward_impl(const char* who, const float* state0, int ld0, const float* L, 
   launch<DD, RTT, TR>(state0, ld0, L, stride_b, stride_r, stride_c, stride_ch, mask, W1, b1, W2, b2, Wih, bih, Whh,  \
                       bhh, Wo, bo, wg, bg, B, N, C, P, num_prop, avg ? 1 : 0, score, state_out, ldso, states,        \
                       (int)grid, s, who)
-#define LNZ_GGNN_LAUNCH(DD)                                                                     \
-  return rows_per_tile == 32 ? (states ? LNZ_GGNN_LAUNCH_(DD, 2, true) : LNZ_GGNN_LAUNCH_(DD, 2, false)) \
-                             : (states ? LNZ_GGNN_LAUNCH_(DD, 4, true) : LNZ_GGNN_LAUNCH_(DD, 4, false))
-  switch (D) {
-    case 32: LNZ_GGNN_LAUNCH(32);
-    case 64: LNZ_GGNN_LAUNCH(64);
-    case 96: LNZ_GGNN_LAUNCH(96);
-    default: LNZ_GGNN_LAUNCH(128);
-  }
+#define LNZ_GGNN_LAUNCH(DD)                                                                               \
+  (rows_per_tile == 32 ? (states ? LNZ_GGNN_LAUNCH_(DD, 2, true) : LNZ_GGNN_LAUNCH_(DD, 2, false)) \
+                       : (states ? LNZ_GGNN_LAUNCH_(DD, 4, true) : LNZ_GGNN_LAUNCH_(DD, 4, false)))
+  LNZ_GGNN_WIDTHS(D, LNZ_GGNN_LAUNCH)
 #undef LNZ_GGNN_LAUNCH
 #undef LNZ_GGNN_LAUNCH_
 }

@@ -2,8 +2,8 @@
 // loss.backward()): one step of backpropagation through time per launch, and the readout's backward.
 //
 // lnz_ggnn_backward_step — from S_t (the trajectory of lnz_ggnn_forward_states) and dS' = dL/dS_{t+1}: the
-// step is recomputed on chip with the forward's arithmetic (H_c, M_c, A_c, gi, gh, r, z, n: the same
-// tile_gemm chains, the same aggregate, the same cell), then
+// step is recomputed on chip with the forward's arithmetic (H_c, M_c, A_c, gi, gh, r, z, n: the forward's own
+// routines of ggnn_tile.hpp — its prologue, message block, gates and the cell's three expressions), then
 //     dn = dS' (1 - z), dz = dS' (S - n), dS = dS' z
 //     dn_pre = dn (1 - n^2), dz_pre = dz z (1 - z), dr_pre = dn_pre gh_n r (1 - r)
 //     dgi = [dr_pre, dz_pre, dn_pre], dgh = [dr_pre, dz_pre, dn_pre r]
@@ -33,10 +33,9 @@
 //
 // lnz_ggnn_readout_backward — lnz_gat_readout_backward's scheme (a workgroup per molecule, per-molecule
 // partials in a workspace, added in a fixed order by a second launch) at the GGNN's width D <= 128.
-#include <float.h>
-
 #include "common.hpp"
 #include "ggnn_tile.hpp"
+#include "partial_sum.hpp"
 
 namespace {
 
@@ -79,31 +78,15 @@ __global__ __launch_bounds__(GNT) void ggnn_backward_step_kernel(
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int m = lane & 15, g = lane >> 4;
-  const int mpt = GR / N;
-  const int64_t mol0 = (int64_t)blockIdx.x * mpt;
-  const int nm = (int)(B - mol0 < mpt ? B - mol0 : mpt);
-  const int rows = nm * N;
-  const int64_t row0 = mol0 * N;   // first global row of the tile
+  const TileSpan ts = tile_span<RT>(B, N);
+  const int rows = ts.rows;
+  const int64_t row0 = ts.mol0 * N;   // first global row of the tile
 
-  // ---- the state, the bit masks and denominators of L (as ggnn_forward_kernel reads them)
-  for (int idx = tid; idx < GR * DQ; idx += GNT) {
-    const int r = idx / DQ, q = idx - r * DQ;
-    f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (r < rows) v = *reinterpret_cast<const f32x4*>(S + (row0 + r) * (int64_t)lds_ + 4 * q);
-    *reinterpret_cast<f32x4*>(Sb + r * SS + 4 * q) = v;
-  }
-  for (int idx = tid; idx < GR * C; idx += GNT) {
-    const int r = idx / C, c = idx - r * C;
-    unsigned bm = 0;
-    if (r < rows) {
-      const int ml = r / N, i = r - ml * N;
-      const float* Lr = L + (mol0 + ml) * stride_b + i * stride_r + c * stride_ch;
-      for (int j = 0; j < N; ++j) bm |= (Lr[j * stride_c] != 0.0f ? 1u : 0u) << j;
-    }
-    bits[c * GR + r] = bm;
-    inv[c * GR + r] = avg ? 1.0f / ((float)__popc(bm) + FLT_EPSILON) : 1.0f;
-  }
-  if (tid < GR) rowbase[tid] = tid < rows ? (tid / N) * N : 0;
+  // ---- the state, the bit masks and denominators of L: the forward's prologue
+  load_state_tile<D, RT>(Sb, S, row0, lds_, rows);
+  load_edge_bits<RT>(bits, L, stride_b, stride_r, stride_c, stride_ch, ts, N, C,
+                     [&](const int at, const int degree) { inv[at] = ggnn_edge_weight(avg, degree); });
+  set_rowbase<RT>(rowbase, N, rows);
   __syncthreads();
   for (int idx = tid; idx < GR * C; idx += GNT) {
     const int r = idx / C, c = idx - r * C;
@@ -124,100 +107,33 @@ __global__ __launch_bounds__(GNT) void ggnn_backward_step_kernel(
   const float* const m_frag = Mb + m * SS + 4 * g;
   const int fo = m * SS + 4 * g;   // the fragment offset in a plane
 
-  // ---- the step, recomputed: ggnn_forward_kernel's channel loop, H_c and A_c also to global memory
+  // ---- the step, recomputed: the forward's channel loop, H_c and A_c also to global memory
   unsigned long long hpos = 0;     // bit 8 c + 4 rt + e: H_c > 0 at (row 16 rt + m, hidden column f0 + e)
+  const MessageTile mt = {Sb, Mb, Ab, Hb, bits, inv, rowbase};
   f32x4 acc[3][RT];
-#pragma unroll
-  for (int t = 0; t < 3; ++t)
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) acc[t][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  zero_tiles(acc);
   for (int c = 0; c < C; ++c) {
-    {
-      f32x4 h[1][RT];
+    ggnn_message<D, RT>(
+        mt, c, W1, b1, W2, b2, wave, m, g,
+        [&](const int rt, const f32x4& v) {
 #pragma unroll
-      for (int rt = 0; rt < RT; ++rt) h[0][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-      const float* const wp[1] = {W1 + ((int64_t)c * GHID + 16 * wave + m) * D + 4 * g};
-      tile_gemm<1, DB, RT>(s_frag, SS, wp, h);
-      const f32x4 bv = *reinterpret_cast<const f32x4*>(b1 + c * GHID + f0);
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt) {
-        f32x4 v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          v[e] = fmaxf(h[0][rt][e] + bv[e], 0.0f);
-          hpos |= (unsigned long long)(v[e] > 0.0f ? 1u : 0u) << (8 * c + 4 * rt + e);
-        }
-        *reinterpret_cast<f32x4*>(Hb + (16 * rt + m) * HS + f0) = v;
-        if (16 * rt + m < rows)
-          *reinterpret_cast<f32x4*>(Hcat + (row0 + 16 * rt + m) * ((int64_t)C * GHID) + c * GHID + f0) = v;
-      }
-    }
-    __syncthreads();
-    if (owner) {
-      f32x4 mm[1][RT];
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt) mm[0][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-      const float* const wp[1] = {W2 + ((int64_t)c * D + 16 * wave + m) * GHID + 4 * g};
-      tile_gemm<1, GHID / 16, RT>(h_frag, HS, wp, mm);
-      const f32x4 bv = *reinterpret_cast<const f32x4*>(b2 + c * D + f0);
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt)
-        *reinterpret_cast<f32x4*>(Mb + (16 * rt + m) * SS + f0) = mm[0][rt] + bv;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < GR * DQ; idx += GNT) {
-      const int r = idx / DQ, q = idx - r * DQ;
-      unsigned bm = bits[c * GR + r];
-      const float wgt = inv[c * GR + r];
-      const float* const src = Mb + rowbase[r] * SS + 4 * q;
-      f32x4 s = {0.0f, 0.0f, 0.0f, 0.0f};
-      while (bm) {
-        const int j = __ffs(bm) - 1;
-        bm &= bm - 1;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(src + j * SS);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s[e] = fmaf(wgt, v[e], s[e]);
-      }
-      *reinterpret_cast<f32x4*>(Ab + r * SS + 4 * q) = s;
-      if (r < rows) *reinterpret_cast<f32x4*>(Acat + (row0 + r) * ((int64_t)C * D) + c * D + 4 * q) = s;
-    }
-    __syncthreads();
-    if (owner) {
-      const float* const row = Wih + (int64_t)(16 * wave + m) * ((int64_t)C * D) + c * D + 4 * g;
-      const int64_t gate = (int64_t)D * C * D;
-      const float* const wp[3] = {row, row + gate, row + 2 * gate};
-      f32x4 part[3][RT];
-#pragma unroll
-      for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) part[t][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-      tile_gemm<3, DB, RT>(a_frag, SS, wp, part);
-#pragma unroll
-      for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) acc[t][rt] += part[t][rt];
-    }
+          for (int e = 0; e < 4; ++e) hpos |= (unsigned long long)(v[e] > 0.0f ? 1u : 0u) << (8 * c + 4 * rt + e);
+          if (16 * rt + m < rows)
+            *reinterpret_cast<f32x4*>(Hcat + (row0 + 16 * rt + m) * ((int64_t)C * GHID) + c * GHID + f0) = v;
+        },
+        [&](const int r, const int q, const f32x4& s) {
+          if (r < rows) *reinterpret_cast<f32x4*>(Acat + (row0 + r) * ((int64_t)C * D) + c * D + 4 * q) = s;
+        });
+    if (owner) gate_accumulate<D, RT>(a_frag, Wih, c, C, wave, m, g, acc);
   }
   f32x4 ds[1][RT];   // dS_t of this lane's four features
-#pragma unroll
-  for (int rt = 0; rt < RT; ++rt) ds[0][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  zero_tiles(ds);
   if (owner) {
     f32x4 gh[3][RT];
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt) gh[t][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    {
-      const float* const row = Whh + (int64_t)(16 * wave + m) * D + 4 * g;
-      const float* const wp[3] = {row, row + D * D, row + 2 * D * D};
-      tile_gemm<3, DB, RT>(s_frag, SS, wp, gh);
-    }
-    // ---- the cell and its backward on this wave's features; the planes are written for every row of the
-    // tile (a dead row: dS' = 0, so zeros)
-    const f32x4 b_r = *reinterpret_cast<const f32x4*>(bih + f0) + *reinterpret_cast<const f32x4*>(bhh + f0);
-    const f32x4 b_z = *reinterpret_cast<const f32x4*>(bih + D + f0) + *reinterpret_cast<const f32x4*>(bhh + D + f0);
-    const f32x4 b_in = *reinterpret_cast<const f32x4*>(bih + 2 * D + f0);
-    const f32x4 b_hn = *reinterpret_cast<const f32x4*>(bhh + 2 * D + f0);
+    hidden_gates<D, RT>(s_frag, Whh, wave, m, g, gh);
+    // ---- the cell (LNZ_GRU_CELL's expressions) and its backward on this wave's features; the planes are written
+    // for every row of the tile (a dead row: dS' = 0, so zeros)
+    const GruBias b = gru_bias<D>(bih, bhh, f0);
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
       const int rl = 16 * rt + m;
@@ -228,10 +144,10 @@ __global__ __launch_bounds__(GNT) void ggnn_backward_step_kernel(
       f32x4 pr, pz, pn, pq;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float r = sigmoidf_((acc[0][rt][e] + gh[0][rt][e]) + b_r[e]);
-        const float z = sigmoidf_((acc[1][rt][e] + gh[1][rt][e]) + b_z[e]);
-        const float ghn = gh[2][rt][e] + b_hn[e];
-        const float n = tanhf((acc[2][rt][e] + b_in[e]) + r * ghn);
+        const float r = gru_gate(acc[0][rt][e], gh[0][rt][e], b.r[e]);
+        const float z = gru_gate(acc[1][rt][e], gh[1][rt][e], b.z[e]);
+        const float ghn = gh[2][rt][e] + b.hn[e];
+        const float n = gru_candidate(acc[2][rt][e], b.in[e], r, ghn);
         const float dn = dsn[e] * (1.0f - z);
         const float dz = dsn[e] * (so[e] - n);
         ds[0][rt][e] = dsn[e] * z;
@@ -260,8 +176,7 @@ __global__ __launch_bounds__(GNT) void ggnn_backward_step_kernel(
     const float* const w1[1] = {row + D};
     const float* const w2[1] = {row + 2 * D};
     f32x4 p0[1][RT], p1[1][RT], p2[1][RT];   // a chain of D terms per gate, then the adds: short sums
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) p0[0][rt] = p1[0][rt] = p2[0][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    zero_tiles(p0), zero_tiles(p1), zero_tiles(p2);
     tile_gemm<1, DB, RT>(Pr + fo, SS, w0, p0);
     tile_gemm<1, DB, RT>(Pz + fo, SS, w1, p1);
     tile_gemm<1, DB, RT>(Pq + fo, SS, w2, p2);
@@ -271,8 +186,7 @@ __global__ __launch_bounds__(GNT) void ggnn_backward_step_kernel(
   for (int c = 0; c < C; ++c) {
     if (owner) {   // dA_c = dgi W_ih[:, cD ..]: feature k = row k of WihT[c]
       f32x4 da[1][RT], da1[1][RT], da2[1][RT];
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt) da[0][rt] = da1[0][rt] = da2[0][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      zero_tiles(da), zero_tiles(da1), zero_tiles(da2);
       const float* const row = WihT + ((int64_t)c * D + 16 * wave + m) * (3 * D) + 4 * g;
       const float* const w0[1] = {row};
       const float* const w1[1] = {row + D};
@@ -307,8 +221,7 @@ __global__ __launch_bounds__(GNT) void ggnn_backward_step_kernel(
     __syncthreads();
     {   // dHpre_c = (dM_c W2_c) [H_c > 0]: hidden column h = row h of W2T[c]
       f32x4 dh[1][RT];
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt) dh[0][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      zero_tiles(dh);
       const float* const wp[1] = {W2T + ((int64_t)c * GHID + 16 * wave + m) * D + 4 * g};
       tile_gemm<1, DB, RT>(m_frag, SS, wp, dh);
       const unsigned hm = (unsigned)(hpos >> (8 * c)) & 0xffu;
@@ -326,8 +239,7 @@ __global__ __launch_bounds__(GNT) void ggnn_backward_step_kernel(
     if (owner) {   // dS += dHpre_c W1_c: feature k = row k of W1T[c]
       const float* const wp[1] = {W1T + ((int64_t)c * D + 16 * wave + m) * GHID + 4 * g};
       f32x4 part[1][RT];
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt) part[0][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      zero_tiles(part);
       tile_gemm<1, GHID / 16, RT>(h_frag, HS, wp, part);
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) ds[0][rt] += part[0][rt];
@@ -437,33 +349,6 @@ __global__ __launch_bounds__(256) void ggnn_readout_backward_kernel(
   }
 }
 
-// out[col] = the sum over the B rows of ws [B][M]; fixed order: four contiguous quarters of the rows, each
-// ascending, then ((q0 + q1) + q2) + q3.  The columns are [dWo | dbo | dwg | dbg] in that order.
-__global__ __launch_bounds__(256) void ggnn_partial_sum_kernel(const float* __restrict__ ws, int B, int M, int nWo,
-                                                               int nbo, int nwg, float* __restrict__ dWo,
-                                                               float* __restrict__ dbo, float* __restrict__ dwg,
-                                                               float* __restrict__ dbg) {
-  __shared__ float part[4][64];
-  const int x = threadIdx.x & 63, s = threadIdx.x >> 6;
-  const int col = blockIdx.x * 64 + x;
-  const int q = (B + 3) / 4;
-  const int b0 = s * q, b1 = min(B, b0 + q);
-  float a = 0.0f;
-  if (col < M)
-    for (int b = b0; b < b1; ++b) a += ws[(int64_t)b * M + col];
-  part[s][x] = a;
-  __syncthreads();
-  if (s == 0 && col < M) {
-    const float v = ((part[0][x] + part[1][x]) + part[2][x]) + part[3][x];
-    if (col < nWo) dWo[col] = v;
-    else if (col < nWo + nbo) dbo[col - nWo] = v;
-    else if (col < nWo + nbo + nwg) dwg[col - nWo - nbo] = v;
-    else dbg[0] = v;
-  }
-}
-
-inline uint64_t span(uint64_t rows, int ld, int width) { return ((rows - 1) * (uint64_t)ld + width) * sizeof(float); }
-
 }  // namespace
 
 extern "C" int lnz_ggnn_backward_step(const float* S, int lds, const float* dSnext, int ldd, const float* L,
@@ -513,16 +398,10 @@ extern "C" int lnz_ggnn_backward_step(const float* S, int lds, const float* dSne
   const int64_t grid = ((int64_t)B + mpt - 1) / mpt;
   hipStream_t s = (hipStream_t)stream;
   lnz::note_kernel("ggnn_backward_step_kernel<%d>", D);
-#define LNZ_GGNN_STEP(DD)                                                                                             \
-  return launch_step<DD>(S, lds, dSnext, ldd, L, stride_b, stride_r, stride_c, stride_ch, W1, b1, W2, b2, Wih, bih,   \
-                         Whh, bhh, W1T, W2T, WihT, WhhT, B, N, C, avg ? 1 : 0, dS, ldo, dgi, dghn, A, dM, H, dHpre,   \
-                         (int)grid, s)
-  switch (D) {
-    case 32: LNZ_GGNN_STEP(32);
-    case 64: LNZ_GGNN_STEP(64);
-    case 96: LNZ_GGNN_STEP(96);
-    default: LNZ_GGNN_STEP(128);
-  }
+#define LNZ_GGNN_STEP(DD)                                                                                      \
+  launch_step<DD>(S, lds, dSnext, ldd, L, stride_b, stride_r, stride_c, stride_ch, W1, b1, W2, b2, Wih, bih, Whh, \
+                  bhh, W1T, W2T, WihT, WhhT, B, N, C, avg ? 1 : 0, dS, ldo, dgi, dghn, A, dM, H, dHpre, (int)grid, s)
+  LNZ_GGNN_WIDTHS(D, LNZ_GGNN_STEP)
 #undef LNZ_GGNN_STEP
 }
 
@@ -550,7 +429,6 @@ extern "C" int lnz_ggnn_readout_backward(const float* Slast, int ld, const uint8
   const int rc = lnz::check_launch("lnz_ggnn_readout_backward");
   if (rc != LNZ_OK) return rc;
   const int M = P * D + P + D + 1;
-  hipLaunchKernelGGL(ggnn_partial_sum_kernel, dim3((unsigned)((M + 63) / 64)), dim3(256), 0, (hipStream_t)stream,
-                     workspace, B, M, P * D, P, D, dWo, dbo, dwg, dbg);
-  return lnz::check_launch("lnz_ggnn_readout_backward (sum of the partials)");
+  Segments seg = {{dWo, dbo, dwg, dbg, nullptr}, {P * D, P, D, 1, 0}};
+  return sum_partials(workspace, B, M, seg, (hipStream_t)stream, "lnz_ggnn_readout_backward (sum of the partials)");
 }

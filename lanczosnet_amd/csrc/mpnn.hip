@@ -22,8 +22,8 @@
 // (ggnn_tile.hpp), weights streamed from L2.  [P_c | Q_c] is ONE 128-column product (wave w < 4: the 16
 // columns 16 w .. of P_c, wave w >= 4: of Q_c — the two halves of the rows of W1_c, read where they
 // lie), R_c runs on the VALU over the set bits only, M_c = R_c W2_c^T is a K = 64 product of the waves
-// that own features, whose gate accumulators live across the channel loop as in ggnn.hip; gh and the
-// GRU cell are ggnn.hip's.  Three barriers per channel, two per step.  LDS at D = 128, R = 64: S, M_c
+// that own features, whose gate accumulators live across the channel loop as in ggnn.hip; the prologue,
+// the gate products, gh, the GRU cell and the state store are ggnn_tile.hpp's routines, ggnn.hip's own.  Three barriers per channel, two per step.  LDS at D = 128, R = 64: S, M_c
 // 64 x 132 floats each + [P|Q] 64 x 132 + R_c 64 x 68 + masks = 123,136 B.  No atomics, no
 // cross-workgroup traffic, every sum in a fixed order: bit-reproducible, and a row's bits do not depend
 // on the tile height.  The folded form W_ih[:, c] W2_c ([3D, 64] per channel) was not built.
@@ -42,8 +42,6 @@
 // features), j ascending.  X is re-read from L2 in every step: a full tile of sixteen 32-row molecules is
 // 256 KB at D = 128, more than a workgroup's LDS, and a tile with fewer molecules would leave MFMA rows
 // empty.  Rows outside the mask are never loaded; a molecule without a masked row reads exactly 0.
-#include <float.h>
-
 #include "common.hpp"
 #include "ggnn_tile.hpp"
 
@@ -69,7 +67,6 @@ __global__ __launch_bounds__(GNT) void mpnn_forward_kernel(
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int GR = 16 * RT;    // rows per tile
   constexpr int SS = D + 4;      // row stride of S and M_c
-  constexpr int DQ = D / 4;      // float4 per state row
   constexpr int DB = D / 16;     // 16-feature blocks of a state row: waves 0 .. DB-1 own one each
   constexpr int HQ = MHID / 4;   // float4 per row of R_c
   float* const Sb = smem;
@@ -83,30 +80,15 @@ __global__ __launch_bounds__(GNT) void mpnn_forward_kernel(
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int m = lane & 15, g = lane >> 4;
-  const int mpt = GR / N;                                  // molecules per tile
-  const int64_t mol0 = (int64_t)blockIdx.x * mpt;
-  const int nm = (int)(B - mol0 < mpt ? B - mol0 : mpt);   // molecules of this tile
-  const int rows = nm * N;                                 // live rows; the others stay zero and unread
+  const TileSpan ts = tile_span<RT>(B, N);
+  const int64_t row0 = ts.mol0 * N;      // first global row of the tile
+  const int rows = ts.rows;
 
   // ---- the state, the bit masks and degrees of L, the molecule of every row
-  for (int idx = tid; idx < GR * DQ; idx += GNT) {
-    const int r = idx / DQ, q = idx - r * DQ;
-    f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (r < rows) v = *reinterpret_cast<const f32x4*>(state0 + (mol0 * N + r) * (int64_t)ld0 + 4 * q);
-    *reinterpret_cast<f32x4*>(Sb + r * SS + 4 * q) = v;
-  }
-  for (int idx = tid; idx < GR * C; idx += GNT) {
-    const int r = idx / C, c = idx - r * C;
-    unsigned bm = 0;
-    if (r < rows) {
-      const int ml = r / N, i = r - ml * N;
-      const float* Lr = L + (mol0 + ml) * stride_b + i * stride_r + c * stride_ch;
-      for (int j = 0; j < N; ++j) bm |= (Lr[j * stride_c] != 0.0f ? 1u : 0u) << j;   // NaN != 0: an edge
-    }
-    bits[c * GR + r] = bm;
-    deg[c * GR + r] = (float)__popc(bm);
-  }
-  if (tid < GR) rowbase[tid] = tid < rows ? (tid / N) * N : 0;
+  load_state_tile<D, RT>(Sb, state0, row0, ld0, rows);
+  load_edge_bits<RT>(bits, L, stride_b, stride_r, stride_c, stride_ch, ts, N, C,
+                     [&](const int at, const int degree) { deg[at] = (float)degree; });
+  set_rowbase<RT>(rowbase, N, rows);
   __syncthreads();
 
   const bool owner = wave < DB;          // wave-uniform: this wave owns features 16 wave .. 16 wave + 15
@@ -122,15 +104,11 @@ __global__ __launch_bounds__(GNT) void mpnn_forward_kernel(
   for (int step = 0; step < num_prop; ++step) {
     // gate accumulators of this wave's feature block: [0] r, [1] z, [2] gi_n
     f32x4 acc[3][RT];
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt) acc[t][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    zero_tiles(acc);
     for (int c = 0; c < C; ++c) {
       {   // [P_c | Q_c + b1_c]: columns 16 wave ..
         f32x4 h[1][RT];
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) h[0][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        zero_tiles(h);
         const float* const wp[1] = {W1 + ((int64_t)c * MHID + hrow) * (2 * D) + hoff + 4 * g};
         tile_gemm<1, DB, RT>(s_frag, SS, wp, h);
         f32x4 bv = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -159,8 +137,7 @@ __global__ __launch_bounds__(GNT) void mpnn_forward_kernel(
       __syncthreads();
       if (owner) {   // M_c = R_c W2_c^T + deg_c b2_c [/ (deg_c + EPS)]: features 16 wave ..
         f32x4 mm[1][RT];
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) mm[0][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        zero_tiles(mm);
         const float* const wp[1] = {W2 + ((int64_t)c * D + 16 * wave + m) * MHID + 4 * g};
         tile_gemm<1, MHID / 16, RT>(r_frag, RS, wp, mm);
         const f32x4 bv = *reinterpret_cast<const f32x4*>(b2 + c * D + f0);
@@ -173,64 +150,16 @@ __global__ __launch_bounds__(GNT) void mpnn_forward_kernel(
         }
       }
       __syncthreads();
-      if (owner) {   // gi += M_c W_ih[:, c D ..]^T: tiles r, z, gi_n
-        const float* const row = Wih + (int64_t)(16 * wave + m) * ((int64_t)C * D) + c * D + 4 * g;
-        const int64_t gate = (int64_t)D * C * D;
-        const float* const wp[3] = {row, row + gate, row + 2 * gate};
-        f32x4 part[3][RT];   // a chain of D terms per channel, then one add: the error of a short sum
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-#pragma unroll
-          for (int rt = 0; rt < RT; ++rt) part[t][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        tile_gemm<3, DB, RT>(m_frag, SS, wp, part);
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-#pragma unroll
-          for (int rt = 0; rt < RT; ++rt) acc[t][rt] += part[t][rt];
-      }
+      if (owner) gate_accumulate<D, RT>(m_frag, Wih, c, C, wave, m, g, acc);
     }
-    // gh = S W_hh^T (the state is still the step's input): r and z join gi, gh_n stays apart.  Every wave
-    // reads ALL columns of S here, so the barrier below stands between these reads and the cell's writes
     f32x4 gh[3][RT];
-    if (owner) {
-#pragma unroll
-      for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) gh[t][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-      const float* const row = Whh + (int64_t)(16 * wave + m) * D + 4 * g;
-      const float* const wp[3] = {row, row + D * D, row + 2 * D * D};
-      tile_gemm<3, DB, RT>(s_frag, SS, wp, gh);
-    }
+    if (owner) hidden_gates<D, RT>(s_frag, Whh, wave, m, g, gh);
     __syncthreads();
-    if (owner) {   // the GRU cell on this wave's features
-      const f32x4 b_r = *reinterpret_cast<const f32x4*>(bih + f0) + *reinterpret_cast<const f32x4*>(bhh + f0);
-      const f32x4 b_z = *reinterpret_cast<const f32x4*>(bih + D + f0) + *reinterpret_cast<const f32x4*>(bhh + D + f0);
-      const f32x4 b_in = *reinterpret_cast<const f32x4*>(bih + 2 * D + f0);
-      const f32x4 b_hn = *reinterpret_cast<const f32x4*>(bhh + 2 * D + f0);
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt) {
-        float* const sp = Sb + (16 * rt + m) * SS + f0;
-        const f32x4 so = *reinterpret_cast<const f32x4*>(sp);
-        f32x4 sn;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float r = sigmoidf_((acc[0][rt][e] + gh[0][rt][e]) + b_r[e]);
-          const float z = sigmoidf_((acc[1][rt][e] + gh[1][rt][e]) + b_z[e]);
-          const float n = tanhf((acc[2][rt][e] + b_in[e]) + r * (gh[2][rt][e] + b_hn[e]));
-          sn[e] = (1.0f - z) * n + z * so[e];
-        }
-        *reinterpret_cast<f32x4*>(sp) = sn;
-      }
-    }
+    if (owner) LNZ_GRU_CELL(D, RT);
     __syncthreads();
   }
-
   // ---- the final state
-  for (int idx = tid; idx < rows * DQ; idx += GNT) {
-    const int r = idx / DQ, q = idx - r * DQ;
-    *reinterpret_cast<f32x4*>(state_out + (mol0 * N + r) * (int64_t)ldso + 4 * q) =
-        *reinterpret_cast<const f32x4*>(Sb + r * SS + 4 * q);
-  }
+  store_state_tile<D>(state_out + row0 * (int64_t)ldso, ldso, Sb, rows);
 }
 
 template <int D, int RT>
@@ -396,16 +325,6 @@ int launch_set2vec(const float* X, int ld, const uint8_t* mask, const float* Wg,
   return lnz::check_launch("lnz_set2vec_readout");
 }
 
-int device_cus() {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
-    (void)hipGetLastError();
-    cus = 256;
-  }
-  return cus;
-}
-
 }  // namespace
 
 extern "C" int lnz_mpnn_forward(const float* state0, int ld0, const float* L, int64_t stride_b, int64_t stride_r,
@@ -416,33 +335,17 @@ extern "C" int lnz_mpnn_forward(const float* state0, int ld0, const float* L, in
   const char* const who = "lnz_mpnn_forward";
   LNZ_REQUIRE(state0 && L && W1 && b1 && W2 && b2 && Wih && bih && Whh && bhh && state_out, LNZ_EINVAL,
               "%s: null pointer", who);
-  LNZ_REQUIRE(B > 0 && N > 0, LNZ_EINVAL, "%s: B = %d, N = %d must be positive", who, B, N);
-  LNZ_REQUIRE(N <= GMAXN && C >= 1 && C <= GMAXC && D >= 32 && D <= GMAXD && D % 32 == 0 && num_prop >= 0,
-              LNZ_ENOTSUP,
-              "%s: N = %d, C = %d, D = %d, num_prop = %d outside 1 <= N <= 32, 1 <= C <= 8, "
-              "D a multiple of 32 and <= 128, num_prop >= 0", who, N, C, D, num_prop);
-  LNZ_REQUIRE(ld0 >= D && ldso >= D, LNZ_EINVAL, "%s: ld0 = %d, ldso = %d below the width %d", who, ld0, ldso, D);
-  LNZ_REQUIRE(stride_b >= 0 && stride_r >= 0 && stride_c >= 0 && stride_ch >= 0, LNZ_EINVAL,
-              "%s: negative stride of L", who);
-  LNZ_REQUIRE(ld0 % 4 == 0 && ldso % 4 == 0 && aligned16(state0) && aligned16(state_out) && aligned16(W1) &&
-                  aligned16(b1) && aligned16(W2) && aligned16(b2) && aligned16(Wih) && aligned16(bih) &&
-                  aligned16(Whh) && aligned16(bhh),
-              LNZ_ENOTSUP, "%s: the rows of state0, state_out and of the weights must be 16-byte "
-              "aligned (ld0 = %d, ldso = %d)", who, ld0, ldso);
   {
-    const uint64_t rows = (uint64_t)B * N;
-    const uint64_t n0 = ((rows - 1) * (uint64_t)ld0 + D) * sizeof(float);
-    const uint64_t no = ((rows - 1) * (uint64_t)ldso + D) * sizeof(float);
-    LNZ_REQUIRE(!overlap(state_out, no, state0, n0), LNZ_EINVAL, "%s: state_out must not alias state0", who);
+    const float* const w[8] = {W1, b1, W2, b2, Wih, bih, Whh, bhh};
+    const int rc = check_propagation(who, state0, ld0, state_out, ldso, stride_b, stride_r, stride_c, stride_ch, w, B,
+                                     N, C, D, nullptr, num_prop);
+    if (rc != LNZ_OK) return rc;
   }
+  LNZ_REQUIRE(!overlap(state_out, span((uint64_t)B * N, ldso, D), state0, span((uint64_t)B * N, ld0, D)), LNZ_EINVAL,
+              "%s: state_out must not alias state0", who);
   LNZ_REQUIRE(tile_rows == 0 || tile_rows == 32 || tile_rows == 64, LNZ_EINVAL,
               "%s: tile_rows = %d is not 0 (chosen by the batch), 32 or 64", who, tile_rows);
-  int rows_per_tile = tile_rows;
-  if (rows_per_tile == 0) {
-    // 32-row tiles while they all fit in one round of the compute units, 64-row tiles beyond
-    const int mpt32 = 32 / N;
-    rows_per_tile = ((int64_t)B + mpt32 - 1) / mpt32 <= device_cus() ? 32 : 64;
-  }
+  const int rows_per_tile = choose_tile_rows(B, N, tile_rows);
   const int mpt = rows_per_tile / N;
   const int64_t grid = ((int64_t)B + mpt - 1) / mpt;
   hipStream_t s = (hipStream_t)stream;
@@ -450,13 +353,8 @@ extern "C" int lnz_mpnn_forward(const float* state0, int ld0, const float* L, in
 #define LNZ_MPNN_LAUNCH_(DD, RTT)                                                                                  \
   launch_mpnn<DD, RTT>(state0, ld0, L, stride_b, stride_r, stride_c, stride_ch, W1, b1, W2, b2, Wih, bih, Whh, bhh, \
                        B, N, C, num_prop, avg ? 1 : 0, state_out, ldso, (int)grid, s)
-#define LNZ_MPNN_LAUNCH(DD) return rows_per_tile == 32 ? LNZ_MPNN_LAUNCH_(DD, 2) : LNZ_MPNN_LAUNCH_(DD, 4)
-  switch (D) {
-    case 32: LNZ_MPNN_LAUNCH(32);
-    case 64: LNZ_MPNN_LAUNCH(64);
-    case 96: LNZ_MPNN_LAUNCH(96);
-    default: LNZ_MPNN_LAUNCH(128);
-  }
+#define LNZ_MPNN_LAUNCH(DD) (rows_per_tile == 32 ? LNZ_MPNN_LAUNCH_(DD, 2) : LNZ_MPNN_LAUNCH_(DD, 4))
+  LNZ_GGNN_WIDTHS(D, LNZ_MPNN_LAUNCH)
 #undef LNZ_MPNN_LAUNCH
 #undef LNZ_MPNN_LAUNCH_
 }
@@ -475,11 +373,8 @@ extern "C" int lnz_set2vec_readout(const float* X, int ld, const uint8_t* mask, 
   LNZ_REQUIRE(ld >= D, LNZ_EINVAL, "%s: ld = %d below the width %d", who, ld, D);
   LNZ_REQUIRE(ld % 4 == 0 && aligned16(X) && aligned16(Wg) && aligned16(bg) && aligned16(W1T) && aligned16(w2),
               LNZ_ENOTSUP, "%s: the rows of X and of the weights must be 16-byte aligned (ld = %d)", who, ld);
-  {
-    const uint64_t rows = (uint64_t)B * N;
-    const uint64_t nx = ((rows - 1) * (uint64_t)ld + D) * sizeof(float);
-    LNZ_REQUIRE(!overlap(score, (uint64_t)B * P * sizeof(float), X, nx), LNZ_EINVAL, "%s: score must not alias X", who);
-  }
+  LNZ_REQUIRE(!overlap(score, (uint64_t)B * P * sizeof(float), X, span((uint64_t)B * N, ld, D)), LNZ_EINVAL,
+              "%s: score must not alias X", who);
   LNZ_REQUIRE(mols_per_group >= 0 && mols_per_group <= SMOL, LNZ_EINVAL,
               "%s: mols_per_group = %d is not 0 (chosen by the batch) or 1 .. 16", who, mols_per_group);
   // molecules per workgroup: as few as spread the batch over the compute units, at most the 16 rows of a tile
@@ -491,10 +386,8 @@ extern "C" int lnz_set2vec_readout(const float* X, int ld, const uint8_t* mask, 
   }
   hipStream_t s = (hipStream_t)stream;
   lnz::note_kernel("set2vec_readout_kernel<%d> x %d", D, mpw);
-  switch (D) {
-    case 32: return launch_set2vec<32>(X, ld, mask, Wg, bg, W1T, w2, Wout, bout, B, N, P, num_step, mpw, score, s);
-    case 64: return launch_set2vec<64>(X, ld, mask, Wg, bg, W1T, w2, Wout, bout, B, N, P, num_step, mpw, score, s);
-    case 96: return launch_set2vec<96>(X, ld, mask, Wg, bg, W1T, w2, Wout, bout, B, N, P, num_step, mpw, score, s);
-    default: return launch_set2vec<128>(X, ld, mask, Wg, bg, W1T, w2, Wout, bout, B, N, P, num_step, mpw, score, s);
-  }
+#define LNZ_SET2VEC_LAUNCH(DD) \
+  launch_set2vec<DD>(X, ld, mask, Wg, bg, W1T, w2, Wout, bout, B, N, P, num_step, mpw, score, s)
+  LNZ_GGNN_WIDTHS(D, LNZ_SET2VEC_LAUNCH)
+#undef LNZ_SET2VEC_LAUNCH
 }

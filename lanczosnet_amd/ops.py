@@ -2609,6 +2609,57 @@ GGNN_MAX_NODES, GGNN_MAX_CHANNELS, GGNN_MAX_WIDTH, GGNN_WIDTH_STEP, GGNN_MAX_OUT
 GGNN_MSG_HIDDEN = 128   # model/ggnn.py:59-61
 
 
+def _propagation_operands(who, state, L, W1, b1, W2, b2, Wih, bih, Whh, bhh, hidden, w1_cols=1, name='state0',
+                          like=()):
+  """What the gated-propagation kernels share of their arguments: `state` [B, N, D] (named `name` in the
+  errors; `like` = further (name, tensor) pairs of its shape) and a float32 L [B, N, N, C] checked, the eight
+  propagation operands as float32 contiguous tensors of the shapes the kernels read — message hidden width
+  `hidden`, W1 [C, hidden, w1_cols D] -> ((B, N, C, D), the row strides of `state` and `like`, the operands)."""
+  if state.dim() != 3 or L.dim() != 4 or L.dtype != torch.float32:
+    raise LnzError(_lib.LNZ_EINVAL, '%s: %s [B, N, D] and a float32 L [B, N, N, C] expected' % (who, name))
+  B, N, D = state.shape
+  C = L.shape[3]
+  rows = ((name, state),) + tuple(like)
+  if tuple(L.shape[:3]) != (B, N, N) or any(tuple(t.shape) != (B, N, D) for _, t in rows):
+    raise LnzError(_lib.LNZ_EINVAL, '%s: %s and L %s do not fit'
+                   % (who, ', '.join('%s %s' % (n, tuple(t.shape)) for n, t in rows), tuple(L.shape)))
+  lds = [_gat_rows(t, who) for _, t in rows]
+  W1, b1, W2, b2 = _f32c(W1), _f32c(b1), _f32c(W2), _f32c(b2)
+  Wih, bih, Whh, bhh = _f32c(Wih), _f32c(bih).reshape(-1), _f32c(Whh), _f32c(bhh).reshape(-1)
+  for t, shape in ((W1, (C, hidden, w1_cols * D)), (b1, (C, hidden)), (W2, (C, D, hidden)), (b2, (C, D)),
+                   (Wih, (3 * D, C * D)), (bih, (3 * D,)), (Whh, (3 * D, D)), (bhh, (3 * D,))):
+    if tuple(t.shape) != shape:
+      raise LnzError(_lib.LNZ_EINVAL, '%s: operand of shape %s where %s is expected' % (who, tuple(t.shape), shape))
+  return (B, N, C, D), lds, (W1, b1, W2, b2, Wih, bih, Whh, bhh)
+
+
+def _gated_readout_operands(who, B, N, D, mask, Wo, bo, wg, bg, together=False):
+  """The gated readout's operands as float32 contiguous Wo [P, D], bo [P], wg [D], bg [1] and the mask [B, N]
+  (or None) as uint8 -> (P, mask, (Wo, bo, wg, bg)).  together: one error names all four operands."""
+  Wo, bo, wg, bg = _f32c(Wo), _f32c(bo).reshape(-1), _f32c(wg).reshape(-1), _f32c(bg).reshape(-1)
+  P = Wo.shape[0]
+  for t, shape in ((Wo, (P, D)), (bo, (P,)), (wg, (D,)), (bg, (1,))):
+    if tuple(t.shape) != shape:
+      if together:
+        raise LnzError(_lib.LNZ_EINVAL, '%s: head operands %s, %s, %s, %s do not fit D = %d'
+                       % (who, tuple(Wo.shape), tuple(bo.shape), tuple(wg.shape), tuple(bg.shape), D))
+      raise LnzError(_lib.LNZ_EINVAL, '%s: operand of shape %s where %s is expected' % (who, tuple(t.shape), shape))
+  if mask is not None:
+    if tuple(mask.shape) != (B, N):
+      raise LnzError(_lib.LNZ_EINVAL, '%s: mask %s, expected %s' % (who, tuple(mask.shape), (B, N)))
+    mask = (mask != 0).to(torch.uint8).contiguous()
+  return P, mask, (Wo, bo, wg, bg)
+
+
+def _state_buffer(who, name, t, B, N, D, device):
+  """A [B, N, D] output of the propagation kernels (allocated where `t` is None) and its row stride"""
+  if t is None:
+    t = torch.empty((B, N, D), dtype=torch.float32, device=device)
+  if tuple(t.shape) != (B, N, D):
+    raise LnzError(_lib.LNZ_EINVAL, '%s: %s %s, expected %s' % (who, name, tuple(t.shape), (B, N, D)))
+  return t, _gat_rows(t, who)
+
+
 def ggnn_forward(state0, L, mask, W1, b1, W2, b2, Wih, bih, Whh, bhh, Wo, bo, wg, bg, num_prop, avg=True,
                  state_out=None, return_state=False, tile_rows=0):
   """lnz_ggnn_forward (model/ggnn.py:137-197): every propagation step and the readout in one launch.
@@ -2618,54 +2669,19 @@ def ggnn_forward(state0, L, mask, W1, b1, W2, b2, Wih, bih, Whh, bhh, Wo, bo, wg
   (the GRU cell), Wo [P, D], bo [P], wg [1, D] or [D], bg [1] -> score [B, P]; with return_state (or a
   `state_out` buffer [B, N, D]) also the final state.  tile_rows: 0 = chosen by the batch, 32 or 64 rows of
   state per workgroup (a row's bits do not depend on it)."""
+  who = 'ggnn_forward'
   _need_cuda(state0, L, mask, W1, b1, W2, b2, Wih, bih, Whh, bhh, Wo, bo, wg, bg, state_out)
-  if state0.dim() != 3 or L.dim() != 4 or L.dtype != torch.float32:
-    raise LnzError(_lib.LNZ_EINVAL, 'ggnn_forward: state0 [B, N, D] and a float32 L [B, N, N, C] expected')
-  B, N, D = state0.shape
-  C = L.shape[3]
-  if tuple(L.shape[:3]) != (B, N, N):
-    raise LnzError(_lib.LNZ_EINVAL, 'ggnn_forward: state0 %s and L %s do not fit' % (tuple(state0.shape), tuple(L.shape)))
-  ld0 = _gat_rows(state0, 'ggnn_forward')
-  W1, b1, W2, b2 = _f32c(W1), _f32c(b1), _f32c(W2), _f32c(b2)
-  Wih, bih, Whh, bhh = _f32c(Wih), _f32c(bih).reshape(-1), _f32c(Whh), _f32c(bhh).reshape(-1)
-  Wo, bo, wg, bg = _f32c(Wo), _f32c(bo).reshape(-1), _f32c(wg).reshape(-1), _f32c(bg).reshape(-1)
-  P = Wo.shape[0]
-  Hd = GGNN_MSG_HIDDEN
-  for t, shape in ((W1, (C, Hd, D)), (b1, (C, Hd)), (W2, (C, D, Hd)), (b2, (C, D)), (Wih, (3 * D, C * D)),
-                   (bih, (3 * D,)), (Whh, (3 * D, D)), (bhh, (3 * D,)), (Wo, (P, D)), (bo, (P,)), (wg, (D,)),
-                   (bg, (1,))):
-    if tuple(t.shape) != shape:
-      raise LnzError(_lib.LNZ_EINVAL, 'ggnn_forward: operand of shape %s where %s is expected'
-                     % (tuple(t.shape), shape))
-  if mask is not None:
-    if tuple(mask.shape) != (B, N):
-      raise LnzError(_lib.LNZ_EINVAL, 'ggnn_forward: mask %s, expected %s' % (tuple(mask.shape), (B, N)))
-    mask = (mask != 0).to(torch.uint8).contiguous()
-  if state_out is None and return_state:
-    state_out = torch.empty((B, N, D), dtype=torch.float32, device=state0.device)
+  (B, N, C, D), (ld0,), prop = _propagation_operands(who, state0, L, W1, b1, W2, b2, Wih, bih, Whh, bhh,
+                                                     GGNN_MSG_HIDDEN)
+  P, mask, head = _gated_readout_operands(who, B, N, D, mask, Wo, bo, wg, bg)
   ldso = D
-  if state_out is not None:
-    if tuple(state_out.shape) != (B, N, D):
-      raise LnzError(_lib.LNZ_EINVAL, 'ggnn_forward: state_out %s, expected %s' % (tuple(state_out.shape), (B, N, D)))
-    ldso = _gat_rows(state_out, 'ggnn_forward')
+  if state_out is not None or return_state:
+    state_out, ldso = _state_buffer(who, 'state_out', state_out, B, N, D, state0.device)
   score = torch.empty((B, P), dtype=torch.float32, device=state0.device)
   with torch.cuda.device(state0.device):
-    _abi().ggnn_forward(state0, ld0, L, L.stride(0), L.stride(1), L.stride(2), L.stride(3), mask, W1, b1, W2, b2,
-                        Wih, bih, Whh, bhh, Wo, bo, wg, bg, B, N, C, D, P, int(num_prop), int(bool(avg)), score,
-                        state_out, ldso, int(tile_rows))
+    _abi().ggnn_forward(state0, ld0, L, L.stride(0), L.stride(1), L.stride(2), L.stride(3), mask, *prop, *head, B,
+                        N, C, D, P, int(num_prop), int(bool(avg)), score, state_out, ldso, int(tile_rows))
   return (score, state_out) if state_out is not None else score
-
-
-def _ggnn_operands(who, C, D, W1, b1, W2, b2, Wih, bih, Whh, bhh):
-  """The eight propagation operands as float32 contiguous tensors of the shapes the kernels read."""
-  W1, b1, W2, b2 = _f32c(W1), _f32c(b1), _f32c(W2), _f32c(b2)
-  Wih, bih, Whh, bhh = _f32c(Wih), _f32c(bih).reshape(-1), _f32c(Whh), _f32c(bhh).reshape(-1)
-  Hd = GGNN_MSG_HIDDEN
-  for t, shape in ((W1, (C, Hd, D)), (b1, (C, Hd)), (W2, (C, D, Hd)), (b2, (C, D)), (Wih, (3 * D, C * D)),
-                   (bih, (3 * D,)), (Whh, (3 * D, D)), (bhh, (3 * D,))):
-    if tuple(t.shape) != shape:
-      raise LnzError(_lib.LNZ_EINVAL, '%s: operand of shape %s where %s is expected' % (who, tuple(t.shape), shape))
-  return W1, b1, W2, b2, Wih, bih, Whh, bhh
 
 
 def ggnn_forward_states(state0, L, mask, W1, b1, W2, b2, Wih, bih, Whh, bhh, Wo, bo, wg, bg, num_prop, avg=True,
@@ -2675,23 +2691,9 @@ def ggnn_forward_states(state0, L, mask, W1, b1, W2, b2, Wih, bih, Whh, bhh, Wo,
   t, states[num_prop] the final state.  Nothing else is saved for the backward."""
   who = 'ggnn_forward_states'
   _need_cuda(state0, L, mask, W1, b1, W2, b2, Wih, bih, Whh, bhh, Wo, bo, wg, bg, states)
-  if state0.dim() != 3 or L.dim() != 4 or L.dtype != torch.float32:
-    raise LnzError(_lib.LNZ_EINVAL, '%s: state0 [B, N, D] and a float32 L [B, N, N, C] expected' % who)
-  B, N, D = state0.shape
-  C = L.shape[3]
-  if tuple(L.shape[:3]) != (B, N, N):
-    raise LnzError(_lib.LNZ_EINVAL, '%s: state0 %s and L %s do not fit' % (who, tuple(state0.shape), tuple(L.shape)))
-  ld0 = _gat_rows(state0, who)
-  W1, b1, W2, b2, Wih, bih, Whh, bhh = _ggnn_operands(who, C, D, W1, b1, W2, b2, Wih, bih, Whh, bhh)
-  Wo, bo, wg, bg = _f32c(Wo), _f32c(bo).reshape(-1), _f32c(wg).reshape(-1), _f32c(bg).reshape(-1)
-  P = Wo.shape[0]
-  for t, shape in ((Wo, (P, D)), (bo, (P,)), (wg, (D,)), (bg, (1,))):
-    if tuple(t.shape) != shape:
-      raise LnzError(_lib.LNZ_EINVAL, '%s: operand of shape %s where %s is expected' % (who, tuple(t.shape), shape))
-  if mask is not None:
-    if tuple(mask.shape) != (B, N):
-      raise LnzError(_lib.LNZ_EINVAL, '%s: mask %s, expected %s' % (who, tuple(mask.shape), (B, N)))
-    mask = (mask != 0).to(torch.uint8).contiguous()
+  (B, N, C, D), (ld0,), prop = _propagation_operands(who, state0, L, W1, b1, W2, b2, Wih, bih, Whh, bhh,
+                                                     GGNN_MSG_HIDDEN)
+  P, mask, head = _gated_readout_operands(who, B, N, D, mask, Wo, bo, wg, bg)
   T = int(num_prop)
   if T < 0:
     raise NotSupported(_lib.LNZ_ENOTSUP, '%s: num_prop = %d' % (who, T))
@@ -2702,9 +2704,8 @@ def ggnn_forward_states(state0, L, mask, W1, b1, W2, b2, Wih, bih, Whh, bhh, Wo,
                    % (who, tuple(states.shape), (T + 1, B, N, D)))
   score = torch.empty((B, P), dtype=torch.float32, device=state0.device)
   with torch.cuda.device(state0.device):
-    _abi().ggnn_forward_states(state0, ld0, L, L.stride(0), L.stride(1), L.stride(2), L.stride(3), mask, W1, b1,
-                               W2, b2, Wih, bih, Whh, bhh, Wo, bo, wg, bg, B, N, C, D, P, T, int(bool(avg)), score,
-                               None, D, states, int(tile_rows))
+    _abi().ggnn_forward_states(state0, ld0, L, L.stride(0), L.stride(1), L.stride(2), L.stride(3), mask, *prop,
+                               *head, B, N, C, D, P, T, int(bool(avg)), score, None, D, states, int(tile_rows))
   return score, states
 
 
@@ -2736,15 +2737,9 @@ def ggnn_backward_step(S, dSnext, L, W1, b1, W2, b2, Wih, bih, Whh, bhh, transpo
   tr = tuple(transposes) if transposes is not None else ()
   bufs = tuple(buffers) if buffers is not None else ()
   _need_cuda(S, dSnext, L, W1, b1, W2, b2, Wih, bih, Whh, bhh, dS, *(tr + bufs))
-  if S.dim() != 3 or L.dim() != 4 or L.dtype != torch.float32:
-    raise LnzError(_lib.LNZ_EINVAL, '%s: S [B, N, D] and a float32 L [B, N, N, C] expected' % who)
-  B, N, D = S.shape
-  C = L.shape[3]
-  if tuple(L.shape[:3]) != (B, N, N) or tuple(dSnext.shape) != (B, N, D):
-    raise LnzError(_lib.LNZ_EINVAL, '%s: S %s, dSnext %s and L %s do not fit'
-                   % (who, tuple(S.shape), tuple(dSnext.shape), tuple(L.shape)))
-  lds, ldd = _gat_rows(S, who), _gat_rows(dSnext, who)
-  W1, b1, W2, b2, Wih, bih, Whh, bhh = _ggnn_operands(who, C, D, W1, b1, W2, b2, Wih, bih, Whh, bhh)
+  (B, N, C, D), (lds, ldd), prop = _propagation_operands(who, S, L, W1, b1, W2, b2, Wih, bih, Whh, bhh,
+                                                         GGNN_MSG_HIDDEN, name='S', like=(('dSnext', dSnext),))
+  W1, _, W2, _, Wih, _, Whh, _ = prop
   if transposes is None:
     tr = ggnn_pack_transposes(W1, W2, Wih, Whh)
   Hd = GGNN_MSG_HIDDEN
@@ -2754,11 +2749,7 @@ def ggnn_backward_step(S, dSnext, L, W1, b1, W2, b2, Wih, bih, Whh, bhh, transpo
     if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous():
       raise LnzError(_lib.LNZ_EINVAL, '%s: transposed weight %s where a contiguous float32 %s is expected'
                      % (who, tuple(t.shape), shape))
-  if dS is None:
-    dS = torch.empty((B, N, D), dtype=torch.float32, device=S.device)
-  if tuple(dS.shape) != (B, N, D):
-    raise LnzError(_lib.LNZ_EINVAL, '%s: dS %s, expected %s' % (who, tuple(dS.shape), (B, N, D)))
-  ldo = _gat_rows(dS, who)
+  dS, ldo = _state_buffer(who, 'dS', dS, B, N, D, S.device)
   if buffers is None:
     bufs = ggnn_step_buffers(B, N, C, D, S.device)
   if len(bufs) != 6:
@@ -2768,9 +2759,8 @@ def ggnn_backward_step(S, dSnext, L, W1, b1, W2, b2, Wih, bih, Whh, bhh, transpo
       raise LnzError(_lib.LNZ_EINVAL, '%s: row-space buffer %s where a contiguous float32 %s is expected'
                      % (who, tuple(t.shape), (B * N, w)))
   with torch.cuda.device(S.device):
-    _abi().ggnn_backward_step(S, lds, dSnext, ldd, L, L.stride(0), L.stride(1), L.stride(2), L.stride(3), W1, b1,
-                              W2, b2, Wih, bih, Whh, bhh, tr[0], tr[1], tr[2], tr[3], B, N, C, D, int(bool(avg)),
-                              dS, ldo, *bufs)
+    _abi().ggnn_backward_step(S, lds, dSnext, ldd, L, L.stride(0), L.stride(1), L.stride(2), L.stride(3), *prop,
+                              *tr, B, N, C, D, int(bool(avg)), dS, ldo, *bufs)
   return dS, bufs
 
 
@@ -2831,29 +2821,16 @@ def ggnn_readout_backward(Slast, mask, Wo, bo, wg, bg, dscore, dSlast=None):
     raise LnzError(_lib.LNZ_EINVAL, '%s: Slast [B, N, D] expected' % who)
   B, N, D = Slast.shape
   ld = _gat_rows(Slast, who)
-  Wo, bo, wg, bg = _f32c(Wo), _f32c(bo).reshape(-1), _f32c(wg).reshape(-1), _f32c(bg).reshape(-1)
-  P = Wo.shape[0]
-  if tuple(Wo.shape) != (P, D) or bo.numel() != P or wg.numel() != D or bg.numel() != 1:
-    raise LnzError(_lib.LNZ_EINVAL, '%s: head operands %s, %s, %s, %s do not fit D = %d'
-                   % (who, tuple(Wo.shape), tuple(bo.shape), tuple(wg.shape), tuple(bg.shape), D))
+  P, mask, head = _gated_readout_operands(who, B, N, D, mask, Wo, bo, wg, bg, together=True)
   if tuple(dscore.shape) != (B, P):
     raise LnzError(_lib.LNZ_EINVAL, '%s: dscore %s, expected %s' % (who, tuple(dscore.shape), (B, P)))
   dscore = _f32c(dscore)
-  if mask is not None:
-    if tuple(mask.shape) != (B, N):
-      raise LnzError(_lib.LNZ_EINVAL, '%s: mask %s, expected %s' % (who, tuple(mask.shape), (B, N)))
-    mask = (mask != 0).to(torch.uint8).contiguous()
-  if dSlast is None:
-    dSlast = torch.empty((B, N, D), dtype=torch.float32, device=Slast.device)
-  if tuple(dSlast.shape) != (B, N, D):
-    raise LnzError(_lib.LNZ_EINVAL, '%s: dSlast %s, expected %s' % (who, tuple(dSlast.shape), (B, N, D)))
-  ldg = _gat_rows(dSlast, who)
+  dSlast, ldg = _state_buffer(who, 'dSlast', dSlast, B, N, D, Slast.device)
   new = lambda *s: torch.empty(s, dtype=torch.float32, device=Slast.device)  # noqa: E731
   dWo, dbo, dwg, dbg = new(P, D), new(P), new(D), new(1)
   with torch.cuda.device(Slast.device):
     ws = new(max(int(_abi().ggnn_readout_backward_workspace_floats(B, D, P)), 1))
-    _abi().ggnn_readout_backward(Slast, ld, mask, Wo, bo, wg, bg, dscore, B, N, D, P, ws, dSlast, ldg, dWo, dbo,
-                                 dwg, dbg)
+    _abi().ggnn_readout_backward(Slast, ld, mask, *head, dscore, B, N, D, P, ws, dSlast, ldg, dWo, dbo, dwg, dbg)
   return dSlast, dWo, dbo, dwg, dbg
 
 
@@ -2871,28 +2848,12 @@ def mpnn_forward(state0, L, W1, b1, W2, b2, Wih, bih, Whh, bhh, num_prop, avg=Tr
   tile_rows: 0 = chosen by the batch, 32 or 64 rows of state per workgroup (a row's bits do not depend on it)."""
   who = 'mpnn_forward'
   _need_cuda(state0, L, W1, b1, W2, b2, Wih, bih, Whh, bhh, state_out)
-  if state0.dim() != 3 or L.dim() != 4 or L.dtype != torch.float32:
-    raise LnzError(_lib.LNZ_EINVAL, '%s: state0 [B, N, D] and a float32 L [B, N, N, C] expected' % who)
-  B, N, D = state0.shape
-  C = L.shape[3]
-  if tuple(L.shape[:3]) != (B, N, N):
-    raise LnzError(_lib.LNZ_EINVAL, '%s: state0 %s and L %s do not fit' % (who, tuple(state0.shape), tuple(L.shape)))
-  ld0 = _gat_rows(state0, who)
-  W1, b1, W2, b2 = _f32c(W1), _f32c(b1), _f32c(W2), _f32c(b2)
-  Wih, bih, Whh, bhh = _f32c(Wih), _f32c(bih).reshape(-1), _f32c(Whh), _f32c(bhh).reshape(-1)
-  Hd = MPNN_MSG_HIDDEN
-  for t, shape in ((W1, (C, Hd, 2 * D)), (b1, (C, Hd)), (W2, (C, D, Hd)), (b2, (C, D)), (Wih, (3 * D, C * D)),
-                   (bih, (3 * D,)), (Whh, (3 * D, D)), (bhh, (3 * D,))):
-    if tuple(t.shape) != shape:
-      raise LnzError(_lib.LNZ_EINVAL, '%s: operand of shape %s where %s is expected' % (who, tuple(t.shape), shape))
-  if state_out is None:
-    state_out = torch.empty((B, N, D), dtype=torch.float32, device=state0.device)
-  if tuple(state_out.shape) != (B, N, D):
-    raise LnzError(_lib.LNZ_EINVAL, '%s: state_out %s, expected %s' % (who, tuple(state_out.shape), (B, N, D)))
-  ldso = _gat_rows(state_out, who)
+  (B, N, C, D), (ld0,), prop = _propagation_operands(who, state0, L, W1, b1, W2, b2, Wih, bih, Whh, bhh,
+                                                     MPNN_MSG_HIDDEN, w1_cols=2)
+  state_out, ldso = _state_buffer(who, 'state_out', state_out, B, N, D, state0.device)
   with torch.cuda.device(state0.device):
-    _abi().mpnn_forward(state0, ld0, L, L.stride(0), L.stride(1), L.stride(2), L.stride(3), W1, b1, W2, b2, Wih, bih,
-                        Whh, bhh, B, N, C, D, int(num_prop), int(bool(avg)), state_out, ldso, int(tile_rows))
+    _abi().mpnn_forward(state0, ld0, L, L.stride(0), L.stride(1), L.stride(2), L.stride(3), *prop, B, N, C, D,
+                        int(num_prop), int(bool(avg)), state_out, ldso, int(tile_rows))
   return state_out
 
 

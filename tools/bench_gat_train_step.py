@@ -32,7 +32,7 @@ from tools.bench_gat import config  # noqa: E402
 
 ROUTES = (('gat_torch', 'torch'), ('gat_hip_train', 'hip'))   # switch off, switch on
 GROUPS = (('backward_kernels', ('gat_attention_backward_kernel', 'gat_readout_backward_kernel',
-                                'gat_partial_sum_kernel')),
+                                'partial_sum_kernel')),
           ('forward_kernels', ('gat_attention_kernel', 'gat_readout_kernel')),
           ('linears', ('f32_linear_kernel',)))
 

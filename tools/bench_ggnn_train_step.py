@@ -32,7 +32,7 @@ from tools.bench_ggnn import config  # noqa: E402
 
 ROUTES = (('ggnn_torch', 'torch'), ('ggnn_hip_train', 'hip'))   # switch off, switch on
 GROUPS = (('step_kernel', ('ggnn_backward_step_kernel',)),
-          ('readout_backward', ('ggnn_readout_backward_kernel', 'ggnn_partial_sum_kernel')),
+          ('readout_backward', ('ggnn_readout_backward_kernel', 'partial_sum_kernel')),
           ('forward_kernel', ('ggnn_forward_kernel',)),
           ('linears', ('f32_linear_kernel',)),
           ('library_gemms', ('Cijk_', 'gemm', 'Gemm')))

@@ -59,6 +59,10 @@ ATTENTION_CASES = [
     (32, 8, 16, 4, 1, False, 0, 'plain'),
     (32, 1, 1, 32, 1, True, 0, 'plain'),
     (1, 8, 16, 32, 3, True, 0, 'plain'),
+    # a round of four heads after the first with live and idle waves: H = 5 (1 of 4), 13 (1 of 4), 6 (2 of 4)
+    (9, 2, 5, 8, 2, True, 0, 'plain'),
+    (32, 1, 13, 32, 1, False, 0, 'plain'),
+    (17, 3, 6, 16, 2, True, 4, 'plain'),
 ]
 
 

@@ -11,7 +11,12 @@ channel order against float64, eight runs per shape, the eight shapes below (B <
 C 2, D 32, 15 steps; e32 itself 1e-7 .. 6e-7), so K = 4 holds for 'avg'; 'sum' 1.2 .. 2.6 at one step
 but 1.9 .. 10.5 at 15 steps (7.9 at N 31, C 2, D 32; 10.5 at N 32, C 1, D 96; e32 up to 5.9e-5: an
 unnormalised sum over up to 32 neighbours grows the state's sensitivity step by step), so for 'sum'
-K is that measured spread, 10.5.  The kernel's own output never enters the bar.
+K is that measured spread, 10.5.  tools/ggnn_reference_spread.py (CPU only) re-measures these figures from
+this file's own operand draws, the thirteen shapes below, state and score: 'avg' 1.2 .. 2.9, 'sum' at a
+shape's own num_prop 1.3 .. 5.7 and at 15 steps up to 7.2 (N 32, C 1, D 96) and 13.1 (the score at N 31, C 2,
+D 32, which the test runs at 2 steps: 4.0); the five rows with several molecules per tile give 'avg' <= 2.9
+and 'sum' <= 4.6.  The figure of a 15-step 'sum' moves with the draws; K stays at 10.5, the lower of the two
+measurements and so the stricter bar.  The kernel's own output never enters the bar.
 Module level: max(1e-5, 4 e_ref) max|s64| with e_ref read from the fixture."""
 import warnings
 
@@ -80,8 +85,11 @@ def _run(S, L, W, mask, num_prop, agg, Ld=None, pad=0, tile_rows=0):
 
 
 def _check(tag, S, L, W, mask, num_prop, agg, **kw):
+  from lanczosnet_amd import ops
   score, state, outbuf = _run(S, L, W, mask, num_prop, agg, tile_rows=64, **kw)
+  assert ops.last_kernel() == 'ggnn_forward_kernel<%d, 4>' % S.shape[2]
   score32, state32, _ = _run(S, L, W, mask, num_prop, agg, tile_rows=32, **kw)
+  assert ops.last_kernel() == 'ggnn_forward_kernel<%d, 2>' % S.shape[2]
   assert torch.equal(score32, score) and torch.equal(state32, state)   # a row's bits do not depend on the tile height
   s32, y32 = _mirror(S, L, W, mask, num_prop, agg, torch.float32)
   s64, y64 = _mirror(S, L, W, mask, num_prop, agg, torch.float64)
@@ -105,6 +113,12 @@ KERNEL_CASES = [
     (32, 8, 128, 3, 15, 'avg', 'ragged', 0, 'plain'),
     (32, 7, 128, 65, 2, 'avg', None, 0, 'plain'),
     (32, 1, 96, 1, 0, 'sum', 'one', 0, 'plain'),
+    # several molecules per tile and a further tile behind its dead rows; steps at D = 96 and D = 64 at both heights
+    (5, 3, 96, 14, 3, 'avg', 'ragged', 4, 'plain'),       # tiles of 6, 6, 2 molecules (32 rows), of 12, 2 (64 rows)
+    (32, 2, 96, 3, 2, 'sum', None, 0, 'sliced'),          # D = 96 with all 32 bits of a row mask
+    (11, 2, 64, 7, 3, 'sum', 'one', 0, 'expanded'),       # 2, 2, 2, 1 and 5, 2
+    (3, 1, 128, 23, 2, 'avg', 'ragged', 8, 'plain'),      # 10 per 32-row tile, 21 per 64-row tile: 63 live rows
+    (16, 8, 64, 5, 2, 'avg', None, 0, 'plain'),           # C at its limit, tiles exactly full, one molecule left
 ]
 
 

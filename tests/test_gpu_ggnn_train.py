@@ -31,7 +31,8 @@ ULP = 2.0 ** -23
 # gradient tensors of a case; e32 itself 5e-8 .. 1.1e-6): 'avg' 1.8 .. 2.3 (2.19 at N 5, 1.83 at N 16, 2.29 at
 # N 31: dbih, 1.78 at N 32 with 15 steps), 'sum' 1.0 .. 2.5 (1.00 at N 1, where five of the nine truths are
 # identically zero, 2.10 at N 17, 2.51 at N 32: dbhh; no 'sum' case runs 15 steps here) — below 4 for both
-# aggregates, so K stays at the project's 4.
+# aggregates, so K stays at the project's 4.  The two cases with several molecules per tile: 1.72 at N 5, D 96, 'avg'
+# (dbih), 2.14 at N 11, D 64, 'sum' (dbhh).
 K = {'avg': 4.0, 'sum': 4.0}
 
 # (N, C, D, B, steps, agg, row padding, how L reaches the kernel); B = 65 crosses a tile boundary with a
@@ -44,6 +45,8 @@ STEP_CASES = [
     (31, 2, 32, 65, 2, 'avg', 4, 'expanded'),
     (32, 8, 128, 3, 15, 'avg', 0, 'plain'),
     (32, 1, 96, 2, 3, 'sum', 0, 'plain'),
+    (5, 3, 96, 14, 3, 'avg', 4, 'plain'),                 # tiles of 6, 6, 2 molecules: dead rows, then a tile
+    (11, 2, 64, 7, 3, 'sum', 0, 'plain'),                 # tiles of 2, 2, 2, 1
 ]
 
 
@@ -90,6 +93,7 @@ def _hip_backward(S, dST, Ld, W, steps, agg, pad=0):
   for t in range(steps - 1, -1, -1):
     St, _ = _padded(states[t], pad)
     spare, _ = ops.ggnn_backward_step(St, dS, Ld, *Wd[:8], transposes=tr, avg=avg, dS=spare, buffers=bufs)
+    assert ops.last_kernel() == 'ggnn_backward_step_kernel<%d>' % D
     dS, spare = spare, dS
     grads = ops.ggnn_step_weight_grads(St, bufs, C, grads)
   return [dS] + list(grads), (buf_a, buf_b)
@@ -246,7 +250,7 @@ def test_the_ops_are_bitwise_reproducible_and_the_raw_ops_give_the_same_bits():
 
 
 @pytest.mark.parametrize('N,C,D,B,steps,tile', [(5, 2, 32, 3, 2, 0), (31, 7, 128, 5, 3, 64), (17, 2, 64, 4, 15, 32),
-                                                 (8, 1, 96, 2, 0, 0)])
+                                                 (8, 1, 96, 2, 0, 0), (5, 3, 96, 14, 3, 64), (11, 2, 64, 7, 3, 32)])
 def test_forward_states_has_the_bits_of_the_forward_and_leaves_the_trajectory(N, C, D, B, steps, tile):
   from lanczosnet_amd import ops
   S, L, W = GM.draw_operands(97 + N, B, N, C, D)
@@ -254,6 +258,8 @@ def test_forward_states_has_the_bits_of_the_forward_and_leaves_the_trajectory(N,
   mask = _mask('ragged', B, N, 6).cuda()
   score, final = ops.ggnn_forward(Sd, Ld, mask, *Wd, steps, avg=True, return_state=True, tile_rows=tile)
   s2, states = ops.ggnn_forward_states(Sd, Ld, mask, *Wd, steps, avg=True, tile_rows=tile)
+  if tile:
+    assert ops.last_kernel() == 'ggnn_forward_kernel<%d, %d>' % (D, tile // 16)
   assert tuple(states.shape) == (steps + 1, B, N, D)
   assert torch.equal(s2, score) and torch.equal(states[steps], final) and torch.equal(states[0], Sd)
   for t in range(steps):   # every S_t is the state after t steps of the forward

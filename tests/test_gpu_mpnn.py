@@ -8,11 +8,15 @@ the kernel has to be within max(K e32, 4 fp32 ulps) max|ref64| of float64.  (The
 propagation is the factored mirror: it agrees with the pairwise one to 1e-15, test_mpnn_cpu.py.)
 K starts at the project's 4: another summation order draws another sample of the same rounding.
 Measured before relying on it (CPU, the float32 pairwise mirror with one-ulp-perturbed operands and a
-permuted channel order against float64, eight draws per shape, the eight shapes below (B <= 9) at their own
+permuted channel order against float64, eight draws per shape, the thirteen shapes below (B <= 9) at their own
 num_prop and at 7, each with 'avg' and with 'sum'), worst / best e32 of the eight draws: 'avg' 1.2 .. 5.0
-(worst: N 1, C 1, D 32, 7 steps; e32 itself 5e-8 .. 6e-7), 'sum' 1.6 .. 5.3 (worst: N 32, C 8, D 128, 7 steps;
+(worst: N 1, C 1, D 32, 7 steps; e32 itself 5e-8 .. 6e-7), 'sum' 1.5 .. 5.3 (worst: N 32, C 8, D 128, 7 steps;
 e32 up to 1.3e-4: an unnormalised sum over up to 32 neighbours grows the state's sensitivity step by step).
-Set2Vec (the shapes below, one-ulp-perturbed operands, eight draws): 2.1 .. 4.2 (worst: N 5, D 32, 3 steps).
+The five rows with several molecules per tile stay below both: 'avg' 1.17 .. 1.72 (worst: N 16, C 8, D 64,
+2 steps), 'sum' 1.45 .. 2.95 (worst: N 32, C 2, D 96, 7 steps).
+Set2Vec (the shapes below, one-ulp-perturbed operands, eight draws): 1.2 .. 4.2 (worst: N 5, D 32, 3 steps;
+the two D = 96 shapes 1.97 and 1.24).  GRU(0, S), the zero-L case of the cell test, both float32 mirrors,
+D 32 .. 128: 1.1 .. 2.0.
 All three exceed 4, so K is the measured spread: 5.0, 5.3 and 4.2.
 tools/mpnn_reference_spread.py (CPU only) re-measures these figures from this file's own operand draws.
 The kernel's own output never enters the bar.
@@ -84,11 +88,19 @@ KERNEL_CASES = [
     (32, 8, 128, 3, 7, 'avg', 0, 'plain'),
     (32, 7, 128, 65, 2, 'avg', 0, 'plain'),
     (32, 1, 96, 1, 0, 'sum', 0, 'plain'),
+    # several molecules per tile and a further tile behind its dead rows; steps at D = 96 (six of the eight waves
+    # own features, all eight produce [P|Q]) and at D = 64 at both heights
+    (5, 3, 96, 14, 3, 'avg', 4, 'plain'),                 # tiles of 6, 6, 2 molecules (32 rows), of 12, 2 (64 rows)
+    (32, 2, 96, 3, 2, 'sum', 0, 'sliced'),                # D = 96 with all 32 bits of a row mask
+    (11, 2, 64, 7, 3, 'sum', 0, 'expanded'),              # 2, 2, 2, 1 and 5, 2
+    (3, 1, 128, 23, 2, 'avg', 8, 'plain'),                # 10 per 32-row tile, 21 per 64-row tile: 63 live rows
+    (16, 8, 64, 5, 2, 'avg', 0, 'plain'),                 # C at its limit, tiles exactly full, one molecule left
 ]
 
 
 @pytest.mark.parametrize('N,C,D,B,num_prop,agg,pad,lkind', KERNEL_CASES)
 def test_mpnn_forward_matches_float64(N, C, D, B, num_prop, agg, pad, lkind):
+  from lanczosnet_amd import ops
   S, L, W = _operands(4000 + N + 7 * C + D, B, N, C, D)
   if lkind == 'expanded':   # one channel, seen C times through a zero stride
     L = L[..., :1].expand(B, N, N, C)
@@ -105,7 +117,9 @@ def test_mpnn_forward_matches_float64(N, C, D, B, num_prop, agg, pad, lkind):
   assert (L < 0).any() and bool((L[0, 0, :, 0] != 0).all())
   before = Ld.clone()
   state, outbuf = _run(S, Ld, W, num_prop, agg, pad=pad, tile_rows=64)
+  assert ops.last_kernel() == 'mpnn_forward_kernel<%d, 4>' % D
   state32, _ = _run(S, Ld, W, num_prop, agg, pad=pad, tile_rows=32)
+  assert ops.last_kernel() == 'mpnn_forward_kernel<%d, 2>' % D
   assert torch.equal(state32, state)                          # a row's bits do not depend on the tile height
   again, _ = _run(S, Ld, W, num_prop, agg, pad=pad, tile_rows=64)
   assert torch.equal(again, state)                            # bitwise from call to call
@@ -170,6 +184,71 @@ def test_the_tile_height_follows_the_batch_and_bad_arguments_raise():
     ops.mpnn_forward(S, Ld, *Wd, 1)                            # a host tensor
 
 
+# ------------------------------------------------------------------- the cell, across the two forwards
+ZERO_MESSAGE = dict(N=5, B=14, C=2, steps=3)   # tiles of 6, 6, 2 molecules (32 rows) and of 12, 2 (64 rows)
+
+
+def zero_message_case(D):
+  """CPU.  With L identically zero every message is exactly 0 in both models (GGNN: an empty bit row sums nothing
+  and the gate product of zeros is +0; MPNN: R = 0, deg = 0, 0 / (0 + eps) = 0), so ggnn_forward and mpnn_forward
+  both compute GRU(0, S) step by step.  -> (S, L, the MPNN operands, the GGNN operands with the MPNN draw's four
+  cell operands, the float64 truth, e32 of the float32 MPNN mirror, e32 of the float32 GGNN mirror); the truth is
+  the float64 MPNN mirror, and the float64 GGNN mirror and torch.nn.GRUCell on a zero input agree with it."""
+  import ggnn_mirror as GG
+  import test_gpu_ggnn as TG
+  N, B, C, steps = (ZERO_MESSAGE[k] for k in ('N', 'B', 'C', 'steps'))
+  S, _, W = _operands(4500 + D, B, N, C, D)
+  Wg = TG._operands(3500 + D, B, N, C, D)[2]
+  Wg[4:8] = W[4:8]                                             # one cell: Wih, bih, Whh, bhh
+  L = torch.zeros(B, N, N, C)
+  d = lambda ws: [w.double() for w in ws]  # noqa: E731
+  truth = G.propagate_factored(S.double(), L.double(), *d(W), steps, agg='avg')
+  cell = torch.nn.GRUCell(C * D, D).double()
+  with torch.no_grad():
+    for p, w in zip((cell.weight_ih, cell.bias_ih, cell.weight_hh, cell.bias_hh), W[4:8]):
+      p.copy_(w.double())
+    h = S.double().reshape(B * N, D)
+    for _ in range(steps):
+      h = cell(torch.zeros(B * N, C * D, dtype=torch.float64), h)
+  scale = float(truth.abs().max())
+  for agg in ('avg', 'sum'):
+    for other in (h.reshape(B, N, D), G.propagate_factored(S.double(), L.double(), *d(W), steps, agg=agg),
+                  GG.propagate(S.double(), L.double(), *d(Wg[:8]), steps, agg=agg)):
+      assert float((other - truth).abs().max()) <= 1e-14 * scale
+  e32 = [float((r.double() - truth).abs().max()) / scale
+         for r in (G.propagate_pairwise(S, L, *W, steps, agg='avg'), GG.propagate(S, L, *Wg[:8], steps, agg='avg'))]
+  return S, L, W, Wg, truth, e32[0], e32[1]
+
+
+@pytest.mark.parametrize('D', [32, 64, 96, 128])
+def test_the_cell_has_the_same_bits_in_ggnn_forward_and_in_mpnn_forward(D):
+  """ggnn_tile.hpp: "the arithmetic all three kernels promise to share to the bit".  GRU(0, S) from both forwards
+  with the same cell operands: each within this file's bar of float64, the same bits at both tile heights, and
+  the same bits in the two kernels."""
+  from lanczosnet_amd import ops
+  S, L, W, Wg, truth, e32_m, e32_g = zero_message_case(D)
+  steps = ZERO_MESSAGE['steps']
+  scale = float(truth.abs().max())
+  Sd, Ld, Wd, Wgd = S.cuda(), L.cuda(), [w.cuda() for w in W], [w.cuda() for w in Wg]
+  for agg in ('avg', 'sum'):
+    states = {}
+    for rows in (32, 64):
+      m = ops.mpnn_forward(Sd, Ld, *Wd, steps, avg=agg == 'avg', tile_rows=rows)
+      assert ops.last_kernel() == 'mpnn_forward_kernel<%d, %d>' % (D, rows // 16)
+      g = ops.ggnn_forward(Sd, Ld, None, *Wgd, steps, avg=agg == 'avg', return_state=True, tile_rows=rows)[1]
+      assert ops.last_kernel() == 'ggnn_forward_kernel<%d, %d>' % (D, rows // 16)
+      states[rows] = (m, g)
+      for who, got, e32 in (('mpnn_forward', m, e32_m), ('ggnn_forward', g, e32_g)):
+        err, bar = float((got.double().cpu() - truth).abs().max()) / scale, max(K[agg] * e32, 4.0 * ULP)
+        print('%s GRU(0, S) D %d %s, %d-row tiles: %.2e of the scale, float32 reference %.2e, bar %.2e'
+              % (who, D, agg, rows, err, e32, bar))
+        assert torch.isfinite(got).all() and err <= bar, who
+    for k, who in enumerate(('mpnn_forward', 'ggnn_forward')):
+      assert torch.equal(states[32][k], states[64][k]), who       # a row's bits do not depend on the tile height
+    for rows in (32, 64):
+      assert torch.equal(states[rows][0], states[rows][1]), rows  # one cell: the same bits in both kernels
+
+
 # ----------------------------------------------------------------------------------------- Set2Vec
 def _set_operands(seed, B, N, D, P, mkind, w2_scale=1.0):
   g = torch.Generator().manual_seed(seed)
@@ -203,13 +282,18 @@ SET_CASES = [
     (32, 128, 17, 10, 16, 'ragged'),
     (32, 128, 2, 10, 16, None),
     (7, 64, 3, 0, 1, 'ragged'),
+    # D = 96: the energy loop gives lanes 0 .. 7 of a sixteen-lane group two float4 and lanes 8 .. 15 one
+    (9, 96, 19, 4, 16, 'ragged'),                         # groups of 16 + 3, of 5, 5, 5, 4
+    (32, 96, 3, 3, 16, 'ragged'),
 ]
 
 
 @pytest.mark.parametrize('N,D,B,steps,P,mkind', SET_CASES)
 def test_set2vec_readout_matches_float64(N, D, B, steps, P, mkind):
   X, mask, W = _set_operands(5000 + N + D + B, B, N, D, P, mkind)
+  from lanczosnet_amd import ops
   score = _set_run(X, mask, W, steps, mols_per_group=16)       # B = 17: a full tile of 16 and a remainder of one
+  assert ops.last_kernel() == 'set2vec_readout_kernel<%d> x 16' % D
   assert torch.equal(_set_run(X, mask, W, steps, mols_per_group=16), score)   # bitwise from call to call
   for mpw in (0, 1, 5):   # a molecule's bits do not depend on the molecules per workgroup (0: chosen by the batch)
     assert torch.equal(_set_run(X, mask, W, steps, mols_per_group=mpw), score), mpw

@@ -121,6 +121,17 @@ def test_float64_mirrors_match_the_reference_float64_scores(name, factored):
   assert np.array_equal(batch['L'], L0)                                  # the mirror leaves L alone
 
 
+@pytest.mark.parametrize('D', [32, 64, 96, 128])
+def test_a_zero_l_leaves_both_mirrors_with_the_gru_cell_on_a_zero_input(D):
+  """the yardstick of the GPU test that compares the cell of ggnn_forward and mpnn_forward: with L = 0 the float64
+  MPNN and GGNN mirrors, 'avg' and 'sum', are torch.nn.GRUCell on a zero input (asserted inside, to 1e-14)"""
+  import test_gpu_mpnn as T
+  S, L, W, Wg, truth, e32_m, e32_g = T.zero_message_case(D)
+  assert not L.any() and all(torch.equal(a, b) for a, b in zip(W[4:8], Wg[4:8]))
+  assert float((truth - S.double()).abs().max()) > 1e-2                  # the state moved
+  assert 0.0 < e32_m < 1e-5 and 0.0 < e32_g < 1e-5
+
+
 def test_the_module_float64_torch_restatement_matches_the_reference_on_the_host():
   """route 'mpnn_torch' is plain torch: called directly (forward() itself refuses a CPU module) in float64 it
   reproduces the reference's float64 scores, MLP and embedding, masked and not"""

@@ -5,8 +5,11 @@ num_prop and at 7, with 'avg' and with 'sum': the float32 pairwise mirror (tests
 evaluated eight times — once as drawn, seven times with every operand moved by -1, 0 or +1 ulp and the
 channels of the gate sum in a random order — and each run's error against the float64 mirror is taken;
 the figure is worst / best of the eight.  The same for Set2Vec (the per-molecule loop, operands moved by
-an ulp).  No kernel runs and no GPU is needed: the bar of the GPU tests comes from the reference alone.
-Prints one line per shape and the largest ratio per kind (measured: 'avg' 5.0, 'sum' 5.3, Set2Vec 4.2).
+an ulp), and for GRU(0, S), the zero-L case of the test that compares the cell of the two forwards (both
+float32 mirrors).  No kernel runs and no GPU is needed: the bar of the GPU tests comes from the reference alone.
+Prints one line per shape and the largest ratio per kind (measured: 'avg' 5.00, 'sum' 5.29, Set2Vec 4.17 — all
+three at the shapes they had before; the rows with several molecules per tile and D = 96 / 64 steps give
+'avg' <= 1.72, 'sum' <= 2.95, Set2Vec at D = 96 <= 1.97, GRU(0, S) <= 1.98).
 
     python tools/mpnn_reference_spread.py
 """
@@ -59,6 +62,28 @@ def propagation():
   return worst
 
 
+def cell():
+  """the zero-message case of the test that compares the cell across the two forwards: GRU(0, S), both mirrors"""
+  import ggnn_mirror as GG
+  worst = 0.0
+  steps = T.ZERO_MESSAGE['steps']
+  for D in (32, 64, 96, 128):
+    S, L, W, Wg, r64, _, _ = T.zero_message_case(D)
+    scale = float(r64.abs().max())
+    for who, ws, fn in (('mpnn', W, G.propagate_pairwise), ('ggnn', Wg[:8], GG.propagate)):
+      g = torch.Generator().manual_seed(3)
+      errors = []
+      for k in range(DRAWS):
+        Sp = one_ulp(S, g) if k else S
+        Wp = [one_ulp(w, g) for w in ws] if k else ws
+        order = torch.randperm(L.shape[3], generator=g).tolist() if k else None
+        errors.append(float((fn(Sp, L, *Wp, steps, agg='avg', order=order).double() - r64).abs().max()) / scale)
+      worst = max(worst, ratio(errors))
+      print('GRU(0, S) %s D %d steps %d: e32 %.2e .. %.2e, worst / best %.2f'
+            % (who, D, steps, min(errors), max(errors), ratio(errors)), flush=True)
+  return worst
+
+
 def set2vec():
   worst = 0.0
   for N, D, B, steps, P, mkind in T.SET_CASES:
@@ -82,5 +107,6 @@ def set2vec():
 if __name__ == '__main__':
   torch.set_num_threads(min(8, os.cpu_count() or 1))
   w = propagation()
+  c = cell()
   s = set2vec()
-  print("largest worst / best: 'avg' %.2f, 'sum' %.2f, Set2Vec %.2f" % (w['avg'], w['sum'], s))
+  print("largest worst / best: 'avg' %.2f, 'sum' %.2f, GRU(0, S) %.2f, Set2Vec %.2f" % (w['avg'], w['sum'], c, s))

@@ -84,7 +84,8 @@ int lnz_abi_version(void);
 const char* lnz_last_error(void);
 /* The kernel (name with template arguments) the calling thread's last lnz_lanczosnet_forward /
  * _input_grad launch selected — the launchers choose between the strip and 32 x 32-tile kernels by
- * shape and plan; measurements name what ran instead of restating the rule. */
+ * shape and plan; measurements name what ran instead of restating the rule.  The other launchers
+ * that choose between kernels or instantiations note theirs the same way (named at each entry). */
 const char* lnz_last_kernel(void);
 
 /* ---- R1: graph Laplacian ------------------------------------------------------------
@@ -92,8 +93,14 @@ const char* lnz_last_kernel(void);
  * bond-type channel e (channel 1+e), written channels-last like the collate output.
  * Replaces utils/data_helper.py:92-116,155-156 (normalize_adj / get_laplacian 'L4'),
  * dataset/get_qm8_data.py:62-75 and the L part of dataset/qm8.py:225-262.
- * adjs [B,N,N,E]; n_nodes [B] (rows/cols >= n are written as exact zeros); L [B,N,N,E+1].
- * Arithmetic in fp64 (the reference builds L4 in float64), stored as float32. */
+ * adjs [B,N,N,E]; n_nodes [B] (rows/cols >= n are written as exact zeros and never enter a degree,
+ * whatever they hold; a count outside [0, N] is clamped to it, as lnz_collate_qm8 clamps);
+ * L [B,N,N,E+1].  Arithmetic in fp64 (the reference builds L4 in float64), stored as float32.
+ * A row of I + A whose sum is not positive — zero or negative — gives a zero row and column (the
+ * reference's inf -> 0 guard covers the zero sum; for a negative one it returns NaN, see below).
+ * lnz_last_kernel() names laplacian_l4_kernel<staged> (a graph's adjacency block staged in LDS by
+ * 16-byte loads: it fits beside the degrees in 64 KiB, N*N*E is a multiple of 4 and adjs is 16-byte
+ * aligned) or laplacian_l4_kernel<direct>; the same bits either way. */
 int lnz_laplacian_l4(const float* adjs, const int32_t* n_nodes, int B, int N, int E,
                      float* L, lnz_stream_t stream);
 /* Every kind of get_laplacian (utils/data_helper.py:119-166 over normalize_adj :92-116), same
@@ -102,7 +109,10 @@ int lnz_laplacian_l4(const float* adjs, const int32_t* n_nodes, int B, int N, in
  * the normalised matrix, D^-x of an isolated node = 0 like the reference's inf guard), alpha only
  * for kind 6 (reference default 0.5).  The reference's offline scripts store L6 / L7 of the simple
  * graph for the ChebyNet / DCNN baselines (dataset/get_qm8_data.py:73-77,
- * dataset/get_graph_data.py:70-75).  kind 4 is lnz_laplacian_l4 bit for bit. */
+ * dataset/get_graph_data.py:70-75).  n_nodes is clamped to [0, N] as above.  kind 4 is
+ * lnz_laplacian_l4 bit for bit wherever every row sum of I + A is >= 0.  For a negative row sum the
+ * two differ: lnz_laplacian keeps the reference's pow(d, -1/2) = NaN (that row and column are NaN),
+ * lnz_laplacian_l4 writes a zero row and column.  lnz_last_kernel() names laplacian_kind_kernel<kind>. */
 int lnz_laplacian(const float* adjs, const int32_t* n_nodes, int B, int N, int E, int kind,
                   double alpha, float* L, lnz_stream_t stream);
 
@@ -676,7 +686,8 @@ int lnz_spectral_mlp_grad(const float* D, int B, int K, const int32_t* dist_host
  * (clamped to [0, num_atom) as the forward clamps) of dx[b * mol_stride + i * row_stride + c], c <
  * width — autograd's embedding backward (model/lanczos_net.py:154), without atomics: workgroup
  * (a, chunk) writes partials[chunk][a][width], the gradient is their sum over `chunks` (any fixed
- * order).  ids [B, N] int64; width in {16, 32, 64, 128}; strides in floats, multiples of 4. */
+ * order).  ids [B, N] int64; width in {16, 32, 64, 128}; strides in floats, multiples of 4.
+ * lnz_last_kernel() names embedding_grad_kernel<CPL> (CPL columns per lane: 1 up to width 64, else 2). */
 int lnz_embedding_grad(const int64_t* ids, int B, int N, const float* dx, int64_t mol_stride,
                        int64_t row_stride, int width, int num_atom, int chunks, float* partials,
                        lnz_stream_t stream);
@@ -1348,7 +1359,9 @@ int lnz_set2vec_readout(const float* X, int ld, const uint8_t* mask, const float
  *     on the dense adjacency;
  *   node_feat [B,N] int64 (pad 0), mask [B,N] u8, label [B,P], n_nodes [B] int32.
  * (D, V) then come from lnz_lanczos_ritz on L[..., 0] instead of the pickled D_simple/V_simple.
- * An id outside [0, n_mol) yields an empty molecule (n_nodes = 0).  N*N*E*4 + (E+1)*N*8 <= 64 KiB. */
+ * An id outside [0, n_mol) yields an empty molecule (n_nodes = 0, a zero label); a molecule of more
+ * than N atoms is cut to its first N (bonds into the cut atoms are dropped, n_nodes = N).
+ * N*N*E*4 + (E+1)*N*8 <= 64 KiB (LNZ_ENOTSUP beyond).  lnz_last_kernel() names collate_qm8_kernel. */
 int lnz_collate_qm8(const int64_t* mol_off, const int64_t* edge_off, const uint8_t* atoms,
                     const uint32_t* edges, const float* labels, const int64_t* ids, int64_t n_mol,
                     int B, int N, int E, int P, int64_t* node_feat, uint8_t* mask, float* label,
@@ -1359,7 +1372,11 @@ int lnz_collate_qm8(const int64_t* mol_off, const int64_t* edge_off, const uint8
  * Replaces operators/src/cuda/segment_reduction.cu:39-69 (+ launchers :72-95) behind
  * operators/functions/unsorted_segment_sum.py:8-44.  `out` must be pre-zeroed by the caller
  * (as :25-26 does).  The output batch stride is num_segments*dim2 (the reference kernel's
- * dim1*dim2 stride, :48, is only in-bounds when num_segments == dim1; identical there). */
+ * dim1*dim2 stride, :48, is only in-bounds when num_segments == dim1; identical there).
+ * An id outside [0, num_segments) contributes nothing forward and receives zeros backward (the
+ * reference would write and read out of bounds).  lnz_last_kernel() names the forward's
+ * segsum_fwd_lds_kernel<VEC> x NW (VEC floats per lane, the rows split over NW waves) or
+ * segsum_fwd_atomic_kernel, and the backward's segsum_bwd_kernel<VEC>. */
 int lnz_unsorted_segment_sum_forward(const float* data, const int64_t* segment_ids, int B,
                                      int dim1, int dim2, int num_segments, float* out,
                                      lnz_stream_t stream);

@@ -109,5 +109,6 @@ extern "C" int lnz_collate_qm8(const int64_t* mol_off, const int64_t* edge_off,
   hipLaunchKernelGGL(collate_qm8_kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, mol_off,
                      edge_off, atoms, edges, labels, ids, (int)n_mol, N, E, P, node_feat, mask,
                      label, L, n_nodes);
+  lnz::note_kernel("collate_qm8_kernel");
   return lnz::check_launch("lnz_collate_qm8");
 }

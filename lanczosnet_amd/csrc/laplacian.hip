@@ -12,7 +12,7 @@ __global__ __launch_bounds__(256) void laplacian_l4_kernel(const float* __restri
                                                            int N, int E, float* __restrict__ L) {
   extern __shared__ __attribute__((aligned(16))) double sdeg[];  // [(E+1) * N] -> d^-1/2
   const int b = blockIdx.x;
-  const int n = n_nodes[b];
+  const int n = min(max(n_nodes[b], 0), N);  // counts outside [0, N] are clamped, as the collate does
   const int E1 = E + 1;
   const float* Ab = adjs + (int64_t)b * N * N * E;
   float* Lb = L + (int64_t)b * N * N * E1;
@@ -93,9 +93,11 @@ extern "C" int lnz_laplacian_l4(const float* adjs, const int32_t* n_nodes, int B
   if (staged <= 64 * 1024 && ((size_t)N * N * E) % 4 == 0 && (((uintptr_t)adjs) & 15) == 0) {
     hipLaunchKernelGGL(laplacian_l4_kernel<true>, dim3(B), dim3(256), staged, (hipStream_t)stream,
                        adjs, n_nodes, N, E, L);
+    lnz::note_kernel("laplacian_l4_kernel<staged>");
   } else {
     hipLaunchKernelGGL(laplacian_l4_kernel<false>, dim3(B), dim3(256), lds, (hipStream_t)stream, adjs,
                        n_nodes, N, E, L);
+    lnz::note_kernel("laplacian_l4_kernel<direct>");
   }
   return lnz::check_launch("lnz_laplacian_l4");
 }
@@ -114,7 +116,7 @@ __global__ __launch_bounds__(256) void laplacian_kind_kernel(const float* __rest
                                                              float* __restrict__ L) {
   extern __shared__ __attribute__((aligned(16))) double sdeg[];  // [(E+1) * N]: d, then d^-x
   const int b = blockIdx.x;
-  const int n = n_nodes[b];
+  const int n = min(max(n_nodes[b], 0), N);  // counts outside [0, N] are clamped, as the collate does
   const int E1 = E + 1;
   const float* Ab = adjs + (int64_t)b * N * N * E;
   float* Lb = L + (int64_t)b * N * N * E1;
@@ -178,6 +180,7 @@ extern "C" int lnz_laplacian(const float* adjs, const int32_t* n_nodes, int B, i
   LNZ_REQUIRE(lds <= 64 * 1024, LNZ_ENOTSUP, "lnz_laplacian: (E+1)*N too large");
   hipLaunchKernelGGL(laplacian_kind_kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, adjs,
                      n_nodes, N, E, kind, alpha, L);
+  lnz::note_kernel("laplacian_kind_kernel<%d>", kind);
   return lnz::check_launch("lnz_laplacian");
 }
 
@@ -319,11 +322,13 @@ extern "C" int lnz_unsorted_segment_sum_forward(const float* data, const int64_t
     else
       hipLaunchKernelGGL(segsum_fwd_lds_kernel<1>, grid, dim3(64 * nw), copy * nw,
                          (hipStream_t)stream, data, segment_ids, dim1, dim2, num_segments, out);
+    lnz::note_kernel("segsum_fwd_lds_kernel<%d> x %d", vec4 ? 4 : 1, nw);
   } else {
     int64_t total = (int64_t)B * dim1 * dim2;
     int64_t g = (total + 255) / 256;
     hipLaunchKernelGGL(segsum_fwd_atomic_kernel, dim3((int)(g > 2048 ? 2048 : g)), dim3(256), 0,
                        (hipStream_t)stream, data, segment_ids, total, dim1, dim2, num_segments, out);
+    lnz::note_kernel("segsum_fwd_atomic_kernel");
   }
   return lnz::check_launch("lnz_unsorted_segment_sum_forward");
 }
@@ -344,6 +349,7 @@ extern "C" int lnz_unsorted_segment_sum_backward(const float* grad_out, const in
   else
     hipLaunchKernelGGL(segsum_bwd_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, grad_out,
                        segment_ids, rows, dim1, dim2, num_segments, grad_data);
+  lnz::note_kernel("segsum_bwd_kernel<%d>", vec4 ? 4 : 1);
   return lnz::check_launch("lnz_unsorted_segment_sum_backward");
 }
 
@@ -422,5 +428,6 @@ extern "C" int lnz_embedding_grad(const int64_t* ids, int B, int N, const float*
   if (width <= 64) LNZ_EG(1);
   else LNZ_EG(2);
 #undef LNZ_EG
+  lnz::note_kernel("embedding_grad_kernel<%d>", width <= 64 ? 1 : 2);
   return lnz::check_launch("lnz_embedding_grad");
 }

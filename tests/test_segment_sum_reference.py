@@ -11,12 +11,16 @@ holds its outputs on the seeded inputs of the CPU test (`tests/golden/make_golde
   coincide (all batch entries share their ids and num_segments == dim1 — the only in-bounds use of
   both): forward scatter-add and backward gather.  Without the built operator the
   comparison is with the oracle's restatement, which the CPU test pins to the reference bit for bit.
+* GPU, every route of the two launchers (the rows of builder_cases.py, shown on their routes without a GPU
+  by test_builder_cases_cpu.py): per-batch ids against the oracle's GPU-semantics restatement, the route
+  read from ops.last_kernel(), and ids outside [0, num_segments) — nothing forward, zeros backward.
 """
 import numpy as np
 import pytest
 import torch
 
 import oracle
+import builder_cases as bc
 from oracle import ref_build
 
 REF_OP = ref_build.load()
@@ -92,6 +96,70 @@ def test_hip_segment_sum_equals_the_built_reference():
     gout = rs.randn(B, D1, D2).astype(np.float32)
     gd = ops.unsorted_segment_sum_backward(dev(gout), dev(ids), D1).cpu().numpy()
     np.testing.assert_array_equal(gd, _ref_backward(gout, ids))              # gather: exact
+
+
+def _one_float_in(x):
+  """x on the device as a contiguous view that starts one float into a flat buffer (4 bytes off 16)"""
+  buf = torch.full((x.size + 5,), float('nan'), device='cuda:0')
+  view = buf[1:1 + x.size].view(x.shape)
+  view.copy_(torch.from_numpy(x))
+  assert view.is_contiguous() and view.data_ptr() % 16 == 4
+  return view
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('row', range(len(bc.SEGSUM_FORWARD)))
+def test_hip_segment_sum_forward_on_every_route_of_its_launcher(row):
+  """The rows of builder_cases.SEGSUM_FORWARD — the 4-wave row split, the row split on the float4 path, a
+  dynamic LDS size of exactly 64 KiB, the atomic fallback and its grid-stride loop, an unaligned operand —
+  with per-batch ids against the oracle's restatement of the GPU semantics, the route asserted through
+  ops.last_kernel().  Integer-valued data: every order of summation is exact, the bar is equality.  One row
+  runs again with ids of -1, S and 2^31 planted: those rows add nothing (the rule restated in numpy — the
+  oracle indexes with the id and cannot serve)."""
+  from lanczosnet_amd import ops
+  B, D1, D2, S, aligned, kernel, why = bc.SEGSUM_FORWARD[row]
+  dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to('cuda:0')  # noqa: E731
+  data, ids = bc.segsum_inputs(B, D1, D2, S, seed=10 + row)
+  got = ops.unsorted_segment_sum_forward(dev(data) if aligned else _one_float_in(data), dev(ids), S)
+  assert ops.last_kernel() == kernel, (ops.last_kernel(), why)
+  np.testing.assert_array_equal(got.cpu().numpy(), oracle.unsorted_segment_sum_forward_gpu_semantics(data, ids, S))
+  if not aligned:
+    assert torch.equal(got, ops.unsorted_segment_sum_forward(dev(data), dev(ids), S))
+    assert ops.last_kernel() != kernel
+  if row == bc.SEGSUM_FORWARD_OUT_OF_RANGE:
+    data, ids = bc.segsum_inputs(B, D1, D2, S, seed=10 + row, out_of_range=True)
+    got = ops.unsorted_segment_sum_forward(dev(data), dev(ids), S)
+    assert ops.last_kernel() == kernel
+    np.testing.assert_array_equal(got.cpu().numpy().astype(np.float64), bc.segsum_forward_rule(data, ids, S))
+
+
+@pytest.mark.gpu
+def test_hip_segment_sum_atomic_fallback_drops_out_of_range_ids():
+  from lanczosnet_amd import ops
+  B, D1, D2, S, _, kernel, _ = bc.SEGSUM_FORWARD[6]
+  data, ids = bc.segsum_inputs(B, D1, D2, S, seed=30, out_of_range=True)
+  got = ops.unsorted_segment_sum_forward(torch.from_numpy(data).cuda(), torch.from_numpy(ids).cuda(), S)
+  assert ops.last_kernel() == kernel == 'segsum_fwd_atomic_kernel'
+  np.testing.assert_array_equal(got.cpu().numpy().astype(np.float64), bc.segsum_forward_rule(data, ids, S))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('row', range(len(bc.SEGSUM_BACKWARD)))
+def test_hip_segment_sum_backward_on_both_instantiations(row):
+  """The rows of builder_cases.SEGSUM_BACKWARD: more rows than waves (the wave-stride loop turns) on <4>,
+  and <1>; each again with ids of -1, S and 2^31 planted: those rows are zeros."""
+  from lanczosnet_amd import ops
+  B, D1, D2, S, kernel, why = bc.SEGSUM_BACKWARD[row]
+  dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to('cuda:0')  # noqa: E731
+  _, ids = bc.segsum_inputs(B, D1, D2, S, seed=20 + row)
+  gout = np.random.RandomState(40 + row).randint(-8, 9, size=(B, S, D2)).astype(np.float32)
+  got = ops.unsorted_segment_sum_backward(dev(gout), dev(ids), D1)
+  assert ops.last_kernel() == kernel, (ops.last_kernel(), why)
+  np.testing.assert_array_equal(got.cpu().numpy(), oracle.unsorted_segment_sum_backward_gpu_semantics(gout, ids, D1))
+  _, bad = bc.segsum_inputs(B, D1, D2, S, seed=20 + row, out_of_range=True)
+  got = ops.unsorted_segment_sum_backward(dev(gout), dev(bad), D1)
+  assert ops.last_kernel() == kernel
+  np.testing.assert_array_equal(got.cpu().numpy(), bc.segsum_backward_rule(gout, bad))
 
 
 def test_operator_classes_have_the_reference_surface_and_refuse_cpu_tensors():

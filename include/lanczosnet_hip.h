@@ -675,7 +675,11 @@ int lnz_spectral_gains_rows(const float* D, int B, int K, const int32_t* dist_ho
  * lnz_spectral_mlp_grad_floats(S) floats into partials [L][parts][T]:
  *   dW0 [128][S] | dW2 [128][128] | dW4 [128][128] | dW6 [S][128] | db0, db2, db4 [3][128] | db6 [S] | pad
  * and the gradients are the sum of a layer's partials over the `parts` index (any fixed order: one
- * reduction for all eight).  S <= 8; exact fp32. */
+ * reduction for all eight).  S <= 8; exact fp32.
+ * Contracts the tests pin (tests/test_gpu_mlp_grad_edges.py): entries of `rows` at or beyond *n_rows
+ * are never read; a workgroup whose part index owns no 64-row tile (parts > tiles) writes a partial
+ * of zeros, so `partials` needs no initialisation; D and the listed rows of dG must be finite (a
+ * row's features are D^p: 0 for an underflowing power, which is a valid input). */
 int lnz_spectral_mlp_grad_floats(int S);
 int lnz_spectral_mlp_grad_parts(int n_rows_max, int num_layer, int n_cu);
 int lnz_spectral_mlp_grad(const float* D, int B, int K, const int32_t* dist_host, int S,
@@ -861,7 +865,15 @@ int lnz_lanczosnet_input_grad(const lnz_forward_args* args, lnz_stream_t stream)
  * model/lanczos_net.py:95-123), in eigen space:
  *   dG[l][b][k][s] = sum_o (V^T dY_l)[k][o] * ((V^T X_l) W_{l,s}^T)[k][o]
  * Reads dy (all num_layer slots, as left by lnz_lanczosnet_input_grad), act / x0 (X_l), V, mask,
- * plan and the FORWARD weight packs Wp / w_off (not the transposed ones); writes dgains. */
+ * plan and the FORWARD weight packs Wp / w_off (not the transposed ones); writes dgains.
+ * Contracts the tests pin (tests/test_gpu_gain_grad_edges.py): dgains is zero-initialised by the
+ * caller and only the slots k < K of a molecule's own rows are written, so a slot k >= n stays or
+ * becomes exactly 0 (V[:, :, k] = 0 there); rows of act / x0 / dy at or beyond a molecule's node
+ * count may hold any FINITE value (they meet V's zero rows; the forward leaves bias-driven values
+ * in a molecule's 4-row padding) — a non-finite value there is not filtered; a non-finite entry of
+ * V is staged as 0 in every form (strips and tiles), so it stays with its own molecule.
+ * lnz_last_kernel() names the form that ran: lanczosnet_strip_gain_grad_kernel on the strip plan,
+ * lanczosnet_gain_grad_kernel<4,1> / <4,0> (din0 % 64 == 0 / otherwise) on the tile plan. */
 int lnz_lanczosnet_gain_grad(const lnz_forward_args* args, lnz_stream_t stream);
 /* Messages of conv layer msg_layer, msg = cat_c(M_c X_l): with dY_l they give the weight gradient
  * of the reference's Linear(15 d -> 128) as ONE library GEMM, dW_l = dY_l^T msg
@@ -916,7 +928,17 @@ int lnz_plan_strips(const uint8_t* mask, int B, int N, int n_cu, int32_t* strips
  *   dY_compact [R,dhid]     (optional) the rows below a molecule's node extent, compact
  *   dWhead     [P+1,dhid], dbhead [P+1], dbias_last [dhid] (column sums of dY)
  * workspace: lnz_head_backward_workspace_floats(P, n_wg) floats; n_wg workgroups walk the molecules
- * (the partial sums are added in workgroup order: deterministic).  dhid = 128, N <= 32, P <= 31. */
+ * (the partial sums are added in workgroup order: deterministic; n_wg in 1..4096, clamped to B).
+ * dhid = 128, N <= 32, P <= 31.
+ * Contracts the tests pin (tests/test_gpu_head_grad_edges.py):
+ *  - a molecule with an EMPTY mask contributes nothing: its dY rows are exactly 0 and the parameter
+ *    gradients are those of the batch without it (torch autograd gives 0 / 0 = NaN for its score);
+ *  - rows of X_last outside the mask (holes, the rows from the node extent to 31) may hold any FINITE
+ *    value — their dz is exactly 0, so they enter dWhead as 0 * x; a non-finite value there is not
+ *    filtered and would poison dWhead;
+ *  - dY_compact receives rows [row_off[b], row_off[b] + extent_b) of every molecule (hole rows
+ *    included, bit-equal to dY) and nothing else of it is written;
+ *  - dY is computed per molecule: its bits do not depend on n_wg. */
 int64_t lnz_head_backward_workspace_floats(int P, int n_wg);
 /* Node extents (last real node + 1; the training kernels size a molecule by it), their exclusive
  * prefix sums (first row of a molecule in the compact numbering of the message matrix,

@@ -1205,6 +1205,7 @@ extern "C" int lnz_lanczosnet_gain_grad(const lnz_forward_args* args, lnz_stream
   if (lnz::strip_gain_grad_eligible(a))
     return lnz::launch_strip_gain_grad(a, (hipStream_t)stream);
   const int grid = a.plan ? a.plan_wg_cap : (a.B + 3) / 4;
+  lnz::note_kernel("lanczosnet_gain_grad_kernel<4,%d>", a.din0 % 64 == 0 ? 1 : 0);
   if (a.din0 % 64 == 0)
     hipLaunchKernelGGL((lanczosnet_gain_grad_kernel<4, 1>), dim3(grid), dim3(512), 0, (hipStream_t)stream, a);
   else

@@ -1920,6 +1920,7 @@ int launch_strip_messages(const lnz_forward_args& a, hipStream_t s) {
 int launch_strip_gain_grad(const lnz_forward_args& a, hipStream_t s) {
   const size_t bytes = (size_t)strip_lds_floats(LNZ_STRIP_SUB, a.n_long) * sizeof(float);
   // per launch: the attribute is per device, and a process may drive several (DataParallel)
+  note_kernel("lanczosnet_strip_gain_grad_kernel");
   LNZ_DYNAMIC_LDS(lanczosnet_strip_gain_grad_kernel, 160 * 1024, "conv_strip.hip");
   hipLaunchKernelGGL(lanczosnet_strip_gain_grad_kernel, dim3(a.strip_cap), dim3(512), bytes, s, a);
   return check_launch("lnz_lanczosnet_gain_grad (strips)");

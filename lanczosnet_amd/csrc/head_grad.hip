@@ -11,6 +11,8 @@
 // for 0.4 GFLOP.  Here a workgroup walks its share of the molecules with the head weights in LDS,
 // keeps its parameter-gradient partials in registers and writes them once; a second tiny launch adds
 // the partials in workgroup order (deterministic: no atomics).
+// A molecule with an empty mask contributes nothing (every dz of it is an exact 0; autograd's masked
+// mean is 0 / 0 there), and rows outside the mask enter dW_head as 0 * x: X must be finite on them.
 #include "common.hpp"
 
 namespace {
@@ -270,12 +272,13 @@ extern "C" int lnz_head_backward(const float* X_last, const uint8_t* mask, const
                                  int N, int P, int dhid, int n_wg, float* workspace, float* dY,
                                  float* dY_compact, float* dWhead, float* dbhead, float* dbias_last,
                                  lnz_stream_t stream) {
-  LNZ_REQUIRE(X_last && mask && grad_score && Whead && bhead && workspace && dY && dWhead && dbhead &&
-                  dbias_last && B > 0,
-              LNZ_EINVAL, "lnz_head_backward: null pointer or B=%d", B);
+  // (first: lnz_head_backward_workspace_floats is 0 for such a P, so the workspace may be empty)
   LNZ_REQUIRE(dhid == DH && N >= 1 && N <= 32 && P >= 1 && P <= PMAX, LNZ_ENOTSUP,
               "lnz_head_backward: built for hidden width 128, N <= 32, head width <= 31 (dhid=%d N=%d P=%d)",
               dhid, N, P);
+  LNZ_REQUIRE(X_last && mask && grad_score && Whead && bhead && workspace && dY && dWhead && dbhead &&
+                  dbias_last && B > 0,
+              LNZ_EINVAL, "lnz_head_backward: null pointer or B=%d", B);
   LNZ_REQUIRE(n_wg >= 1 && n_wg <= 4096, LNZ_EINVAL, "lnz_head_backward: n_wg=%d", n_wg);
   LNZ_REQUIRE(!dY_compact || row_off, LNZ_EINVAL, "lnz_head_backward: dY_compact without row_off");
   LNZ_REQUIRE(!Wgate == !bgate, LNZ_EINVAL, "lnz_head_backward: Wgate and bgate come together");

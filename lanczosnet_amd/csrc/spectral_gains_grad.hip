@@ -305,10 +305,11 @@ extern "C" int lnz_spectral_mlp_grad(const float* D, int B, int K, const int32_t
                                      int num_layer, const int32_t* rows, const int32_t* n_rows,
                                      const float* dG, const float* const* ptrs, int parts,
                                      float* partials, lnz_stream_t stream) {
+  // (first: a caller that sizes `partials` by lnz_spectral_mlp_grad_floats(S) = 0 passes an empty buffer)
+  LNZ_REQUIRE(S >= 1 && S <= SX, LNZ_ENOTSUP, "lnz_spectral_mlp_grad: S=%d not in 1..%d", S, SX);
   LNZ_REQUIRE(D && dist_host && dG && ptrs && partials, LNZ_EINVAL, "lnz_spectral_mlp_grad: null pointer");
   LNZ_REQUIRE(B > 0 && K > 0 && num_layer > 0 && num_layer <= 16 && parts > 0 && parts <= 65535,
               LNZ_EINVAL, "lnz_spectral_mlp_grad: bad sizes (B=%d K=%d L=%d parts=%d)", B, K, num_layer, parts);
-  LNZ_REQUIRE(S >= 1 && S <= SX, LNZ_ENOTSUP, "lnz_spectral_mlp_grad: S=%d not in 1..%d", S, SX);
   LNZ_REQUIRE(!rows == !n_rows, LNZ_EINVAL, "lnz_spectral_mlp_grad: rows and n_rows come together");
   GradArgs a;
   a.D = D, a.rows = rows, a.n_rows = n_rows, a.dG = dG;

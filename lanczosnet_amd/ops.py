@@ -1626,11 +1626,12 @@ def split_laplacian_pack(Lp):
   return Lh
 
 
-def spectral_mlp_grad(D, dist, layers, dG, rows=None, rows_max=None):
+def spectral_mlp_grad(D, dist, layers, dG, rows=None, rows_max=None, parts=None):
   """lnz_spectral_mlp_grad: parameter gradients of the spectral-filter MLPs of every conv layer from
   dG [L, B*K, S] in one launch.  layers: per conv layer the 4 (weight, bias) pairs of its
   `spectral_filter[l]` (raw parameters).  rows: (gain_rows, n_gain_rows) of plan_batch() or None;
-  rows_max: host-side upper bound of the live row count (sizes the grid; default B*K).  Returns
+  rows_max: host-side upper bound of the live row count (sizes the grid; default B*K).  parts: the
+  number of workgroups (partials) per layer; None = lnz_spectral_mlp_grad_parts' choice.  Returns
   [(dW0, db0), (dW2, db2), (dW4, db4), (dW6, db6)], each stacked over the layers ([L, ...])."""
   _need_cuda(D, dG)
   D = _f32c(D)
@@ -1644,7 +1645,8 @@ def spectral_mlp_grad(D, dist, layers, dG, rows=None, rows_max=None):
     for (w, b) in lins:
       keep += [_f32c(w.detach()), _f32c(b.detach())]
   dev = D.device
-  parts = _abi().spectral_mlp_grad_parts(int(rows_max or B * K), L, _n_cu(dev))
+  if parts is None:
+    parts = _abi().spectral_mlp_grad_parts(int(rows_max or B * K), L, _n_cu(dev))
   T = _abi().spectral_mlp_grad_floats(S)
   partials = torch.empty((L, parts, T), dtype=torch.float32, device=dev)
   with torch.cuda.device(dev):

@@ -770,8 +770,10 @@ typedef struct lnz_forward_args {
                                  of workgroup g = (molecule A, molecule B or -1, split row); NULL =
                                  one tile per molecule, 4 per workgroup, in batch order.  The plan
                                  changes the time, and the scores only by fp32 re-association
-                                 (<= 1e-6 relative; tested at 1e-5).  Pair tiles (B >= 0):
-                                 gemm_mode 0 with filter_kind 0 only.                               */
+                                 (<= 1e-6 relative; tested at 1e-5).  Pair tiles (B >= 0) exist in
+                                 every kernel that reads the tile plan: diagonal gains and dense
+                                 filters in eigen space, both widths (the strip kernels, gemm_mode 1
+                                 among them, read `strips` instead).                                 */
   const int32_t* n_wg;        /* device scalar written by lnz_plan_tiles: workgroups in use          */
   int plan_wg_cap;            /* lnz_plan_wg_cap(B, n_cu): workgroup entries in `plan` (= grid size) */
   /* ---- training (gemm_mode 0, filter_kind 0, dhid 128).  All buffers are
@@ -853,6 +855,31 @@ typedef struct lnz_forward_args {
                                  sum (<0,0,1,..>).  Both forms give the same bits.  Must be re-packed
                                  when Wp changes.                                                     */
 } lnz_forward_args;
+/* Contracts of the forward the tests pin (tests/test_gpu_strip_forward_edges.py,
+ * tests/test_gpu_tile_forward_edges.py), for the strip kernels and the 32-row tile kernels alike:
+ *  - A molecule's extent is its last node the mask keeps + 1; its eigen slots are k < min(extent, K).  V must be
+ *    zero at rows >= extent and slots >= extent (the reference's collate, lnz_lanczos_ritz on the extent).
+ *  - Slots k >= extent of G.  filter_kind 0: never read, in any instantiation and either gemm_mode — any bit
+ *    pattern there, NaN included, leaves the same bits in every output (lnz_spectral_gains_rows may leave them
+ *    uninitialised).  filter_kind 1: rows and columns k >= extent of DD that fall inside the molecule's row block
+ *    (strips: its extent rounded up to 4 rows; tiles: its rows of the tile) ARE read and meet the zero rows of
+ *    V^T X: any FINITE value leaves the same bits, a non-finite one is not filtered (0 x NaN) —
+ *    lnz_ada_symmetrize_filters hands over finite values.
+ *  - A node the mask leaves out but L keeps (a hole, or a last node inside the molecule's row block) keeps its
+ *    own state and feeds its neighbours; only the head's sum AND count skip it: score = mean over the nodes the
+ *    mask keeps.  A molecule with an empty mask has no contract (0 / 0).
+ *  - state_out and act_out are zeroed by the caller.  On strips a molecule's rows 0 .. rows4 - 1 are written
+ *    (rows4 = extent rounded up to 4, at least 4): real nodes, holes, and padding rows, which hold finite
+ *    bias-driven values; rows >= rows4 stay exactly zero.  On tiles a single tile writes all 32 rows of its
+ *    molecule, a pair tile rows 0 .. split - 1 of its first and 0 .. 31 - split of its second molecule; the
+ *    rest stays zero.  Only the rows the mask keeps carry a meaning for the caller.
+ *  - A molecule's outputs depend on its batch position, its neighbours in a strip or tile and the padded N only
+ *    through the re-association of fp32 sums (within the float32 reference's own error).
+ *  - lnz_last_kernel() names what ran: lanczosnet_strip_kernel<0,0,1,false,false> (a launch that may fold the
+ *    rare bond-type channels), <0,0,false,false> (channel loop: no_fold, act_out, n_edge < 3 or > 7), <0,0,true,
+ *    false> (short channels), <0,2,false|true,false> (dense filters), <0,0,false,true> (gemm_mode 1); without a
+ *    strip plan lanczosnet_forward_kernel<4,10,0,0,1> (width 128, input width a multiple of 64), <4,10,0,0,-1>
+ *    (width 128, input width 32 or 96), <2,10,0,0,-1> (width 64), <4,10,2,0,0> / <2,10,2,0,0> (dense filters). */
 int lnz_lanczosnet_forward(const lnz_forward_args* args, lnz_stream_t stream);
 /* Backward of the conv stack w.r.t. its node-state inputs, in the forward's own structure:
  *   dX_l = sum_c M_c (dY_l W_c),   dY_{l-1} = dX_l * [X_l > 0]

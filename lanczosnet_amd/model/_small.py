@@ -97,6 +97,8 @@ class _SmallMixin:
         if not self.general:
             emb = torch.nn.functional.pad(self.embedding.weight.detach().float(),
                                           (0, din0p - din0)).contiguous()
+        # (tests/forward_cases.narrow_plan rebuilds din0 / Wp / w_off / embedding / Wf of this dict for an unpadded
+        # 32-column layer 0 of a width-128 model, to reach lanczosnet_forward_kernel<4,10,0,0,-1>: keep it in step)
         plan = dict(sig=sig, num_layer=self.num_layer, din0=din0p, din0_raw=din0, dhid=dhid,
                     dout=P, filter_kind=self.filter_kind,
                     short=list(self.short_diffusion_dist), n_long=self.num_scale_long,

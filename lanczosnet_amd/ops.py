@@ -1789,8 +1789,9 @@ def plan_tiles(mask_u8, allow_pairs, n_cu=None):
 
 
 def pairing_supported(plan):
-  """Pair tiles exist in every forward kernel there is (the spectral channels run in eigen space:
-  diagonal gains of LanczosNet, dense K x K filters of AdaLanczosNet); kept for the callers that ask."""
+  """Pair tiles exist in every forward kernel that reads the tile plan (the spectral channels run in eigen
+  space: diagonal gains of LanczosNet, dense K x K filters of AdaLanczosNet — include/lanczosnet_hip.h,
+  lnz_forward_args.plan; held to float64 by tests/test_gpu_tile_forward_edges.py); kept for the callers that ask."""
   return True
 
 

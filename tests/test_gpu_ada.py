@@ -410,6 +410,9 @@ def test_ada_dense_filters_on_pair_tiles(n_cu, tiles16):
     T, Q = ops.ada_lanczos_layer(Le, _t(b['node_mask']), _t(q1)[:, :, None], K)
     tcat = ops.ada_t_powers(T, cfg['long_diffusion_dist']).view(B, -1)
     DDp = net._ada_dense_filters(plan, tcat)
+    # the forward's contract on dense filters (include/lanczosnet_hip.h): finite in EVERY slot, the ones
+    # k >= extent of a small molecule included (they are read against zero rows, 0 x NaN is not filtered)
+    assert torch.isfinite(DDp).all()
     Lp = ops.pack_laplacian(_t(L))
     mk = _t(b['node_mask'])
     tiles = ops.plan_tiles(mk, allow_pairs=True, n_cu=n_cu)

@@ -48,6 +48,8 @@ extern "C" {
  *    _workspace_floats query: additive, the version stays);
  *    + the MPNN baseline's fused edge-network propagation and Set2Vec readout (lnz_mpnn_forward,
  *    lnz_set2vec_readout: additive, the version stays);
+ *    + the backward of that propagation (lnz_mpnn_forward_states, lnz_mpnn_backward_step: additive, the
+ *    version stays);
  *    + lnz_forward_args.rare_strips / .no_fold / .rare_debug at the END of the block (the strip forward's folded form of
  *    the rare bond-type channels, on by default: zeros = folded where cheaper; additive, the version
  *    stays — a caller built against the shorter block must zero-fill lnz_forward_args_size() bytes);
@@ -1374,6 +1376,45 @@ int lnz_mpnn_forward(const float* state0, int ld0, const float* L, int64_t strid
                      const float* b2, const float* Wih, const float* bih, const float* Whh, const float* bhh, int B,
                      int N, int C, int D, int num_prop, int avg, float* state_out, int ldso, int tile_rows,
                      lnz_stream_t stream);
+
+/* ---- the backward of the MPNN propagation, csrc/mpnn.hip and csrc/mpnn_grad.hip ----
+ * lnz_mpnn_forward_states: lnz_mpnn_forward (the same kernel body, arguments, envelope and errors; the final
+ * state has its bits at either tile height) that also leaves the state trajectory states
+ * [num_prop + 1][B N][D] (row stride D, 16-byte aligned, no overlap with state0 or state_out): S_t at the start
+ * of step t, S_T after the last.  state_out may be NULL here (the final state is states[num_prop]).  Nothing else
+ * is saved: the backward recomputes a step from S_t.  lnz_last_kernel() names mpnn_forward_states_kernel. */
+int lnz_mpnn_forward_states(const float* state0, int ld0, const float* L, int64_t stride_b, int64_t stride_r,
+                            int64_t stride_c, int64_t stride_ch, const float* W1, const float* b1, const float* W2,
+                            const float* b2, const float* Wih, const float* bih, const float* Whh, const float* bhh,
+                            int B, int N, int C, int D, int num_prop, int avg, float* state_out, int ldso,
+                            float* states, int tile_rows, lnz_stream_t stream);
+
+/* lnz_mpnn_backward_step: one propagation step of backpropagation through time for the whole batch, launched
+ * for t = T-1 .. 0.  S [B N, lds] = S_t, dSnext [B N, ldd] = dL/dS_{t+1}; the step is recomputed on chip with
+ * the forward's arithmetic (P_c, Q_c, R_c, M_c, gi, gh, r, z, n), then
+ *   dn = dS' (1 - z), dz = dS' (S - n), dS = dS' z, pn = dn (1 - n^2), pz = dz z (1 - z), pr = pn gh_n r (1 - r),
+ *   dgi = [pr, pz, pn], dgh = [pr, pz, pn r], dS += dgh Whh ; per channel c:
+ *   dM_c = dgi Wih[:, cD:(c+1)D] (avg != 0: divided by deg_c[a] + FLT_EPSILON), dR_c = dM_c W2_c,
+ *   act_c[a, b, h] = (L[a, b, c] != 0 and Q_c[a, h] + P_c[b, h] > 0), dQ_c[a, h] = dR_c[a, h] #{b: act_c[a, b, h]},
+ *   dP_c[b, h] = sum over a (ascending) with act_c[a, b, h] of dR_c[a, h], dS += dP_c W1n_c + dQ_c W1s_c
+ * W1, b1, .. bhh: the forward's operands; W1T [C][2][D][64] (W1T[c][0] = W1n_c^T, W1T[c][1] = W1s_c^T),
+ * W2T [C][64][D], WihT [C][D][3 D] (block c = Wih[:, cD:(c+1)D]^T), WhhT [D][3 D]: their transposes, packed by
+ * the caller.  Out: dS [B N, ldo] = dL/dS_t and the row-space operands of this step's weight gradients,
+ * contiguous: dgi [B N][3 D], dghn [B N][D] (the n part of dgh; its r and z parts are dgi's), M [B N][C D] =
+ * cat_c M_c, R [B N][C 64] = cat_c R_c, dM [B N][C D] (scaled), dPQ [B N][C][dP_c 64 | dQ_c 64].  The caller
+ * contracts them over the rows (dWih = dgi^T M, dWhh = dgh^T S, dW2_c = dM_c^T R_c, db2_c = sum_a deg_c[a]
+ * dM_c[a], dW1_c = [dP_c^T S | dQ_c^T S], db1_c = sum dQ_c, dbih, dbhh the column sums of dgi, dgh) and may reuse
+ * the buffers for the next step.  The envelope of lnz_mpnn_forward (N <= 32, C <= 8, D a multiple of 32 and
+ * <= 128: LNZ_ENOTSUP, as are rows that are not 16-byte aligned); null pointers, B or N <= 0, a row stride below
+ * D, negative strides of L, an output overlapping an input or another output: LNZ_EINVAL.  L is read through
+ * its four strides and never written.  32-row tiles, 147,072 B of dynamic LDS at D = 128; no atomics, every sum
+ * in a fixed order: bit-reproducible. */
+int lnz_mpnn_backward_step(const float* S, int lds, const float* dSnext, int ldd, const float* L, int64_t stride_b,
+                           int64_t stride_r, int64_t stride_c, int64_t stride_ch, const float* W1, const float* b1,
+                           const float* W2, const float* b2, const float* Wih, const float* bih, const float* Whh,
+                           const float* bhh, const float* W1T, const float* W2T, const float* WihT,
+                           const float* WhhT, int B, int N, int C, int D, int avg, float* dS, int ldo, float* dgi,
+                           float* dghn, float* M, float* R, float* dM, float* dPQ, lnz_stream_t stream);
 
 /* lnz_set2vec_readout: Set2Vec (model/set2set.py:79-100) and output_func in ONE launch.  Per molecule, with
  * X = the rows of X [B N, ld] where mask [B, N] != 0 (NULL: all N rows), q* [2 D] = 0, mem [D] = 0, num_step times

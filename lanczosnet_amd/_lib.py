@@ -193,6 +193,10 @@ SIGNATURES = {
                                             _P]),
     'lnz_mpnn_forward': (C.c_int, [_P, _I, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I,
                                    _P, _I, _I, _P]),
+    'lnz_mpnn_forward_states': (C.c_int, [_P, _I, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I,
+                                          _I, _P, _I, _P, _I, _P]),
+    'lnz_mpnn_backward_step': (C.c_int, [_P, _I, _P, _I, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                         _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     'lnz_set2vec_readout': (C.c_int, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P]),
     'lnz_unsorted_segment_sum_forward': (C.c_int, [_P, _P, _I, _I, _I, _I, _P, _P]),
     'lnz_unsorted_segment_sum_backward': (C.c_int, [_P, _P, _I, _I, _I, _I, _P, _P]),

@@ -15,6 +15,9 @@
 // Every one of the N rows of a molecule propagates: a padded row has degree 0, message exactly 0 and
 // evolves under GRU(0, h).  L is only ever compared with zero (a NaN or a negative entry is an edge),
 // never written.  The kernel leaves the final state; the readout is the second kernel.
+// lnz_mpnn_forward_states is the same body (mpnn_forward_body) under a kernel with one more pointer: it also
+// leaves the state trajectory [num_prop + 1][B N][D], all the backward (mpnn_grad.hip) keeps of the forward.
+// The message block ([P_c | Q_c], R_c, M_c) stands in mpnn_tile.hpp, shared to the letter with that backward.
 //
 // Shape as built: ggnn.hip's.  A workgroup of eight waves owns a tile of floor(R / N) whole molecules,
 // R = 64 or 32 rows, whose state stays in LDS for every step.  L is read once, through its four strides,
@@ -44,11 +47,10 @@
 // empty.  Rows outside the mask are never loaded; a molecule without a masked row reads exactly 0.
 #include "common.hpp"
 #include "ggnn_tile.hpp"
+#include "mpnn_tile.hpp"
 
 namespace {
 
-constexpr int MHID = 64;        // message hidden width (model/mpnn.py:60-62)
-constexpr int RS = MHID + 4;    // row stride of R_c (floats)
 constexpr int SMOL = 16;        // molecules per Set2Vec workgroup: the rows of one MFMA tile
 
 // floats of dynamic LDS: S, M [GR][D + 4], [P|Q] [GR][132], R [GR][68], bits + deg [8][GR], rowbase [GR]
@@ -56,19 +58,21 @@ __host__ __device__ constexpr int mpnn_lds_floats(int D, int GR) {
   return 2 * GR * (D + 4) + GR * HS + GR * RS + 2 * GMAXC * GR + GR;
 }
 
-template <int D, int RT>
-__global__ __launch_bounds__(GNT) void mpnn_forward_kernel(
+// The body of both kernels below.  TRAJ (lnz_mpnn_forward_states): also the state trajectory
+// [num_prop + 1][B N][D] — S_t at the start of step t, S_T after the last —, a copy of the LDS rows that the
+// arithmetic does not see; `states` is null and unread otherwise.
+template <int D, int RT, bool TRAJ>
+__device__ __forceinline__ void mpnn_forward_body(
     const float* __restrict__ state0, const int ld0, const float* __restrict__ L, const int64_t stride_b,
     const int64_t stride_r, const int64_t stride_c, const int64_t stride_ch, const float* __restrict__ W1,
     const float* __restrict__ b1, const float* __restrict__ W2, const float* __restrict__ b2,
     const float* __restrict__ Wih, const float* __restrict__ bih, const float* __restrict__ Whh,
     const float* __restrict__ bhh, const int B, const int N, const int C, const int num_prop, const int avg,
-    float* __restrict__ state_out, const int ldso) {
+    float* __restrict__ state_out, const int ldso, float* __restrict__ states) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int GR = 16 * RT;    // rows per tile
   constexpr int SS = D + 4;      // row stride of S and M_c
   constexpr int DB = D / 16;     // 16-feature blocks of a state row: waves 0 .. DB-1 own one each
-  constexpr int HQ = MHID / 4;   // float4 per row of R_c
   float* const Sb = smem;
   float* const Mb = Sb + GR * SS;
   float* const Hb = Mb + GR * SS;                                       // [row][P_c 0..63 | Q_c 64..127]
@@ -92,64 +96,21 @@ __global__ __launch_bounds__(GNT) void mpnn_forward_kernel(
   __syncthreads();
 
   const bool owner = wave < DB;          // wave-uniform: this wave owns features 16 wave .. 16 wave + 15
-  const int f0 = 16 * wave + 4 * g;      // this lane's four features (owner waves) / columns of [P|Q]
   const float* const s_frag = Sb + m * SS + 4 * g;
-  const float* const r_frag = Rb + m * RS + 4 * g;
   const float* const m_frag = Mb + m * SS + 4 * g;
-  // the row of W1_c [64, 2 D] behind this wave's 16 columns of [P|Q]: waves 0 .. 3 the neighbour half
-  // (columns 0 .. D-1 of the rows 16 wave ..), waves 4 .. 7 the own half (columns D .. of the rows 16 (wave - 4) ..)
-  const int hrow = 16 * (wave & 3) + m;
-  const int hoff = wave < 4 ? 0 : D;
+  const EdgeTile et = {Sb, Mb, Hb, Rb, bits, deg, rowbase};
+  const auto put_state = [&](const int t) {
+    store_state_tile<D>(states + ((int64_t)t * B * N + row0) * D, D, Sb, rows);
+  };
 
   for (int step = 0; step < num_prop; ++step) {
+    if constexpr (TRAJ) put_state(step);
     // gate accumulators of this wave's feature block: [0] r, [1] z, [2] gi_n
     f32x4 acc[3][RT];
     zero_tiles(acc);
-    for (int c = 0; c < C; ++c) {
-      {   // [P_c | Q_c + b1_c]: columns 16 wave ..
-        f32x4 h[1][RT];
-        zero_tiles(h);
-        const float* const wp[1] = {W1 + ((int64_t)c * MHID + hrow) * (2 * D) + hoff + 4 * g};
-        tile_gemm<1, DB, RT>(s_frag, SS, wp, h);
-        f32x4 bv = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (wave >= 4) bv = *reinterpret_cast<const f32x4*>(b1 + c * MHID + 16 * (wave - 4) + 4 * g);
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
-          *reinterpret_cast<f32x4*>(Hb + (16 * rt + m) * HS + f0) = h[0][rt] + bv;
-      }
-      __syncthreads();
-      // R_c[a] = sum over the set bits b of relu(Q_c[a] + P_c[b]): four hidden columns of one row per task
-      for (int idx = tid; idx < GR * HQ; idx += GNT) {
-        const int r = idx / HQ, q = idx - r * HQ;
-        unsigned bm = bits[c * GR + r];
-        const f32x4 qv = *reinterpret_cast<const f32x4*>(Hb + r * HS + MHID + 4 * q);
-        const float* const src = Hb + rowbase[r] * HS + 4 * q;
-        f32x4 s = {0.0f, 0.0f, 0.0f, 0.0f};
-        while (bm) {
-          const int j = __ffs(bm) - 1;
-          bm &= bm - 1;
-          const f32x4 v = *reinterpret_cast<const f32x4*>(src + j * HS);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) s[e] += fmaxf(qv[e] + v[e], 0.0f);
-        }
-        *reinterpret_cast<f32x4*>(Rb + r * RS + 4 * q) = s;
-      }
-      __syncthreads();
-      if (owner) {   // M_c = R_c W2_c^T + deg_c b2_c [/ (deg_c + EPS)]: features 16 wave ..
-        f32x4 mm[1][RT];
-        zero_tiles(mm);
-        const float* const wp[1] = {W2 + ((int64_t)c * D + 16 * wave + m) * MHID + 4 * g};
-        tile_gemm<1, MHID / 16, RT>(r_frag, RS, wp, mm);
-        const f32x4 bv = *reinterpret_cast<const f32x4*>(b2 + c * D + f0);
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) {
-          const float dg = deg[c * GR + 16 * rt + m];
-          f32x4 v = mm[0][rt] + dg * bv;
-          if (avg) v = v / (dg + FLT_EPSILON);   // model/mpnn.py:172-177: the sum, then the division
-          *reinterpret_cast<f32x4*>(Mb + (16 * rt + m) * SS + f0) = v;
-        }
-      }
-      __syncthreads();
+    for (int c = 0; c < C; ++c) {   // three barriers per channel
+      edge_message<D, RT>(et, c, W1, b1, W2, b2, avg, wave, m, g, [](int, int, const f32x4&) {},
+                          [](int, const f32x4&) {});
       if (owner) gate_accumulate<D, RT>(m_frag, Wih, c, C, wave, m, g, acc);
     }
     f32x4 gh[3][RT];
@@ -159,20 +120,52 @@ __global__ __launch_bounds__(GNT) void mpnn_forward_kernel(
     __syncthreads();
   }
   // ---- the final state
+  if constexpr (TRAJ) put_state(num_prop);
   store_state_tile<D>(state_out + row0 * (int64_t)ldso, ldso, Sb, rows);
+}
+
+template <int D, int RT>
+__global__ __launch_bounds__(GNT) void mpnn_forward_kernel(
+    const float* __restrict__ state0, const int ld0, const float* __restrict__ L, const int64_t stride_b,
+    const int64_t stride_r, const int64_t stride_c, const int64_t stride_ch, const float* __restrict__ W1,
+    const float* __restrict__ b1, const float* __restrict__ W2, const float* __restrict__ b2,
+    const float* __restrict__ Wih, const float* __restrict__ bih, const float* __restrict__ Whh,
+    const float* __restrict__ bhh, const int B, const int N, const int C, const int num_prop, const int avg,
+    float* __restrict__ state_out, const int ldso) {
+  mpnn_forward_body<D, RT, false>(state0, ld0, L, stride_b, stride_r, stride_c, stride_ch, W1, b1, W2, b2, Wih, bih,
+                                  Whh, bhh, B, N, C, num_prop, avg, state_out, ldso, nullptr);
+}
+
+template <int D, int RT>
+__global__ __launch_bounds__(GNT) void mpnn_forward_states_kernel(
+    const float* __restrict__ state0, const int ld0, const float* __restrict__ L, const int64_t stride_b,
+    const int64_t stride_r, const int64_t stride_c, const int64_t stride_ch, const float* __restrict__ W1,
+    const float* __restrict__ b1, const float* __restrict__ W2, const float* __restrict__ b2,
+    const float* __restrict__ Wih, const float* __restrict__ bih, const float* __restrict__ Whh,
+    const float* __restrict__ bhh, const int B, const int N, const int C, const int num_prop, const int avg,
+    float* __restrict__ state_out, const int ldso, float* __restrict__ states) {
+  mpnn_forward_body<D, RT, true>(state0, ld0, L, stride_b, stride_r, stride_c, stride_ch, W1, b1, W2, b2, Wih, bih,
+                                 Whh, bhh, B, N, C, num_prop, avg, state_out, ldso, states);
 }
 
 template <int D, int RT>
 int launch_mpnn(const float* state0, int ld0, const float* L, int64_t sb, int64_t sr, int64_t sc, int64_t sch,
                 const float* W1, const float* b1, const float* W2, const float* b2, const float* Wih,
                 const float* bih, const float* Whh, const float* bhh, int B, int N, int C, int num_prop, int avg,
-                float* state_out, int ldso, int grid, hipStream_t s) {
+                float* state_out, int ldso, float* states, int grid, hipStream_t s, const char* who) {
   const size_t lds = sizeof(float) * (size_t)mpnn_lds_floats(D, 16 * RT);
-  auto kfn = mpnn_forward_kernel<D, RT>;
-  LNZ_DYNAMIC_LDS(kfn, lds, "mpnn.hip");
-  hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(GNT), lds, s, state0, ld0, L, sb, sr, sc, sch, W1, b1, W2, b2,
-                     Wih, bih, Whh, bhh, B, N, C, num_prop, avg, state_out, ldso);
-  return lnz::check_launch("lnz_mpnn_forward");
+  if (states != nullptr) {
+    auto kfn = mpnn_forward_states_kernel<D, RT>;
+    LNZ_DYNAMIC_LDS(kfn, lds, "mpnn.hip");
+    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(GNT), lds, s, state0, ld0, L, sb, sr, sc, sch, W1, b1, W2, b2,
+                       Wih, bih, Whh, bhh, B, N, C, num_prop, avg, state_out, ldso, states);
+  } else {
+    auto kfn = mpnn_forward_kernel<D, RT>;
+    LNZ_DYNAMIC_LDS(kfn, lds, "mpnn.hip");
+    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(GNT), lds, s, state0, ld0, L, sb, sr, sc, sch, W1, b1, W2, b2,
+                       Wih, bih, Whh, bhh, B, N, C, num_prop, avg, state_out, ldso);
+  }
+  return lnz::check_launch(who);
 }
 
 // ------------------------------------------------------------------------------------------ Set2Vec
@@ -325,6 +318,48 @@ int launch_set2vec(const float* X, int ld, const uint8_t* mask, const float* Wg,
   return lnz::check_launch("lnz_set2vec_readout");
 }
 
+int mpnn_forward_impl(const char* who, const float* state0, int ld0, const float* L, int64_t stride_b,
+                      int64_t stride_r, int64_t stride_c, int64_t stride_ch, const float* W1, const float* b1,
+                      const float* W2, const float* b2, const float* Wih, const float* bih, const float* Whh,
+                      const float* bhh, int B, int N, int C, int D, int num_prop, int avg, float* state_out, int ldso,
+                      float* states, int tile_rows, lnz_stream_t stream) {
+  {
+    const float* const w[8] = {W1, b1, W2, b2, Wih, bih, Whh, bhh};
+    const int rc = check_propagation(who, state0, ld0, state_out, ldso, stride_b, stride_r, stride_c, stride_ch, w, B,
+                                     N, C, D, nullptr, num_prop);
+    if (rc != LNZ_OK) return rc;
+  }
+  const uint64_t rows = (uint64_t)B * N;
+  const uint64_t n0 = span(rows, ld0, D), no = span(rows, ldso, D);
+  LNZ_REQUIRE(state_out == nullptr || !overlap(state_out, no, state0, n0), LNZ_EINVAL,
+              "%s: state_out must not alias state0", who);
+  if (states != nullptr) {
+    const uint64_t nst = ((uint64_t)num_prop + 1) * rows * D * sizeof(float);
+    LNZ_REQUIRE(aligned16(states), LNZ_ENOTSUP, "%s: states must be 16-byte aligned", who);
+    LNZ_REQUIRE(!overlap(states, nst, state0, n0) && (state_out == nullptr || !overlap(states, nst, state_out, no)),
+                LNZ_EINVAL, "%s: states must not alias state0 or state_out", who);
+    if (state_out == nullptr) {   // the final state goes where the trajectory keeps it
+      state_out = states + (uint64_t)num_prop * rows * D;
+      ldso = D;
+    }
+  }
+  LNZ_REQUIRE(tile_rows == 0 || tile_rows == 32 || tile_rows == 64, LNZ_EINVAL,
+              "%s: tile_rows = %d is not 0 (chosen by the batch), 32 or 64", who, tile_rows);
+  const int rows_per_tile = choose_tile_rows(B, N, tile_rows);
+  const int mpt = rows_per_tile / N;
+  const int64_t grid = ((int64_t)B + mpt - 1) / mpt;
+  hipStream_t s = (hipStream_t)stream;
+  lnz::note_kernel(states ? "mpnn_forward_states_kernel<%d, %d>" : "mpnn_forward_kernel<%d, %d>", D,
+                   rows_per_tile / 16);
+#define LNZ_MPNN_LAUNCH_(DD, RTT)                                                                                  \
+  launch_mpnn<DD, RTT>(state0, ld0, L, stride_b, stride_r, stride_c, stride_ch, W1, b1, W2, b2, Wih, bih, Whh, bhh, \
+                       B, N, C, num_prop, avg ? 1 : 0, state_out, ldso, states, (int)grid, s, who)
+#define LNZ_MPNN_LAUNCH(DD) (rows_per_tile == 32 ? LNZ_MPNN_LAUNCH_(DD, 2) : LNZ_MPNN_LAUNCH_(DD, 4))
+  LNZ_GGNN_WIDTHS(D, LNZ_MPNN_LAUNCH)
+#undef LNZ_MPNN_LAUNCH
+#undef LNZ_MPNN_LAUNCH_
+}
+
 }  // namespace
 
 extern "C" int lnz_mpnn_forward(const float* state0, int ld0, const float* L, int64_t stride_b, int64_t stride_r,
@@ -335,28 +370,21 @@ extern "C" int lnz_mpnn_forward(const float* state0, int ld0, const float* L, in
   const char* const who = "lnz_mpnn_forward";
   LNZ_REQUIRE(state0 && L && W1 && b1 && W2 && b2 && Wih && bih && Whh && bhh && state_out, LNZ_EINVAL,
               "%s: null pointer", who);
-  {
-    const float* const w[8] = {W1, b1, W2, b2, Wih, bih, Whh, bhh};
-    const int rc = check_propagation(who, state0, ld0, state_out, ldso, stride_b, stride_r, stride_c, stride_ch, w, B,
-                                     N, C, D, nullptr, num_prop);
-    if (rc != LNZ_OK) return rc;
-  }
-  LNZ_REQUIRE(!overlap(state_out, span((uint64_t)B * N, ldso, D), state0, span((uint64_t)B * N, ld0, D)), LNZ_EINVAL,
-              "%s: state_out must not alias state0", who);
-  LNZ_REQUIRE(tile_rows == 0 || tile_rows == 32 || tile_rows == 64, LNZ_EINVAL,
-              "%s: tile_rows = %d is not 0 (chosen by the batch), 32 or 64", who, tile_rows);
-  const int rows_per_tile = choose_tile_rows(B, N, tile_rows);
-  const int mpt = rows_per_tile / N;
-  const int64_t grid = ((int64_t)B + mpt - 1) / mpt;
-  hipStream_t s = (hipStream_t)stream;
-  lnz::note_kernel("mpnn_forward_kernel<%d, %d>", D, rows_per_tile / 16);
-#define LNZ_MPNN_LAUNCH_(DD, RTT)                                                                                  \
-  launch_mpnn<DD, RTT>(state0, ld0, L, stride_b, stride_r, stride_c, stride_ch, W1, b1, W2, b2, Wih, bih, Whh, bhh, \
-                       B, N, C, num_prop, avg ? 1 : 0, state_out, ldso, (int)grid, s)
-#define LNZ_MPNN_LAUNCH(DD) (rows_per_tile == 32 ? LNZ_MPNN_LAUNCH_(DD, 2) : LNZ_MPNN_LAUNCH_(DD, 4))
-  LNZ_GGNN_WIDTHS(D, LNZ_MPNN_LAUNCH)
-#undef LNZ_MPNN_LAUNCH
-#undef LNZ_MPNN_LAUNCH_
+  return mpnn_forward_impl(who, state0, ld0, L, stride_b, stride_r, stride_c, stride_ch, W1, b1, W2, b2, Wih, bih, Whh,
+                           bhh, B, N, C, D, num_prop, avg, state_out, ldso, nullptr, tile_rows, stream);
+}
+
+extern "C" int lnz_mpnn_forward_states(const float* state0, int ld0, const float* L, int64_t stride_b,
+                                       int64_t stride_r, int64_t stride_c, int64_t stride_ch, const float* W1,
+                                       const float* b1, const float* W2, const float* b2, const float* Wih,
+                                       const float* bih, const float* Whh, const float* bhh, int B, int N, int C,
+                                       int D, int num_prop, int avg, float* state_out, int ldso, float* states,
+                                       int tile_rows, lnz_stream_t stream) {
+  const char* const who = "lnz_mpnn_forward_states";
+  LNZ_REQUIRE(state0 && L && W1 && b1 && W2 && b2 && Wih && bih && Whh && bhh && states, LNZ_EINVAL,
+              "%s: null pointer", who);
+  return mpnn_forward_impl(who, state0, ld0, L, stride_b, stride_r, stride_c, stride_ch, W1, b1, W2, b2, Wih, bih, Whh,
+                           bhh, B, N, C, D, num_prop, avg, state_out, ldso, states, tile_rows, stream);
 }
 
 extern "C" int lnz_set2vec_readout(const float* X, int ld, const uint8_t* mask, const float* Wg, const float* bg,

@@ -23,8 +23,19 @@ Set2Vec steps and `output_func`.  Everything else — gradients, dropout in trai
 embedding`, shapes outside the envelope — takes 'mpnn_torch', a device-side differentiable torch
 restatement in the factored form of the kernel (the first Linear of the edge network split over the
 concatenation; `M_c = Â_c (S E_c)` for 'embedding'), with one UserWarning per module that names the
-reason.  There is no CPU path and no HIP backward.
+reason.  There is no CPU path.
+
+Route 'mpnn_hip_train' (opt-in: `LANCZOSNET_MPNN_BACKWARD=hip`, or `net.mpnn_backward_impl = 'hip'`; a call
+that needs gradients inside the same envelope): the propagation is one `torch.autograd.Function` — the
+[num_atom, D] table and its gather, ONE `mpnn_forward_states` launch (route 'mpnn_hip''s kernel body and bits,
+plus the state trajectory [num_prop + 1, B, N, D]: nothing else is saved, against one [B, N, N, 64] tensor per
+channel and step on 'mpnn_torch'), and under `loss.backward()` one `mpnn_backward_step` launch per step
+t = T-1 .. 0 (the step is recomputed on chip from S_t) with the step's weight gradients by the library GEMM,
+`embedding_grad` into the table and the tiny input gradients in torch (csrc/mpnn_grad.hip).  Set2Vec and
+`output_func` stay ordinary autograd on S_T (`set2vec_batched`): there is no Set2Vec backward kernel.  Dropout
+in training, `msg_func: embedding` and every shape reason still take 'mpnn_torch'.
 """
+import os
 import warnings
 
 import numpy as np
@@ -42,8 +53,53 @@ EPS = float(np.finfo(np.float32).eps)
 MPNN_INPUT_STEP = 32   # lnz_f32_linear: K (= input_dim) a multiple of 32
 
 
+class _MpnnTrainFunction(torch.autograd.Function):
+    """The propagation of route 'mpnn_hip_train': forward = `MPNN._hip_forward`'s table, gather and kernel body,
+    leaving the state trajectory and returning S_T; backward = the steps T-1 .. 0 (each recomputed from its S_t,
+    its weight gradients accumulated by the library GEMM), the table's gradient by atom id (all N rows take
+    part, the padding id included, as in the reference), the input layer and the embedding in torch.  Inputs
+    after the five plain ones: node_embedding.weight, input_func W, b, the stacked W1, b1, W2, b2, the cell's
+    W_ih, b_ih, W_hh, b_hh."""
+
+    @staticmethod
+    def forward(ctx, avg, num_prop, transposes, node_feat, L, emb, Win, bin_, *operands):
+        f = lambda x: x.detach().float().contiguous()  # noqa: E731
+        emb, Win, bin_ = f(emb), f(Win), f(bin_)
+        operands = tuple(f(x) for x in operands)
+        table = ops.f32_linear(emb, Win, bias=bin_)
+        states = ops.mpnn_forward_states(table[node_feat], L, *operands, num_prop, avg=avg)
+        ctx.avg, ctx.transposes, ctx.operands, ctx.input = avg, transposes, operands, (emb, Win)
+        ctx.save_for_backward(node_feat, L)
+        ctx.states = states
+        return states[states.shape[0] - 1].clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dST):
+        node_feat, L = ctx.saved_tensors
+        states, prop = ctx.states, ctx.operands
+        emb, Win = ctx.input
+        T, B, N, D = states.shape[0] - 1, states.shape[1], states.shape[2], states.shape[3]
+        C = L.shape[3]
+        dS = dST.float().contiguous()
+        grads = None
+        if T > 0:
+            spare, bufs = torch.empty_like(dS), ops.mpnn_step_buffers(B, N, C, D, dS.device)
+            deg = ops.mpnn_edge_degrees(L)
+            for t in range(T - 1, -1, -1):
+                spare, _ = ops.mpnn_backward_step(states[t], dS, L, *prop, transposes=ctx.transposes, avg=ctx.avg,
+                                                  dS=spare, buffers=bufs)
+                dS, spare = spare, dS
+                grads = ops.mpnn_step_weight_grads(states[t], bufs, C, deg, grads)
+        dtable = ops.embedding_grad(node_feat.contiguous(), dS, D, emb.shape[0])
+        dWin, dbin, demb = dtable.t() @ emb, dtable.sum(dim=0), dtable @ Win
+        return (None,) * 5 + (demb, dWin, dbin) + (tuple(grads) if grads is not None else (None,) * 8)
+
+
 class MPNN(nn.Module):
     """Message Passing Neural Networks (Gilmer et al., ICML 2017) as the reference builds it for QM8."""
+    # 'torch': a call that needs gradients takes route 'mpnn_torch'; 'hip': route 'mpnn_hip_train'
+    mpnn_backward_impl = os.environ.get('LANCZOSNET_MPNN_BACKWARD', 'torch')
 
     def __init__(self, config):
         super().__init__()
@@ -84,6 +140,7 @@ class MPNN(nn.Module):
         self.loss_func = losses[m.loss]()
         self._init_param()
         self._pack_cache = None
+        self._transpose_cache = None
         self._param_list = None
         self.last_route = None
 
@@ -126,6 +183,7 @@ class MPNN(nn.Module):
         (`p.data.clamp_()`, `p.data = x`) and a parameter replaced by another object need this call.
         `load_state_dict` and `.to()/.cuda()/.float()` call it themselves."""
         self._pack_cache = None
+        self._transpose_cache = None
         self._param_list = None
 
     def _apply(self, fn, *a, **kw):
@@ -154,15 +212,27 @@ class MPNN(nn.Module):
         self._pack_cache = (sig, (table, prop, read))
         return self._pack_cache[1]
 
+    @torch.no_grad()
+    def _transposes(self):
+        """(W1T, W2T, WihT, WhhT) of ops.mpnn_backward_step, once per weight version like `_packs`."""
+        sig = self._param_signature()
+        if self._transpose_cache is not None and self._transpose_cache[0] == sig:
+            return self._transpose_cache[1]
+        W1, _, W2, _ = self._msg_operands()
+        packs = ops.mpnn_pack_transposes(W1, W2, self.update_func.weight_ih, self.update_func.weight_hh)
+        self._transpose_cache = (sig, packs)
+        return packs
+
     # -- which route serves a call ----------------------------------------------------------------
     def _needs_grad(self):
         return torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
 
     def _why_not_hip(self, N, L, needs_grad, drop):
-        """None when route 'mpnn_hip' serves the call, else the reason in words.  No GPU needed to ask."""
+        """None when route 'mpnn_hip' (or, for a call that needs gradients with the switch on, route
+        'mpnn_hip_train') serves the call, else the reason in words.  No GPU needed to ask."""
         C, D = self.num_edgetype + 1, self.hidden_dim
-        if needs_grad:
-            return 'gradients are required (there is no HIP backward for MPNN)'
+        if needs_grad and self.mpnn_backward_impl != 'hip':
+            return 'gradients are required (the HIP backward is opt-in: LANCZOSNET_MPNN_BACKWARD=hip)'
         if drop:
             return 'dropout=%r in training' % self.dropout
         if self.msg_func_name != 'MLP':
@@ -212,7 +282,10 @@ class MPNN(nn.Module):
         node_feat, L, label, mask = t['node_feat'], t['L'], t['label'], t['mask']
         drop = self.training and self.dropout > 0
         why = self._why_not_hip(node_feat.shape[1], L, self._needs_grad(), drop)
-        if why is None:
+        if why is None and self._needs_grad():
+            self.last_route = 'mpnn_hip_train'
+            score = self._hip_train_forward(node_feat, L, mask)
+        elif why is None:
             self.last_route = 'mpnn_hip'
             score = self._hip_forward(node_feat, L, mask)
         else:
@@ -231,6 +304,15 @@ class MPNN(nn.Module):
         table, prop, read = self._packs()
         state = ops.mpnn_forward(table[node_feat], L, *prop, self.num_prop, avg=self.aggregate_type == 'avg')
         return ops.set2vec_readout(state, mask, *read, self.num_step_set2vec)
+
+    def _hip_train_forward(self, node_feat, L, mask):
+        """The propagation on the HIP kernels (`_MpnnTrainFunction`), Set2Vec and output_func by autograd on S_T."""
+        cell = self.update_func
+        state = _MpnnTrainFunction.apply(
+            self.aggregate_type == 'avg', self.num_prop, self._transposes(), node_feat, L,
+            self.node_embedding.weight, self.input_func[0].weight, self.input_func[0].bias, *self._msg_operands(),
+            cell.weight_ih, cell.bias_ih, cell.weight_hh, cell.bias_hh)
+        return self.output_func(set2vec_batched(self.att_func, state, mask))
 
     def _torch_forward(self, node_feat, L, mask, dropout=False):
         """Differentiable torch restatement of model/mpnn.py:126-207 on device tensors, in the factored

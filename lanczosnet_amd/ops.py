@@ -2860,6 +2860,127 @@ def mpnn_forward(state0, L, W1, b1, W2, b2, Wih, bih, Whh, bhh, num_prop, avg=Tr
   return state_out
 
 
+def mpnn_forward_states(state0, L, W1, b1, W2, b2, Wih, bih, Whh, bhh, num_prop, avg=True, states=None, tile_rows=0):
+  """lnz_mpnn_forward_states: mpnn_forward (same operands, envelope, errors and bits) that leaves the state
+  trajectory -> states [num_prop + 1, B, N, D]: states[t] = S_t at the start of step t, states[num_prop] the
+  final state.  Nothing else is saved for the backward."""
+  who = 'mpnn_forward_states'
+  _need_cuda(state0, L, W1, b1, W2, b2, Wih, bih, Whh, bhh, states)
+  (B, N, C, D), (ld0,), prop = _propagation_operands(who, state0, L, W1, b1, W2, b2, Wih, bih, Whh, bhh,
+                                                     MPNN_MSG_HIDDEN, w1_cols=2)
+  T = int(num_prop)
+  if T < 0:
+    raise NotSupported(_lib.LNZ_ENOTSUP, '%s: num_prop = %d' % (who, T))
+  if states is None:
+    states = torch.empty((T + 1, B, N, D), dtype=torch.float32, device=state0.device)
+  if tuple(states.shape) != (T + 1, B, N, D) or states.dtype != torch.float32 or not states.is_contiguous():
+    raise LnzError(_lib.LNZ_EINVAL, '%s: states %s, expected a contiguous float32 %s'
+                   % (who, tuple(states.shape), (T + 1, B, N, D)))
+  with torch.cuda.device(state0.device):
+    _abi().mpnn_forward_states(state0, ld0, L, L.stride(0), L.stride(1), L.stride(2), L.stride(3), *prop, B, N, C, D,
+                               T, int(bool(avg)), None, D, states, int(tile_rows))
+  return states
+
+
+def mpnn_pack_transposes(W1, W2, Wih, Whh):
+  """The transposed weights lnz_mpnn_backward_step reads (its data-gradient products contract over the output
+  index of a forward weight): W1 [C, 64, 2 D], W2 [C, D, 64], Wih [3 D, C D], Whh [3 D, D] -> W1T [C, 2, D, 64]
+  (W1T[c, 0] = the neighbour half of W1_c transposed, W1T[c, 1] the own half), W2T [C, 64, D], WihT [C, D, 3 D]
+  (block c = Wih[:, cD:(c+1)D]^T), WhhT [D, 3 D].  Once per weight version."""
+  C, Hd, D2 = W1.shape
+  D = D2 // 2
+  f = lambda x: x.detach().float().contiguous()  # noqa: E731
+  return (f(W1.reshape(C, Hd, 2, D).permute(0, 2, 3, 1)), f(W2.transpose(1, 2)),
+          f(Wih.reshape(3 * D, C, D).permute(1, 2, 0)), f(Whh.t()))
+
+
+def mpnn_step_buffers(B, N, C, D, device):
+  """The row-space outputs of one mpnn_backward_step besides dS: (dgi [B N, 3 D], dghn [B N, D], M [B N, C D],
+  R [B N, C 64], dM [B N, C D], dPQ [B N, C 128] = per channel [dP_c | dQ_c]); a step loop allocates them once."""
+  new = lambda w: torch.empty((B * N, w), dtype=torch.float32, device=device)  # noqa: E731
+  return (new(3 * D), new(D), new(C * D), new(C * MPNN_MSG_HIDDEN), new(C * D), new(2 * C * MPNN_MSG_HIDDEN))
+
+
+def _mpnn_step_widths(C, D):
+  return (3 * D, D, C * D, C * MPNN_MSG_HIDDEN, C * D, 2 * C * MPNN_MSG_HIDDEN)
+
+
+def mpnn_backward_step(S, dSnext, L, W1, b1, W2, b2, Wih, bih, Whh, bhh, transposes=None, avg=True, dS=None,
+                       buffers=None):
+  """lnz_mpnn_backward_step: one propagation step of backpropagation through time.  S [B, N, D] = S_t (a
+  slice of mpnn_forward_states' trajectory), dSnext [B, N, D] = dL/dS_{t+1} (row strides beyond D are fine
+  for both and for dS), L and the eight propagation operands as in mpnn_forward, transposes =
+  mpnn_pack_transposes(W1, W2, Wih, Whh) (None: packed here), buffers = mpnn_step_buffers(..) (None:
+  allocated here; overwritten) -> (dS [B, N, D] = dL/dS_t, buffers).  The weight gradients of the step are
+  contractions of the buffers over the rows (mpnn_step_weight_grads)."""
+  who = 'mpnn_backward_step'
+  tr = tuple(transposes) if transposes is not None else ()
+  bufs = tuple(buffers) if buffers is not None else ()
+  _need_cuda(S, dSnext, L, W1, b1, W2, b2, Wih, bih, Whh, bhh, dS, *(tr + bufs))
+  (B, N, C, D), (lds, ldd), prop = _propagation_operands(who, S, L, W1, b1, W2, b2, Wih, bih, Whh, bhh,
+                                                         MPNN_MSG_HIDDEN, w1_cols=2, name='S',
+                                                         like=(('dSnext', dSnext),))
+  W1, _, W2, _, Wih, _, Whh, _ = prop
+  if transposes is None:
+    tr = mpnn_pack_transposes(W1, W2, Wih, Whh)
+  Hd = MPNN_MSG_HIDDEN
+  if len(tr) != 4:
+    raise LnzError(_lib.LNZ_EINVAL, '%s: four transposed weights expected' % who)
+  for t, shape in zip(tr, ((C, 2, D, Hd), (C, Hd, D), (C, D, 3 * D), (D, 3 * D))):
+    if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous():
+      raise LnzError(_lib.LNZ_EINVAL, '%s: transposed weight %s where a contiguous float32 %s is expected'
+                     % (who, tuple(t.shape), shape))
+  dS, ldo = _state_buffer(who, 'dS', dS, B, N, D, S.device)
+  if buffers is None:
+    bufs = mpnn_step_buffers(B, N, C, D, S.device)
+  if len(bufs) != 6:
+    raise LnzError(_lib.LNZ_EINVAL, '%s: six row-space buffers expected' % who)
+  for t, w in zip(bufs, _mpnn_step_widths(C, D)):
+    if tuple(t.shape) != (B * N, w) or t.dtype != torch.float32 or not t.is_contiguous():
+      raise LnzError(_lib.LNZ_EINVAL, '%s: row-space buffer %s where a contiguous float32 %s is expected'
+                     % (who, tuple(t.shape), (B * N, w)))
+  with torch.cuda.device(S.device):
+    _abi().mpnn_backward_step(S, lds, dSnext, ldd, L, L.stride(0), L.stride(1), L.stride(2), L.stride(3), *prop,
+                              *tr, B, N, C, D, int(bool(avg)), dS, ldo, *bufs)
+  return dS, bufs
+
+
+def mpnn_edge_degrees(L):
+  """deg [B N, C] float32 = the number of entries != 0 (a NaN is one) in every row of every channel of L
+  [B, N, N, C]: what db2 of mpnn_step_weight_grads weighs the rows with.  Once per backward."""
+  B, N, _, C = L.shape
+  return (L != 0).sum(dim=2).to(torch.float32).reshape(B * N, C)
+
+
+def mpnn_step_weight_grads(S, buffers, C, deg, grads=None):
+  """The weight gradients of one step from what mpnn_backward_step left, by the library GEMM of every other
+  training route here (_tn_row_splits; the C blocks of dW2 in one batched GEMM): dW1 [C, 64, 2 D] = [dP_c^T S |
+  dQ_c^T S], db1 = sum dQ_c, dW2 [C, D, 64] = dM_c^T R_c, db2 = sum_a deg_c[a] dM_c[a], dWih [3 D, C D] = dgi^T M,
+  dbih, dWhh [3 D, D] = dgh^T S, dbhh (column sums).  deg = mpnn_edge_degrees(L).  grads: the eight accumulators
+  of the earlier steps (added into, in place) or None -> the eight tensors."""
+  dgi, dghn, M, R_, dM, dPQ = buffers
+  R, D = dghn.shape
+  Hd = MPNN_MSG_HIDDEN
+  S2 = S.reshape(R, D)
+  dgh = torch.cat((dgi[:, :2 * D], dghn), dim=1)
+  k = GGNN_GRAD_SPLITS if R >= GGNN_GRAD_SPLIT_ROWS else 1
+  Rs = R // k
+  # [k, Rs, C, D]^T [k, Rs, C, 64] per (slice, channel), the k slices added in order, then the last R % k rows
+  dW2 = torch.bmm(dM[:k * Rs].view(k, Rs, C, D).permute(0, 2, 3, 1).reshape(k * C, D, Rs),
+                  R_[:k * Rs].view(k, Rs, C, Hd).permute(0, 2, 1, 3).reshape(k * C, Rs, Hd)).view(k, C, D, Hd).sum(dim=0)
+  if k * Rs < R:
+    dW2 = dW2 + torch.bmm(dM[k * Rs:].view(-1, C, D).permute(1, 2, 0), R_[k * Rs:].view(-1, C, Hd).transpose(0, 1))
+  # rows of dPQ^T S: (c, half, h) -> dW1[c, h, half D ..]
+  dW1 = _tn_row_splits(dPQ, S2).view(C, 2, Hd, D).permute(0, 2, 1, 3).reshape(C, Hd, 2 * D)
+  new = (dW1, dPQ.view(R, C, 2, Hd)[:, :, 1].sum(dim=0), dW2, (deg.view(R, C, 1) * dM.view(R, C, D)).sum(dim=0),
+         _tn_row_splits(dgi, M), dgi.sum(dim=0), _tn_row_splits(dgh, S2), dgh.sum(dim=0))
+  if grads is None:
+    return list(new)
+  for acc, x in zip(grads, new):
+    acc.add_(x)
+  return grads
+
+
 def set2vec_pack(gates, W_1):
   """The packed operands of set2vec_readout, once per weight version: gates = ((W_f, b_f), (W_i, b_i), (W_o,
   b_o), (W_m, b_m)), each [D, 2 D] / [D] -> (Wg [4, D, 2 D], bg [4, D], W1T [D, D] = W_1 transposed)."""

@@ -647,8 +647,15 @@ int lnz_pack_laplacian_ident(const float* L, int64_t stride_b, int64_t stride_r,
  * mlp_pack: per layer, lnz_spectral_mlp_pack_size(S) floats written by
  * lnz_pack_spectral_mlp().  dist_host: S integer exponents (host memory).
  * kind 0 = 'MLP'; kind 1 = plain powers G = D^p (the non-MLP branch, :118-121; mlp_pack unused).
- * D [B,K]; G [num_layer,B,S,K]. */
+ * D [B,K]; G [num_layer,B,S,K].
+ * The pack ends in two images of W0 and W6 for the compact form of the first and the last Linear
+ * (the default; LNZ_GAINS_COMPACT=0, read once per process, selects the padded form, which does
+ * not read them): behind the prefetch slack, nothing in front of them moved and the size grew by
+ * 3072 floats.  lnz_spectral_mlp_pack_source() states where float f of those images comes from:
+ * the flat index i into the row-major W0 [128,S], returned as i, or into W6 [S,128], returned
+ * as 2^32 + i; -1: the float is zero; -2: f lies outside the two images.  Host only, no GPU. */
 int64_t lnz_spectral_mlp_pack_size(int S);
+int64_t lnz_spectral_mlp_pack_source(int S, int64_t f);
 int lnz_pack_spectral_mlp(const float* W0, const float* b0, const float* W2, const float* b2,
                           const float* W4, const float* b4, const float* W6, const float* b6,
                           int S, float* pack, lnz_stream_t stream);

@@ -138,6 +138,7 @@ SIGNATURES = {
     'lnz_strip_cap': (C.c_int, [_I]),
     'lnz_plan_tiles': (C.c_int, [_P, _I, _I, _I, _I, _P, _P, _P]),
     'lnz_spectral_mlp_pack_size': (C.c_int64, [_I]),
+    'lnz_spectral_mlp_pack_source': (C.c_int64, [_I, _L]),
     'lnz_pack_spectral_mlp': (C.c_int, [_P] * 8 + [_I, _P, _P]),
     'lnz_pack_spectral_mlp_layers': (C.c_int, [_P, _I, _I, _P, _P]),
     'lnz_spectral_mlp_grad_parts': (C.c_int, [_I, _I, _I]),

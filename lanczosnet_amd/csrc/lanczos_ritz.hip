@@ -1054,6 +1054,8 @@ static size_t prep_lds_bytes(int N, int C) {
 // (A same-batch variant, gains consumers spinning on per-molecule `done` flags, was built and
 // measured: 253 us with the QL eigensolver, 244 us with the parallel one — slower than the plain
 // launches once all molecules finish within a narrow window; it was removed.)
+// COMPACT: the form of the gains MLP's first and last Linear (gains_body.hpp).
+template <bool COMPACT>
 __global__ __launch_bounds__(256, 2) void prepare_batch_gains_kernel(
     const float* __restrict__ L, int64_t sb, int64_t sr, int64_t sc, int64_t sch, int N, int C,
     float4* __restrict__ Lp, const uint8_t* __restrict__ mask, int B, int n_cu, int allow_pairs,
@@ -1102,7 +1104,7 @@ __global__ __launch_bounds__(256, 2) void prepare_batch_gains_kernel(
     const int idx = 32 * t + (lane & 31);
     const bool valid = idx < R;
     const int row = valid ? rows_g[idx] : 0;
-    lnz_gains::gains_mlp_tile(Dg, row, valid, l, lane, Bg, K, dist, S, mlp_pack, G);
+    lnz_gains::gains_mlp_tile<COMPACT>(Dg, row, valid, l, lane, Bg, K, dist, S, mlp_pack, G);
   }
 }
 
@@ -1158,7 +1160,8 @@ extern "C" int lnz_prepare_batch_prev_gains(
   const int64_t n_cons = (tiles * num_layer + 3) / 4;
   const int64_t grid = 2 * (int64_t)B + 2 + n_cons;
   LNZ_REQUIRE(grid < (1ll << 31), LNZ_ENOTSUP, "lnz_prepare_batch_prev_gains: batch too large");
-  hipLaunchKernelGGL(prepare_batch_gains_kernel, dim3((unsigned)grid), dim3(256),
+  auto kernel = lnz_gains::compact_form() ? prepare_batch_gains_kernel<true> : prepare_batch_gains_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256),
                      prep_lds_bytes(N, C), (hipStream_t)stream, L, stride_b, stride_r, stride_c, stride_ch, N, C,
                      (float4*)Lp, mask, B, n_cu, allow_pairs, lnz_plan_wg_cap(B, n_cu), plan, n_wg,
                      K, gain_rows, n_gain_rows, n_nodes, D, V, dist, S, num_layer, mlp_pack, G_prev,

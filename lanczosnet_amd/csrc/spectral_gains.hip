@@ -28,6 +28,20 @@ __global__ void pack_w0_kernel(const float* __restrict__ W0, int S, float* __res
   out[idx] = f < S ? W0[(32 * ot + (lane & 31)) * S + f] : 0.0f;
 }
 
+// the compact form's images W0c | W6c behind the prefetch slack (gains_body.hpp: compact_source)
+__device__ inline float compact_elem(const float* __restrict__ W0, const float* __restrict__ W6,
+                                     int S, int f) {
+  int tensor;
+  const int64_t src = compact_source(S, f, &tensor);
+  return tensor == 0 ? W0[src] : tensor == 6 ? W6[src] : 0.0f;
+}
+
+__global__ void pack_compact_kernel(const float* __restrict__ W0, const float* __restrict__ W6,
+                                    int S, float* __restrict__ pack) {
+  const int f = OFF_W0C + blockIdx.x * blockDim.x + threadIdx.x;
+  if (f < PACK_SIZE) pack[f] = compact_elem(W0, W6, S, f);
+}
+
 // A byte mover that rides along (lnz_spectral_gains_rows_split): the workgroups behind the MLP's
 // (blockIdx.x >= main_x) turn the batch's packed Laplacian into the split-precision strip kernel's
 // form (into `dst`: another buffer, or the pack itself), one 16 KiB chunk each — the gains launch sits between the pack and the forward
@@ -48,6 +62,7 @@ __device__ __forceinline__ bool ride_along(const SplitRide& r, const int lane) {
 // rows / n_rows (optional): compact list of the (b*K + k) eigen slots that carry a Ritz pair
 // (k < min(n_b, K), lnz_plan_batch) — the slots of zero-padded eigen columns are skipped: their
 // gains never reach an output (the V column is zero, model/lanczos_net.py:114-117).
+template <bool COMPACT>
 __global__ __launch_bounds__(64) void spectral_gains_mlp_kernel(
     const float* __restrict__ D, int R, int B, int K, DistArr dist, int S,
     const float* __restrict__ mlp_pack, const int32_t* __restrict__ rows,
@@ -59,12 +74,13 @@ __global__ __launch_bounds__(64) void spectral_gains_mlp_kernel(
   const int idx = blockIdx.x * 32 + (lane & 31);
   const bool valid = idx < R;
   const int row = valid ? (rows ? rows[idx] : idx) : 0;
-  gains_mlp_tile(D, row, valid, blockIdx.y, lane, B, K, dist, S, mlp_pack, G);
+  gains_mlp_tile<COMPACT>(D, row, valid, blockIdx.y, lane, B, K, dist, S, mlp_pack, G);
 }
 
 // Two row tiles per wavefront: every weight fragment streamed from L2 feeds 8 MFMAs instead of 4
 // (the one-tile kernel pulls 144 KB per 592 MFMAs through the CU's vector-memory path), four
 // independent accumulator chains, one wave per SIMD (the whole 512-register file).
+template <bool COMPACT>
 __global__ __launch_bounds__(64) void spectral_gains_mlp2_kernel(
     const float* __restrict__ D, int R, int B, int K, DistArr dist, int S,
     const float* __restrict__ mlp_pack, const int32_t* __restrict__ rows,
@@ -81,7 +97,7 @@ __global__ __launch_bounds__(64) void spectral_gains_mlp2_kernel(
     valid[t] = idx < R;
     row[t] = valid[t] ? (rows ? rows[idx] : idx) : 0;
   }
-  gains_mlp_tiles<2>(D, row, valid, blockIdx.y, lane, B, K, dist, S, mlp_pack, G);
+  gains_mlp_tiles<2, COMPACT>(D, row, valid, blockIdx.y, lane, B, K, dist, S, mlp_pack, G);
 }
 
 // non-MLP branch (model/lanczos_net.py:118-121): G[l][b][s][k] = D[b,k]^p_s for every layer
@@ -101,6 +117,13 @@ __global__ void spectral_gains_pow_kernel(const float* __restrict__ D, int B, in
 extern "C" int64_t lnz_spectral_mlp_pack_size(int S) {
   (void)S;
   return PACK_SIZE;
+}
+
+extern "C" int64_t lnz_spectral_mlp_pack_source(int S, int64_t f) {
+  if (S < 1 || S > SMAX || f < OFF_W0C || f >= PACK_SIZE) return -2;
+  int tensor;
+  const int64_t src = compact_source(S, (int)f, &tensor);
+  return tensor < 0 ? -1 : ((int64_t)(tensor == 6) << 32) + src;
 }
 
 extern "C" int lnz_pack_spectral_mlp(const float* W0, const float* b0, const float* W2,
@@ -123,7 +146,9 @@ extern "C" int lnz_pack_spectral_mlp(const float* W0, const float* b0, const flo
   if ((rc = lnz_pack_bias_rows(b4, HID, pack + OFF_B4, stream))) return rc;
   if ((rc = lnz_pack_rows_k8(W6, S, HID, HID, pack + OFF_W6, stream))) return rc;
   if ((rc = lnz_pack_bias_rows(b6, S, pack + OFF_B6, stream))) return rc;
-  return LNZ_OK;
+  hipLaunchKernelGGL(pack_compact_kernel, dim3((PACK_SIZE - OFF_W0C + 255) / 256), dim3(256), 0,
+                     (hipStream_t)stream, W0, W6, S, pack);
+  return lnz::check_launch("lnz_pack_spectral_mlp(compact)");
 }
 
 // All conv layers' MLP packs in ONE launch (a training step re-packs every layer after the
@@ -170,6 +195,8 @@ __global__ void pack_spectral_mlp_layers_kernel(MlpLayerPtrs ptrs, int S, float*
     v = rows_k8_elem(pl[4], HID, HID, HID, HID / 8, f - OFF_W4);
   } else if (f < OFF_W6 + 16 * 256) {
     v = rows_k8_elem(pl[6], S, HID, HID, HID / 8, f - OFF_W6);
+  } else if (f >= OFF_W0C) {
+    v = compact_elem(pl[0], pl[6], S, f);
   }
   pack[(int64_t)l * PACK_SIZE + f] = v;
 }
@@ -225,13 +252,10 @@ extern "C" int lnz_spectral_gains_rows_split_to(const float* D, int B, int K, co
     const int64_t extra_x = (chunks + num_layer - 1) / num_layer;
     LNZ_REQUIRE(ride.main_x + extra_x < (1ll << 31), LNZ_ENOTSUP, "lnz_spectral_gains_rows_split: pack too large");
     dim3 grid((unsigned)(ride.main_x + extra_x), num_layer);
-    if (two) {
-      hipLaunchKernelGGL(spectral_gains_mlp2_kernel, grid, dim3(64), 0, s, D, R, B, K, dist, S,
-                         mlp_pack, rows, n_rows, G, ride);
-    } else {
-      hipLaunchKernelGGL(spectral_gains_mlp_kernel, grid, dim3(64), 0, s, D, R, B, K, dist, S,
-                         mlp_pack, rows, n_rows, G, ride);
-    }
+    auto kernel = two ? (compact_form() ? spectral_gains_mlp2_kernel<true> : spectral_gains_mlp2_kernel<false>)
+                      : (compact_form() ? spectral_gains_mlp_kernel<true> : spectral_gains_mlp_kernel<false>);
+    hipLaunchKernelGGL(kernel, grid, dim3(64), 0, s, D, R, B, K, dist, S, mlp_pack, rows, n_rows, G,
+                       ride);
   } else {
     int64_t total = (int64_t)num_layer * B * S * K;
     hipLaunchKernelGGL(spectral_gains_pow_kernel, dim3((int)((total + 255) / 256)), dim3(256), 0,

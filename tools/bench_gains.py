@@ -1,5 +1,11 @@
-"""Spectral-gains launch time on the bench batch (live rows), 1 MI355X.  usage: bench_gains.py [reps]"""
+"""Spectral-gains launch time on the bench batch (live rows), 1 MI355X.
+usage: bench_gains.py [reps] [--padded]     --padded: the padded first and last Linear
+(LNZ_GAINS_COMPACT=0, which the library reads once per process), the default's in-build reference"""
 import os, sys, json
+PADDED = '--padded' in sys.argv
+if PADDED:
+  sys.argv.remove('--padded')
+  os.environ['LNZ_GAINS_COMPACT'] = '0'
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import oracle
@@ -25,5 +31,6 @@ for _ in range(reps): run()
 e[1].record(); torch.cuda.synchronize()
 Gf = ops.spectral_gains(D, cfg['long_diffusion_dist'], 7, plan['mlp_pack'])
 live = int(rows[1].item())
-print(json.dumps({'gains_ms': round(e[0].elapsed_time(e[1]) / reps, 4), 'live_rows': live,
+print(json.dumps({'form': 'padded' if os.environ.get('LNZ_GAINS_COMPACT') == '0' else 'compact',
+                  'gains_ms': round(e[0].elapsed_time(e[1]) / reps, 4), 'live_rows': live,
                   'checksum': float(Gf.double().abs().sum())}))

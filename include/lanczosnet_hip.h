@@ -50,6 +50,8 @@ extern "C" {
  *    lnz_set2vec_readout: additive, the version stays);
  *    + the backward of that propagation (lnz_mpnn_forward_states, lnz_mpnn_backward_step: additive, the
  *    version stays);
+ *    + the GPNN baseline's fused partition propagation, state MLP, gated propagation and readout
+ *    (lnz_gpnn_forward: additive, the version stays);
  *    + lnz_forward_args.rare_strips / .no_fold / .rare_debug at the END of the block (the strip forward's folded form of
  *    the rare bond-type channels, on by default: zeros = folded where cheaper; additive, the version
  *    stays — a caller built against the shorter block must zero-fill lnz_forward_args_size() bytes);
@@ -1439,6 +1441,42 @@ int lnz_mpnn_backward_step(const float* S, int lds, const float* dSnext, int ldd
 int lnz_set2vec_readout(const float* X, int ld, const uint8_t* mask, const float* Wg, const float* bg,
                         const float* W1T, const float* w2, const float* Wout, const float* bout, int B, int N, int D,
                         int P, int num_step, float* score, int mols_per_group, lnz_stream_t stream);
+
+/* ---- the GPNN baseline (model/gpnn.py:141-251, config/qm8_gpnn.yaml), csrc/gpnn.hip ----
+ * All num_prop outer steps and the readout in ONE launch.  state0 [B N, ld0] is
+ * input_func(embedding(node_feat)); with C = num_bond_type + 1 channels, state width D, message hidden width
+ * 128 and state_func's hidden width 512, per outer step on the state S
+ *   Sc = S; num_prop_cluster times Sc = part(Sc, L_cluster) ;  Sx = S; num_prop_cut times Sx = part(Sx, L_cut)
+ *   part(X, Lp): M = relu(X W1_0^T + b1_0) W2_0^T + b2_0                           (msg_func[0])
+ *                A = Ŵ M per molecule; Ŵ = Lp, for avg != 0 Ŵ[i, j] = Lp[i, j] / (sum_j Lp[i, j] + FLT_EPSILON)
+ *                X' = GRUCell(A, X)           (update_func_partition: Wpih [3 D][D], bpih, Wphh [3 D][D], bphh)
+ *   S = relu([S | Sc | Sx] Ws1^T + bs1) Ws2^T + bs2                  (state_func: Ws1 [512][3 D], Ws2 [D][512])
+ *   S = one step of lnz_ggnn_forward on S     (msg_func[0 .. C-1]: W1 [C][128][D], b1, W2 [C][D][128], b2; L != 0;
+ *                                              update_func: Wih [3 D][C D], bih, Whh [3 D][D], bhh)
+ * then the readout of lnz_ggnn_forward (Wo [P][D], bo, wg [D], bg [1]; mask [B, N] u8, NULL: all N rows; no
+ * masked row: NaN).  All N rows of a molecule take part.  L through its four strides as in lnz_ggnn_forward:
+ * only compared with zero, a NaN or a negative entry is an edge.  L_cluster and L_cut (element (b, i, j) at
+ * b cl_stride_b + i cl_stride_r + j cl_stride_c floats, ct_* likewise, strides >= 0) enter BY VALUE; the 'avg'
+ * row sum runs j ascending in float32; non-finite entries are outside the contract.  None of the three is
+ * written.  A count of 0 hands S itself to state_func in place of Sc / Sx; num_prop = 0: the readout of state0.
+ * state_out [B N, ldso] (may be NULL) receives the final state.
+ * 1 <= N <= 32, 1 <= C <= 8, D a multiple of 32 and <= 128, 1 <= P <= 16, the three counts >= 0, ld0 / ldso
+ * multiples of 4, state0 / state_out / the weights 16-byte aligned, tile_rows = 64 (not built) (LNZ_ENOTSUP
+ * otherwise); null pointers, B or N <= 0, ld0 / ldso below D, negative strides, score or state_out overlapping
+ * state0 or each other, tile_rows other than 0, 32, 64: LNZ_EINVAL.  A workgroup holds S, Sc and Sx of
+ * floor(32 / N) molecules in LDS for all steps (111,744 B of dynamic LDS at D = 128).  Exact-fp32 MFMA, no
+ * atomics, every sum in a fixed order: bit-reproducible, and a molecule's bits do not depend on its place in the
+ * batch.  lnz_last_kernel() names gpnn_forward_kernel<D, 2>. */
+int lnz_gpnn_forward(const float* state0, int ld0, const float* L, int64_t stride_b, int64_t stride_r,
+                     int64_t stride_c, int64_t stride_ch, const float* L_cluster, int64_t cl_stride_b,
+                     int64_t cl_stride_r, int64_t cl_stride_c, const float* L_cut, int64_t ct_stride_b,
+                     int64_t ct_stride_r, int64_t ct_stride_c, const uint8_t* mask, const float* W1,
+                     const float* b1, const float* W2, const float* b2, const float* Wih, const float* bih,
+                     const float* Whh, const float* bhh, const float* Wpih, const float* bpih, const float* Wphh,
+                     const float* bphh, const float* Ws1, const float* bs1, const float* Ws2, const float* bs2,
+                     const float* Wo, const float* bo, const float* wg, const float* bg, int B, int N, int C, int D,
+                     int P, int num_prop, int num_prop_cluster, int num_prop_cut, int avg, float* score,
+                     float* state_out, int ldso, int tile_rows, lnz_stream_t stream);
 
 
 /* ---- next row (SURVEY.md 8f rank 1 + 3): device-side collate from a packed molecule shard ----

@@ -198,6 +198,8 @@ SIGNATURES = {
                                           _I, _P, _I, _P, _I, _P]),
     'lnz_mpnn_backward_step': (C.c_int, [_P, _I, _P, _I, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                          _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    'lnz_gpnn_forward': (C.c_int, [_P, _I, _P, _L, _L, _L, _L, _P, _L, _L, _L, _P, _L, _L, _L, _P] + [_P] * 20 +
+                         [_I] * 9 + [_P, _P, _I, _I, _P]),
     'lnz_set2vec_readout': (C.c_int, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P]),
     'lnz_unsorted_segment_sum_forward': (C.c_int, [_P, _P, _I, _I, _I, _I, _P, _P]),
     'lnz_unsorted_segment_sum_backward': (C.c_int, [_P, _P, _I, _I, _I, _I, _P, _P]),

@@ -13,6 +13,7 @@ Reference interfaces replaced (paths relative to the reference repo):
   gat_attention_backward / gat_readout_backward / gat_layer_backward   the same lines under loss.backward()
   ggnn_forward        model/ggnn.py:143-197 (all num_prop steps and the readout)
   mpnn_forward        model/mpnn.py:136-196 (all num_prop steps, msg_func 'MLP')
+  gpnn_forward        model/gpnn.py:158-251 (all outer steps: partition propagations, state_func, the GGNN step; readout)
   set2vec_readout     model/set2set.py:79-100 and output_func (model/mpnn.py:199-207)
 """
 import torch
@@ -3015,3 +3016,47 @@ def set2vec_readout(X, mask, Wg, bg, W1T, W_2, Wout, bout, num_step, mols_per_gr
     _abi().set2vec_readout(X, ld, mask, Wg, bg, W1T, w2, Wout, bout, B, N, D, P, int(num_step), score,
                            int(mols_per_group))
   return score
+
+
+# ---------------------------------------------------------------------------------------- GPNN
+GPNN_STATE_HIDDEN = 512   # model/gpnn.py:68-72
+
+
+def gpnn_forward(state0, L, L_cluster, L_cut, mask, W1, b1, W2, b2, Wih, bih, Whh, bhh, Wpih, bpih, Wphh, bphh,
+                 Ws1, bs1, Ws2, bs2, Wo, bo, wg, bg, num_prop, num_prop_cluster, num_prop_cut, avg=True,
+                 state_out=None, return_state=False, tile_rows=0):
+  """lnz_gpnn_forward (model/gpnn.py:141-251): every outer step — the partition propagations, state_func, the
+  GGNN step — and the readout in one launch.  state0 [B, N, D], L [B, N, N, C] float32 in any strides (read as
+  L != 0), L_cluster / L_cut [B, N, N] float32 in any strides (read BY VALUE); none of the three is written.
+  mask [B, N] or None (all N rows).  W1 .. bhh, Wo .. bg as in ggnn_forward (msg_func, update_func, the
+  readout); Wpih [3 D, D], bpih [3 D], Wphh [3 D, D], bphh [3 D] (update_func_partition); Ws1 [512, 3 D],
+  bs1 [512], Ws2 [D, 512], bs2 [D] (state_func) -> score [B, P]; with return_state (or a `state_out` buffer
+  [B, N, D]) also the final state.  tile_rows: 0 or 32 (the 64-row tile is not built: NotSupported)."""
+  who = 'gpnn_forward'
+  _need_cuda(state0, L, L_cluster, L_cut, mask, W1, b1, W2, b2, Wih, bih, Whh, bhh, Wpih, bpih, Wphh, bphh, Ws1,
+             bs1, Ws2, bs2, Wo, bo, wg, bg, state_out)
+  (B, N, C, D), (ld0,), prop = _propagation_operands(who, state0, L, W1, b1, W2, b2, Wih, bih, Whh, bhh,
+                                                     GGNN_MSG_HIDDEN)
+  for name, t in (('L_cluster', L_cluster), ('L_cut', L_cut)):
+    if t.dtype != torch.float32 or tuple(t.shape) != (B, N, N):
+      raise LnzError(_lib.LNZ_EINVAL, '%s: %s is %s %s, not float32 %s' % (who, name, t.dtype, tuple(t.shape),
+                                                                           (B, N, N)))
+  Wpih, bpih, Wphh, bphh = _f32c(Wpih), _f32c(bpih).reshape(-1), _f32c(Wphh), _f32c(bphh).reshape(-1)
+  Ws1, bs1, Ws2, bs2 = _f32c(Ws1), _f32c(bs1).reshape(-1), _f32c(Ws2), _f32c(bs2).reshape(-1)
+  Hs = GPNN_STATE_HIDDEN
+  for t, shape in ((Wpih, (3 * D, D)), (bpih, (3 * D,)), (Wphh, (3 * D, D)), (bphh, (3 * D,)),
+                   (Ws1, (Hs, 3 * D)), (bs1, (Hs,)), (Ws2, (D, Hs)), (bs2, (D,))):
+    if tuple(t.shape) != shape:
+      raise LnzError(_lib.LNZ_EINVAL, '%s: operand of shape %s where %s is expected' % (who, tuple(t.shape), shape))
+  P, mask, head = _gated_readout_operands(who, B, N, D, mask, Wo, bo, wg, bg)
+  ldso = D
+  if state_out is not None or return_state:
+    state_out, ldso = _state_buffer(who, 'state_out', state_out, B, N, D, state0.device)
+  score = torch.empty((B, P), dtype=torch.float32, device=state0.device)
+  with torch.cuda.device(state0.device):
+    _abi().gpnn_forward(state0, ld0, L, L.stride(0), L.stride(1), L.stride(2), L.stride(3), L_cluster,
+                        L_cluster.stride(0), L_cluster.stride(1), L_cluster.stride(2), L_cut, L_cut.stride(0),
+                        L_cut.stride(1), L_cut.stride(2), mask, *prop, Wpih, bpih, Wphh, bphh, Ws1, bs1, Ws2, bs2,
+                        *head, B, N, C, D, P, int(num_prop), int(num_prop_cluster), int(num_prop_cut),
+                        int(bool(avg)), score, state_out, ldso, int(tile_rows))
+  return (score, state_out) if state_out is not None else score

@@ -404,3 +404,19 @@ def strip_split_mfma_issued(strips, cfg):
     f32 += S * 64
   return dict(mfma_f16_issued=int(f16), mfma_f32_issued=int(f32),
               flops_issued=int(f16) * FLOP_PER_MFMA16X32_F16 + int(f32) * FLOP_PER_MFMA16)
+
+
+def gpnn_flop_per_row_step(D, C, num_prop_cluster, num_prop_cut, msg_hidden=128, state_hidden=512):
+  """gpnn_forward_kernel: the products of one outer step per state row (model/gpnn.py:216-230), every padded
+  row counted, aggregates and the cells' elementwise work left out —
+    the GGNN step      C (2 D h + 2 h D + 2 D 3D) + 2 D 3D          (msg_func[c], gi, gh; h = 128)
+    a partition step   2 D h + 2 h D + 2 D 3D + 2 D 3D              (msg_func[0], the partition cell's gi and gh)
+    state_func         2 (3 D) H + 2 H D                            (H = 512)
+  D 128, C 7, counts (1, 1): 1,245,184 + 2 x 262,144 + 524,288 = 2,293,760."""
+  gate = 2 * D * 3 * D
+  msg = 2 * D * msg_hidden + 2 * msg_hidden * D
+  ggnn_step = C * (msg + gate) + gate
+  partition_step = msg + 2 * gate
+  state_mlp = 2 * 3 * D * state_hidden + 2 * state_hidden * D
+  return dict(ggnn_step=ggnn_step, partition_step=partition_step, state_mlp=state_mlp,
+              total=ggnn_step + (num_prop_cluster + num_prop_cut) * partition_step + state_mlp)

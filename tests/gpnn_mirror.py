@@ -1,0 +1,180 @@
+"""Helper of the GPNN tests (not a test): a torch restatement of the reference's GPNN forward written from
+its formulas, the case table of tests/golden/gpnn.npz and the parameter and input draws that the fixture's
+generator and the tests share.
+
+Per outer step on S [B, N, D] (model/gpnn.py:216-230):
+    Sc = S;  num_prop_cluster times:  Sc = part(Sc, L_cluster)
+    Sx = S;  num_prop_cut     times:  Sx = part(Sx, L_cut)
+    part(X, Lp):  M = relu(X W1_0^T + b1_0) W2_0^T + b2_0 ;  A = Ŵ M ;  X' = cell_partition(A, X)
+                  Ŵ = Lp ('sum'),  Ŵ[i, j] = Lp[i, j] / (sum_j Lp[i, j] + FLT_EPSILON) ('avg'): BY VALUE
+    S  = relu([S | Sc | Sx] Ws1^T + bs1) Ws2^T + bs2
+    S  = one step of ggnn_mirror.propagate on S (L != 0, msg_func[0 .. C-1], update_func)
+    score = the readout of ggnn_mirror
+state_0 = input_func(embedding(node_feat)); every one of the N rows takes part in every step.  The functions
+compute in the dtype of their operands: float64 operands give the yardstick, float32 operands on the CPU the
+reference arithmetic whose own error the kernel tests measure.  None of L, L_cluster, L_cut is written.
+
+The drawn batches are ggnn_mirror.draw_inputs' (an L with negative entries and degree-zero rows) with node
+labels in [0, 3) beside them; L_cluster / L_cut are the L4 matrices of the label split of the simple graph
+(`partition_laplacians`, a numpy restatement of utils/spectral_graph_partition.py:35-50 that gives the
+reference's bits): non-negative entries and a positive diagonal on every row, the padded rows included."""
+import os
+
+import numpy as np
+import torch
+
+import ggnn_mirror as G
+from lanczosnet_amd.utils.arg_helper import AttrDict
+
+GOLDEN = G.GOLDEN
+EPS = G.EPS
+HIDDEN = G.HIDDEN
+STATE_HIDDEN = 512
+NUM_ATOM = G.NUM_ATOM
+NUM_PARTITION = 3
+
+# name -> (model keys, where the batch comes from, pass the mask): 'collate' = tests/golden/collate_batch.npz
+# with the labels of the reference's spectral_clustering (stored in gpnn.npz), (seed, B, N) = draw_inputs
+CASES = {
+    'a': (dict(hidden=128, num_prop=10, cluster=1, cut=1, agg='avg', update='GRU', num_bond_type=6), 'collate', True),
+    'b': (dict(hidden=128, num_prop=3, cluster=2, cut=0, agg='sum', update='GRU', num_bond_type=6), 'collate', True),
+    'c': (dict(hidden=32, num_prop=2, cluster=1, cut=1, agg='avg', update='GRU', num_bond_type=1), (91, 3, 5), True),
+    'd': (dict(hidden=128, num_prop=4, cluster=1, cut=1, agg='avg', update='GRU', num_bond_type=6), (92, 2, 32), False),
+    'e': (dict(hidden=32, num_prop=2, cluster=1, cut=1, agg='avg', update='RNN', num_bond_type=1), (93, 3, 5), True),
+}
+PARAM_SEED = {'a': 61, 'b': 62, 'c': 63, 'd': 64, 'e': 65}
+
+
+def make_config(hidden, num_prop, cluster, cut, agg, update, num_bond_type, input_dim=64, output_dim=16,
+                dropout=0.0, msg='MLP'):
+  model = dict(name='GPNN', num_partition=NUM_PARTITION, input_dim=input_dim, hidden_dim=hidden,
+               output_dim=output_dim, num_layer=1, num_prop=num_prop, num_prop_cluster=cluster, num_prop_cut=cut,
+               update_func=update, msg_func=msg, aggregate_type=agg, dropout=dropout, loss='MSE')
+  return AttrDict(dict(seed=1234, dataset=dict(num_atom=NUM_ATOM, num_bond_type=num_bond_type), model=model))
+
+
+def partition_laplacians(L_simple, node_label):
+  """utils/spectral_graph_partition.py:35-50 for a batch, in numpy float64 with the reference's own operation
+  order (np.power(rowsum, -0.5), (r_i A_ij) r_j), rounded once: L_simple [B, N, N], node_label [B, N] ->
+  (L_cluster, L_cut) [B, N, N] float32."""
+  L_simple = np.asarray(L_simple, np.float64)
+  B, N, _ = L_simple.shape
+  out_cl, out_ct = np.zeros((B, N, N), np.float32), np.zeros((B, N, N), np.float32)
+  for b in range(B):
+    adj = L_simple[b] - np.diag(np.diag(L_simple[b]))
+    adj[adj != 0] = 1.0
+    lab = np.asarray(node_label[b])
+    same = (lab[:, None] == lab[None, :]).astype(np.float64)
+    adj_cluster = adj * same
+    for dst, a in ((out_cl, adj_cluster), (out_ct, adj - adj_cluster)):
+      A = np.eye(N) + a
+      r = np.power(A.sum(1), -0.5)
+      dst[b] = ((r[:, None] * A) * r[None, :]).astype(np.float32)
+  return out_cl, out_ct
+
+
+def draw_inputs(seed, B, N, C, P=16, density=0.3):
+  """ggnn_mirror.draw_inputs(seed, ..) — ragged node counts, a sparse symmetric L with negative entries and
+  degree-zero rows — plus node labels in [0, NUM_PARTITION) from RandomState(seed + 1000) and the partition
+  Laplacians of channel 0's graph under them."""
+  batch = G.draw_inputs(seed, B, N, C, P=P, density=density)
+  batch['node_label'] = np.random.RandomState(seed + 1000).randint(0, NUM_PARTITION, size=(B, N)).astype(np.int64)
+  batch['L_cluster'], batch['L_cut'] = partition_laplacians(batch['L'][..., 0], batch['node_label'])
+  return batch
+
+
+def case_inputs(name, collate_labels=None):
+  """-> (config, dict of numpy arrays node_feat / L / L_cluster / L_cut / node_label / node_mask / label,
+  whether the mask is passed).  collate_labels: the [24, 26] labels of the collate fixture (None: read from
+  tests/golden/gpnn.npz, where the generator left the reference's spectral_clustering labels)."""
+  keys, src, use_mask = CASES[name]
+  cfg = make_config(**keys)
+  if src == 'collate':
+    c = np.load(os.path.join(GOLDEN, 'collate_batch.npz'))
+    batch = {k: c[k] for k in ('node_feat', 'L', 'node_mask', 'label')}
+    if collate_labels is None:
+      collate_labels = np.load(os.path.join(GOLDEN, 'gpnn.npz'))['collate_node_label']
+    batch['node_label'] = np.asarray(collate_labels).astype(np.int64)
+    batch['L_cluster'], batch['L_cut'] = partition_laplacians(batch['L'][..., 0], batch['node_label'])
+  else:
+    batch = draw_inputs(src[0], src[1], src[2], keys['num_bond_type'] + 1)
+  return cfg, batch, use_mask
+
+
+draw_params = G.draw_params
+readout = G.readout
+
+
+def partition_weights(Lp, agg, dtype):
+  """Ŵ [B, N, N] in `dtype` from Lp, by value; Lp itself is not touched."""
+  W = Lp.to(dtype)
+  if agg == 'avg':
+    W = W / (W.sum(dim=2, keepdim=True) + EPS)
+  return W
+
+
+def cell(x, h, Wih, bih, Whh, bhh, update='GRU'):
+  """nn.GRUCell / nn.RNNCell(relu) on [.., D] operands"""
+  D = h.shape[-1]
+  gi = x @ Wih.t() + bih
+  gh = h @ Whh.t() + bhh
+  if update == 'RNN':
+    return torch.relu(gi + gh)
+  r = torch.sigmoid(gi[..., :D] + gh[..., :D])
+  z = torch.sigmoid(gi[..., D:2 * D] + gh[..., D:2 * D])
+  n = torch.tanh(gi[..., 2 * D:] + r * gh[..., 2 * D:])
+  return (1.0 - z) * n + z * h
+
+
+def propagate(S, L, L_cluster, L_cut, W1, b1, W2, b2, Wih, bih, Whh, bhh, Wpih, bpih, Wphh, bphh, Ws1, bs1, Ws2,
+              bs2, num_prop, num_cluster, num_cut, agg='avg', update='GRU', order=None):
+  """S [B, N, D] and the sixteen propagation operands in the order of ops.gpnn_forward -> the state after
+  num_prop outer steps.  order: the channel order of the GGNN step's gi sum (None = ascending)."""
+  Wcl = partition_weights(L_cluster, agg, S.dtype)
+  Wct = partition_weights(L_cut, agg, S.dtype)
+
+  def part(X, W):
+    M = torch.relu(X @ W1[0].t() + b1[0]) @ W2[0].t() + b2[0]
+    return cell(W @ M, X, Wpih, bpih, Wphh, bphh, update)
+
+  for _ in range(num_prop):
+    Sc, Sx = S, S
+    for _i in range(num_cluster):
+      Sc = part(Sc, Wcl)
+    for _i in range(num_cut):
+      Sx = part(Sx, Wct)
+    S = torch.relu(torch.cat([S, Sc, Sx], dim=2) @ Ws1.t() + bs1) @ Ws2.t() + bs2
+    S = G.propagate(S, L, W1, b1, W2, b2, Wih, bih, Whh, bhh, 1, agg=agg, update=update, order=order)
+  return S
+
+
+def operands(P, C, dtype=torch.float64):
+  """The twenty kernel operands (sixteen of the propagation, four of the readout) from a state_dict-like
+  dict of arrays / tensors, in the order of ops.gpnn_forward."""
+  g = lambda k: (P[k] if isinstance(P[k], torch.Tensor) else torch.as_tensor(np.asarray(P[k]))).to(dtype)  # noqa: E731
+  W1 = torch.stack([g('msg_func.%d.0.weight' % c) for c in range(C)])
+  b1 = torch.stack([g('msg_func.%d.0.bias' % c) for c in range(C)])
+  W2 = torch.stack([g('msg_func.%d.2.weight' % c) for c in range(C)])
+  b2 = torch.stack([g('msg_func.%d.2.bias' % c) for c in range(C)])
+  return (W1, b1, W2, b2,
+          g('update_func.weight_ih'), g('update_func.bias_ih'), g('update_func.weight_hh'), g('update_func.bias_hh'),
+          g('update_func_partition.weight_ih'), g('update_func_partition.bias_ih'),
+          g('update_func_partition.weight_hh'), g('update_func_partition.bias_hh'),
+          g('state_func.0.weight'), g('state_func.0.bias'), g('state_func.2.weight'), g('state_func.2.bias'),
+          g('output_func.0.weight'), g('output_func.0.bias'), g('att_func.0.weight'), g('att_func.0.bias'))
+
+
+def forward(P, cfg, node_feat, L, L_cluster, L_cut, mask, dtype=torch.float64, return_state=False):
+  """The whole net from the parameters P (name -> array) -> score [B, P] in `dtype`."""
+  m = cfg.model
+  C = cfg.dataset.num_bond_type + 1
+  g = lambda k: torch.as_tensor(np.asarray(P[k])).to(dtype)  # noqa: E731
+  t = lambda x: torch.as_tensor(np.asarray(x)).to(dtype)  # noqa: E731
+  nf = torch.as_tensor(np.asarray(node_feat)).long()
+  ops_ = operands(P, C, dtype)
+  S = g('embedding.weight')[nf] @ g('input_func.0.weight').t() + g('input_func.0.bias')
+  S = propagate(S, t(L), t(L_cluster), t(L_cut), *ops_[:16], m.num_prop, m.num_prop_cluster, m.num_prop_cut,
+                agg=m.aggregate_type, update=m.update_func)
+  mk = None if mask is None else torch.as_tensor(np.asarray(mask))
+  score = readout(S, mk, *ops_[16:])
+  return (score, S) if return_state else score

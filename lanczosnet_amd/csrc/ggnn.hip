@@ -40,8 +40,9 @@
 // Tile height: a tile's 15 steps take the same time whatever the batch, so R = 64 (half the weight
 // reads per row) serves batches that fill the chip and R = 32 batches whose 32-row tiles all fit in one
 // round of the compute units (tile_rows = 0 chooses; a row's arithmetic and bits are the same in
-// both).  The prologue, the message block, the gates, the cell and the state store are ggnn_tile.hpp's,
-// shared to the letter with ggnn_grad.hip and mpnn.hip; this file keeps the step loop and the readout.
+// both).  The prologue, the step (LNZ_GGNN_TILE_STEP: the message block, the gates, the cell), the state store and the
+// readout (gated_readout) are ggnn_tile.hpp's, shared to the letter with ggnn_grad.hip, mpnn.hip and gpnn.hip;
+// this file keeps the LDS layout, the loop over the steps with the trajectory's stores, and the entry points.
 // R = 128 (192 accumulator registers per lane at 256 threads) and the folded form F_c =
 // W_ih[:, c] W2_c were not built.  Measurements: DESIGN.md §4.12.
 #include "common.hpp"
@@ -68,7 +69,6 @@ __global__ __launch_bounds__(GNT) void ggnn_forward_kernel(
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int GR = 16 * RT;    // rows per tile
   constexpr int SS = D + 4;      // row stride of S, M_c, A_c
-  constexpr int DB = D / 16;     // 16-feature blocks of a state row: waves 0 .. DB-1 own one each
   float* const Sb = smem;
   float* const Mb = Sb + GR * SS;
   float* const Ab = Mb + GR * SS;
@@ -82,7 +82,7 @@ __global__ __launch_bounds__(GNT) void ggnn_forward_kernel(
   const int m = lane & 15, g = lane >> 4;
   const TileSpan ts = tile_span<RT>(B, N);
   const int64_t mol0 = ts.mol0, row0 = ts.mol0 * N;   // first molecule and first global row of the tile
-  const int nm = ts.nm, rows = ts.rows;
+  const int rows = ts.rows;
 
   // ---- the state, the bit masks and denominators of L, the molecule of every row
   load_state_tile<D, RT>(Sb, state0, row0, ld0, rows);
@@ -91,9 +91,6 @@ __global__ __launch_bounds__(GNT) void ggnn_forward_kernel(
   set_rowbase<RT>(rowbase, N, rows);
   __syncthreads();
 
-  const bool owner = wave < DB;          // wave-uniform: this wave owns features 16 wave .. 16 wave + 15
-  const float* const s_frag = Sb + m * SS + 4 * g;
-  const float* const a_frag = Ab + m * SS + 4 * g;
   const MessageTile mt = {Sb, Mb, Ab, Hb, bits, inv, rowbase};
 
   // the state trajectory [num_prop + 1][B N][D] (TRAJ: lnz_ggnn_forward_states; `states` is null and unread
@@ -105,47 +102,14 @@ __global__ __launch_bounds__(GNT) void ggnn_forward_kernel(
 
   for (int step = 0; step < num_prop; ++step) {
     if constexpr (TRAJ) put_state(step);
-    // gate accumulators of this wave's feature block: [0] r, [1] z, [2] gi_n
-    f32x4 acc[3][RT];
-    zero_tiles(acc);
-    for (int c = 0; c < C; ++c) {   // three barriers per channel
-      ggnn_message<D, RT>(mt, c, W1, b1, W2, b2, wave, m, g, [](int, const f32x4&) {},
-                          [](int, int, const f32x4&) {});
-      if (owner) gate_accumulate<D, RT>(a_frag, Wih, c, C, wave, m, g, acc);
-    }
-    f32x4 gh[3][RT];
-    if (owner) hidden_gates<D, RT>(s_frag, Whh, wave, m, g, gh);
-    __syncthreads();
-    if (owner) LNZ_GRU_CELL(D, RT);
-    __syncthreads();
+    LNZ_GGNN_TILE_STEP(D, RT, mt, W1, b1, W2, b2, Wih, bih, Whh, bhh, C);
   }
 
   // ---- the final state, on request
   if constexpr (TRAJ) put_state(num_prop);
   if (state_out != nullptr) store_state_tile<D>(state_out + row0 * (int64_t)ldso, ldso, Sb, rows);
-  // ---- readout: slot p < P: Wo[p] s + bo[p]; slot P: sigmoid(wg s + bg); d ascending
-  float* const ys = Hb;   // [row][GMAXP + 1]: H_c is dead
-  for (int idx = tid; idx < rows * (P + 1); idx += GNT) {
-    const int r = idx / (P + 1), p = idx - r * (P + 1);
-    const float* const w = p < P ? Wo + (int64_t)p * D : wg;
-    float a = 0.0f;
-    for (int d = 0; d < D; ++d) a = fmaf(Sb[r * SS + d], w[d], a);
-    a += p < P ? bo[p] : bg[0];
-    ys[r * (GMAXP + 1) + p] = p < P ? a : sigmoidf_(a);
-  }
-  __syncthreads();
-  for (int idx = tid; idx < nm * P; idx += GNT) {
-    const int ml = idx / P, p = idx - ml * P;
-    float s = 0.0f, cnt = 0.0f;
-    for (int i = 0; i < N; ++i) {
-      if (mask == nullptr || mask[(mol0 + ml) * N + i] != 0) {
-        const int r = ml * N + i;
-        s += ys[r * (GMAXP + 1) + p] * ys[r * (GMAXP + 1) + P];
-        cnt += 1.0f;
-      }
-    }
-    score[(mol0 + ml) * P + p] = s / cnt;   // (no masked row: 0 / 0, the reference's mean of nothing)
-  }
+  // ---- readout, its slots in the H block: H_c is dead
+  gated_readout<D>(Sb, Hb, mask, Wo, bo, wg, bg, ts, N, P, score);
 }
 
 template <int D, int RT, bool TRAJ>
@@ -177,20 +141,11 @@ int forward_impl(const char* who, const float* state0, int ld0, const float* L, 
                                      N, C, D, &P, num_prop);
     if (rc != LNZ_OK) return rc;
   }
-  const uint64_t rows = (uint64_t)B * N;
-  const uint64_t n0 = span(rows, ld0, D), no = span(rows, ldso, D), nsc = (uint64_t)B * P * sizeof(float);
-  LNZ_REQUIRE(!overlap(score, nsc, state0, n0), LNZ_EINVAL, "%s: score must not alias state0", who);
-  LNZ_REQUIRE(state_out == nullptr || (!overlap(state_out, no, state0, n0) && !overlap(state_out, no, score, nsc)),
-              LNZ_EINVAL, "%s: state_out must not alias state0 or score", who);
-  if (states != nullptr) {
-    const uint64_t nst = ((uint64_t)num_prop + 1) * rows * D * sizeof(float);
-    LNZ_REQUIRE(aligned16(states), LNZ_ENOTSUP, "%s: states must be 16-byte aligned", who);
-    LNZ_REQUIRE(!overlap(states, nst, state0, n0) && !overlap(states, nst, score, nsc) &&
-                    (state_out == nullptr || !overlap(states, nst, state_out, no)),
-                LNZ_EINVAL, "%s: states must not alias state0, score or state_out", who);
+  {
+    const int rc = check_outputs(who, state0, ld0, score, state_out, ldso, states, B, N, D, P, num_prop, tile_rows,
+                                 "0 (chosen by the batch), 32 or 64");
+    if (rc != LNZ_OK) return rc;
   }
-  LNZ_REQUIRE(tile_rows == 0 || tile_rows == 32 || tile_rows == 64, LNZ_EINVAL,
-              "%s: tile_rows = %d is not 0 (chosen by the batch), 32 or 64", who, tile_rows);
   const int rows_per_tile = choose_tile_rows(B, N, tile_rows);
   const int mpt = rows_per_tile / N;
   const int64_t grid = ((int64_t)B + mpt - 1) / mpt;

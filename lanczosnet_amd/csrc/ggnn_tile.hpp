@@ -1,8 +1,9 @@
 // The gated-propagation tile of the GGNN forward (ggnn.hip), of one step of its backward (ggnn_grad.hip,
-// which recomputes the step with the forward's arithmetic) and of the MPNN forward (mpnn.hip): the
-// envelope, the MFMA tile product, the prologue, the GGNN message block, the gates, the GRU cell and the
-// state store, each written once.  What stands here is the arithmetic all three kernels promise to share
-// to the bit: change it here or nowhere.
+// which recomputes the step with the forward's arithmetic), of the MPNN forward and backward step (mpnn.hip,
+// mpnn_grad.hip) and of the GPNN forward (gpnn.hip): the envelope, the MFMA tile product, the prologue, the
+// message MLP and the GGNN message block, the gates, the GRU cell, the whole GGNN step, the gated readout, the
+// cell's backward and the state store, each written once.  What stands here is the arithmetic these kernels
+// promise to share to the bit: change it here or nowhere.
 #pragma once
 #include <float.h>
 #include <stdio.h>
@@ -137,30 +138,35 @@ struct MessageTile {
   const int* rowbase;
 };
 
-// Channel c of a step, by the whole workgroup:  H_c = relu(S W1_c^T + b1_c) (wave w: hidden columns 16 w ..),
-// M_c = H_c W2_c^T + b2_c (owner waves: features 16 w ..), A_c = Â_c M_c (four features of one row per task,
-// the set bits of the row in ascending j).  A barrier after each.  with_h(rt, v) sees this lane's four hidden
-// values of row 16 rt + m, with_a(r, q, s) the features 4 q .. of row r of A_c, as they are stored: the
-// backward keeps them, the forward passes nothing.
-template <int D, int RT, class FH, class FA>
-__device__ __forceinline__ void ggnn_message(const MessageTile t, const int c, const float* __restrict__ W1,
-                                             const float* __restrict__ b1, const float* __restrict__ W2,
-                                             const float* __restrict__ b2, const int wave, const int m,
-                                             const int g, FH&& with_h, FA&& with_a) {
-  constexpr int GR = 16 * RT, SS = D + 4, DQ = D / 4, DB = D / 16;
+// A hook that keeps nothing: what the forwards pass where the backward keeps H_c and A_c
+struct NoHook {
+  template <class... A>
+  __device__ __forceinline__ void operator()(A&&...) const {}
+};
+
+// M = relu(X W1^T + b1) W2^T + b2 for one message function (W1 [128][D], b1 [128], W2 [D][128], b2 [D]) by the
+// whole workgroup:  H = relu(X W1^T + b1) into Hb (wave w: hidden columns 16 w ..), M = H W2^T + b2 into Mb
+// (owner waves: features 16 w ..).  A barrier after each half.  with_h(rt, v) sees this lane's four hidden
+// values of row 16 rt + m as they are stored.
+template <int D, int RT, class FH>
+__device__ __forceinline__ void message_mlp(const float* Xb, float* Mb, float* Hb, const float* __restrict__ W1,
+                                            const float* __restrict__ b1, const float* __restrict__ W2,
+                                            const float* __restrict__ b2, const int wave, const int m, const int g,
+                                            FH&& with_h) {
+  constexpr int SS = D + 4, DB = D / 16;
   const int f0 = 16 * wave + 4 * g;
   {
     f32x4 h[1][RT];
     zero_tiles(h);
-    const float* const wp[1] = {W1 + ((int64_t)c * GHID + 16 * wave + m) * D + 4 * g};
-    tile_gemm<1, DB, RT>(t.Sb + m * SS + 4 * g, SS, wp, h);
-    const f32x4 bv = *reinterpret_cast<const f32x4*>(b1 + c * GHID + f0);
+    const float* const wp[1] = {W1 + (int64_t)(16 * wave + m) * D + 4 * g};
+    tile_gemm<1, DB, RT>(Xb + m * SS + 4 * g, SS, wp, h);
+    const f32x4 bv = *reinterpret_cast<const f32x4*>(b1 + f0);
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
       f32x4 v;
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] = fmaxf(h[0][rt][e] + bv[e], 0.0f);
-      *reinterpret_cast<f32x4*>(t.Hb + (16 * rt + m) * HS + f0) = v;
+      *reinterpret_cast<f32x4*>(Hb + (16 * rt + m) * HS + f0) = v;
       with_h(rt, v);
     }
   }
@@ -168,13 +174,27 @@ __device__ __forceinline__ void ggnn_message(const MessageTile t, const int c, c
   if (wave < DB) {
     f32x4 mm[1][RT];
     zero_tiles(mm);
-    const float* const wp[1] = {W2 + ((int64_t)c * D + 16 * wave + m) * GHID + 4 * g};
-    tile_gemm<1, GHID / 16, RT>(t.Hb + m * HS + 4 * g, HS, wp, mm);
-    const f32x4 bv = *reinterpret_cast<const f32x4*>(b2 + c * D + f0);
+    const float* const wp[1] = {W2 + (int64_t)(16 * wave + m) * GHID + 4 * g};
+    tile_gemm<1, GHID / 16, RT>(Hb + m * HS + 4 * g, HS, wp, mm);
+    const f32x4 bv = *reinterpret_cast<const f32x4*>(b2 + f0);
 #pragma unroll
-    for (int rt = 0; rt < RT; ++rt) *reinterpret_cast<f32x4*>(t.Mb + (16 * rt + m) * SS + f0) = mm[0][rt] + bv;
+    for (int rt = 0; rt < RT; ++rt) *reinterpret_cast<f32x4*>(Mb + (16 * rt + m) * SS + f0) = mm[0][rt] + bv;
   }
   __syncthreads();
+}
+
+// Channel c of a step, by the whole workgroup:  M_c = message_mlp of channel c's weights on S, then A_c = Â_c M_c
+// (four features of one row per task, the set bits of the row in ascending j) and a barrier.  with_h: message_mlp's;
+// with_a(r, q, s) sees the features 4 q .. of row r of A_c as they are stored: the backward keeps them, the
+// forward passes NoHook.
+template <int D, int RT, class FH, class FA>
+__device__ __forceinline__ void ggnn_message(const MessageTile t, const int c, const float* __restrict__ W1,
+                                             const float* __restrict__ b1, const float* __restrict__ W2,
+                                             const float* __restrict__ b2, const int wave, const int m,
+                                             const int g, FH&& with_h, FA&& with_a) {
+  constexpr int GR = 16 * RT, SS = D + 4, DQ = D / 4;
+  message_mlp<D, RT>(t.Sb, t.Mb, t.Hb, W1 + (int64_t)c * GHID * D, b1 + c * GHID, W2 + (int64_t)c * D * GHID,
+                     b2 + c * D, wave, m, g, with_h);
   for (int idx = threadIdx.x; idx < GR * DQ; idx += GNT) {
     const int r = idx / DQ, q = idx - r * DQ;
     unsigned bm = t.bits[c * GR + r];
@@ -270,6 +290,161 @@ __device__ __forceinline__ float gru_candidate(const float gi_n, const float b_i
     }                                                                                        \
   } while (0)
 
+// One GGNN step in place on the kernel's state tile Sb (= mt.Sb) by the whole workgroup: per channel the message
+// block and the owner waves' gate product (three barriers per channel), gh = S W_hh^T, a barrier, the cell, a
+// barrier.  On entry Sb is complete behind a barrier and M, A, H are free; on exit the same holds.  The forwards'
+// step (ggnn.hip, gpnn.hip); ggnn_grad.hip keeps a loop of its own, with hooks and the backward in between.  From
+// the MessageTile and the message and cell weights given and the kernel's Sb, wave, m, g.  A macro like
+// LNZ_GRU_CELL: as an inlined function the step left every digest where it was but got another register
+// allocation in ggnn.hip (ggnn_forward_kernel<128, 2> 165 -> 127 VGPRs) and the launch ran 9 % (B = 64) and 3 %
+// (B = 1024) longer at the yaml shape; pasted, ggnn.hip keeps its registers and its time.
+#define LNZ_GGNN_TILE_STEP(D, RT, mt, W1, b1, W2, b2, Wih, bih_, Whh, bhh_, C)                               \
+  do {                                                                                                       \
+    const float* const lnz_bih_ = (bih_);                                                                    \
+    const float* const lnz_bhh_ = (bhh_);                                                                    \
+    {                                                                                                        \
+      const float* const bih = lnz_bih_; /* the names LNZ_GRU_CELL reads */                                  \
+      const float* const bhh = lnz_bhh_;                                                                     \
+      const bool owner = wave < D / 16; /* wave-uniform: this wave owns features 16 wave .. 16 wave + 15 */  \
+      f32x4 acc[3][RT]; /* gate accumulators of this wave's feature block: [0] r, [1] z, [2] gi_n */         \
+      zero_tiles(acc);                                                                                       \
+      for (int c = 0; c < C; ++c) {                                                                          \
+        ggnn_message<D, RT>(mt, c, W1, b1, W2, b2, wave, m, g, NoHook{}, NoHook{});                          \
+        if (owner) gate_accumulate<D, RT>((mt).Ab + m * (D + 4) + 4 * g, Wih, c, C, wave, m, g, acc);        \
+      }                                                                                                      \
+      f32x4 gh[3][RT];                                                                                       \
+      if (owner) hidden_gates<D, RT>(Sb + m * (D + 4) + 4 * g, Whh, wave, m, g, gh);                         \
+      __syncthreads();                                                                                       \
+      if (owner) LNZ_GRU_CELL(D, RT);                                                                        \
+      __syncthreads();                                                                                       \
+    }                                                                                                        \
+  } while (0)
+
+// The gated masked-mean readout of a tile's final state: y = (Wo s + bo) * sigmoid(wg s + bg) per live row,
+// score = the mean of y over the molecule's rows with mask != 0 (all N rows without a mask).  ys [row][GMAXP + 1]
+// is scratch LDS (the forwards pass the H block, dead by then): slot p < P: Wo[p] s + bo[p]; slot P:
+// sigmoid(wg s + bg); d ascending.
+template <int D>
+__device__ __forceinline__ void gated_readout(const float* Sb, float* ys, const unsigned char* __restrict__ mask,
+                                              const float* __restrict__ Wo, const float* __restrict__ bo,
+                                              const float* __restrict__ wg, const float* __restrict__ bg,
+                                              const TileSpan ts, const int N, const int P,
+                                              float* __restrict__ score) {
+  constexpr int SS = D + 4;
+  const int tid = threadIdx.x;
+  for (int idx = tid; idx < ts.rows * (P + 1); idx += GNT) {
+    const int r = idx / (P + 1), p = idx - r * (P + 1);
+    const float* const w = p < P ? Wo + (int64_t)p * D : wg;
+    float a = 0.0f;
+    for (int d = 0; d < D; ++d) a = fmaf(Sb[r * SS + d], w[d], a);
+    a += p < P ? bo[p] : bg[0];
+    ys[r * (GMAXP + 1) + p] = p < P ? a : sigmoidf_(a);
+  }
+  __syncthreads();
+  for (int idx = tid; idx < ts.nm * P; idx += GNT) {
+    const int ml = idx / P, p = idx - ml * P;
+    float s = 0.0f, cnt = 0.0f;
+    for (int i = 0; i < N; ++i) {
+      if (mask == nullptr || mask[(ts.mol0 + ml) * N + i] != 0) {
+        const int r = ml * N + i;
+        s += ys[r * (GMAXP + 1) + p] * ys[r * (GMAXP + 1) + P];
+        cnt += 1.0f;
+      }
+    }
+    score[(ts.mol0 + ml) * P + p] = s / cnt;   // (no masked row: 0 / 0, the reference's mean of nothing)
+  }
+}
+
+// ---------------------------------------------------------------------------------- the cell's backward
+// bitsT[c][row] = the per-molecule transpose of bits: bit i = edge (i, row).  bits and rowbase complete behind a
+// barrier; the caller's next barriers stand between this and the first read of bitsT.
+template <int RT>
+__device__ __forceinline__ void transpose_edge_bits(unsigned* bitsT, const unsigned* bits, const int* rowbase,
+                                                    const int N, const int C, const int rows) {
+  constexpr int GR = 16 * RT;
+  for (int idx = threadIdx.x; idx < GR * C; idx += GNT) {
+    const int r = idx / C, c = idx - r * C;
+    unsigned bt = 0;
+    if (r < rows) {
+      const int base = rowbase[r], j = r - base;
+      for (int i = 0; i < N; ++i) bt |= ((bits[c * GR + base + i] >> j) & 1u) << i;
+    }
+    bitsT[c * GR + r] = bt;
+  }
+}
+
+// The GRU cell of a step recomputed and differentiated, by the whole workgroup.  From the step's input state Sb,
+// the finished gate accumulators acc (gi without its bias) and dS' = dL/dS_{t+1} (dSn, the tile's rows from
+// row0 on):
+//     gh = S W_hh^T ; r, z, n as LNZ_GRU_CELL has them
+//     dn = dS' (1 - z), dz = dS' (S - n), ds = dS' z
+//     pn = dn (1 - n^2), pz = dz z (1 - z), pr = pn gh_n r (1 - r), pq = pn r
+// The planes are written for every row of the tile (a dead row: dS' = 0, so zeros), dgi = [pr, pz, pn] and
+// dghn = pq for the live rows; a barrier; then ds += dgh W_hh on the owner waves (feature k = row k of WhhT
+// [D][3 D], the contraction over r, z, n in that order: a chain of D terms per gate, then the adds: short sums).
+// ds = dS_t of this lane's four features so far; the planes are complete behind the barrier.  From the kernel's
+// Sb, Pr, Pz, Pn, Pq, acc, bih, Whh, bhh, WhhT, dSn, ldd, row0, rows, dgi, dghn, wave, m, g, owner, f0, fo
+// (= m SS + 4 g, the fragment offset in a plane) and ds.  A macro like LNZ_GRU_CELL, for its reason: as an
+// inlined function the same text got another register allocation (ggnn_backward_step_kernel<128> 128 -> 130
+// VGPRs, mpnn_backward_step_kernel<32> 122 -> 138: a wave per SIMD less in the occupancy table); pasted, both
+// step kernels compile to what they were.
+#define LNZ_GRU_CELL_BACKWARD(D, RT)                                                                       \
+  do {                                                                                                     \
+    zero_tiles(ds);                                                                                        \
+    if (owner) {                                                                                           \
+      f32x4 gh[3][RT];                                                                                     \
+      hidden_gates<D, RT>(Sb + fo, Whh, wave, m, g, gh);                                                   \
+      const GruBias b = gru_bias<D>(bih, bhh, f0);                                                         \
+      _Pragma("unroll") for (int rt = 0; rt < RT; ++rt) {                                                  \
+        const int rl = 16 * rt + m;                                                                        \
+        const bool live = rl < rows;                                                                       \
+        const f32x4 so = *reinterpret_cast<const f32x4*>(Sb + rl * SS + f0);                               \
+        f32x4 dsn = {0.0f, 0.0f, 0.0f, 0.0f};                                                              \
+        if (live) dsn = *reinterpret_cast<const f32x4*>(dSn + (row0 + rl) * (int64_t)ldd + f0);            \
+        f32x4 pr, pz, pn, pq;                                                                              \
+        _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                                    \
+          const float r = gru_gate(acc[0][rt][e], gh[0][rt][e], b.r[e]);                                   \
+          const float z = gru_gate(acc[1][rt][e], gh[1][rt][e], b.z[e]);                                   \
+          const float ghn = gh[2][rt][e] + b.hn[e];                                                        \
+          const float n = gru_candidate(acc[2][rt][e], b.in[e], r, ghn);                                   \
+          const float dn = dsn[e] * (1.0f - z);                                                            \
+          const float dz = dsn[e] * (so[e] - n);                                                           \
+          ds[0][rt][e] = dsn[e] * z;                                                                       \
+          pn[e] = dn * (1.0f - n * n);                                                                     \
+          pz[e] = dz * (z * (1.0f - z));                                                                   \
+          pr[e] = (pn[e] * ghn) * (r * (1.0f - r));                                                        \
+          pq[e] = pn[e] * r;                                                                               \
+        }                                                                                                  \
+        *reinterpret_cast<f32x4*>(Pr + rl * SS + f0) = pr;                                                 \
+        *reinterpret_cast<f32x4*>(Pz + rl * SS + f0) = pz;                                                 \
+        *reinterpret_cast<f32x4*>(Pn + rl * SS + f0) = pn;                                                 \
+        *reinterpret_cast<f32x4*>(Pq + rl * SS + f0) = pq;                                                 \
+        if (live) {                                                                                        \
+          float* const gp = dgi + (row0 + rl) * (int64_t)(3 * D) + f0;                                     \
+          *reinterpret_cast<f32x4*>(gp) = pr;                                                              \
+          *reinterpret_cast<f32x4*>(gp + D) = pz;                                                          \
+          *reinterpret_cast<f32x4*>(gp + 2 * D) = pn;                                                      \
+          *reinterpret_cast<f32x4*>(dghn + (row0 + rl) * (int64_t)D + f0) = pq;                            \
+        }                                                                                                  \
+      }                                                                                                    \
+    }                                                                                                      \
+    __syncthreads();                                                                                       \
+    if (owner) {                                                                                           \
+      const float* const row = WhhT + (int64_t)(16 * wave + m) * (3 * D) + 4 * g;                          \
+      const float* const w0[1] = {row};                                                                    \
+      const float* const w1[1] = {row + D};                                                                \
+      const float* const w2[1] = {row + 2 * D};                                                            \
+      f32x4 p0[1][RT], p1[1][RT], p2[1][RT];                                                               \
+      zero_tiles(p0);                                                                                      \
+      zero_tiles(p1);                                                                                      \
+      zero_tiles(p2);                                                                                      \
+      tile_gemm<1, DB, RT>(Pr + fo, SS, w0, p0);                                                           \
+      tile_gemm<1, DB, RT>(Pz + fo, SS, w1, p1);                                                           \
+      tile_gemm<1, DB, RT>(Pq + fo, SS, w2, p2);                                                           \
+      _Pragma("unroll") for (int rt = 0; rt < RT; ++rt) ds[0][rt] += (p0[0][rt] + p1[0][rt]) + p2[0][rt];  \
+    }                                                                                                      \
+  } while (0)
+
 // dst [rows][ld] = the live rows of Sb (dst = the tile's first row of the destination)
 template <int D>
 __device__ __forceinline__ void store_state_tile(float* __restrict__ dst, const int ld, const float* Sb,
@@ -333,6 +508,29 @@ inline int check_propagation(const char* who, const float* state0, int ld0, cons
                   weights_aligned,
               LNZ_ENOTSUP, "%s: the rows of state0, state_out and of the weights must be 16-byte "
               "aligned (ld0 = %d, ldso = %d)", who, ld0, ldso);
+  return LNZ_OK;
+}
+
+// What lnz_ggnn_forward*, lnz_gpnn_forward ask of their outputs, after check_propagation: score, state_out
+// (may be null) and the trajectory `states` [num_prop + 1][B N][D] (null for an entry point without one) alias
+// neither state0 nor each other, and tile_rows is 0 or a height; `heights` names the entry point's in words.
+inline int check_outputs(const char* who, const float* state0, int ld0, const float* score, const float* state_out,
+                         int ldso, const float* states, int B, int N, int D, int P, int num_prop, int tile_rows,
+                         const char* heights) {
+  const uint64_t rows = (uint64_t)B * N;
+  const uint64_t n0 = span(rows, ld0, D), no = span(rows, ldso, D), nsc = (uint64_t)B * P * sizeof(float);
+  LNZ_REQUIRE(!overlap(score, nsc, state0, n0), LNZ_EINVAL, "%s: score must not alias state0", who);
+  LNZ_REQUIRE(state_out == nullptr || (!overlap(state_out, no, state0, n0) && !overlap(state_out, no, score, nsc)),
+              LNZ_EINVAL, "%s: state_out must not alias state0 or score", who);
+  if (states != nullptr) {
+    const uint64_t nst = ((uint64_t)num_prop + 1) * rows * D * sizeof(float);
+    LNZ_REQUIRE(aligned16(states), LNZ_ENOTSUP, "%s: states must be 16-byte aligned", who);
+    LNZ_REQUIRE(!overlap(states, nst, state0, n0) && !overlap(states, nst, score, nsc) &&
+                    (state_out == nullptr || !overlap(states, nst, state_out, no)),
+                LNZ_EINVAL, "%s: states must not alias state0, score or state_out", who);
+  }
+  LNZ_REQUIRE(tile_rows == 0 || tile_rows == 32 || tile_rows == 64, LNZ_EINVAL, "%s: tile_rows = %d is not %s", who,
+              tile_rows, heights);
   return LNZ_OK;
 }
 

@@ -19,7 +19,8 @@
 // three states S, Sc, Sx and the M, A, H blocks of the message stay in LDS from the first step to the readout.
 // The prologue reads L into per-row bit masks (ggnn_tile.hpp) and the two partition graphs into per-row weight
 // vectors [row][32] (gpnn_tile.hpp: the 'avg' division is done once, there).  The partition step and the state
-// MLP are gpnn_tile.hpp's; the GGNN step is ggnn.hip:106-121 on ggnn_tile.hpp's functions, symbol for symbol.
+// MLP are gpnn_tile.hpp's; the GGNN step and the readout are ggnn_tile.hpp's LNZ_GGNN_TILE_STEP and gated_readout, the
+// very text and function ggnn.hip uses.
 // All products run on v_mfma_f32_16x16x4_f32 through tile_gemm, weights from global memory (L2 resident: 3.4 MB
 // at the yaml shape), states from LDS.  Barriers per outer step with counts (1, 1): 1 behind the two copies,
 // 2 x 5 in the partition steps, 9 in the state MLP, 3 C + 2 in the GGNN step.
@@ -65,7 +66,6 @@ __global__ __launch_bounds__(GNT) void gpnn_forward_kernel(
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int GR = 16 * RT;    // rows per tile
   constexpr int SS = D + 4;      // row stride of the state blocks
-  constexpr int DB = D / 16;     // 16-feature blocks of a state row: waves 0 .. DB-1 own one each
   float* const Sb = smem;
   float* const Scb = Sb + GR * SS;
   float* const Sxb = Scb + GR * SS;
@@ -81,8 +81,8 @@ __global__ __launch_bounds__(GNT) void gpnn_forward_kernel(
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int m = lane & 15, g = lane >> 4;
   const TileSpan ts = tile_span<RT>(B, N);
-  const int64_t mol0 = ts.mol0, row0 = ts.mol0 * N;
-  const int nm = ts.nm, rows = ts.rows;
+  const int64_t row0 = ts.mol0 * N;
+  const int rows = ts.rows;
 
   // ---- the state, the bit masks and denominators of L, the weights of the partition graphs
   load_state_tile<D, RT>(Sb, state0, row0, ld0, rows);
@@ -92,19 +92,7 @@ __global__ __launch_bounds__(GNT) void gpnn_forward_kernel(
   set_rowbase<RT>(rowbase, N, rows);
   __syncthreads();
 
-  const bool owner = wave < DB;
-  const float* const s_frag = Sb + m * SS + 4 * g;
-  const float* const a_frag = Ab + m * SS + 4 * g;
   const MessageTile mt = {Sb, Mb, Ab, Hb, bits, inv, rowbase};
-  // the names the step of ggnn.hip and LNZ_GRU_CELL read
-  const float* const W1 = msg.W1;
-  const float* const b1 = msg.b1;
-  const float* const W2 = msg.W2;
-  const float* const b2 = msg.b2;
-  const float* const Wih = upd.Wih;
-  const float* const bih = upd.bih;
-  const float* const Whh = upd.Whh;
-  const float* const bhh = upd.bhh;
 
   for (int step = 0; step < num_prop; ++step) {
     // ---- within the clusters, then between them: each from the step's S
@@ -112,54 +100,22 @@ __global__ __launch_bounds__(GNT) void gpnn_forward_kernel(
     if (num_cut > 0) copy_state_tile<D, RT>(Sxb, Sb);
     __syncthreads();
     for (int i = 0; i < num_cluster; ++i)
-      partition_step<D, RT>(Scb, Mb, Ab, Hb, wts, rowbase, N, rows, W1, b1, W2, b2, par.Wih, par.bih, par.Whh,
-                            par.bhh, wave, m, g);
-    for (int i = 0; i < num_cut; ++i)
-      partition_step<D, RT>(Sxb, Mb, Ab, Hb, wts + GR * GMAXN, rowbase, N, rows, W1, b1, W2, b2, par.Wih, par.bih,
+      partition_step<D, RT>(Scb, Mb, Ab, Hb, wts, rowbase, N, rows, msg.W1, msg.b1, msg.W2, msg.b2, par.Wih, par.bih,
                             par.Whh, par.bhh, wave, m, g);
+    for (int i = 0; i < num_cut; ++i)
+      partition_step<D, RT>(Sxb, Mb, Ab, Hb, wts + GR * GMAXN, rowbase, N, rows, msg.W1, msg.b1, msg.W2, msg.b2,
+                            par.Wih, par.bih, par.Whh, par.bhh, wave, m, g);
     // ---- the state MLP
     state_mlp<D, RT>(Sb, num_cluster > 0 ? Scb : Sb, num_cut > 0 ? Sxb : Sb, Hb, stf.W1, stf.b1, stf.W2, stf.b2, wave,
                      m, g);
-    // ---- the GGNN step (ggnn.hip)
-    f32x4 acc[3][RT];
-    zero_tiles(acc);
-    for (int c = 0; c < C; ++c) {
-      ggnn_message<D, RT>(mt, c, W1, b1, W2, b2, wave, m, g, [](int, const f32x4&) {},
-                          [](int, int, const f32x4&) {});
-      if (owner) gate_accumulate<D, RT>(a_frag, Wih, c, C, wave, m, g, acc);
-    }
-    f32x4 gh[3][RT];
-    if (owner) hidden_gates<D, RT>(s_frag, Whh, wave, m, g, gh);
-    __syncthreads();
-    if (owner) LNZ_GRU_CELL(D, RT);
-    __syncthreads();
+    // ---- the GGNN step
+    LNZ_GGNN_TILE_STEP(D, RT, mt, msg.W1, msg.b1, msg.W2, msg.b2, upd.Wih, upd.bih, upd.Whh, upd.bhh, C);
   }
 
   // ---- the final state, on request
   if (state_out != nullptr) store_state_tile<D>(state_out + row0 * (int64_t)ldso, ldso, Sb, rows);
-  // ---- readout (ggnn.hip): slot p < P: Wo[p] s + bo[p]; slot P: sigmoid(wg s + bg); d ascending
-  float* const ys = Hb;   // [row][GMAXP + 1]: H is dead
-  for (int idx = tid; idx < rows * (P + 1); idx += GNT) {
-    const int r = idx / (P + 1), p = idx - r * (P + 1);
-    const float* const w = p < P ? Wo + (int64_t)p * D : wg;
-    float a = 0.0f;
-    for (int d = 0; d < D; ++d) a = fmaf(Sb[r * SS + d], w[d], a);
-    a += p < P ? bo[p] : bg[0];
-    ys[r * (GMAXP + 1) + p] = p < P ? a : sigmoidf_(a);
-  }
-  __syncthreads();
-  for (int idx = tid; idx < nm * P; idx += GNT) {
-    const int ml = idx / P, p = idx - ml * P;
-    float s = 0.0f, cnt = 0.0f;
-    for (int i = 0; i < N; ++i) {
-      if (mask == nullptr || mask[(mol0 + ml) * N + i] != 0) {
-        const int r = ml * N + i;
-        s += ys[r * (GMAXP + 1) + p] * ys[r * (GMAXP + 1) + P];
-        cnt += 1.0f;
-      }
-    }
-    score[(mol0 + ml) * P + p] = s / cnt;   // (no masked row: 0 / 0, the reference's mean of nothing)
-  }
+  // ---- readout, its slots in the H block: H is dead
+  gated_readout<D>(Sb, Hb, mask, Wo, bo, wg, bg, ts, N, P, score);
 }
 
 template <int D>
@@ -209,13 +165,11 @@ extern "C" int lnz_gpnn_forward(const float* state0, int ld0, const float* L, in
     LNZ_REQUIRE(more_aligned, LNZ_ENOTSUP,
                 "%s: the rows of the partition cell's and of state_func's weights must be 16-byte aligned", who);
   }
-  const uint64_t rows = (uint64_t)B * N;
-  const uint64_t n0 = span(rows, ld0, D), no = span(rows, ldso, D), nsc = (uint64_t)B * P * sizeof(float);
-  LNZ_REQUIRE(!overlap(score, nsc, state0, n0), LNZ_EINVAL, "%s: score must not alias state0", who);
-  LNZ_REQUIRE(state_out == nullptr || (!overlap(state_out, no, state0, n0) && !overlap(state_out, no, score, nsc)),
-              LNZ_EINVAL, "%s: state_out must not alias state0 or score", who);
-  LNZ_REQUIRE(tile_rows == 0 || tile_rows == 32 || tile_rows == 64, LNZ_EINVAL,
-              "%s: tile_rows = %d is not 0 or 32", who, tile_rows);
+  {
+    const int rc = check_outputs(who, state0, ld0, score, state_out, ldso, nullptr, B, N, D, P, num_prop, tile_rows,
+                                 "0 or 32");
+    if (rc != LNZ_OK) return rc;
+  }
   LNZ_REQUIRE(tile_rows != 64, LNZ_ENOTSUP, "%s: the 64-row tile is not built (three states, M, A and H of 64 rows "
               "exceed the LDS); tile_rows = 0 or 32", who);
   const int mpt = 32 / N;

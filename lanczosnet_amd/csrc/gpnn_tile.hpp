@@ -1,7 +1,7 @@
 // What the GPNN forward (gpnn.hip) adds to the gated-propagation tile of ggnn_tile.hpp: the partition graphs'
-// weights, the message MLP without an aggregate behind it, the value-weighted aggregate, the partition cell and
-// the state MLP.  Everything else of a GPNN step (tile_gemm, the prologue, ggnn_message, the gates, the GRU
-// cell, the state store, the envelope) is ggnn_tile.hpp's, untouched.
+// weights, the value-weighted aggregate, the partition step and the state MLP.  Everything else of a GPNN step
+// (tile_gemm, the prologue, message_mlp, the gates, the GRU cell, LNZ_GGNN_TILE_STEP, the readout, the state store,
+// the envelope) is ggnn_tile.hpp's.
 #pragma once
 #include "ggnn_tile.hpp"
 
@@ -53,42 +53,6 @@ __device__ __forceinline__ void copy_state_tile(float* dst, const float* src) {
     reinterpret_cast<f32x4*>(dst)[idx] = reinterpret_cast<const f32x4*>(src)[idx];
 }
 
-// M = relu(X W1^T + b1) W2^T + b2 for one message function (W1 [128][D], b1 [128], W2 [D][128], b2 [D]: the
-// caller passes channel 0's) by the whole workgroup, the wave roles and chains of ggnn_message.  A barrier
-// after each half.
-template <int D, int RT>
-__device__ __forceinline__ void message_mlp(const float* Xb, float* Mb, float* Hb, const float* __restrict__ W1,
-                                            const float* __restrict__ b1, const float* __restrict__ W2,
-                                            const float* __restrict__ b2, const int wave, const int m, const int g) {
-  constexpr int SS = D + 4, DB = D / 16;
-  const int f0 = 16 * wave + 4 * g;
-  {
-    f32x4 h[1][RT];
-    zero_tiles(h);
-    const float* const wp[1] = {W1 + (int64_t)(16 * wave + m) * D + 4 * g};
-    tile_gemm<1, DB, RT>(Xb + m * SS + 4 * g, SS, wp, h);
-    const f32x4 bv = *reinterpret_cast<const f32x4*>(b1 + f0);
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-      f32x4 v;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = fmaxf(h[0][rt][e] + bv[e], 0.0f);
-      *reinterpret_cast<f32x4*>(Hb + (16 * rt + m) * HS + f0) = v;
-    }
-  }
-  __syncthreads();
-  if (wave < DB) {
-    f32x4 mm[1][RT];
-    zero_tiles(mm);
-    const float* const wp[1] = {W2 + (int64_t)(16 * wave + m) * GHID + 4 * g};
-    tile_gemm<1, GHID / 16, RT>(Hb + m * HS + 4 * g, HS, wp, mm);
-    const f32x4 bv = *reinterpret_cast<const f32x4*>(b2 + f0);
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) *reinterpret_cast<f32x4*>(Mb + (16 * rt + m) * SS + f0) = mm[0][rt] + bv;
-  }
-  __syncthreads();
-}
-
 // A = Ŵ M per molecule with the row's N weights w[row][j] from LDS: four features of one row per task,
 // j ascending, fmaf (a zero weight is a term like any other: Lp enters by value).  A dead row gets zeros.
 // A barrier behind it.
@@ -114,7 +78,8 @@ __device__ __forceinline__ void weighted_aggregate(float* Ab, const float* Mb, c
   __syncthreads();
 }
 
-// One partition step in place on the state tile Sb (model/gpnn.py:192-213): M = msg_func[0](S), A = Ŵ M,
+// One partition step in place on the state tile Sb (model/gpnn.py:192-213): M = msg_func[0](S) (message_mlp on
+// channel 0's weights: no bit-mask aggregate behind it), A = Ŵ M,
 // S' = GRUCell_partition(A, S) with Wih [3 D][D] (gate_accumulate with C = 1, c = 0 is the cell's gi).
 // On entry Sb is complete behind a barrier and M, A, H are free; on exit the same holds.
 template <int D, int RT>
@@ -127,7 +92,7 @@ __device__ __forceinline__ void partition_step(float* Sb, float* Mb, float* Ab, 
                                                const int wave, const int m, const int g) {
   constexpr int SS = D + 4;
   const bool owner = wave < D / 16;
-  message_mlp<D, RT>(Sb, Mb, Hb, W1, b1, W2, b2, wave, m, g);
+  message_mlp<D, RT>(Sb, Mb, Hb, W1, b1, W2, b2, wave, m, g, NoHook{});
   weighted_aggregate<D, RT>(Ab, Mb, w, rowbase, N, rows);
   f32x4 acc[3][RT], gh[3][RT];
   if (owner) {

@@ -91,20 +91,11 @@ __global__ __launch_bounds__(GNT) void mpnn_backward_step_kernel(
                      [&](const int at, const int degree) { deg[at] = (float)degree; });
   set_rowbase<RT>(rowbase, N, rows);
   __syncthreads();
-  for (int idx = tid; idx < GR * C; idx += GNT) {
-    const int r = idx / C, c = idx - r * C;
-    unsigned bt = 0;
-    if (r < rows) {
-      const int base = rowbase[r], j = r - base;
-      for (int i = 0; i < N; ++i) bt |= ((bits[c * GR + base + i] >> j) & 1u) << i;
-    }
-    bitsT[c * GR + r] = bt;
-  }
+  transpose_edge_bits<RT>(bitsT, bits, rowbase, N, C, rows);
   // (the barriers of the first channel loop stand between this and the first read of bitsT)
 
   const bool owner = wave < DB;
   const int f0 = 16 * wave + 4 * g;
-  const float* const s_frag = Sb + m * SS + 4 * g;
   const float* const m_frag = Mb + m * SS + 4 * g;
   const int fo = m * SS + 4 * g;   // the fragment offset in a plane
   const EdgeTile et = {Sb, Mb, Hb, Rb, bits, deg, rowbase};
@@ -124,63 +115,9 @@ __global__ __launch_bounds__(GNT) void mpnn_backward_step_kernel(
         });
     if (owner) gate_accumulate<D, RT>(m_frag, Wih, c, C, wave, m, g, acc);
   }
+  // ---- the cell and its backward (ggnn_tile.hpp): the planes, dgi, dghn, and dS_t = dS' z + dgh W_hh so far
   f32x4 ds[1][RT];   // dS_t of this lane's four features
-  zero_tiles(ds);
-  if (owner) {
-    f32x4 gh[3][RT];
-    hidden_gates<D, RT>(s_frag, Whh, wave, m, g, gh);
-    // ---- the cell (LNZ_GRU_CELL's expressions) and its backward on this wave's features; the planes are written
-    // for every row of the tile (a dead row: dS' = 0, so zeros)
-    const GruBias b = gru_bias<D>(bih, bhh, f0);
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-      const int rl = 16 * rt + m;
-      const bool live = rl < rows;
-      const f32x4 so = *reinterpret_cast<const f32x4*>(Sb + rl * SS + f0);
-      f32x4 dsn = {0.0f, 0.0f, 0.0f, 0.0f};
-      if (live) dsn = *reinterpret_cast<const f32x4*>(dSn + (row0 + rl) * (int64_t)ldd + f0);
-      f32x4 pr, pz, pn, pq;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float r = gru_gate(acc[0][rt][e], gh[0][rt][e], b.r[e]);
-        const float z = gru_gate(acc[1][rt][e], gh[1][rt][e], b.z[e]);
-        const float ghn = gh[2][rt][e] + b.hn[e];
-        const float n = gru_candidate(acc[2][rt][e], b.in[e], r, ghn);
-        const float dn = dsn[e] * (1.0f - z);
-        const float dz = dsn[e] * (so[e] - n);
-        ds[0][rt][e] = dsn[e] * z;
-        pn[e] = dn * (1.0f - n * n);
-        pz[e] = dz * (z * (1.0f - z));
-        pr[e] = (pn[e] * ghn) * (r * (1.0f - r));
-        pq[e] = pn[e] * r;
-      }
-      *reinterpret_cast<f32x4*>(Pr + rl * SS + f0) = pr;
-      *reinterpret_cast<f32x4*>(Pz + rl * SS + f0) = pz;
-      *reinterpret_cast<f32x4*>(Pn + rl * SS + f0) = pn;
-      *reinterpret_cast<f32x4*>(Pq + rl * SS + f0) = pq;
-      if (live) {
-        float* const gp = dgi + (row0 + rl) * (int64_t)(3 * D) + f0;
-        *reinterpret_cast<f32x4*>(gp) = pr;
-        *reinterpret_cast<f32x4*>(gp + D) = pz;
-        *reinterpret_cast<f32x4*>(gp + 2 * D) = pn;
-        *reinterpret_cast<f32x4*>(dghn + (row0 + rl) * (int64_t)D + f0) = pq;
-      }
-    }
-  }
-  __syncthreads();
-  if (owner) {   // dS += dgh W_hh: feature k = row k of WhhT, the contraction over r, z, n in that order
-    const float* const row = WhhT + (int64_t)(16 * wave + m) * (3 * D) + 4 * g;
-    const float* const w0[1] = {row};
-    const float* const w1[1] = {row + D};
-    const float* const w2[1] = {row + 2 * D};
-    f32x4 p0[1][RT], p1[1][RT], p2[1][RT];   // a chain of D terms per gate, then the adds: short sums
-    zero_tiles(p0), zero_tiles(p1), zero_tiles(p2);
-    tile_gemm<1, DB, RT>(Pr + fo, SS, w0, p0);
-    tile_gemm<1, DB, RT>(Pz + fo, SS, w1, p1);
-    tile_gemm<1, DB, RT>(Pq + fo, SS, w2, p2);
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) ds[0][rt] += (p0[0][rt] + p1[0][rt]) + p2[0][rt];
-  }
+  LNZ_GRU_CELL_BACKWARD(D, RT);
   const int cb = wave & 3, hrt = wave >> 2;   // dR_c: this wave's block of 16 hidden columns and its row tile
   for (int c = 0; c < C; ++c) {
     // [P_c | Q_c] again (every wave has passed the barrier behind the last read of Hb and Mb)

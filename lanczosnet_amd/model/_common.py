@@ -5,6 +5,8 @@ stacked readout head, masked-mean readout, embedding gradient, the parameter-gra
 Several tests and benchmark fields compare bit for bit across the regimes' routes: where two
 callers need different operands (a detached lookup, a cast, the live parameters) the helper takes
 an explicit argument; it never picks one caller's behaviour for both."""
+import warnings
+
 import torch
 import torch.nn as nn
 
@@ -32,6 +34,33 @@ LARGE_MAX_OPERATORS = 8     # the pack kernel's channel map (`LargeChanMap`)
 
 def _opt(node, key, default):
     return getattr(node, key) if hasattr(node, key) else default
+
+
+# -- what every module of the package asks of a call --------------------------------------------
+class _CallPlumbing:
+    """Mixed into LanczosNet and the baseline modules: does the call need gradients, and are its inputs
+    where the module is."""
+
+    def _needs_grad(self):
+        return torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+
+    def _to_module_device(self, dev, **tensors):
+        """`QM8Runner.test` moves only `D, V` to the GPU and hands over a HOST `L` (and, like every
+        loop of the runner, host-side nothing else) — runner/qm8_runner.py:301-302; the reference
+        model then fails inside `bmm`.  A drop-in should not: inputs that are not on the module's
+        device are moved there, with one warning per module."""
+        out, moved = {}, []
+        for k, t in tensors.items():
+            if isinstance(t, torch.Tensor) and t.device != dev:
+                moved.append(k)
+                t = t.to(dev, non_blocking=True)
+            out[k] = t
+        if moved and not getattr(self, '_warned_host_inputs', False):
+            warnings.warn('lanczosnet_amd: input(s) %s were not on %s and were moved there '
+                          '(reference runner/qm8_runner.py:301-302 leaves L on the host); keep the '
+                          'batch resident on the GPU to avoid the copy' % (', '.join(moved), dev))
+            self._warned_host_inputs = True
+        return out
 
 
 # -- layer-0 state ---------------------------------------------------------------------------

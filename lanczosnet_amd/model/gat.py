@@ -26,13 +26,13 @@ of `torch.stack` / `torch.cat` hands the pieces to the parameters: the C copies 
 every shape reason still take 'gat_torch'.
 """
 import os
-import warnings
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
+from ._baseline import _Baseline
 from ._common import _opt
 
 __all__ = ['GAT']
@@ -92,8 +92,10 @@ class _GatTrainFunction(torch.autograd.Function):
         return (None, None, None, None, None, demb, dWo, dbo, dwg.view(1, -1), dbg) + tuple(grads)
 
 
-class GAT(nn.Module):
+class GAT(_Baseline):
     """Graph Attention Networks (Velickovic et al., ICLR 2018) as the reference builds it for QM8."""
+    _route_prefix = 'gat'
+    _hip_kernels = 'kernels'
     # 'torch': a call that needs gradients takes route 'gat_torch'; 'hip': route 'gat_hip_train'
     gat_backward_impl = os.environ.get('LANCZOSNET_GAT_BACKWARD', 'torch')
 
@@ -128,25 +130,14 @@ class GAT(nn.Module):
         self.att_func = nn.Sequential(nn.Linear(dims[-2], 1), nn.Sigmoid())
         self.output_func = nn.Sequential(nn.Linear(dims[-2], dims[-1]))
 
-        losses = {'CrossEntropy': nn.CrossEntropyLoss, 'MSE': nn.MSELoss, 'L1': nn.L1Loss}
-        if m.loss not in losses:
-            raise ValueError("Non-supported loss function!")
-        self.loss_func = losses[m.loss]()
-        self._init_param()
-        self._pack_cache = None
-        self._param_list = None
-        self.last_route = None
+        self._finish_init(m.loss)
 
     def _init_param(self):
         # model/gat.py:88-123: Xavier-uniform weights, zero biases, in this order
         heads = lambda nets: [l for per_t in nets for per_c in per_t for l in per_c]  # noqa: E731
-        for group in (list(self.att_func), list(self.output_func), heads(self.filter),
-                      heads(self.att_net_1), heads(self.att_net_2)):
-            for layer in group:
-                if isinstance(layer, nn.Linear):
-                    nn.init.xavier_uniform_(layer.weight.data)
-                    if layer.bias is not None:
-                        layer.bias.data.zero_()
+        for group in (self.att_func, self.output_func, heads(self.filter), heads(self.att_net_1),
+                      heads(self.att_net_2)):
+            self._init_linears(group)
 
     # -- the parameters of one layer as stacked operands, block order c H + h ------------------------
     def _used_bias(self, h, t):
@@ -166,48 +157,21 @@ class GAT(nn.Module):
         bias = torch.stack([self._used_bias(h, t) for c, h in blocks])
         return W, a1, b1, a2, b2, bias
 
-    def _param_signature(self):
-        """What the stacked operands are keyed on: the tensor version of every parameter (an optimizer step
-        or any other in-place update bumps it) and the device.  The parameter list is walked once per
-        plan, not per call: 2,357 parameters at the yaml shape."""
-        if self._param_list is None:
-            self._param_list = list(self.parameters())
-        return (str(self.embedding.weight.device),) + tuple(p._version for p in self._param_list)
-
-    def invalidate_plan(self):
-        """Drop the stacked operands.  Writes that bump no tensor version (`p.data.clamp_()`, `p.data = x`,
-        the reference's own `_init_param` idiom) and a parameter replaced by another object need this
-        call.  `load_state_dict` and `.to()/.cuda()/.float()` call it themselves."""
-        self._pack_cache = None
-        self._param_list = None
-
-    def _apply(self, fn, *a, **kw):
-        self.invalidate_plan()
-        return super()._apply(fn, *a, **kw)
-
-    def load_state_dict(self, *a, **kw):
-        self.invalidate_plan()
-        return super().load_state_dict(*a, **kw)
-
-    @torch.no_grad()
     def _packs(self):
-        sig = self._param_signature()
-        if self._pack_cache is not None and self._pack_cache[0] == sig:
-            return self._pack_cache[1]
-        layers = []
-        for t in range(self.num_layer):
-            W, a1, b1, a2, b2, bias = self._layer_operands(t)
-            layers.append(tuple(x.detach().float().contiguous()
-                                for x in (W.reshape(-1, W.shape[2]), a1, b1, a2, b2, bias)))
-        head = tuple(x.detach().float().contiguous() for x in (
-            self.output_func[0].weight, self.output_func[0].bias, self.att_func[0].weight, self.att_func[0].bias))
-        self._pack_cache = (sig, (layers, head))
-        return self._pack_cache[1]
+        """(per layer the six stacked operands of ops.gat_layer, the four of ops.gat_readout), once per weight
+        version"""
+        def build():
+            layers = []
+            for t in range(self.num_layer):
+                W, a1, b1, a2, b2, bias = self._layer_operands(t)
+                layers.append(tuple(x.detach().float().contiguous()
+                                    for x in (W.reshape(-1, W.shape[2]), a1, b1, a2, b2, bias)))
+            head = tuple(x.detach().float().contiguous() for x in (
+                self.output_func[0].weight, self.output_func[0].bias, self.att_func[0].weight, self.att_func[0].bias))
+            return layers, head
+        return self._cached('_pack_cache', build)
 
     # -- which route serves a call ----------------------------------------------------------------
-    def _needs_grad(self):
-        return torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
-
     def _why_not_hip(self, N, L, needs_grad, drop):
         """None when route 'gat_hip' serves the call, else the reason in words.  No GPU needed to ask."""
         C, T = self.num_edgetype + 1, self.num_layer
@@ -229,56 +193,12 @@ class GAT(nn.Module):
             return 'input_dim=%d is not a multiple of %d' % (self.input_dim, GAT_WIDTH_STEP)
         if self.output_dim > ops.GAT_MAX_OUTPUTS:
             return 'output_dim=%d > %d' % (self.output_dim, ops.GAT_MAX_OUTPUTS)
-        if L.dtype != torch.float32 or L.dim() != 4 or L.shape[3] != C:
-            return 'L is %s %s, not float32 [B, N, N, %d]' % (L.dtype, tuple(L.shape), C)
-        if self.embedding.weight.dtype != torch.float32:
-            return 'the parameters are %s, not float32' % self.embedding.weight.dtype
-        return None
-
-    def _to_module_device(self, dev, **tensors):
-        """The reference's runner hands over host tensors (runner/qm8_runner.py:301-302 leaves L on the
-        host): inputs that are not on the module's device are moved there, with one warning per module."""
-        out, moved = {}, []
-        for k, t in tensors.items():
-            if isinstance(t, torch.Tensor) and t.device != dev:
-                moved.append(k)
-                t = t.to(dev, non_blocking=True)
-            out[k] = t
-        if moved and not getattr(self, '_warned_host_inputs', False):
-            warnings.warn('lanczosnet_amd: input(s) %s were not on %s and were moved there '
-                          '(reference runner/qm8_runner.py:301-302 leaves L on the host); keep the '
-                          'batch resident on the GPU to avoid the copy' % (', '.join(moved), dev))
-            self._warned_host_inputs = True
-        return out
+        return self._why_not_hip_operands(L, C)
 
     def forward(self, node_feat, L, label=None, mask=None):
         """node_feat [B, N] long, L [B, N, N, E + 1] float, label [B, P], mask [B, N] (None: the mean
         runs over all N rows, model/gat.py:192-194) -> score [B, P], or (score, loss) with a label."""
-        dev = self.embedding.weight.device
-        if dev.type != 'cuda':
-            raise RuntimeError('lanczosnet_amd models run on the AMD GPU only: move the '
-                               'module and its inputs to cuda (no CPU fallback)')
-        t = self._to_module_device(dev, node_feat=node_feat, L=L, label=label, mask=mask)
-        node_feat, L, label, mask = t['node_feat'], t['L'], t['label'], t['mask']
-        drop = self.training and self.dropout > 0
-        needs_grad = self._needs_grad()
-        why = self._why_not_hip(node_feat.shape[1], L, needs_grad, drop)
-        if why is None and needs_grad:
-            self.last_route = 'gat_hip_train'
-            score = self._hip_train_forward(node_feat, L, mask)
-        elif why is None:
-            self.last_route = 'gat_hip'
-            score = self._hip_forward(node_feat, L, mask)
-        else:
-            self.last_route = 'gat_torch'
-            if not getattr(self, '_warned_torch_route', False):
-                warnings.warn('lanczosnet_amd: GAT takes the differentiable torch restatement (route '
-                              "'gat_torch', slower than the HIP kernels of route 'gat_hip'): %s" % why)
-                self._warned_torch_route = True
-            score = self._torch_forward(node_feat, L, mask, dropout=drop)
-        if label is not None:
-            return score, self.loss_func(score, label)
-        return score
+        return self._dispatch(node_feat=node_feat, L=L, label=label, mask=mask)
 
     @torch.no_grad()
     def _hip_forward(self, node_feat, L, mask):

@@ -24,14 +24,13 @@ backward does not exist yet), dropout in training, `update_func: 'RNN'`, shapes 
 takes 'gpnn_torch', a device-side differentiable torch restatement, with one UserWarning per module that
 names the reason.  There is no CPU path.
 """
-import warnings
-
 import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
+from ._baseline import _Baseline
 from ._common import _opt
 
 __all__ = ['GPNN']
@@ -40,8 +39,9 @@ EPS = float(np.finfo(np.float32).eps)
 GPNN_INPUT_STEP = 32   # lnz_f32_linear: K (= input_dim) a multiple of 32
 
 
-class GPNN(nn.Module):
+class GPNN(_Baseline):
     """Graph Partition Neural Networks (Liao et al., 2018) as the reference builds it for QM8."""
+    _route_prefix = 'gpnn'
 
     def __init__(self, config):
         super().__init__()
@@ -87,32 +87,15 @@ class GPNN(nn.Module):
         self.input_func = nn.Sequential(nn.Linear(self.input_dim, D))
         self.output_func = nn.Sequential(nn.Linear(D, self.output_dim))
 
-        losses = {'CrossEntropy': nn.CrossEntropyLoss, 'MSE': nn.MSELoss, 'L1': nn.L1Loss}
-        if m.loss not in losses:
-            raise ValueError("Non-supported loss function!")
-        self.loss_func = losses[m.loss]()
-        self._init_param()
-        self._pack_cache = None
-        self._param_list = None
-        self.last_route = None
+        self._finish_init(m.loss)
 
     def _init_param(self):
         # model/gpnn.py:107-139.  msg_func is a ModuleList, neither an nn.Sequential nor an nn.Linear: the
         # reference's loop passes over it, its Linears keep torch's default init and nonzero biases
-        for group in (self.input_func, self.state_func, self.msg_func, self.att_func, self.output_func):
-            if isinstance(group, nn.Sequential):
-                for layer in group:
-                    if isinstance(layer, nn.Linear):
-                        nn.init.xavier_uniform_(layer.weight.data)
-                        if layer.bias is not None:
-                            layer.bias.data.zero_()
+        self._init_sequentials((self.input_func, self.state_func, self.msg_func, self.att_func, self.output_func))
         if self.update_kind in ('GRU', 'RNN'):
-            for cell in (self.update_func, self.update_func_partition):
-                nn.init.xavier_uniform_(cell.weight_hh.data)       # hh before ih, as in the reference
-                nn.init.xavier_uniform_(cell.weight_ih.data)
-                if cell.bias:
-                    cell.bias_hh.data.zero_()
-                    cell.bias_ih.data.zero_()
+            self._init_cell(self.update_func)
+            self._init_cell(self.update_func_partition)
         # update_func 'MLP': model/gpnn.py:134-139 tests the two Sequentials themselves for nn.Linear, which
         # they are not: nothing is initialised, torch's default init stays
 
@@ -125,49 +108,23 @@ class GPNN(nn.Module):
         b2 = torch.stack([f[2].bias for f in self.msg_func])
         return W1, b1, W2, b2
 
-    def _param_signature(self):
-        """What the packed operands are keyed on: the tensor version of every parameter (an optimizer
-        step or any other in-place update bumps it) and the device."""
-        if self._param_list is None:
-            self._param_list = list(self.parameters())
-        return (str(self.embedding.weight.device),) + tuple(p._version for p in self._param_list)
-
-    def invalidate_plan(self):
-        """Drop the packed operands and the [num_atom, D] table.  Writes that bump no tensor version
-        (`p.data.clamp_()`, `p.data = x`) and a parameter replaced by another object need this call.
-        `load_state_dict` and `.to()/.cuda()/.float()` call it themselves."""
-        self._pack_cache = None
-        self._param_list = None
-
-    def _apply(self, fn, *a, **kw):
-        self.invalidate_plan()
-        return super()._apply(fn, *a, **kw)
-
-    def load_state_dict(self, *a, **kw):
-        self.invalidate_plan()
-        return super().load_state_dict(*a, **kw)
-
-    @torch.no_grad()
     def _packs(self):
-        """(table [num_atom, D] = input_func(embedding.weight), the twenty operands of ops.gpnn_forward)"""
-        sig = self._param_signature()
-        if self._pack_cache is not None and self._pack_cache[0] == sig:
-            return self._pack_cache[1]
-        f = lambda x: x.detach().float().contiguous()  # noqa: E731
-        cell, part, st = self.update_func, self.update_func_partition, self.state_func
-        operands = tuple(f(x) for x in self._msg_operands() + (
-            cell.weight_ih, cell.bias_ih, cell.weight_hh, cell.bias_hh,
-            part.weight_ih, part.bias_ih, part.weight_hh, part.bias_hh,
-            st[0].weight, st[0].bias, st[2].weight, st[2].bias,
-            self.output_func[0].weight, self.output_func[0].bias, self.att_func[0].weight, self.att_func[0].bias))
-        table = ops.f32_linear(f(self.embedding.weight), f(self.input_func[0].weight), bias=f(self.input_func[0].bias))
-        self._pack_cache = (sig, (table, operands))
-        return self._pack_cache[1]
+        """(table [num_atom, D] = input_func(embedding.weight), the twenty operands of ops.gpnn_forward), once per
+        weight version"""
+        def build():
+            f = lambda x: x.detach().float().contiguous()  # noqa: E731
+            cell, part, st = self.update_func, self.update_func_partition, self.state_func
+            operands = tuple(f(x) for x in self._msg_operands() + (
+                cell.weight_ih, cell.bias_ih, cell.weight_hh, cell.bias_hh,
+                part.weight_ih, part.bias_ih, part.weight_hh, part.bias_hh,
+                st[0].weight, st[0].bias, st[2].weight, st[2].bias,
+                self.output_func[0].weight, self.output_func[0].bias, self.att_func[0].weight, self.att_func[0].bias))
+            table = ops.f32_linear(f(self.embedding.weight), f(self.input_func[0].weight),
+                                   bias=f(self.input_func[0].bias))
+            return table, operands
+        return self._cached('_pack_cache', build)
 
     # -- which route serves a call ----------------------------------------------------------------
-    def _needs_grad(self):
-        return torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
-
     def _why_not_hip(self, N, L, L_cluster, L_cut, needs_grad, drop):
         """None when route 'gpnn_hip' serves the call, else the reason in words.  No GPU needed to ask."""
         C, D = self.num_edgetype + 1, self.hidden_dim
@@ -191,30 +148,7 @@ class GPNN(nn.Module):
         if self.num_prop < 0 or self.num_prop_cluster < 0 or self.num_prop_cut < 0:
             return 'num_prop=%d, num_prop_cluster=%d, num_prop_cut=%d' % (self.num_prop, self.num_prop_cluster,
                                                                          self.num_prop_cut)
-        if L.dtype != torch.float32 or L.dim() != 4 or L.shape[3] != C:
-            return 'L is %s %s, not float32 [B, N, N, %d]' % (L.dtype, tuple(L.shape), C)
-        for name, t in (('L_cluster', L_cluster), ('L_cut', L_cut)):
-            if t.dtype != torch.float32 or t.dim() != 3:
-                return '%s is %s %s, not float32 [B, N, N]' % (name, t.dtype, tuple(t.shape))
-        if self.embedding.weight.dtype != torch.float32:
-            return 'the parameters are %s, not float32' % self.embedding.weight.dtype
-        return None
-
-    def _to_module_device(self, dev, **tensors):
-        """The reference's runner hands over host tensors (runner/qm8_runner.py leaves the graph tensors on
-        the host): inputs that are not on the module's device are moved there, with one warning per module."""
-        out, moved = {}, []
-        for k, t in tensors.items():
-            if isinstance(t, torch.Tensor) and t.device != dev:
-                moved.append(k)
-                t = t.to(dev, non_blocking=True)
-            out[k] = t
-        if moved and not getattr(self, '_warned_host_inputs', False):
-            warnings.warn('lanczosnet_amd: input(s) %s were not on %s and were moved there '
-                          '(the reference runner leaves the graph tensors on the host); keep the '
-                          'batch resident on the GPU to avoid the copy' % (', '.join(moved), dev))
-            self._warned_host_inputs = True
-        return out
+        return self._why_not_hip_operands(L, C, graphs=(('L_cluster', L_cluster), ('L_cut', L_cut)))
 
     def forward(self, node_feat, L, L_cluster, L_cut, label=None, mask=None):
         """node_feat [B, N] long, L [B, N, N, E + 1] float (read as L != 0), L_cluster / L_cut [B, N, N] float
@@ -227,29 +161,7 @@ class GPNN(nn.Module):
             raise NotImplementedError('GPNN: update_func=%r: the reference calls an nn.Sequential with two '
                                       'arguments (model/gpnn.py:187, :210); only GRU and RNN run'
                                       % (self.update_kind,))
-        dev = self.embedding.weight.device
-        if dev.type != 'cuda':
-            raise RuntimeError('lanczosnet_amd models run on the AMD GPU only: move the '
-                               'module and its inputs to cuda (no CPU fallback)')
-        t = self._to_module_device(dev, node_feat=node_feat, L=L, L_cluster=L_cluster, L_cut=L_cut, label=label,
-                                   mask=mask)
-        node_feat, L, L_cluster, L_cut, label, mask = (t['node_feat'], t['L'], t['L_cluster'], t['L_cut'],
-                                                       t['label'], t['mask'])
-        drop = self.training and self.dropout > 0
-        why = self._why_not_hip(node_feat.shape[1], L, L_cluster, L_cut, self._needs_grad(), drop)
-        if why is None:
-            self.last_route = 'gpnn_hip'
-            score = self._hip_forward(node_feat, L, L_cluster, L_cut, mask)
-        else:
-            self.last_route = 'gpnn_torch'
-            if not getattr(self, '_warned_torch_route', False):
-                warnings.warn('lanczosnet_amd: GPNN takes the differentiable torch restatement (route '
-                              "'gpnn_torch', slower than the HIP kernel of route 'gpnn_hip'): %s" % why)
-                self._warned_torch_route = True
-            score = self._torch_forward(node_feat, L, L_cluster, L_cut, mask, dropout=drop)
-        if label is not None:
-            return score, self.loss_func(score, label)
-        return score
+        return self._dispatch(node_feat=node_feat, L=L, L_cluster=L_cluster, L_cut=L_cut, label=label, mask=mask)
 
     @torch.no_grad()
     def _hip_forward(self, node_feat, L, L_cluster, L_cut, mask):

@@ -37,7 +37,8 @@ import torch.nn as nn
 from .. import ops
 from ..utils.data_helper import check_dist
 from ._common import (FUSED_MAX_NODES, FUSED_WIDTHS, LARGE_MAX_OPERATORS, MAX_CHANNELS, MAX_INPUT_DIM,
-                      MAX_SHORT_SCALES, MID_MAX_NODES, STRIP_MAX_LONG_SCALES, STRIP_WIDTH, _opt, input_state, masked_readout)
+                      MAX_SHORT_SCALES, MID_MAX_NODES, STRIP_MAX_LONG_SCALES, STRIP_WIDTH, _CallPlumbing, _opt, input_state,
+                      masked_readout)
 from ._large import _LargeMixin, _LargeSparseFusedFunction, _SparseOperators
 from ._mid import _MidGraphFusedFunction, _MidMixin
 from ._small import _LanczosNetFunction, _LanczosNetFusedFunction, _SmallMixin
@@ -52,7 +53,7 @@ _TRAIN_FUNCTIONS = {'fused_train_hip': _LanczosNetFusedFunction, 'fused_train_to
                     'large_dense_channels_train_hip': _LargeSparseFusedFunction}
 
 
-class _LanczosNetBase(_SmallMixin, _MidMixin, _LargeMixin, nn.Module):
+class _LanczosNetBase(_SmallMixin, _MidMixin, _LargeMixin, _CallPlumbing, nn.Module):
     general = False
     filter_kind = 0                      # 0: diagonal gains on Ritz vectors, 1: dense (Ada)
     # 'fp32' (default): exact fp32 MFMA.  'f16x3': opt-in split precision inside the strip kernel (x_hi
@@ -155,27 +156,6 @@ class _LanczosNetBase(_SmallMixin, _MidMixin, _LargeMixin, nn.Module):
             raise RuntimeError('lanczosnet_amd models run on the AMD GPU only: move the '
                                'module and its inputs to cuda (no CPU fallback)')
         return dev
-
-    def _to_module_device(self, dev, **tensors):
-        """`QM8Runner.test` moves only `D, V` to the GPU and hands over a HOST `L` (and, like every
-        loop of the runner, host-side nothing else) — runner/qm8_runner.py:301-302; the reference
-        model then fails inside `bmm`.  A drop-in should not: inputs that are not on the module's
-        device are moved there, with one warning per module."""
-        out, moved = {}, []
-        for k, t in tensors.items():
-            if isinstance(t, torch.Tensor) and t.device != dev:
-                moved.append(k)
-                t = t.to(dev, non_blocking=True)
-            out[k] = t
-        if moved and not getattr(self, '_warned_host_inputs', False):
-            warnings.warn('lanczosnet_amd: input(s) %s were not on %s and were moved there '
-                          '(reference runner/qm8_runner.py:301-302 leaves L on the host); keep the '
-                          'batch resident on the GPU to avoid the copy' % (', '.join(moved), dev))
-            self._warned_host_inputs = True
-        return out
-
-    def _needs_grad(self):
-        return torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
 
     def invalidate_plan(self):
         """Drop the packed-parameter plans.  They are keyed on (data_ptr, tensor version) of every

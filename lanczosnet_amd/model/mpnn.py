@@ -36,7 +36,6 @@ t = T-1 .. 0 (the step is recomputed on chip from S_t) with the step's weight gr
 in training, `msg_func: embedding` and every shape reason still take 'mpnn_torch'.
 """
 import os
-import warnings
 
 import numpy as np
 import torch
@@ -44,6 +43,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
+from ._baseline import _Baseline
 from ._common import _opt
 from .set2set import Set2Vec, set2vec_batched
 
@@ -96,8 +96,11 @@ class _MpnnTrainFunction(torch.autograd.Function):
         return (None,) * 5 + (demb, dWin, dbin) + (tuple(grads) if grads is not None else (None,) * 8)
 
 
-class MPNN(nn.Module):
+class MPNN(_Baseline):
     """Message Passing Neural Networks (Gilmer et al., ICML 2017) as the reference builds it for QM8."""
+    _route_prefix = 'mpnn'
+    _hip_kernels = 'kernels'
+    _cache_slots = ('_pack_cache', '_transpose_cache')
     # 'torch': a call that needs gradients takes route 'mpnn_torch'; 'hip': route 'mpnn_hip_train'
     mpnn_backward_impl = os.environ.get('LANCZOSNET_MPNN_BACKWARD', 'torch')
 
@@ -134,33 +137,14 @@ class MPNN(nn.Module):
         self.att_func = Set2Vec(D, self.num_step_set2vec)
         self.output_func = nn.Sequential(nn.Linear(2 * D, self.output_dim))
 
-        losses = {'CrossEntropy': nn.CrossEntropyLoss, 'MSE': nn.MSELoss, 'L1': nn.L1Loss}
-        if m.loss not in losses:
-            raise ValueError("Non-supported loss function!")
-        self.loss_func = losses[m.loss]()
-        self._init_param()
-        self._pack_cache = None
-        self._transpose_cache = None
-        self._param_list = None
-        self.last_route = None
+        self._finish_init(m.loss)
 
     def _init_param(self):
         # model/mpnn.py:85-108.  The loop runs over input_func, output_func and att_func; att_func is a
         # Set2Vec, neither an nn.Sequential nor an nn.Linear, and is passed over; edge_func is not in the
         # list at all: its Linears keep torch's default init and nonzero biases
-        for group in (self.input_func, self.output_func, self.att_func):
-            if isinstance(group, nn.Sequential):
-                for layer in group:
-                    if isinstance(layer, nn.Linear):
-                        nn.init.xavier_uniform_(layer.weight.data)
-                        if layer.bias is not None:
-                            layer.bias.data.zero_()
-        cell = self.update_func
-        nn.init.xavier_uniform_(cell.weight_hh.data)       # hh before ih, as in the reference
-        nn.init.xavier_uniform_(cell.weight_ih.data)
-        if cell.bias:
-            cell.bias_hh.data.zero_()
-            cell.bias_ih.data.zero_()
+        self._init_sequentials((self.input_func, self.output_func, self.att_func))
+        self._init_cell(self.update_func)
 
     # -- the packed operands of route 'mpnn_hip' -------------------------------------------------------
     def _msg_operands(self):
@@ -171,62 +155,33 @@ class MPNN(nn.Module):
         b2 = torch.stack([f[2].bias for f in self.edge_func])
         return W1, b1, W2, b2
 
-    def _param_signature(self):
-        """What the packed operands are keyed on: the tensor version of every parameter (an optimizer
-        step or any other in-place update bumps it) and the device."""
-        if self._param_list is None:
-            self._param_list = list(self.parameters())
-        return (str(self.node_embedding.weight.device),) + tuple(p._version for p in self._param_list)
+    def _embedding_weight(self):
+        return self.node_embedding.weight
 
-    def invalidate_plan(self):
-        """Drop the packed operands and the [num_atom, D] table.  Writes that bump no tensor version
-        (`p.data.clamp_()`, `p.data = x`) and a parameter replaced by another object need this call.
-        `load_state_dict` and `.to()/.cuda()/.float()` call it themselves."""
-        self._pack_cache = None
-        self._transpose_cache = None
-        self._param_list = None
-
-    def _apply(self, fn, *a, **kw):
-        self.invalidate_plan()
-        return super()._apply(fn, *a, **kw)
-
-    def load_state_dict(self, *a, **kw):
-        self.invalidate_plan()
-        return super().load_state_dict(*a, **kw)
-
-    @torch.no_grad()
     def _packs(self):
         """(table [num_atom, D] = input_func(node_embedding.weight), the eight operands of ops.mpnn_forward,
         the six of ops.set2vec_readout), once per weight version"""
-        sig = self._param_signature()
-        if self._pack_cache is not None and self._pack_cache[0] == sig:
-            return self._pack_cache[1]
-        f = lambda x: x.detach().float().contiguous()  # noqa: E731
-        cell, att = self.update_func, self.att_func
-        prop = tuple(f(x) for x in self._msg_operands() + (cell.weight_ih, cell.bias_ih, cell.weight_hh, cell.bias_hh))
-        Wg, bg, W1T = ops.set2vec_pack([(g[0].weight.detach(), g[0].bias.detach()) for g in att.LSTM.gates()],
-                                       att.W_1.detach())
-        read = (Wg, bg, W1T, f(att.W_2).reshape(-1), f(self.output_func[0].weight), f(self.output_func[0].bias))
-        table = ops.f32_linear(f(self.node_embedding.weight), f(self.input_func[0].weight),
-                               bias=f(self.input_func[0].bias))
-        self._pack_cache = (sig, (table, prop, read))
-        return self._pack_cache[1]
+        def build():
+            f = lambda x: x.detach().float().contiguous()  # noqa: E731
+            cell, att = self.update_func, self.att_func
+            prop = tuple(f(x) for x in self._msg_operands() + (cell.weight_ih, cell.bias_ih, cell.weight_hh,
+                                                               cell.bias_hh))
+            Wg, bg, W1T = ops.set2vec_pack([(g[0].weight.detach(), g[0].bias.detach()) for g in att.LSTM.gates()],
+                                           att.W_1.detach())
+            read = (Wg, bg, W1T, f(att.W_2).reshape(-1), f(self.output_func[0].weight), f(self.output_func[0].bias))
+            table = ops.f32_linear(f(self.node_embedding.weight), f(self.input_func[0].weight),
+                                   bias=f(self.input_func[0].bias))
+            return table, prop, read
+        return self._cached('_pack_cache', build)
 
-    @torch.no_grad()
     def _transposes(self):
         """(W1T, W2T, WihT, WhhT) of ops.mpnn_backward_step, once per weight version like `_packs`."""
-        sig = self._param_signature()
-        if self._transpose_cache is not None and self._transpose_cache[0] == sig:
-            return self._transpose_cache[1]
-        W1, _, W2, _ = self._msg_operands()
-        packs = ops.mpnn_pack_transposes(W1, W2, self.update_func.weight_ih, self.update_func.weight_hh)
-        self._transpose_cache = (sig, packs)
-        return packs
+        def build():
+            W1, _, W2, _ = self._msg_operands()
+            return ops.mpnn_pack_transposes(W1, W2, self.update_func.weight_ih, self.update_func.weight_hh)
+        return self._cached('_transpose_cache', build)
 
     # -- which route serves a call ----------------------------------------------------------------
-    def _needs_grad(self):
-        return torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
-
     def _why_not_hip(self, N, L, needs_grad, drop):
         """None when route 'mpnn_hip' (or, for a call that needs gradients with the switch on, route
         'mpnn_hip_train') serves the call, else the reason in words.  No GPU needed to ask."""
@@ -248,56 +203,13 @@ class MPNN(nn.Module):
             return 'output_dim=%d > %d' % (self.output_dim, ops.MPNN_MAX_OUTPUTS)
         if self.num_prop < 0 or self.num_step_set2vec < 0:
             return 'num_prop=%d, num_step_set2vec=%d' % (self.num_prop, self.num_step_set2vec)
-        if L.dtype != torch.float32 or L.dim() != 4 or L.shape[3] != C:
-            return 'L is %s %s, not float32 [B, N, N, %d]' % (L.dtype, tuple(L.shape), C)
-        if self.node_embedding.weight.dtype != torch.float32:
-            return 'the parameters are %s, not float32' % self.node_embedding.weight.dtype
-        return None
-
-    def _to_module_device(self, dev, **tensors):
-        """The reference's runner hands over host tensors (runner/qm8_runner.py:301-302 leaves L on the
-        host): inputs that are not on the module's device are moved there, with one warning per module."""
-        out, moved = {}, []
-        for k, t in tensors.items():
-            if isinstance(t, torch.Tensor) and t.device != dev:
-                moved.append(k)
-                t = t.to(dev, non_blocking=True)
-            out[k] = t
-        if moved and not getattr(self, '_warned_host_inputs', False):
-            warnings.warn('lanczosnet_amd: input(s) %s were not on %s and were moved there '
-                          '(reference runner/qm8_runner.py:301-302 leaves L on the host); keep the '
-                          'batch resident on the GPU to avoid the copy' % (', '.join(moved), dev))
-            self._warned_host_inputs = True
-        return out
+        return self._why_not_hip_operands(L, C)
 
     def forward(self, node_feat, L, label=None, mask=None):
         """node_feat [B, N] long, L [B, N, N, E + 1] float (read as L != 0, never written), label [B, P],
         mask [B, N] (read as != 0; None: Set2Vec reads all N rows, model/mpnn.py:203-205) -> score [B, P],
         or (score, loss) with a label."""
-        dev = self.node_embedding.weight.device
-        if dev.type != 'cuda':
-            raise RuntimeError('lanczosnet_amd models run on the AMD GPU only: move the '
-                               'module and its inputs to cuda (no CPU fallback)')
-        t = self._to_module_device(dev, node_feat=node_feat, L=L, label=label, mask=mask)
-        node_feat, L, label, mask = t['node_feat'], t['L'], t['label'], t['mask']
-        drop = self.training and self.dropout > 0
-        why = self._why_not_hip(node_feat.shape[1], L, self._needs_grad(), drop)
-        if why is None and self._needs_grad():
-            self.last_route = 'mpnn_hip_train'
-            score = self._hip_train_forward(node_feat, L, mask)
-        elif why is None:
-            self.last_route = 'mpnn_hip'
-            score = self._hip_forward(node_feat, L, mask)
-        else:
-            self.last_route = 'mpnn_torch'
-            if not getattr(self, '_warned_torch_route', False):
-                warnings.warn('lanczosnet_amd: MPNN takes the differentiable torch restatement (route '
-                              "'mpnn_torch', slower than the HIP kernels of route 'mpnn_hip'): %s" % why)
-                self._warned_torch_route = True
-            score = self._torch_forward(node_feat, L, mask, dropout=drop)
-        if label is not None:
-            return score, self.loss_func(score, label)
-        return score
+        return self._dispatch(node_feat=node_feat, L=L, label=label, mask=mask)
 
     @torch.no_grad()
     def _hip_forward(self, node_feat, L, mask):

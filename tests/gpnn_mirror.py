@@ -148,6 +148,18 @@ def propagate(S, L, L_cluster, L_cut, W1, b1, W2, b2, Wih, bih, Whh, bhh, Wpih, 
   return S
 
 
+def identity_state_mlp(D):
+  """(Ws1 [512, 3 D], bs1, Ws2 [D, 512], bs2) of a state_func that returns its S block exactly in float32: row
+  i < D of Ws1 is e_i and row D + i is -e_i on the S block, all else 0; row i of Ws2 is +1 at column i and -1 at
+  column D + i; no biases.  Then state_func([S | Sc | Sx]) = relu(s) - relu(-s) = s in any summation order: every
+  other term of each chain is a product with zero."""
+  Ws1, Ws2 = torch.zeros(STATE_HIDDEN, 3 * D), torch.zeros(D, STATE_HIDDEN)
+  i = torch.arange(D)
+  Ws1[i, i], Ws1[D + i, i] = 1.0, -1.0
+  Ws2[i, i], Ws2[i, D + i] = 1.0, -1.0
+  return Ws1, torch.zeros(STATE_HIDDEN), Ws2, torch.zeros(D)
+
+
 def operands(P, C, dtype=torch.float64):
   """The twenty kernel operands (sixteen of the propagation, four of the readout) from a state_dict-like
   dict of arrays / tensors, in the order of ops.gpnn_forward."""

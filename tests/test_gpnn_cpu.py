@@ -279,3 +279,29 @@ def test_partition_laplacians_match_the_reference():
   assert pad.any() and np.array_equal(np.diagonal(Lct.numpy(), axis1=1, axis2=2)[pad], np.ones(int(pad.sum()), np.float32))
   with pytest.raises(ValueError):
     get_L_cluster_cut(torch.zeros(2, 3, 3), torch.zeros(2, 4, dtype=torch.long))
+
+
+@pytest.mark.parametrize('D', [32, 64, 96, 128])
+def test_the_identity_state_mlp_returns_its_state_block_exactly_in_float32(D):
+  """the construction behind test_gpu_gpnn's comparison of the GGNN step in gpnn_forward and in ggnn_forward: with
+  these weights state_func is the identity on S to the bit, whatever stands in the Sc and Sx blocks and in whatever
+  order the chains are summed, so GPNN with both partition counts 0 is the GGNN recurrence"""
+  Ws1, bs1, Ws2, bs2 = M.identity_state_mlp(D)
+  assert tuple(Ws1.shape) == (M.STATE_HIDDEN, 3 * D) and tuple(Ws2.shape) == (D, M.STATE_HIDDEN)
+  assert int((Ws1 != 0).sum()) == 2 * D and int((Ws2 != 0).sum()) == 2 * D and not bs1.any() and not bs2.any()
+  assert not Ws1[:, D:].any() and not Ws1[2 * D:].any() and not Ws2[:, 2 * D:].any()
+  g = torch.Generator().manual_seed(40 + D)
+  S = torch.randn(14, 5, D, generator=g) * torch.tensor([1e-20, 1.0, 1e20, 3.0, 1e-3]).view(1, 5, 1)
+  other = torch.randn(14, 5, 2 * D, generator=g)
+  out = torch.relu(torch.cat([S, other], dim=2) @ Ws1.t() + bs1) @ Ws2.t() + bs2
+  assert out.dtype == torch.float32 and torch.equal(out, S)
+  perm = torch.randperm(M.STATE_HIDDEN, generator=g)                          # another order of the hidden sum
+  assert torch.equal(torch.relu(torch.cat([S, other], dim=2) @ Ws1[perm].t()) @ Ws2[:, perm].t(), S)
+  # ... and through the mirror: GPNN without partition steps is the GGNN recurrence to the bit
+  W = [0.1 * torch.randn(*s, generator=g) for s in ((2, M.HIDDEN, D), (2, M.HIDDEN), (2, D, M.HIDDEN), (2, D),
+                                                      (3 * D, 2 * D), (3 * D,), (3 * D, D), (3 * D,))]
+  L = (torch.rand(14, 5, 5, 2, generator=g) < 0.4).float()
+  z = torch.zeros(14, 5, 5)
+  part = [torch.zeros(3 * D, D), torch.zeros(3 * D), torch.zeros(3 * D, D), torch.zeros(3 * D)]
+  mine = M.propagate(S, L, z, z, *W, *part, Ws1, bs1, Ws2, bs2, 3, 0, 0)
+  assert torch.equal(mine, M.G.propagate(S, L, *W, 3))

@@ -299,6 +299,35 @@ def test_a_molecules_bits_do_not_depend_on_its_position_in_the_batch(N, D, B, k)
   assert torch.equal(back.flip(0), full) and torch.equal(back_state.flip(0), full_state)
 
 
+@pytest.mark.parametrize('D', [32, 64, 96, 128])
+def test_the_ggnn_step_and_readout_have_the_same_bits_in_ggnn_forward_and_in_gpnn_forward(D):
+  """ggnn_tile.hpp's LNZ_GGNN_TILE_STEP and gated_readout are the step and the readout of both forwards.  With both partition
+  counts 0 and the identity state MLP (gpnn_mirror.identity_state_mlp: state_func returns S exactly in float32, in
+  any summation order; tests/test_gpnn_cpu.py) gpnn_forward is the GGNN recurrence, so it has to give
+  ggnn_forward's final state and score to the bit, at the shape of test_gpu_mpnn.ZERO_MESSAGE: tiles of 6, 6 and
+  2 molecules."""
+  from lanczosnet_amd import ops
+  N, B, C, T = 5, 14, 2, 3
+  S, L, Lcl, Lct, W = _operands(6000 + D, B, N, C, D)
+  W[12:16] = M.identity_state_mlp(D)
+  Sd, Ld, Lcld, Lctd, Wd = S.cuda(), L.cuda(), Lcl.cuda(), Lct.cuda(), [w.cuda() for w in W]
+  mask = _mask('ragged', B, N, 17 + D).cuda()
+  assert len(set(mask.sum(dim=1).tolist())) > 1                              # ragged
+  for agg in ('avg', 'sum'):
+    p_score, p_state = ops.gpnn_forward(Sd, Ld, Lcld, Lctd, mask, *Wd, T, 0, 0, avg=agg == 'avg', return_state=True)
+    assert ops.last_kernel() == 'gpnn_forward_kernel<%d, 2>' % D
+    g_score, g_state = ops.ggnn_forward(Sd, Ld, mask, *Wd[:8], *Wd[16:], T, avg=agg == 'avg', return_state=True,
+                                        tile_rows=32)
+    assert ops.last_kernel() == 'ggnn_forward_kernel<%d, 2>' % D
+    differ = (p_state != g_state).nonzero()
+    print('GGNN step in gpnn_forward vs ggnn_forward D %d %s: %d of %d state elements differ%s'
+          % (D, agg, len(differ), p_state.numel(), '' if len(differ) == 0 else ', first at %s: %r vs %r' % (
+              tuple(differ[0].tolist()), float(p_state[tuple(differ[0])]), float(g_state[tuple(differ[0])]))))
+    assert torch.isfinite(g_state).all() and float((g_state - Sd).abs().max()) > 1e-3    # the steps did run
+    assert torch.equal(p_state, g_state), agg
+    assert torch.equal(p_score, g_score), agg
+
+
 def test_a_molecule_without_nodes_scores_nan_and_its_neighbours_stay_finite():
   from lanczosnet_amd import ops
   N, C, D, B = 5, 2, 32, 4

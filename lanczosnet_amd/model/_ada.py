@@ -74,7 +74,14 @@ class AdaLanczosNet(_LanczosNetBase):
         q1 = self._draw_q1(B, N, L.device) if self.num_scale_long > 0 else None
         drop = self.training and self.dropout > 0.0
         off = self._off_nominal(L.shape[1], drop)
-        if off:
+        # (a differentiable L: the Functions below return no gradient for it, the restatement does)
+        diff = self._differentiable_inputs(node_feat=node_feat, L=L)
+        needs_grad = self._needs_grad(node_feat, L)
+        if diff and not off:
+            self._warn_differentiable_inputs(diff)
+            self.last_route = 'ada_torch'
+            score = self._torch_forward_ada(node_feat, L, mask, q1, dropout=drop)
+        elif off:
             # every configuration the reference class accepts runs: outside what the fused kernels
             # are built for, on the device-side restatement of the same operator sequence
             if off not in self.__dict__.setdefault('_warned_off_nominal', set()):
@@ -84,16 +91,19 @@ class AdaLanczosNet(_LanczosNetBase):
                               'width %d / %d, N <= %d, no training dropout): using the device-side '
                               'torch restatement of model/ada_lanczos_net.py:289-368, which is slower'
                               % ((off,) + FUSED_WIDTHS + (FUSED_MAX_NODES,)))
-            with torch.set_grad_enabled(self._needs_grad()):
+            self.last_route = 'ada_torch'
+            with torch.set_grad_enabled(needs_grad):
                 score = self._torch_forward_ada(node_feat, L, mask, q1, dropout=drop)
-        elif self._needs_grad():
+        elif needs_grad:
             # forward = HIP kernels; backward = HIP conv-stack backward + library GEMMs for the
             # filter MLPs + autograd through the fp64 Lanczos layer (_AdaLanczosNetFusedFunction)
             # where built, else autograd through the whole torch restatement
             fn = _AdaLanczosNetFusedFunction if self._fused_backward_supported() else \
                 _AdaLanczosNetFunction
+            self.last_route = 'ada_train_hip' if fn is _AdaLanczosNetFusedFunction else 'ada_train_torch'
             score = fn.apply(self, node_feat, L, mask, q1, *[p for p in self.parameters()])
         else:
+            self.last_route = 'ada_hip'
             score = self._hip_forward_ada(node_feat, L, mask, q1)
         if label is not None:
             return score, self.loss_func(score, label)
@@ -527,6 +537,7 @@ class _AdaLanczosNetFusedFunction(torch.autograd.Function):
         return score
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, grad_score):
         m = ctx.module
         node_feat, L, mask, q1, mask_u8, Lp, Q, DDp, act, tile_buf, n_mol, tcat = ctx.saved_tensors[:12]
@@ -638,6 +649,7 @@ class _AdaLanczosNetFunction(torch.autograd.Function):
         return module._hip_forward_ada(node_feat, L, mask, q1)
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, grad_score):
         module = ctx.module
         node_feat, L, mask, q1 = ctx.saved_tensors

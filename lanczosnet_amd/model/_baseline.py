@@ -108,22 +108,33 @@ class _Baseline(_CallPlumbing, nn.Module):
             return 'the parameters are %s, not float32' % self._embedding_weight().dtype
         return None
 
-    def _dispatch(self, **inputs):
-        """The tail of every `forward`.  inputs: node_feat, the graph tensors, `label`, mask last, in the order of
-        the signature.  Everything goes to the module's device; `_why_not_hip(N, *graphs, needs_grad, drop)`
-        picks the route, whose method gets (node_feat, *graphs, mask) -> score, or (score, loss) with a label."""
+    def _guard_device(self):
         dev = self._embedding_weight().device
         if dev.type != 'cuda':
             raise RuntimeError('lanczosnet_amd models run on the AMD GPU only: move the '
                                'module and its inputs to cuda (no CPU fallback)')
+        return dev
+
+    def _dispatch(self, **inputs):
+        """The tail of every `forward`.  inputs: node_feat, the graph tensors, `label`, mask last, in the order of
+        the signature.  Everything goes to the module's device; `_why_not_hip(N, *graphs, needs_grad, drop)`
+        picks the route, whose method gets (node_feat, *graphs, mask) -> score, or (score, loss) with a label."""
+        dev = self._guard_device()
         inputs = self._to_module_device(dev, **inputs)
         label = inputs.pop('label')
         args = tuple(inputs.values())
         drop = self.training and self.dropout > 0
-        needs_grad = self._needs_grad()
+        needs_grad = self._needs_grad(*args)
         why = self._why_not_hip(args[0].shape[1], *args[1:-1], needs_grad, drop)
+        # (the HIP backward returns no gradient for an input: the restatement differentiates through it, with
+        # a warning of its own, once per module)
+        diff = self._differentiable_inputs(**inputs) if why is None else []
         name, prefix = type(self).__name__, self._route_prefix
-        if why is None and needs_grad:
+        if diff:
+            self.last_route = prefix + '_torch'
+            self._warn_differentiable_inputs(diff)
+            score = self._torch_forward(*args, dropout=drop)
+        elif why is None and needs_grad:
             self.last_route = prefix + '_hip_train'
             score = self._hip_train_forward(*args)
         elif why is None:

@@ -37,12 +37,37 @@ def _opt(node, key, default):
 
 
 # -- what every module of the package asks of a call --------------------------------------------
+def _requires_grad(t):
+    return isinstance(t, torch.Tensor) and t.is_floating_point() and t.requires_grad
+
+
 class _CallPlumbing:
     """Mixed into LanczosNet and the baseline modules: does the call need gradients, and are its inputs
     where the module is."""
 
-    def _needs_grad(self):
-        return torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+    def _needs_grad(self, *inputs):
+        """A parameter requires grad, or one of the call's floating tensors `inputs` does (features from an
+        upstream encoder, a learned operator): either way the score has to carry a graph."""
+        if not torch.is_grad_enabled():
+            return False
+        return any(p.requires_grad for p in self.parameters()) or any(map(_requires_grad, inputs))
+
+    @staticmethod
+    def _differentiable_inputs(**tensors):
+        """Names of the floating tensors among `tensors` that require grad ([] where autograd is off).  The
+        hand-written backward passes treat every input as data, so a call with one of these is served by the
+        differentiable torch restatement (the training switches)."""
+        if not torch.is_grad_enabled():
+            return []
+        return [k for k, t in tensors.items() if _requires_grad(t)]
+
+    def _warn_differentiable_inputs(self, names):
+        """Once per module: the call left the HIP routes because an input requires grad."""
+        if not getattr(self, '_warned_differentiable_inputs', False):
+            self._warned_differentiable_inputs = True
+            warnings.warn('lanczosnet_amd: input(s) %s require grad; the HIP training routes treat the inputs as '
+                          'data, so this call takes the differentiable torch restatement, which is slower '
+                          '(detach the inputs to stay on the HIP route)' % ', '.join(names))
 
     def _to_module_device(self, dev, **tensors):
         """`QM8Runner.test` moves only `D, V` to the GPU and hands over a HOST `L` (and, like every
@@ -236,6 +261,12 @@ def _spectral_mlp_param_grads(m, grads, D, dG, live_rows=None, n_live=None, stat
                 grads[id(m.spectral_filter[t][i].weight)] = gl[li][0][t]
                 grads[id(m.spectral_filter[t][i].bias)] = gl[li][1][t]
     if S > 0 and m._has_mlp() and id(m.spectral_filter[0][lin_idx[0]].weight) not in grads:
+        # (a frozen MLP tensor gets no gradient: autograd.grad refuses one that does not require grad)
+        mlp_params = [p_ for p_ in ([m.spectral_filter[t][i].weight for i in lin_idx for t in range(Lnum)] +
+                                    [m.spectral_filter[t][i].bias for i in lin_idx for t in range(Lnum)])
+                      if p_.requires_grad]
+        if not mlp_params:
+            return
         pows = torch.stack([torch.pow(D.float(), p) for p in m.long_diffusion_dist],
                            dim=2).view(B * K, S)
         if live_rows is not None and not static_rows:
@@ -258,8 +289,6 @@ def _spectral_mlp_param_grads(m, grads, D, dG, live_rows=None, n_live=None, stat
                 h = _BatchedLinear.apply(h, Wst, bst)
                 if li + 1 < len(lin_idx):
                     h = torch.relu(h)
-            mlp_params = [m.spectral_filter[t][i].weight for i in lin_idx for t in range(Lnum)] + \
-                         [m.spectral_filter[t][i].bias for i in lin_idx for t in range(Lnum)]
             gg = torch.autograd.grad(h, mlp_params, dG)
         for p_, g_ in zip(mlp_params, gg):
             grads[id(p_)] = g_

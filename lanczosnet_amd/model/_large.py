@@ -629,6 +629,7 @@ class _LargeSparseFusedFunction(torch.autograd.Function):
         return score
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, grad_score):
         m, op = ctx.module, ctx.op
         node_feat, X0, D, V, mask_u8, n_nodes, Xs = ctx.saved_tensors[:7]

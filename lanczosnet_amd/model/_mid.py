@@ -117,6 +117,7 @@ class _MidGraphFusedFunction(torch.autograd.Function):
         return score
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, grad_score):
         m = ctx.module
         node_feat, X0, L, D, V, mask_u8, Xwork = ctx.saved_tensors[:7]

@@ -365,6 +365,7 @@ class _LanczosNetFusedFunction(torch.autograd.Function):
         return score
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, grad_score):
         m = ctx.module
         node_feat, D, V, mask_u8, Lp, G, act, tile_buf, n_mol = ctx.saved_tensors[:9]
@@ -425,6 +426,7 @@ class _LanczosNetFunction(torch.autograd.Function):
         return module._hip_forward(node_feat, L, D, V, mask)
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, grad_score):
         module = ctx.module
         node_feat, L, D, V, mask = ctx.saved_tensors

@@ -70,6 +70,7 @@ class _LanczosNetBase(_SmallMixin, _MidMixin, _LargeMixin, _CallPlumbing, nn.Mod
     # the torch recomputation everywhere (the gradient oracle the HIP backward is tested against)
     backward_impl = os.environ.get('LANCZOSNET_BACKWARD', 'hip')
     _spectral_hidden = 128               # model/lanczos_net.py:50-56
+    last_route = None                    # the `_route` name of the latest forward
 
     def _spectral_io(self):
         return self.num_scale_long
@@ -208,7 +209,8 @@ class _LanczosNetBase(_SmallMixin, _MidMixin, _LargeMixin, _CallPlumbing, nn.Mod
                 and self.input_dim <= MAX_INPUT_DIM)
 
     def _route(self, N, K, channels, needs_grad, drop, capturing, sparse_one_operator=False,
-               sparse_typed_operators=False, *, dense_one_operator=False, dense_channel_operators=False):
+               sparse_typed_operators=False, *, dense_one_operator=False, dense_channel_operators=False,
+               inputs_grad=False):
         """The path `forward` takes for graphs of N nodes, K Ritz pairs and `channels` operator
         channels (needs_grad: `_needs_grad()`; drop: dropout > 0 in training; capturing: the
         current stream is being captured into a HIP graph; sparse_one_operator: L is an untyped
@@ -217,7 +219,9 @@ class _LanczosNetBase(_SmallMixin, _MidMixin, _LargeMixin, _CallPlumbing, nn.Mod
         one sparse image each with its fp32 values — and the images raised no flag; dense_one_operator: L is a dense
         float32 tensor on the device whose channels are ONE symmetric operator, its clean image with values riding
         on it; dense_channel_operators: ... whose 3 .. 8 channels are distinct symmetric operators under
-        `large_sparse_channels == 'each'`, their images riding on it — `_dense_operators`).  No GPU needed to ask.
+        `large_sparse_channels == 'each'`, their images riding on it — `_dense_operators`; inputs_grad: autograd
+        is on and a floating input of the call — node_feat, L, D or V — requires grad: the HIP backward passes
+        treat the inputs as data, so such a call is 'torch' whatever else holds).  No GPU needed to ask.
           'fused'              <= 32 nodes: the fused MFMA kernels (`_hip_forward`)
           'fused_train_hip'    ... training, HIP backward (`_LanczosNetFusedFunction`)
           'fused_train_torch'  ... training, backward through `_torch_forward` (`_LanczosNetFunction`)
@@ -234,7 +238,10 @@ class _LanczosNetBase(_SmallMixin, _MidMixin, _LargeMixin, _CallPlumbing, nn.Mod
                                (the same Function on the tensor's images)
           'library'            > 32 nodes or an architecture outside the fused kernels, inference:
                                hipBLASLt conv + HIP spectral gains (`_large_graph_forward`)
-          'torch'              gradients or dropout outside the kernels: `_torch_forward`"""
+          'torch'              gradients or dropout outside the kernels, or gradients for an input:
+                               `_torch_forward`"""
+        if inputs_grad:
+            return 'torch'
         if (N <= FUSED_MAX_NODES and not drop and self._fused_supported()
                 and self._fused_channels_ok()):
             if not needs_grad:
@@ -342,11 +349,17 @@ class _LanczosNetBase(_SmallMixin, _MidMixin, _LargeMixin, _CallPlumbing, nn.Mod
         ops.forget_autograd_kernel()   # (last_kernel(): the previous step's backward is history)
         N = L.shape[1]
         capturing = torch.cuda.is_current_stream_capturing()
-        dense = self._dense_operators(L, V.shape[2], drop, capturing)
-        route = self._route(N, V.shape[2], L.shape[3], self._needs_grad(), drop, capturing,
-                            sparse_one_operator=self._sparse_one_operator(L, drop, capturing),
-                            sparse_typed_operators=self._sparse_typed_operators(L, drop, capturing),
-                            dense_one_operator=dense == 'one', dense_channel_operators=dense == 'each')
+        # (a differentiable input: no route but 'torch' can answer, the batch's images are not examined)
+        diff = self._differentiable_inputs(node_feat=node_feat, L=L, D=D, V=V)
+        dense = None if diff else self._dense_operators(L, V.shape[2], drop, capturing)
+        route = self._route(N, V.shape[2], L.shape[3], self._needs_grad(node_feat, L, D, V), drop, capturing,
+                            sparse_one_operator=not diff and self._sparse_one_operator(L, drop, capturing),
+                            sparse_typed_operators=not diff and self._sparse_typed_operators(L, drop, capturing),
+                            dense_one_operator=dense == 'one', dense_channel_operators=dense == 'each',
+                            inputs_grad=bool(diff))
+        self.last_route = route
+        if diff:
+            self._warn_differentiable_inputs(diff)
         if isinstance(L, ops.SparseLaplacian):
             # the batch of dataset.collate_graph_edges: its image serves the sparse large-graph
             # layers; every other route reads the dense tensor
@@ -357,7 +370,7 @@ class _LanczosNetBase(_SmallMixin, _MidMixin, _LargeMixin, _CallPlumbing, nn.Mod
                 L = L.to(dev)
             if route not in ('large_hip', 'large_train_hip', 'large_typed_train_hip') or capturing:
                 L = self._densify(L, "route '%s'" % route)
-        if N <= FUSED_MAX_NODES and not route.startswith('fused'):
+        if N <= FUSED_MAX_NODES and not route.startswith('fused') and not diff:
             self._warn_library_path(drop)
         if _TRAIN_FUNCTIONS.get(route) is _LargeSparseFusedFunction:
             # (the batch's own image(s), or those `_dense_operators` left riding on the tensor)

@@ -582,6 +582,10 @@ def test_ada_training_gradients_match_reference_autograd():
   gi = g['grad_idx']
   with _fixed_randn(g['q1'][gi]):
     score, loss = net(_t(nf[gi]), _t(L[gi]), label=_t(lab[gi]), mask=_t(mask[gi]))
+  assert net.last_route == 'ada_train_hip'
+  with _fixed_randn(g['q1'][gi]), torch.no_grad():
+    net(_t(nf[gi]), _t(L[gi]), mask=_t(mask[gi]))
+  assert net.last_route == 'ada_hip'
   rel_loss = abs(float(loss.detach()) - float(g['loss'])) / abs(float(g['loss']))
   loss.backward()
   gd = dict(net.named_parameters())

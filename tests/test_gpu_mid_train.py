@@ -115,10 +115,10 @@ def _deviation(grads, truth):
 def _against_float64(net, X, L, D, V, mask, label, tag, launches):
   _hip(net)
   loss, g = _step(net, X, L, D, V, mask, label)
-  assert _ran_hip() and len(launches) == 1
+  assert _ran_hip() and len(launches) == 1 and net.last_route == 'mid_train_hip'
   net.mid_backward_impl = 'torch'
   loss_t, g_t = _step(net, X, L, D, V, mask, label)
-  assert len(launches) == 1
+  assert len(launches) == 1 and net.last_route == 'torch'
   loss64, truth = _truth(net, X, L, D, V, mask, label)
   e_hip, e_torch = _deviation(g, truth), _deviation(g_t, truth)
   print('%s: gradients vs float64 autograd, worst of |g|: HIP %.2e (%s), torch route %.2e (%s); loss %.2e / %.2e'

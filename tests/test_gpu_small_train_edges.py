@@ -125,16 +125,18 @@ def _host_net(c):
   return net
 
 
-def _truth(net, X, L, D, V, mask, label, dtype=torch.float64):
+def _truth(net, X, L, D, V, mask, label, dtype=torch.float64, objective=None, inputs=False):
   """The reference's forward (model/lanczos_net.py:143-197, model/lanczos_net_general.py) restated in
   `dtype` from the raw parameters, with autograd.  Returns (loss, parameter gradients by name,
-  [dLoss/dout_l] per conv layer (pre-activation), dLoss/dX_0)."""
+  [dLoss/dout_l] per conv layer (pre-activation), dLoss/dX_0).  objective: a callable score -> scalar in place
+  of the module's loss; inputs: a fifth value, dLoss/d(D, V) by name."""
   P = {k: v.detach().to(dtype).requires_grad_(True) for k, v in net.named_parameters()}
   B, N = mask.shape
-  Lc, Vd = L.to(dtype).permute(0, 3, 1, 2), V.to(dtype)
+  Lc = L.to(dtype).permute(0, 3, 1, 2)
+  Dd, Vd = (t.to(dtype).clone().requires_grad_(True) for t in (D, V))
   x0 = X.to(dtype).clone().requires_grad_(True) if net.general else P['embedding.weight'][X]
   S, nl = net.num_scale_long, net.num_layer
-  pows = torch.stack([D.to(dtype) ** p for p in net.long_diffusion_dist], dim=2) if S else None
+  pows = torch.stack([Dd ** p for p in net.long_diffusion_dist], dim=2) if S else None
   state, outs = x0, []
   for t in range(nl):
     W, bias = P['filter.%d.weight' % t], P['filter.%d.bias' % t]
@@ -163,10 +165,14 @@ def _truth(net, X, L, D, V, mask, label, dtype=torch.float64):
   y = (state @ P['filter.%d.weight' % nl].t() + P['filter.%d.bias' % nl]) * \
       torch.sigmoid(state @ P['att_func.0.weight'].t() + P['att_func.0.bias'])
   m = (mask != 0).to(dtype).unsqueeze(2)
-  loss = net.loss_func((y * m).sum(dim=1) / m.sum(dim=1), label.to(dtype))
+  score = (y * m).sum(dim=1) / m.sum(dim=1)
+  loss = net.loss_func(score, label.to(dtype)) if objective is None else objective(score)
   names = list(P)
-  g = torch.autograd.grad(loss, [P[k] for k in names] + outs + [x0])
-  return loss.detach(), dict(zip(names, g[:len(names)])), list(g[len(names):-1]), g[-1]
+  g = torch.autograd.grad(loss, [P[k] for k in names] + outs + [x0], retain_graph=inputs)
+  res = loss.detach(), dict(zip(names, g[:len(names)])), list(g[len(names):-1]), g[-1]
+  if not inputs:
+    return res
+  return res + (dict(zip('DV', torch.autograd.grad(loss, [Dd, Vd], allow_unused=True))),)
 
 
 def _host_inputs(c):
@@ -195,6 +201,7 @@ def _device(name):
 def _hip_step(net, args):
   from lanczosnet_amd import ops
   loss, g = _step(net, *args)
+  assert net.last_route == 'fused_train_hip'
   assert ops.last_kernel().startswith(KERNEL), ops.last_kernel()
   return loss, g
 
@@ -215,6 +222,7 @@ def test_parameter_gradients_match_float64_autograd(name):
   loss, g = _hip_step(net, args)
   net.backward_impl = 'torch'
   loss_t, g_t = _step(net, *args)
+  assert net.last_route == 'fused_train_torch'
   loss64, truth, _, _ = _truth_of(name)
   e_hip, e_torch = _deviation(g, truth), _deviation(g_t, truth)
   print('%s: gradients vs float64 autograd, worst of |g|: HIP %.2e (%s), torch route %.2e (%s); loss %.2e / %.2e'

@@ -175,3 +175,197 @@ def test_warning_text_names_the_limits_once():
       'kernel (uniform width 64 or 128, <= 8 short and <= 12 long scales, <= 32 channels in all, no '
       'training dropout): using the device library-GEMM path (hipBLASLt conv + HIP spectral gains; '
       'differentiable torch ops when gradients or dropout are needed), which is slower')
+
+
+# ---- differentiable inputs: the hand-written backward passes treat node_feat, L, D and V as data, so a call in
+#      which one of them requires grad takes the differentiable restatement, whatever the size class, the opt-ins
+#      and the state of the parameters (needs_grad False: every parameter frozen — saliency, a frozen backbone)
+ALL_OPTED = dict(MIDHIP, large_backward_impl='hip', large_typed_backward_impl='hip', large_dense_backward_impl='hip')
+SIZE_CLASSES = [   # N, K, C, what `_route` is told of the batch, the route WITHOUT a differentiable input
+    (9, 20, 2, {}, 'fused_train_hip'),
+    (32, 20, 2, {}, 'fused_train_hip'),
+    (33, 20, 2, {}, 'mid_train_hip'),
+    (128, 32, 2, {}, 'mid_train_hip'),
+    (193, 20, 2, dict(sparse_one_operator=True), 'large_train_hip'),
+    (193, 20, 3, dict(sparse_typed_operators=True), 'large_typed_train_hip'),
+    (129, 20, 2, dict(dense_one_operator=True), 'large_dense_train_hip'),
+    (2048, 64, 2, {}, 'torch'),
+]
+
+
+@pytest.mark.parametrize('params_need_grad', [True, False])
+@pytest.mark.parametrize('N,K,C,batch,plain', SIZE_CLASSES)
+def test_route_with_a_differentiable_input_is_the_torch_route(N, K, C, batch, plain, params_need_grad):
+  net = _module(G, {}, ALL_OPTED)
+  assert net._route(N, K, C, True, False, False, **batch) == plain          # (the case is on a HIP training route)
+  # with an input that requires grad the call needs gradients whatever the parameters say
+  assert net._route(N, K, C, True, False, False, inputs_grad=True, **batch) == 'torch'
+  if not params_need_grad:
+    import torch
+    for p in net.parameters():
+      p.requires_grad_(False)
+    x = torch.zeros(2, N, 10, requires_grad=True)
+    assert not net._needs_grad() and not net._needs_grad(x.detach())
+    assert net._needs_grad(x) and net._needs_grad(x.detach(), None, x)
+    assert net._differentiable_inputs(node_feat=x, L=None, D=x.detach(), V=x) == ['node_feat', 'V']
+    with torch.no_grad():
+      assert not net._needs_grad(x) and net._differentiable_inputs(node_feat=x) == []
+    assert net._route(N, K, C, net._needs_grad(x), False, False, inputs_grad=True, **batch) == 'torch'
+
+
+def test_integer_node_ids_and_capture_do_not_count_as_differentiable_inputs():
+  import torch
+  net = _module(Q, {}, {})
+  ids = torch.zeros(2, 9, dtype=torch.long)
+  assert net._differentiable_inputs(node_feat=ids) == [] and net._needs_grad(ids)   # (the parameters)
+  assert net._route(9, 20, 7, True, False, True, inputs_grad=True) == 'torch'
+  assert net._route(9, 20, 7, True, False, True, inputs_grad=False) == 'fused_train_hip'
+
+
+# ---- frozen parameters in the pieces every hand-written backward shares
+def _mlp_truth(net, D, dG):
+  """float64 autograd of the batched filter MLPs: d <G, dG> / d parameter, by id(parameter), for the MLP
+  tensors that require grad.  G[t] = MLP_t([D^p for p in long_diffusion_dist])."""
+  import torch
+  pows = torch.stack([D.double() ** p for p in net.long_diffusion_dist], dim=2).view(-1, net.num_scale_long)
+  P = {id(p): p.detach().double().requires_grad_(p.requires_grad) for p in net.spectral_filter.parameters()}
+  tot = 0.0
+  for t, seq in enumerate(net.spectral_filter):
+    h = pows
+    for i in (0, 2, 4, 6):
+      h = h @ P[id(seq[i].weight)].t() + P[id(seq[i].bias)]
+      h = torch.relu(h) if i < 6 else h
+    tot = tot + (h * dG[t].double()).sum()
+  need = [k for k, v in P.items() if v.requires_grad]
+  return dict(zip(need, torch.autograd.grad(tot, [P[k] for k in need]))) if need else {}
+
+
+@pytest.mark.parametrize('branch', ["mlp_grad_impl 'torch'", 'nine long scales'])
+@pytest.mark.parametrize('frozen', ['none', 'all', 'one weight', 'layer 0', 'every bias'])
+def test_spectral_mlp_param_grads_with_frozen_mlp_tensors(branch, frozen):
+  """The autograd branch of `_spectral_mlp_param_grads` (`mlp_grad_impl = 'torch'`, more than eight long scales):
+  gradients for exactly the MLP tensors that require grad, equal to float64 autograd of the batched MLP at the
+  project's fp32 bar (conftest.rel_err < 1e-5)."""
+  import torch
+  from conftest import rel_err
+  from lanczosnet_amd.model._common import _spectral_mlp_param_grads
+  nine = branch == 'nine long scales'
+  net = _module(G, dict(LONG(9), num_layer=2, hidden_dim=[128] * 2) if nine else dict(num_layer=2, hidden_dim=[128] * 2),
+                dict(mlp_grad_impl='hip' if nine else 'torch'))
+  mlp = dict(net.spectral_filter.named_parameters())
+  off = {'none': [], 'all': list(mlp), 'one weight': ['1.4.weight'], 'layer 0': [k for k in mlp if k.startswith('0.')],
+         'every bias': [k for k in mlp if k.endswith('bias')]}[frozen]
+  for k in off:
+    mlp[k].requires_grad_(False)
+  gen = torch.Generator().manual_seed(5)
+  B, K, S = 3, 12, net.num_scale_long
+  D = torch.rand(B, K, generator=gen) * 1.9 - 0.95           # (the spectrum of L4 lies in [-1, 1])
+  dG = torch.randn(net.num_layer, B * K, S, generator=gen)
+  for p in net.spectral_filter.parameters():                  # (zero biases: make every tensor matter)
+    if p.dim() == 1:
+      p.data.uniform_(-0.1, 0.1, generator=gen)
+  grads = {}
+  _spectral_mlp_param_grads(net, grads, D, dG)
+  want = _mlp_truth(net, D, dG)
+  assert set(grads) == set(want) == {id(p) for p in mlp.values() if p.requires_grad}
+  for k, p in mlp.items():
+    if p.requires_grad:
+      assert float(want[id(p)].norm()) > 0, k
+      e = rel_err(grads[id(p)].numpy(), want[id(p)].numpy())
+      assert grads[id(p)].dtype == torch.float32 and e < 1e-5, (k, e)
+
+
+def test_param_grad_tuple_on_a_partly_frozen_module():
+  """One entry per parameter in `parameters()` order after the leading Nones: the gradient of a tensor that
+  requires grad, None for a frozen one (though `grads` holds a value for it) and for one `grads` lacks."""
+  import torch
+  from lanczosnet_amd.model._common import param_grad_tuple, scatter_head_grads
+  net = _module(Q, dict(num_layer=2, hidden_dim=[128] * 2), {})
+  names = [k for k, _ in net.named_parameters()]
+  frozen = {'embedding.weight', 'filter.1.bias', 'spectral_filter.0.2.weight', 'att_func.0.weight'}
+  grads = {}
+  for i, (k, p) in enumerate(net.named_parameters()):
+    p.requires_grad_(k not in frozen)
+    if k != 'filter.0.bias':
+      grads[id(p)] = torch.full_like(p, float(i))
+  out = param_grad_tuple(net, grads, 6)
+  assert len(out) == 6 + len(names) and out[:6] == (None,) * 6
+  for i, (k, g) in enumerate(zip(names, out[6:])):
+    if k in frozen or k == 'filter.0.bias':
+      assert g is None, k
+    else:
+      assert g.shape == dict(net.named_parameters())[k].shape and float(g.flatten()[0]) == float(i), k
+  # the stacked head gradient lands on the four head tensors by row, frozen or not
+  P, dh = net.output_dim, 128
+  dWh, dbh = torch.arange((P + 1) * dh, dtype=torch.float32).view(P + 1, dh), torch.arange(P + 1.0)
+  head = {}
+  scatter_head_grads(net, head, dWh, dbh)
+  assert torch.equal(head[id(net.filter[-1].weight)], dWh[:P]) and torch.equal(head[id(net.att_func[0].weight)], dWh[P:])
+  assert torch.equal(head[id(net.filter[-1].bias)], dbh[:P]) and torch.equal(head[id(net.att_func[0].bias)], dbh[P:])
+  got = dict(zip(names, param_grad_tuple(net, head, 6)[6:]))
+  assert got['att_func.0.weight'] is None and torch.equal(got['att_func.0.bias'], dbh[P:])
+  assert [k for k, g in got.items() if g is not None] == ['filter.2.weight', 'filter.2.bias', 'att_func.0.bias']
+
+
+# ---- the same rule in AdaLanczosNet and in the baselines' `_dispatch` (device guards patched: host tensors)
+def test_a_baseline_call_with_a_differentiable_input_takes_the_restatement_and_says_so_once(monkeypatch):
+  """GGNN with its HIP backward opted in: `_why_not_hip` has no objection, so without the rule the call would go
+  to `_GgnnTrainFunction`, which returns None for L.  The warning is the inputs' own: a module that already
+  gave its torch-route warning for another reason still gives this one, once."""
+  import warnings
+  import numpy as np
+  import torch
+  import ggnn_mirror as GG
+  from lanczosnet_amd.model import GGNN
+  from lanczosnet_amd.model._baseline import _Baseline
+  monkeypatch.setattr(_Baseline, '_guard_device', lambda self: torch.device('cpu'))
+  cfg, batch, _ = GG.case_inputs('c')
+  net = GGNN(cfg).train()
+  net.ggnn_backward_impl = 'hip'
+  net._warned_torch_route = True
+  t = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in batch.items()}
+  L = t['L'].clone().requires_grad_(True)
+  assert net._why_not_hip(L.shape[1], L, True, False) is None
+  for p in net.parameters():
+    p.requires_grad_(False)
+  assert not net._needs_grad(t['node_feat'], L.detach(), t['node_mask']) and net._needs_grad(t['node_feat'], L)
+  with warnings.catch_warnings(record=True) as rec:
+    warnings.simplefilter('always')
+    for _ in range(2):
+      score = net(t['node_feat'], L, mask=t['node_mask'])
+      assert net.last_route == 'ggnn_torch'
+  assert len(rec) == 1 and 'input(s) L require grad' in str(rec[0].message)
+  ref = net._torch_forward(t['node_feat'], L.detach(), t['node_mask'], dropout=False)
+  assert torch.equal(score.detach(), ref)
+
+
+def test_an_ada_call_with_a_differentiable_operator_takes_the_restatement(monkeypatch):
+  """AdaLanczosNet inside its kernels' envelope (`_off_nominal` empty), a learned L: route 'ada_torch', one warning,
+  a gradient for L — `_AdaLanczosNetFusedFunction` returns None for it."""
+  import warnings
+  import oracle
+  import torch
+  from lanczosnet_amd.model import AdaLanczosNet
+  from lanczosnet_amd.model.lanczos_net import _LanczosNetBase
+  from lanczosnet_amd.utils.arg_helper import make_model_config
+  monkeypatch.setattr(_LanczosNetBase, '_guard_forward', lambda self, L, mask: torch.device('cpu'))
+  monkeypatch.setattr(AdaLanczosNet, '_spectral_hidden', 16)      # (the 4096-wide filter MLPs are not the subject)
+  cfg = dict(oracle.DEFAULT_QM8_CFG, short_diffusion_dist=[1], long_diffusion_dist=[1, 2], hidden_dim=[128],
+             num_layer=1, num_eig_vec=4)
+  net = AdaLanczosNet(make_model_config(cfg, name='AdaLanczosNet')).train()
+  B, N = 3, 9
+  assert net._off_nominal(N, False) == ''
+  gen = torch.Generator().manual_seed(3)
+  ids = torch.randint(0, net.num_atom, (B, N), generator=gen)
+  A = (torch.rand(B, N, N, generator=gen) < 0.4).float()
+  A = ((A + A.transpose(1, 2)) > 0).float()
+  L = A.unsqueeze(3).expand(B, N, N, net.num_edgetype + 1).clone().requires_grad_(True)
+  with warnings.catch_warnings(record=True) as rec:
+    warnings.simplefilter('always')
+    for _ in range(2):
+      score = net(ids, L, mask=torch.ones(B, N, dtype=torch.uint8))
+      assert net.last_route == 'ada_torch' and score.grad_fn is not None
+  assert len(rec) == 1 and 'input(s) L require grad' in str(rec[0].message)
+  score.sum().backward()
+  assert L.grad is not None and float(L.grad.abs().max()) > 0
+  assert all(p.grad is not None for p in net.parameters())
